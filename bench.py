@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py — QPS of brute-force top-10 search on the MI355X scorer (BASELINE.json metric), + the other single-GPU configs.
+"""bench.py — QPS of brute-force top-10 search on the MI355X scorer (BASELINE.json metric); with --full also the other single-GPU configs.
 
 Timed region (the headline's `value`).  Workload at N=1 = BASELINE.json configs[1] ("C2"): one segment of 10 M x d=768 f32, cosine,
 brute-force exact top-10, resident in HBM.  A *step* = one pass of the hot path over one batch of Q queries: Metric::preprocess of
@@ -8,8 +8,16 @@ BatchFilteredSearcher::peek_top_iter) [+ for N>1 the RCCL all-gather of the per-
 queries are cycled in batches.  Before the W warm-up steps an untimed steady-state run of --prewarm-ms (150 ms, `config.prewarm_steps`) belongs to the set-up,
 like generating the block.  The harness whose shape this replaces: /root/reference/lib/segment/benches/vector_search.rs:21,34-104.
 
+Plain run vs --full.  A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline needs and nothing else: set-up, pre-warm, the W
+warm-up steps, the N timed steps, --dump-outputs if given, the result line.  Everything else - the roofline and the kernel's own duration (runs of
+their own), the check of the timed path against the exact scan, the block-stream points, the batch sweep, the other derived copy, robustness,
+the one-process fan-out, the CPU baseline, the C1 / C3 / TQ4 / C4 legs, at N > 1 the per-stage timing - runs only with --full (its --no-* options
+and --configs as before).
+--dump-outputs DIR: after the timed steps, what the LAST timed step returned to its caller (the top-k lists of its batch: ids.npy float64, scores.npy
+float32, counts.npy float64) is written under DIR; rows and queries come from fixed seeds, so the same arguments give the same inputs on every run.
+
 N>1: one rank per GPU.  Under torchrun (RANK / WORLD_SIZE set) the ranks are the launcher's; WITHOUT it `--gpus N` launches its own ranks
-(re-exec under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`), and refuses (exit 2) when fewer than
+(a child process `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`), and refuses (exit 2) when fewer than
 N devices are visible or when WORLD_SIZE disagrees with --gpus: a run never reports fewer ranks than it was asked for.
   --scaling weak (default) = configs[4] ("C5"): rank r holds its own 10 M-row segment (seed + r), every rank scores the same query batch
       against its segment, the per-rank answers (one packed record: Q x 10 x 8 B of lists + Q x 4 B of counts) are all-gathered over RCCL/xGMI in
@@ -20,18 +28,18 @@ N devices are visible or when WORLD_SIZE disagrees with --gpus: a run never repo
   --scaling strong: ONE 10 M-row segment row-split over the ranks, same gather + merge; value = Q * steps / time.
   Rank 0's side measurements (block-stream roofline, one-process fan-out) run AFTER the process group has ended: no rank waits in an RCCL barrier meanwhile.
 
-Output.  The LAST stdout line is the compact headline (<= 4 KB, `headline()`): metric / value / ms_per_step / config / `roofline` /
+Output.  The LAST stdout line is the compact headline (<= 4 KB, `headline()`): metric / value / ms_per_step / config, and with --full `roofline` /
 `cpu_baseline` + a few numbers of every secondary leg.  Everything else (`batch_sweep`, `robustness`, `one_process_fanout`, the C3 / TQ4 / C4
 legs in full) is written to bench_details.json (--details) and echoed on stderr.
 
-`roofline` (N=1) carries BOTH fractions under explicit names, measured in the same run with HIP-event pairs on the kernel's own stream
+`roofline` (--full, N=1) carries BOTH fractions under explicit names, measured in the same run with HIP-event pairs on the kernel's own stream
 (qmx_query_set_timing / qmx_query_timing):
   block_stream  SURVEY 8(d) / north_star's figure: the exact scan streaming the stored f32 block itself (rows x 3072 B = 30.72 GB) once for 16
                 queries (scan_f32_mfma16_kernel) - and once for 1 query (scan_kernel<RowF32>) in block_stream_q1.  The top-level
                 bound / achieved / peak / frac / traffic are this point's.
   timed_kernel  the dominant kernel of the timed step on the bytes IT streams: by default the prefilter over the derived int8 copy (768 B per
                 row, two launches per pass) whose survivors are re-scored exactly in f32 - the lists are the exact scan's, checked in the run.
-`cpu_baseline` = the CPU oracle (AVX2+FMA restatement of the reference's scorer and its peek_top_iter loop) timed on this box's host cores on a
+`cpu_baseline` (--full) = the CPU oracle (AVX2+FMA restatement of the reference's scorer and its peek_top_iter loop) timed on this box's host cores on a
 bounded sample of the same rows.  The oracle is the checker: nothing in the timed region touches it.
 """
 import argparse
@@ -41,6 +49,7 @@ import json
 import math
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -78,7 +87,7 @@ def parse(argv=None):
                     help="skip the secondary measurement of the same search over the OTHER derived copy (the f16 half copy when the int8 copy is timed, and vice versa)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the Q in {1, 8, 32, 128} x {exact, prefilter} sweep")
     ap.add_argument("--no-robustness", action="store_true", help="skip the C2 search on latent / duplicated rows (needs 46 GB more HBM)")
-    ap.add_argument("--verify", type=int, default=1, help="check samples against the oracle (C2 first batch, C3 / C4 scans and walks)")
+    ap.add_argument("--verify", type=int, default=1, help="with --full: check samples against the oracle (C2 first batch, C3 / C4 scans and walks)")
     ap.add_argument("--configs", default="c1,c3,tq,c4", help="comma list of the secondary single-GPU configs to run (empty = none)")
     ap.add_argument("--config-rows", type=int, default=0, help="rows of C3 / C4 (0 = --rows)")
     ap.add_argument("--iid-walk", action="store_true",
@@ -103,6 +112,12 @@ def parse(argv=None):
                          "and merge on the device, the side legs after the process group - and the line says that it is no scaling measurement")
     ap.add_argument("--test-backend", default="",
                     help="module:factory of an injected compute backend (tests only: the launcher, the collective and the line on CPU; never a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement and check (roofline, block-stream points, batch sweep, other copy, robustness, "
+                         "fan-out, CPU baseline, --configs legs, N > 1 stage timing); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (ids.npy float64 [Q, top], scores.npy float32 [Q, top], counts.npy float64 [Q]; "
+                         "-1 / NaN past a query's count) under DIR")
     return ap.parse_args(argv)
 
 
@@ -321,7 +336,8 @@ def headline(result, details_path=None):
     if isinstance(dc, dict):
         hc["derived_copy"] = "%s (requested %s)" % (dc.get("derived_copy"), dc.get("requested"))      # (the trial's timings: details)
     h["config"] = hc
-    h["roofline"] = compact_roofline(result)
+    if "roofline" in result or "roofline_hbm_point_q16" in result:      # (measured by --full only)
+        h["roofline"] = compact_roofline(result)
     cb = result.get("cpu_baseline")
     if isinstance(cb, dict):
         h["cpu_baseline"] = _pick(cb, "value", "unit", "cores", "kind")
@@ -329,7 +345,9 @@ def headline(result, details_path=None):
         if "single_thread" in cb:
             h["cpu_baseline"]["single_thread_value"] = cb["single_thread"].get("value")
         h["cpu_baseline"]["gpu_matches_oracle_on_sample_bit_exact"] = cb.get("gpu_matches_oracle_on_sample_bit_exact")
-    h["checks"] = _pick(result, "prefilter_equals_exact_scan_whole_block", "recall_at_10")
+    checks = _pick(result, "prefilter_equals_exact_scan_whole_block", "recall_at_10")
+    if checks:      # (--full only)
+        h["checks"] = checks
     optional = []
     sw = result.get("batch_sweep")
     if isinstance(sw, dict):
@@ -386,6 +404,27 @@ def emit(result, details_path):
     print(line, flush=True)
 
 
+def describe_timed_path(result, kernel_symbol, seg_info, requested):
+    """config.timed_path / config.derived_copy / dtype of the line: which path the timed steps ran (the main scan kernel, the derived copy it read)"""
+    result["config"]["timed_path"] = _timed_path(kernel_symbol)
+    result["config"]["derived_copy"] = dict(seg_info, requested=requested)
+    i8_copy = "scan_i8copy_kernel" in kernel_symbol
+    if i8_copy or "scan_f16pair_kernel" in kernel_symbol or "scan_f16half256_kernel" in kernel_symbol:
+        result["dtype"] = "f32 (%s prefilter + exact f32 re-score)" % ("int8" if i8_copy else "f16")
+
+
+def dump_outputs(dirpath, lists, counts, np):
+    """--dump-outputs: the top-k lists of one step as its caller receives them ([Q, top, 2] int32 = id bits, f32 score bits; [Q] counts), as
+    DIR/ids.npy (float64, -1 past a query's count), DIR/scores.npy (float32, NaN past it), DIR/counts.npy (float64)."""
+    lists, counts = lists.cpu().numpy(), counts.cpu().numpy().astype(np.int64)
+    live = np.arange(lists.shape[1])[None, :] < counts[:, None]
+    ids = np.where(live, lists[:, :, 0].view(np.uint32).astype(np.float64), -1.0)
+    scores = np.where(live, lists[:, :, 1].view(np.float32), np.float32(np.nan)).astype(np.float32)
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in (("ids", ids), ("scores", scores), ("counts", counts.astype(np.float64))):
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
@@ -401,7 +440,7 @@ def main(argv=None):
         sys.exit(2)
     if how[0] == "exec":
         print("bench.py: --gpus %d without a launcher: starting %d ranks: %s" % (args.gpus, args.gpus, " ".join(how[1])), file=sys.stderr, flush=True)
-        os.execv(how[1][0], how[1])
+        sys.exit(subprocess.call(how[1]))      # (a child process, not exec: this one may have opened the GPU runtime already)
     _, rank, local_rank, world = how
 
     from qdrant_amd import sharded
@@ -549,6 +588,10 @@ def main(argv=None):
     fence()
     elapsed = time.perf_counter() - t0
     collectives_per_step = (sharded.COLLECTIVE_CALLS - calls0) / float(max(1, args.steps))
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # the last timed step's answer, before anything else runs on its lane: the local lists at N = 1 (the injected backend: the merged ones, like N > 1)
+        last = lanes[(args.steps - 1) % len(lanes)][1]
+        dump_outputs(args.dump_outputs, *((last.out, last.counts) if hip and world == 1 else (last.merged, last.mcounts)), np)
     at = [max(marks[0][0].elapsed_time(e) for e in ev) for ev in marks]      # when each group's last lane passed its mark (ms after the first mark)
     group_ms = [(at[j + 1] - at[j]) / gsz for j in range(len(at) - 1) if at[j + 1] > at[j]]        # device time per step, per group of gsz steps
 
@@ -611,6 +654,18 @@ def main(argv=None):
             dist.destroy_process_group()
         return
 
+    kernel_symbol = F.last_kernel(qh)
+    describe_timed_path(result, kernel_symbol, seg_info, args.split_copy)
+    if not args.full:
+        # a plain run ends here: every side measurement and check below is --full's
+        if world > 1:
+            dist.destroy_process_group()
+        for be, _ in lanes:
+            be.close()
+        if rank == 0:
+            emit(result, args.details)
+        return
+
     from bench_sections import (c1_section, c3_section, c4_section, cpu_baseline, iid_walk_leg, derived_copy_point, hbm_point, one_process_fanout, robustness, tq_section,
                                 _counters_dict)
     kms, kl = C.c_float(), C.c_uint32()
@@ -619,7 +674,6 @@ def main(argv=None):
         F.check(lib.qmx_query_timing(be.qh, C.byref(m1), C.byref(l1)))
         kms.value += m1.value
         kl.value += l1.value
-    kernel_symbol = F.last_kernel(qh)
     kernel_ms = kms.value / max(1, kl.value)
     # With several batches in flight an event pair around a scan also holds the time the launch WAITED behind another batch's scan (one block per CU: the scans
     # take turns), so the timed region's figure is not the kernel's duration.  The kernel's own: the same local searches with ONE batch in flight, right here
@@ -656,10 +710,6 @@ def main(argv=None):
     launches_per_pass = max(1.0, launches_per_step / math.ceil(Q / tile_q)) if prefilter else 1.0
     alg_bytes = int(n * row_bytes / launches_per_pass)
     achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-    result["config"]["timed_path"] = _timed_path(kernel_symbol)
-    result["config"]["derived_copy"] = dict(seg_info, requested=args.split_copy)
-    if prefilter:
-        result["dtype"] = "f32 (%s prefilter + exact f32 re-score)" % ("int8" if i8_copy else "f16")
     result["roofline"] = _roofline(n, dim, kernel_ms, alg_bytes, achieved, int(kl.value), launches_per_step, Q, kernel_symbol, launches_per_pass)
     result["roofline"]["kernel_ms_of"] = ("one batch in flight (16 steps right after the timed region): the kernel's own duration" if kernel_ms != kernel_ms_in_flight
                                           else "the timed region")

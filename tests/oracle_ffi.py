@@ -7,6 +7,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _lib = C.CDLL(os.path.join(ROOT, "oracle", "libqdrant_oracle.so"))
 REF_QUANT_PATH = os.path.join(ROOT, "oracle", "_ref", "libqdrant_ref_quant.so")
+# what those kernels returned on the tests' inputs (tests/golden/make_ref_quant_golden.py): the tests need no oracle/_ref
+REF_GOLDEN_PATH = os.path.join(ROOT, "tests", "golden", "ref_quant_kernels.npz")
 
 COSINE, EUCLID, DOT, MANHATTAN = range(4)
 F32, F16, U8 = range(3)

@@ -1,6 +1,6 @@
 """bench.py's output contract and launcher (host logic, CPU): the LAST stdout line is a compact headline (<= 4 KB) that carries every key the driver
-parses + `roofline` (top level = the SURVEY 8(d) block stream, with `block_stream` and `timed_kernel` under explicit names) + `cpu_baseline`; `--gpus N`
-starts its own N ranks when no launcher did and refuses to run on fewer devices than asked."""
+parses + with --full `roofline` (top level = the SURVEY 8(d) block stream, with `block_stream` and `timed_kernel` under explicit names) + `cpu_baseline`;
+`--gpus N` starts its own N ranks when no launcher did and refuses to run on fewer devices than asked; --dump-outputs writes the last step's lists."""
 import json
 import os
 import subprocess
@@ -115,7 +115,7 @@ def test_gpus_2_fails_loudly_where_two_devices_are_not_visible():
 
 
 def test_gpus_2_launches_its_own_ranks_and_reports_two(tmp_path):
-    """`python bench.py --gpus 2` with NO launcher around it: bench.py re-executes itself under torch.distributed.run, two ranks meet over gloo, the
+    """`python bench.py --gpus 2` with NO launcher around it: bench.py runs itself again under torch.distributed.run (a child process), two ranks meet over gloo, the
     injected oracle backend scores, product code (qdrant_amd.sharded) gathers and merges; the last stdout line says n_gpus 2 / rccl_ranks 2 and the merged
     lists are the oracle's over the union of the two segments."""
     import oracle_ffi as O
@@ -123,9 +123,10 @@ def test_gpus_2_launches_its_own_ranks_and_reports_two(tmp_path):
     details = str(tmp_path / "details.json")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PYTHONPATH"] = HERE + os.pathsep + env.get("PYTHONPATH", "")
+    dump = str(tmp_path / "outputs")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--test-backend", "bench_test_backend:make",
                         "--rows", str(n), "--dim", str(dim), "--batch", str(Q), "--nqueries", str(nq), "--steps", str(steps), "--warmup", "1", "--top", str(top),
-                        "--details", details], capture_output=True, text=True, timeout=600, env=env)
+                        "--details", details, "--dump-outputs", dump], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     assert "starting 2 ranks" in p.stderr
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -151,6 +152,54 @@ def test_gpus_2_launches_its_own_ranks_and_reports_two(tmp_path):
     want = O.DenseStorage(O.F32, O.COSINE, rows).peek_top(O.synth(seed + 1, 0, nq, dim)[b * Q:(b + 1) * Q], top)
     checksum = sum(int(w["idx"].view(np.int32).astype(np.int64).sum()) + int(w["score"].view(np.int32).astype(np.int64).sum()) for w in want)
     assert full["merged_checksum"] == checksum
+    # --dump-outputs: the same merged lists, as float64 ids / float32 scores
+    _assert_dump_is(dump, want, Q, top)
+
+
+def _assert_dump_is(dump, want, Q, top):
+    ids, scores, counts = (np.load(os.path.join(dump, k + ".npy")) for k in ("ids", "scores", "counts"))
+    assert ids.dtype == np.float64 and scores.dtype == np.float32 and counts.dtype == np.float64
+    assert ids.shape == scores.shape == (Q, top) and counts.shape == (Q,)
+    for i, w in enumerate(want):
+        c = len(w["idx"])
+        assert counts[i] == c and ids[i, :c].tolist() == w["idx"].astype(np.float64).tolist()
+        assert np.array_equal(scores[i, :c].view(np.uint32), w["score"].view(np.uint32))
+        assert np.all(ids[i, c:] == -1) and np.all(np.isnan(scores[i, c:]))
+
+
+def test_a_plain_run_times_the_steps_and_dumps_the_last_steps_lists(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the line carries the contract keys of the timed steps and no side measurement; with
+    --dump-outputs the last timed step's lists land under DIR, the same on every run with the same arguments."""
+    import oracle_ffi as O
+    n, dim, Q, nq, top = 700, 24, 4, 12, 10
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["PYTHONPATH"] = HERE + os.pathsep + env.get("PYTHONPATH", "")
+    lines = {}
+    for steps, run in ((5, "a"), (5, "b"), (2, "c")):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--test-backend", "bench_test_backend:make",
+                            "--rows", str(n), "--dim", str(dim), "--batch", str(Q), "--nqueries", str(nq), "--steps", str(steps), "--warmup", "2", "--top", str(top),
+                            "--details", str(tmp_path / ("details_%s.json" % run)), "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines[run] = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+        h = lines[run]
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in h, k
+        assert h["steps"] == steps and h["warmup"] == 2 and h["n_gpus"] == 1 and h["higher_is_better"] is True and h["unit"] == "queries/s"
+        assert h["value"] == pytest.approx(Q / (h["ms_per_step"] * 1e-3), rel=1e-2)
+        assert "roofline" not in h and "cpu_baseline" not in h and "configs" not in h and "checks" not in h
+        rows = O.preprocess(O.COSINE, O.synth(0x5EED0002, 0, n, dim))
+        b = (steps - 1) % (nq // Q)
+        want = O.DenseStorage(O.F32, O.COSINE, rows).peek_top(O.synth(0x5EED0002 + 1, 0, nq, dim)[b * Q:(b + 1) * Q], top)
+        _assert_dump_is(str(tmp_path / run), want, Q, top)
+    for k in ("ids", "scores", "counts"):
+        a, b = np.load(str(tmp_path / "a" / (k + ".npy"))), np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert a.tobytes() == b.tobytes(), k
+
+
+def test_full_is_off_by_default():
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    assert bench.parse([]).dump_outputs == "" and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
 
 
 @pytest.mark.parametrize("name", ["r6_bench", "r6_bench_driver_form"])

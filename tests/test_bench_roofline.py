@@ -14,7 +14,9 @@ HALF = "void qmx::scan_f16pair_kernel<true>(qmx::ScanArgs, qmx::SplitArgs)"
 EXACT16 = "void qmx::scan_f32_mfma16_kernel<6, 4, 1, 0, false, false>(qmx::ScanArgs)"
 
 
-@pytest.mark.parametrize("symbol,elem_bytes,peak,dtype", [(I8, 1, bench.MFMA_I8_PEAK_TOPS, "int8"), (HALF, 2, bench.MFMA_F16_PEAK_TFLOPS, "f16")])
+# (explicit ids: the kernel symbols hold "::", the separator of a test id)
+@pytest.mark.parametrize("symbol,elem_bytes,peak,dtype", [(I8, 1, bench.MFMA_I8_PEAK_TOPS, "int8"), (HALF, 2, bench.MFMA_F16_PEAK_TFLOPS, "f16")],
+                         ids=["int8_copy", "f16_pair_copy"])
 def test_prefilter_kernels_are_priced_on_the_bytes_of_their_copy(symbol, elem_bytes, peak, dtype):
     kernel_ms, launches_per_pass = 0.644 * elem_bytes, 2.0
     alg = int(N * DIM * elem_bytes / launches_per_pass)                     # the pass's two launches cover the copy once: the mean launch

@@ -1,8 +1,8 @@
 """GPU parity: EncodedVectorsU8 (scalar int8 quantization) — encode, encode_query, score, score_internal,
 brute-force top-k on codes, oversampling + rescoring — through the C-ABI against the CPU oracle.
 Integer / quantized work: every comparison is BIT-EXACT against the x86 AVX2 path; the oracle's
-integer leaves are themselves pinned to the reference's own C kernels (oracle/_ref, built from
-lib/quantization/cpp/avx2.c) in tests/test_oracle_golden.py and again here.
+integer leaves are themselves pinned to the reference's own C kernels (lib/quantization/cpp/avx2.c; their outputs
+recorded in tests/golden/ref_quant_kernels.npz) in tests/test_oracle_golden.py and again here.
 Error-bound tests restate lib/quantization/tests/integration/test_avx2.rs:16-57.
 """
 import numpy as np
@@ -64,31 +64,39 @@ def test_sq_encode_score_bit_exact(qa, dist, dim):
     assert np.array_equal(scorer.score_bytes(want_rows[ids[:64]]).view(np.uint32), got[:, :64].view(np.uint32))
 
 
-def test_sq_matches_reference_c_kernels(qa):
-    # the integer leaves of the reference itself (oracle/_ref = lib/quantization/cpp/avx2.c compiled unchanged)
-    if O.load_ref_quant() is None:
-        pytest.skip("oracle/_ref not present")
-    for dist, dim in ((O.DOT, 768), (O.MANHATTAN, 768), (O.EUCLID, 1536), (O.DOT, 2064), (O.DOT, 48)):
+REF_KERNEL_CASES = ((O.DOT, 768), (O.MANHATTAN, 768), (O.EUCLID, 1536), (O.DOT, 2064), (O.DOT, 48))
+
+
+def ref_kernel_cases(qa, isa):
+    """(key, stored rows, quantizer, raw queries, preprocessed queries, oracle with `isa`, ids) of test_sq_matches_reference_c_kernels; the last
+    case: worst-case codes (all 127), whose lane sums beyond 2^24 at dim 2064 exercise the f32 hsum order"""
+    for dist, dim in REF_KERNEL_CASES:
         n = 200
-        rng, vecs, quant, osq = _setup(qa, dist, dim, n, seed=dim + dist, isa=O.ISA_REF)
+        rng, vecs, quant, osq = _setup(qa, dist, dim, n, seed=dim + dist, isa=isa)
         rows = osq.encode_rows(vecs)
-        st = qa.EncodedVectorsU8(rows, quant)
         queries = rng.standard_normal((3, dim)).astype(np.float32)
-        ids = np.arange(n, dtype=np.uint32)
-        got = qa.new_raw_scorer(queries, st).score_points(ids)
-        want = osq.score_points(O.preprocess(dist, queries), ids)
-        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    # worst case codes (all 127): lane sums beyond 2^24 at dim 2064 exercise the f32 hsum order
+        yield "%d_%d" % (dist, dim), rows, quant, queries, O.preprocess(dist, queries), osq, np.arange(n, dtype=np.uint32)
     dim, n = 2064, 8
     quant = qa.ScalarQuantizer(dim, qa.Distance.Dot, 1.0 / 127.0, 0.0)
-    osq = O.SqOracle(O.DOT, dim, quant.alpha, quant.offset, O.ISA_REF)
-    vecs = np.ones((n, dim), dtype=np.float32)
-    rows = osq.encode_rows(vecs)
+    osq = O.SqOracle(O.DOT, dim, quant.alpha, quant.offset, isa)
+    rows = osq.encode_rows(np.ones((n, dim), dtype=np.float32))
     assert rows[:, 4:].min() == 127
-    st = qa.EncodedVectorsU8(rows, quant)
-    got = qa.new_raw_scorer(np.ones((1, dim), dtype=np.float32), st).score_points(np.arange(n, dtype=np.uint32))
-    want = osq.score_points(np.ones((1, dim), dtype=np.float32), np.arange(n))
-    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    ones = np.ones((1, dim), dtype=np.float32)
+    yield "worst_2064", rows, quant, ones, ones, osq, np.arange(n, dtype=np.uint32)
+
+
+def test_sq_matches_reference_c_kernels(qa):
+    # the integer leaves of the reference itself (lib/quantization/cpp/avx2.c compiled unchanged into oracle/_ref): the oracle's scores with those
+    # leaves are recorded in tests/golden/ref_quant_kernels.npz (tests/golden/make_ref_quant_golden.py); where oracle/_ref is built, live ones too
+    gold = np.load(O.REF_GOLDEN_PATH)
+    ref = O.load_ref_quant()
+    for key, rows, quant, queries, qpre, osq, ids in ref_kernel_cases(qa, O.ISA_REF if ref is not None else O.ISA_AUTO):
+        want = gold["sq_scores_" + key]                     # f32 bits [queries, ids]
+        if ref is not None:
+            assert np.array_equal(osq.score_points(qpre, ids).view(np.uint32), want)
+        st = qa.EncodedVectorsU8(rows, quant)
+        got = qa.new_raw_scorer(queries, st).score_points(ids)
+        assert np.array_equal(got.view(np.uint32), want)
 
 
 @pytest.mark.parametrize("dist", [O.DOT, O.EUCLID, O.MANHATTAN])

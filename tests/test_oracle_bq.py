@@ -1,7 +1,7 @@
 """CPU: pins the oracle's EncodedVectorsBin<u128> restatement (oracle/qdrant_oracle.c, BQ block).
 
-  * xor-popcount against the reference's own C kernel `impl_xor_popcnt_sse_uint128` (lib/quantization/cpp/sse.c:54-75,
-    compiled into oracle/_ref by oracle/Makefile) and against a numpy bit count
+  * xor-popcount against the reference's own C kernel `impl_xor_popcnt_sse_uint128` (lib/quantization/cpp/sse.c:54-75; its outputs recorded in
+    tests/golden/ref_quant_kernels.npz, and live where oracle/_ref is built) and against a numpy bit count
   * the reference's test vectors (lib/quantization/tests/integration/test_binary.rs:15-22: every coordinate +-1): there
     the BQ score IS the dot product (test_binary_dot_impl :36-74 allows dim * 0.01; it is exact), inverted pairs negate it
     (:88-127), and sorting by the L1 pairings reproduces the order of the true L1 distances (:238-292, :305-359)
@@ -39,20 +39,36 @@ def test_row_bytes_and_bit_layout():
     assert as_u128[0] == (1 << 0) | (1 << 7) | (1 << 8) | (1 << 127) and as_u128[1] == (1 << 0) | (1 << 71)
 
 
-def test_xor_popcnt_matches_the_reference_c_kernel():
-    ref = O.load_ref_quant()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    fn = ref.impl_xor_popcnt_sse_uint128
-    fn.restype, fn.argtypes = C.c_uint32, [C.c_void_p, C.c_void_p, C.c_uint32]
+XOR_WORDS = (1, 2, 3, 6, 12, 13, 64)
+
+
+def xor_popcnt_cases():
+    """(words index, draw, words, q, v) of test_xor_popcnt_matches_the_reference_c_kernel"""
     rng = np.random.default_rng(5)
-    for words in (1, 2, 3, 6, 12, 13, 64):
-        for _ in range(20):
+    for wi, words in enumerate(XOR_WORDS):
+        for it in range(20):
             q = rng.integers(0, 256, words * 16, dtype=np.uint8)
             v = rng.integers(0, 256, words * 16, dtype=np.uint8)
-            want = int(fn(q.ctypes.data, v.ctypes.data, words))
-            assert int(O.lib.qo_bq_xor_popcnt(q.ctypes.data, v.ctypes.data, words)) == want
-            assert int(np.unpackbits(q ^ v).sum()) == want
+            yield wi, it, words, q, v
+
+
+def _ref_xor_fn(ref, name):
+    fn = getattr(ref, name)
+    fn.restype, fn.argtypes = C.c_uint32, [C.c_void_p, C.c_void_p, C.c_uint32]
+    return fn
+
+
+def test_xor_popcnt_matches_the_reference_c_kernel():
+    # the kernel's outputs on these inputs are recorded in tests/golden/ref_quant_kernels.npz; where oracle/_ref is built, live ones too
+    gold = np.load(O.REF_GOLDEN_PATH)["bq_xor_popcnt_sse"]          # [words, draw]
+    ref = O.load_ref_quant()
+    fn = _ref_xor_fn(ref, "impl_xor_popcnt_sse_uint128") if ref is not None else None
+    for wi, it, words, q, v in xor_popcnt_cases():
+        want = int(gold[wi, it])
+        if fn is not None:
+            assert int(fn(q.ctypes.data, v.ctypes.data, words)) == want
+        assert int(O.lib.qo_bq_xor_popcnt(q.ctypes.data, v.ctypes.data, words)) == want
+        assert int(np.unpackbits(q ^ v).sum()) == want
 
 
 @pytest.mark.parametrize("dim", DIMS)
@@ -82,25 +98,33 @@ def test_default_invert_is_the_segments_choice():
 # (impl_xor_popcnt_scalar{4,8}_{avx,sse}_uint128, lib/quantization/cpp/avx2.c / sse.c, compiled into oracle/_ref) for the
 # plane-weighted popcount, and identities of the encoder that follow from its definition.  Encoder bytes: parity unpinned.
 
-@pytest.mark.parametrize("bits", [4, 8])
-def test_scalar_xor_popcnt_matches_the_reference_c_kernels(bits):
-    ref = O.load_ref_quant()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    fns = [getattr(ref, "impl_xor_popcnt_scalar%d_%s_uint128" % (bits, isa)) for isa in ("avx", "sse")]
-    for fn in fns:
-        fn.restype, fn.argtypes = C.c_uint32, [C.c_void_p, C.c_void_p, C.c_uint32]
+SCALAR_XOR_WORDS = (1, 2, 3, 6, 7, 12, 13, 64)
+
+
+def scalar_xor_popcnt_cases(bits):
+    """(words index, draw, words, v, q planes) of test_scalar_xor_popcnt_matches_the_reference_c_kernels"""
     rng = np.random.default_rng(bits)
-    for words in (1, 2, 3, 6, 7, 12, 13, 64):
-        for _ in range(20):
+    for wi, words in enumerate(SCALAR_XOR_WORDS):
+        for it in range(20):
             v = rng.integers(0, 256, words * 16, dtype=np.uint8)
             q = rng.integers(0, 256, words * 16 * bits, dtype=np.uint8)
-            got = int(O.lib.qo_bq_xor_popcnt_scalar(v.ctypes.data, q.ctypes.data, words, bits))
-            for fn in fns:
-                assert int(fn(q.ctypes.data, v.ctypes.data, words)) == got
-            planes = q.reshape(words, bits, 16)
-            want = sum(int(np.unpackbits(planes[w, b] ^ v[16 * w:16 * w + 16]).sum()) << b for w in range(words) for b in range(bits))
-            assert got == want
+            yield wi, it, words, v, q
+
+
+@pytest.mark.parametrize("bits", [4, 8])
+def test_scalar_xor_popcnt_matches_the_reference_c_kernels(bits):
+    # the kernels' outputs (avx, sse) on these inputs are recorded in tests/golden/ref_quant_kernels.npz; where oracle/_ref is built, live ones too
+    gold = np.load(O.REF_GOLDEN_PATH)["bq_xor_popcnt_scalar%d" % bits]          # [words, draw, (avx, sse)]
+    ref = O.load_ref_quant()
+    fns = [_ref_xor_fn(ref, "impl_xor_popcnt_scalar%d_%s_uint128" % (bits, isa)) for isa in ("avx", "sse")] if ref is not None else []
+    for wi, it, words, v, q in scalar_xor_popcnt_cases(bits):
+        got = int(O.lib.qo_bq_xor_popcnt_scalar(v.ctypes.data, q.ctypes.data, words, bits))
+        assert gold[wi, it].tolist() == [got, got]
+        for fn in fns:
+            assert int(fn(q.ctypes.data, v.ctypes.data, words)) == got
+        planes = q.reshape(words, bits, 16)
+        want = sum(int(np.unpackbits(planes[w, b] ^ v[16 * w:16 * w + 16]).sum()) << b for w in range(words) for b in range(bits))
+        assert got == want
 
 
 @pytest.mark.parametrize("encoding", [0, 1, 2])

@@ -166,30 +166,46 @@ def test_peek_top_iter_chunking_and_deleted():
         assert np.array_equal(a["score"], b["score"]) and set(a["idx"]) == set(b["idx"])
 
 
-# the reference's own C kernels (lib/quantization/cpp/avx2.c, sse.c) compiled into oracle/_ref
-def test_sq_leaves_match_reference_c_kernels():
-    ref = O.load_ref_quant()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+# the reference's own C kernels (lib/quantization/cpp/avx2.c, sse.c): their outputs on these inputs are recorded in tests/golden/ref_quant_kernels.npz
+# (tests/golden/make_ref_quant_golden.py, from oracle/_ref); where oracle/_ref is built the live kernels must still give the recorded bits
+SQ_LEAF_DIMS = (16, 32, 48, 64, 128, 768, 784, 1024, 1536, 2064)
+SQ_LEAF_NAMES = ("impl_score_dot_avx", "impl_score_l1_avx", "impl_score_dot_sse", "impl_score_l1_sse")
+
+
+def sq_leaf_cases():
+    """(dim index, draw, dim, q codes, v codes) of test_sq_leaves_match_reference_c_kernels"""
     rng = np.random.default_rng(42)
-    import ctypes as C
-    for dim in (16, 32, 48, 64, 128, 768, 784, 1024, 1536, 2064):
-        for _ in range(20):
+    for di, dim in enumerate(SQ_LEAF_DIMS):
+        for it in range(20):
             q = rng.integers(0, 128, dim, dtype=np.uint8)
             v = rng.integers(0, 128, dim, dtype=np.uint8)
-            pq, pv = C.c_void_p(q.ctypes.data), C.c_void_p(v.ctypes.data)
-            assert _bits(O.lib.qo_sq_dot_avx(pq, pv, dim)) == _bits(ref.impl_score_dot_avx(pq, pv, dim))
-            assert _bits(O.lib.qo_sq_l1_avx(pq, pv, dim)) == _bits(ref.impl_score_l1_avx(pq, pv, dim))
-            assert _bits(O.lib.qo_sq_dot_sse(pq, pv, dim)) == _bits(ref.impl_score_dot_sse(pq, pv, dim))
-            if dim * 127 < 65536:  # sse.c's 16-bit horizontal add wraps above this (restated as-is)
-                assert _bits(O.lib.qo_sq_l1_sse(pq, pv, dim)) == _bits(ref.impl_score_l1_sse(pq, pv, dim))
-            if dim <= 1040:  # exact-integer regime: every leaf equals the i32 sum
-                exact = float((q.astype(np.int64) * v.astype(np.int64)).sum())
-                assert O.lib.qo_sq_dot_avx(pq, pv, dim) == exact
+            yield di, it, dim, q, v
+
+
+def test_sq_leaves_match_reference_c_kernels():
+    import ctypes as C
+    gold = np.load(O.REF_GOLDEN_PATH)
+    leaves, worst = gold["sq_leaves"], gold["sq_leaf_dot_avx_worst"]          # f32 bits [dim, draw, SQ_LEAF_NAMES]; [1]
+    ref = O.load_ref_quant()
+    for di, it, dim, q, v in sq_leaf_cases():
+        pq, pv = C.c_void_p(q.ctypes.data), C.c_void_p(v.ctypes.data)
+        want = leaves[di, it]
+        if ref is not None:
+            assert [_bits(getattr(ref, f)(pq, pv, dim)) for f in SQ_LEAF_NAMES] == want.tolist()
+        assert _bits(O.lib.qo_sq_dot_avx(pq, pv, dim)) == want[0]
+        assert _bits(O.lib.qo_sq_l1_avx(pq, pv, dim)) == want[1]
+        assert _bits(O.lib.qo_sq_dot_sse(pq, pv, dim)) == want[2]
+        if dim * 127 < 65536:  # sse.c's 16-bit horizontal add wraps above this (restated as-is)
+            assert _bits(O.lib.qo_sq_l1_sse(pq, pv, dim)) == want[3]
+        if dim <= 1040:  # exact-integer regime: every leaf equals the i32 sum
+            exact = float((q.astype(np.int64) * v.astype(np.int64)).sum())
+            assert O.lib.qo_sq_dot_avx(pq, pv, dim) == exact
     # worst-case codes
     q = np.full(2064, 127, dtype=np.uint8)
     pq = C.c_void_p(q.ctypes.data)
-    assert _bits(O.lib.qo_sq_dot_avx(pq, pq, 2064)) == _bits(ref.impl_score_dot_avx(pq, pq, 2064))
+    if ref is not None:
+        assert _bits(ref.impl_score_dot_avx(pq, pq, 2064)) == worst[0]
+    assert _bits(O.lib.qo_sq_dot_avx(pq, pq, 2064)) == worst[0]
 
 
 def test_synth_generator_is_counter_based():

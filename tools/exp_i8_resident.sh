@@ -2,7 +2,7 @@
 # round 6, last session: the int8 prefilter scan with the queries' image resident in LDS (option i8_resident = stages of loads ahead; 0 = the staged kernel)
 out=gpurun_out/r6_i8_resident_experiment.txt
 : > $out
-common="--steps 120 --warmup 12 --configs= --no-sweep --no-robustness --no-cpu --no-other-copy-point --fanout-rows 0 --no-hbm-point"
+common="--full --steps 120 --warmup 12 --configs= --no-sweep --no-robustness --no-cpu --no-other-copy-point --fanout-rows 0 --no-hbm-point"
 for v in ${1:-0 1 0 1}; do
   for lanes in ${2:-4}; do
     line=$(env QMX_I8_RESIDENT=$v python bench.py $common --in-flight $lanes --details /tmp/exp_details.json 2>/tmp/exp_err.txt | tail -1)

@@ -6,7 +6,7 @@ import sys,json
 d=json.loads(sys.stdin.read()); w=d['wide_128_per_pass']; print(w['kernel_ms_per_launch'], w['wall_ms_per_search'], w['hbm_frac_of_8TBps'], d['lists_equal'])")"
 done
 unset QMX_EXPERIMENT_SQW_NT
-common="--steps 60 --warmup 6 --configs= --no-sweep --no-robustness --no-cpu --no-other-copy-point --fanout-rows 0 --no-hbm-point"
+common="--full --steps 60 --warmup 6 --configs= --no-sweep --no-robustness --no-cpu --no-other-copy-point --fanout-rows 0 --no-hbm-point"
 for i in 1 2; do
 python bench.py $common --split-copy half --details /tmp/exp_details.json 2>/dev/null | tail -1 | python3 -c "
 import sys,json

@@ -2,7 +2,7 @@
 # round 6, last session: the size of the sample whose exact k-th best score admits the first launch's candidates (option prescan_shift: sample = rows >> shift, at least 8 192)
 out=gpurun_out/r6_prescan_shift_experiment.txt
 : > $out
-common="--steps 120 --warmup 12 --configs= --no-sweep --no-robustness --no-cpu --no-other-copy-point --fanout-rows 0 --no-hbm-point"
+common="--full --steps 120 --warmup 12 --configs= --no-sweep --no-robustness --no-cpu --no-other-copy-point --fanout-rows 0 --no-hbm-point"
 for v in ${1:-10 9 8 7 11 10 9 8}; do
     line=$(env QMX_PRESCAN_SHIFT=$v python bench.py $common --details /tmp/exp_details.json 2>/tmp/exp_err.txt | tail -1)
     echo "QMX_PRESCAN_SHIFT=$v $(echo "$line" | python3 -c "

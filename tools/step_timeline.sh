@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 REPO=$PWD
 cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python $REPO/bench.py --steps 12 --warmup 3 --no-cpu --no-hbm-point --verify 0 --configs "" "$@" > $OUT/bench.json 2> $OUT/err.log
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python $REPO/bench.py --full --steps 12 --warmup 3 --no-cpu --no-hbm-point --verify 0 --configs "" "$@" > $OUT/bench.json 2> $OUT/err.log
 cd $REPO
 CSV=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
 python3 - "$CSV" > $OUT/timeline.txt <<'PY'
