@@ -65,9 +65,11 @@ typedef enum qmx_dtype {
     QMX_DTYPE_BQ = 5,  /* EncodedVectorsBin<u128>; Encoding and QueryEncoding in qmx_bq_params (default OneBit, SameAsStorage)
                           (lib/quantization/src/encoded_vectors_binary.rs): rows of ceil(dim / 128) * 16 bytes,
                           bit i = vector[i] > 0; invert derives from the distance (quantized_vectors.rs:232) */
-    QMX_DTYPE_TQ = 6   /* EncodedVectorsTQ (lib/quantization/src/encoded_vectors_tq.rs over turboquant/): rows as TurboQuantizer::quantize
+    QMX_DTYPE_TQ = 6,  /* EncodedVectorsTQ (lib/quantization/src/encoded_vectors_tq.rs over turboquant/): rows as TurboQuantizer::quantize
                           writes them, [codes: padded_dim * bits / 8 bytes][scaling_factor f32][l2_length f32 for Euclid]
                           (turboquant/encoding.rs:117-134, 172-258); qmx_tq_params required */
+    QMX_DTYPE_SPARSE = 7  /* sparse vectors (lib/sparse/src/common/sparse_vector.rs): created by qmx_sparse_segment_create only
+                             (qmx_segment_create refuses it), queried through qmx_sparse_query_create */
 } qmx_dtype;
 
 /* Same order as `enum Distance` (lib/segment/src/types.rs:313-322). */
@@ -347,6 +349,35 @@ QMX_API int32_t qmx_segment_set_deleted(qmx_segment *seg, const uint64_t *point_
 QMX_API int32_t qmx_segment_read_rows(const qmx_segment *seg, const uint32_t *ids, uint32_t n,
                                       void *out_rows /* [n][row_bytes] reference layout */);
 QMX_API int32_t qmx_segment_row_bytes(const qmx_segment *seg, uint64_t *out);
+
+/* ---- sparse vectors (QMX_DTYPE_SPARSE) ----
+ * Rows in CSR form: row p = (indices, values)[offsets[p] .. offsets[p + 1]), u32 `DimId` / f32 `DimWeight`.  Host or device arrays.
+ * Each row is sorted by index on the way in (lib/segment/src/data_types/vectors.rs:71-78); duplicate indices or offsets that are not
+ * non-decreasing from 0 are QMX_ERR_BAD_ARG (sparse_vector.rs:302-323).  An optional `IndicesTracker` map (indices_tracker.rs:39-73:
+ * map_keys[i] -> map_values[i], NULL = identity) remaps every row and re-sorts it, so that sums follow `plain_search`'s order; a stored index
+ * the map lacks is QMX_ERR_BAD_ARG.  At most 2^32 - 1 non-zeros per segment.
+ * Scores are `score_vectors` (sparse_vector.rs:66-90): the products of the shared dimensions summed in ascending index order from 0.0, one
+ * rounding per multiply and per add; 0.0 for no shared dimension (the raw scorer, sparse_metric_query_scorer.rs:43).
+ * Served on a sparse segment / query: qmx_query_create_internal, qmx_score_points(_ragged), qmx_score_point, qmx_score_internal,
+ * qmx_search_topk(_async) (Nearest: only points that share a dimension with the query, search_context.rs:92-143; `ids`, filters and
+ * deleted flags as for dense; top = 0 gives empty lists), qmx_query_set_filter / set_stream / destroy, qmx_segment_set_deleted / destroy.
+ * Every other entry point handed one: QMX_ERR_NOT_SUPPORTED. */
+typedef struct qmx_sparse_segment_desc {
+    uint64_t n;                   /* rows */
+    const uint64_t *offsets;      /* [n + 1] */
+    const uint32_t *indices;      /* [offsets[n]] */
+    const float *values;          /* [offsets[n]] */
+    const uint32_t *map_keys;     /* [n_map] or NULL: IndicesTracker, original dimension -> remapped id */
+    const uint32_t *map_values;   /* [n_map] or NULL */
+    uint64_t n_map;
+    int32_t device_id;
+    uint32_t flags;               /* 0 (reserved) */
+} qmx_sparse_segment_desc;
+QMX_API int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *desc, qmx_segment **out);
+/* A batch of nq sparse queries in CSR form (host or device arrays), each sorted by index; under the segment's map each is remapped and
+ * dimensions the map lacks are dropped (`remap_vector`).  Duplicate indices => QMX_ERR_BAD_ARG. */
+QMX_API int32_t qmx_sparse_query_create(const qmx_segment *seg, const uint64_t *offsets, const uint32_t *indices, const float *values, uint32_t nq,
+                                        qmx_query **out);
 /* What a segment holds beside its rows: the derived copy of an f32 dot / cosine block (QMX_SEG_*_COPY flags) and, under QMX_SEG_AUTO_COPY, what the
  * trial at create measured.  (The reference's counterpart is the segment telemetry, `VectorIndexSearchesTelemetry` / `SegmentInfo`: which index and
  * quantization serve a segment is reported, not guessed.) */

@@ -16,7 +16,7 @@ OK, ERR_OUT_OF_MEMORY, ERR_OUT_OF_BOUNDS, ERR_NOT_SUPPORTED, ERR_NOT_READY, ERR_
 STATUS_NAMES = ["OK", "OUT_OF_MEMORY", "OUT_OF_BOUNDS", "NOT_SUPPORTED", "NOT_READY", "TIMEOUT", "OTHER",
                 "CANCELLED", "BAD_ARG", "NO_DEVICE"]
 
-DTYPE_F32, DTYPE_F16, DTYPE_U8, DTYPE_SQ_U8, DTYPE_PQ, DTYPE_BQ, DTYPE_TQ = range(7)
+DTYPE_F32, DTYPE_F16, DTYPE_U8, DTYPE_SQ_U8, DTYPE_PQ, DTYPE_BQ, DTYPE_TQ, DTYPE_SPARSE = range(8)
 COSINE, EUCLID, DOT, MANHATTAN = range(4)
 
 SEG_DATA_ON_DEVICE = 0x1
@@ -78,6 +78,12 @@ class SegmentDesc(C.Structure):
                 ("n", C.c_uint64), ("row_stride_bytes", C.c_uint64), ("data", C.c_void_p),
                 ("device_id", C.c_int32), ("reserved", C.c_int32), ("sq", C.POINTER(SqParams)),
                 ("pq", C.POINTER(PqParams)), ("bq", C.POINTER(BqParams)), ("tq", C.POINTER(TqParams))]
+
+
+class SparseSegmentDesc(C.Structure):
+    """qmx_sparse_segment_desc: CSR rows (u64 offsets, u32 indices, f32 values) and the optional IndicesTracker map."""
+    _fields_ = [("n", C.c_uint64), ("offsets", C.c_void_p), ("indices", C.c_void_p), ("values", C.c_void_p),
+                ("map_keys", C.c_void_p), ("map_values", C.c_void_p), ("n_map", C.c_uint64), ("device_id", C.c_int32), ("flags", C.c_uint32)]
 
 
 class HnswDesc(C.Structure):
@@ -153,6 +159,8 @@ SIGNATURES = {
     "qmx_segment_read_rows": (C.c_int32, [_P, _P, C.c_uint32, _P]),
     "qmx_segment_row_bytes": (C.c_int32, [_P, C.POINTER(C.c_uint64)]),
     "qmx_segment_get_info": (C.c_int32, [_P, C.POINTER(SegmentInfo)]),
+    "qmx_sparse_segment_create": (C.c_int32, [C.POINTER(SparseSegmentDesc), C.POINTER(_P)]),
+    "qmx_sparse_query_create": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.POINTER(_P)]),
     "qmx_preprocess_f32": (C.c_int32, [C.c_int32, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P]),
     "qmx_cast_f32": (C.c_int32, [C.c_int32, C.c_uint32, _P, C.c_uint64, _P]),
     "qmx_query_create": (C.c_int32, [_P, _P, C.c_uint32, C.POINTER(_P)]),

@@ -40,6 +40,7 @@ static int32_t custom_prepare(qmx_query *ex, const qmx_custom_query *queries, ui
 }
 
 int32_t qmx_custom_set_coefficients(qmx_query *ex, const float *coefs, uint32_t n) {
+    QMX_REFUSE_SPARSE(ex);
     QMX_REQUIRE(ex && (n == 0 || coefs), QMX_ERR_BAD_ARG, "NULL argument");
     QMX_HIP(hipSetDevice(ex->device));
     ex->n_cq_coefs = 0;
@@ -52,6 +53,7 @@ int32_t qmx_custom_set_coefficients(qmx_query *ex, const float *coefs, uint32_t 
 }
 
 int32_t qmx_custom_score_points(qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, const uint32_t *ids, uint32_t n, float *scores) {
+    QMX_REFUSE_SPARSE(ex);
     QMX_REQUIRE(ex && (n_queries == 0 || queries) && (n == 0 || (ids && scores)), QMX_ERR_BAD_ARG, "NULL argument");
     QMX_HIP(hipSetDevice(ex->device));
     if (n == 0 || n_queries == 0) return QMX_OK;
@@ -64,6 +66,7 @@ int32_t qmx_custom_score_points(qmx_query *ex, const qmx_custom_query *queries, 
 
 int32_t qmx_custom_search_topk(qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t top, const uint32_t *ids, uint64_t n_ids,
                                qmx_scored_point *out, uint32_t *out_counts) {
+    QMX_REFUSE_SPARSE(ex);
     QMX_REQUIRE(ex && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     QMX_HIP(hipSetDevice(ex->device));
@@ -95,6 +98,7 @@ int32_t qmx_custom_search_topk(qmx_query *ex, const qmx_custom_query *queries, u
 // GraphLayers::search with a custom query as the points scorer (graph_layers.rs:108-149 walks with whatever scorer raw_scorer.rs:228-333 built)
 int32_t qmx_custom_hnsw_search(const qmx_hnsw *g, qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t top, uint32_t ef,
                                qmx_scored_point *out, uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
+    QMX_REFUSE_SPARSE(ex);
     QMX_REQUIRE(g && ex && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_TRY(hnsw_check(g, ex, top, ef));
     QMX_HIP(hipSetDevice(ex->device));
@@ -170,6 +174,7 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
 
 int32_t qmx_multi_score_points(qmx_query *inner, const uint32_t *query_first, uint32_t n_queries, const uint64_t *point_offsets, uint32_t n_points,
                                const uint32_t *ids, uint32_t n, float *scores) {
+    QMX_REFUSE_SPARSE(inner);
     QMX_REQUIRE(inner && query_first && point_offsets && (n == 0 || (ids && scores)), QMX_ERR_BAD_ARG, "NULL argument");
     QMX_HIP(hipSetDevice(inner->device));
     if (n == 0 || n_queries == 0) return QMX_OK;
@@ -183,6 +188,7 @@ int32_t qmx_multi_score_points(qmx_query *inner, const uint32_t *query_first, ui
 int32_t qmx_multi_search_topk(qmx_query *inner, const uint32_t *query_first, uint32_t n_queries, const uint64_t *point_offsets, uint32_t n_points,
                               const uint64_t *point_deleted, uint64_t n_deleted_bits, uint32_t top, const uint32_t *ids, uint64_t n_ids,
                               qmx_scored_point *out, uint32_t *out_counts) {
+    QMX_REFUSE_SPARSE(inner);
     QMX_REQUIRE(inner && query_first && point_offsets && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     QMX_HIP(hipSetDevice(inner->device));
@@ -235,6 +241,7 @@ static int32_t multi_custom_prepare(qmx_query *inner, const uint32_t *example_fi
 
 int32_t qmx_multi_custom_score_points(qmx_query *inner, const uint32_t *example_first, uint32_t n_examples, const qmx_custom_query *queries, uint32_t n_queries,
                                       const uint64_t *point_offsets, uint32_t n_points, const uint32_t *ids, uint32_t n, float *scores) {
+    QMX_REFUSE_SPARSE(inner);
     QMX_REQUIRE(inner && example_first && point_offsets && (n_queries == 0 || queries) && (n == 0 || (ids && scores)), QMX_ERR_BAD_ARG, "NULL argument");
     QMX_HIP(hipSetDevice(inner->device));
     if (n == 0 || n_queries == 0) return QMX_OK;
@@ -248,6 +255,7 @@ int32_t qmx_multi_custom_score_points(qmx_query *inner, const uint32_t *example_
 int32_t qmx_multi_custom_search_topk(qmx_query *inner, const uint32_t *example_first, uint32_t n_examples, const qmx_custom_query *queries, uint32_t n_queries,
                                      const uint64_t *point_offsets, uint32_t n_points, const uint64_t *point_deleted, uint64_t n_deleted_bits, uint32_t top,
                                      const uint32_t *ids, uint64_t n_ids, qmx_scored_point *out, uint32_t *out_counts) {
+    QMX_REFUSE_SPARSE(inner);
     QMX_REQUIRE(inner && example_first && point_offsets && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     QMX_HIP(hipSetDevice(inner->device));
@@ -287,6 +295,7 @@ int32_t qmx_multi_custom_search_topk(qmx_query *inner, const uint32_t *example_f
 int32_t qmx_multi_custom_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const uint32_t *example_first, uint32_t n_examples, const qmx_custom_query *queries,
                                      uint32_t n_queries, const uint64_t *point_offsets, uint32_t n_points, const uint64_t *point_deleted, uint64_t n_deleted_bits,
                                      uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts, qmx_counters *counters) {
+    QMX_REFUSE_SPARSE(inner);
     QMX_REQUIRE(g && inner && example_first && point_offsets && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     const qmx_segment *s = inner->seg;
     QMX_REQUIRE(g->device == s->device, QMX_ERR_BAD_ARG, "graph lives on device %d, the segment on %d", g->device, s->device);

@@ -275,12 +275,15 @@ int32_t qmx_hnsw_export_plain(const qmx_hnsw *g, uint32_t *reindex, uint64_t *le
 }
 
 int32_t qmx_hnsw_build(const qmx_segment *seg, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
+    QMX_REFUSE_SPARSE(seg);
     return qmx_hnsw_build_quantized(seg, nullptr, bp, out);
 }
 
 static int32_t hnsw_build_impl(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, qmx_hnsw **out, const MultiBuild *mb);
 
 int32_t qmx_hnsw_build_quantized(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
+    QMX_REFUSE_SPARSE(seg);
+    QMX_REFUSE_SPARSE(original);
     return hnsw_build_impl(seg, original, bp, out, nullptr);
 }
 
@@ -290,6 +293,10 @@ static int32_t sharded_hnsw_build_body(const qmx_segment *const *segments, const
                                        const qmx_hnsw_build_params *bp, qmx_hnsw **out_graphs, int32_t *out_status);
 int32_t qmx_sharded_hnsw_build(const qmx_segment *const *segments, const qmx_segment *const *originals, uint32_t n_segments,
                                const qmx_hnsw_build_params *bp, qmx_hnsw **out_graphs, int32_t *out_status) {
+    for (uint32_t i = 0; segments && i < n_segments; ++i) {
+        QMX_REFUSE_SPARSE(segments[i]);
+        if (originals) QMX_REFUSE_SPARSE(originals[i]);
+    }
     try {
         return sharded_hnsw_build_body(segments, originals, n_segments, bp, out_graphs, out_status);
     } catch (...) {         // nothing C++ crosses the C ABI
@@ -363,6 +370,8 @@ static int32_t sharded_hnsw_build_body(const qmx_segment *const *segments, const
 
 int32_t qmx_multi_hnsw_build_quantized(const qmx_segment *inner, const qmx_segment *original_inner, const uint64_t *point_offsets, uint32_t n_points,
                                        const uint64_t *point_deleted, uint64_t n_deleted_bits, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
+    QMX_REFUSE_SPARSE(inner);
+    QMX_REFUSE_SPARSE(original_inner);
     QMX_REQUIRE(inner && point_offsets && bp && out, QMX_ERR_BAD_ARG, "NULL argument");
     *out = nullptr;
     QMX_REQUIRE(inner->dtype == QMX_DTYPE_F32 || inner->dtype == QMX_DTYPE_F16 || inner->dtype == QMX_DTYPE_SQ_U8 || inner->dtype == QMX_DTYPE_BQ ||
@@ -379,6 +388,7 @@ int32_t qmx_multi_hnsw_build_quantized(const qmx_segment *inner, const qmx_segme
 }
 int32_t qmx_multi_hnsw_build(const qmx_segment *inner, const uint64_t *point_offsets, uint32_t n_points, const uint64_t *point_deleted,
                              uint64_t n_deleted_bits, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
+    QMX_REFUSE_SPARSE(inner);
     return qmx_multi_hnsw_build_quantized(inner, nullptr, point_offsets, n_points, point_deleted, n_deleted_bits, bp, out);
 }
 
@@ -1045,15 +1055,18 @@ int32_t hnsw_search_sync(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t
 
 int32_t qmx_hnsw_search(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts,
                         const volatile uint8_t *is_stopped, qmx_counters *counters) {
+    QMX_REFUSE_SPARSE(q);
     return hnsw_search_sync(g, q, top, ef, out, out_counts, is_stopped, counters, false);
 }
 int32_t qmx_hnsw_search_acorn(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts,
                               const volatile uint8_t *is_stopped, qmx_counters *counters) {
+    QMX_REFUSE_SPARSE(q);
     return hnsw_search_sync(g, q, top, ef, out, out_counts, is_stopped, counters, true);
 }
 
 int32_t qmx_hnsw_search_traced(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts,
                                qmx_scored_point *pops, uint32_t pop_cap, uint32_t *pop_counts) {
+    QMX_REFUSE_SPARSE(q);
     QMX_REQUIRE(g && q && out && out_counts && pops && pop_counts && pop_cap >= 1, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(!is_device_ptr(out) && !is_device_ptr(out_counts) && !is_device_ptr(pops) && !is_device_ptr(pop_counts), QMX_ERR_BAD_ARG,
                 "qmx_hnsw_search_traced writes host arrays");
@@ -1078,6 +1091,7 @@ int32_t qmx_hnsw_search_traced(const qmx_hnsw *g, qmx_query *q, uint32_t top, ui
 
 int32_t qmx_hnsw_search_async(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out_dev,
                               uint32_t *out_counts_dev, uint32_t *out_scored_dev) {
+    QMX_REFUSE_SPARSE(q);
     QMX_REQUIRE(g && q && out_dev && out_counts_dev, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_TRY(hnsw_check(g, q, top, ef));
     QMX_HIP(hipSetDevice(q->device));
@@ -1092,6 +1106,8 @@ int32_t qmx_hnsw_search_async(const qmx_hnsw *g, qmx_query *q, uint32_t top, uin
 
 int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_query *base, uint32_t top, uint32_t ef, qmx_scored_point *out,
                                      uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
+    QMX_REFUSE_SPARSE(links);
+    QMX_REFUSE_SPARSE(base);
     QMX_REQUIRE(g && links && base && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(base->nq == links->nq && base->device == links->device, QMX_ERR_BAD_ARG, "the two query batches must match");
     QMX_REQUIRE(base->seg->n >= g->n_points, QMX_ERR_OUT_OF_BOUNDS, "graph has %u points, the base-vector segment %llu rows", g->n_points,
@@ -1162,6 +1178,7 @@ int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_qu
 int32_t qmx_multi_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const uint32_t *query_first, uint32_t n_queries, const uint64_t *point_offsets,
                               uint32_t n_points, const uint64_t *point_deleted, uint64_t n_deleted_bits, uint32_t top, uint32_t ef,
                               qmx_scored_point *out, uint32_t *out_counts, qmx_counters *counters) {
+    QMX_REFUSE_SPARSE(inner);
     QMX_REQUIRE(g && inner && query_first && point_offsets && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     const qmx_segment *s = inner->seg;
     QMX_REQUIRE(g->device == s->device, QMX_ERR_BAD_ARG, "graph lives on device %d, the segment on %d", g->device, s->device);

@@ -59,6 +59,8 @@ inline uint64_t next_segment_uid() {
     static std::atomic<uint64_t> counter{0};
     return ++counter;
 }
+struct SparseSeg;     // QMX_DTYPE_SPARSE: rows, posting layout, dimension directory (api_sparse.hip)
+struct SparseQuery;   // ... a batch of sparse queries and their posting plan
 struct qmx_segment {
     const uint64_t uid = next_segment_uid();      // never reused: what a cache keyed by a segment compares (a freed segment's address may come back)
     int device = 0;
@@ -113,6 +115,7 @@ struct qmx_segment {
     bool auto_choice = false;         // QMX_SEG_AUTO_COPY: the copy was chosen by the trial of segment_auto_copy; what it measured:
     float auto_i8_ms = 0.0f, auto_half_ms = 0.0f, auto_i8_verified = 0.0f;
     uint32_t auto_i8_fallback = 0;
+    SparseSeg *sparse = nullptr;      // QMX_DTYPE_SPARSE only
 
     bool fast_layout() const {
         if (dtype == QMX_DTYPE_BQ || dtype == QMX_DTYPE_TQ) return row_stride % 16 == 0 && ((uintptr_t)d_rows % 16) == 0;
@@ -193,7 +196,21 @@ struct qmx_query {
     uint32_t partial_grid_cap = 0;
     bool timing = false;
     const void *last_kernel = nullptr;   // host handle of the last top-k scan / graph walk kernel launched for this batch
+    SparseQuery *sparse = nullptr;       // a batch over a QMX_DTYPE_SPARSE segment (qmx_sparse_query_create / qmx_query_create_internal)
 };
+
+// QMX_DTYPE_SPARSE is served by the entry points include/qdrant_amd.h lists; every other one refuses it
+static inline bool is_sparse(const qmx_segment *s) { return s && s->dtype == QMX_DTYPE_SPARSE; }
+static inline bool is_sparse(const qmx_query *q) { return q && is_sparse(q->seg); }
+static inline int32_t refuse_sparse(const char *fn) {
+    set_error("%s: not supported on a sparse segment (QMX_DTYPE_SPARSE)", fn);
+    return QMX_ERR_NOT_SUPPORTED;
+}
+#define QMX_REFUSE_SPARSE(x)                                 \
+    do {                                                     \
+        if (is_sparse(x)) return refuse_sparse(__func__);    \
+    } while (0)
+
 
 // f32 dot / cosine rows of >= 32 elements scan 8..32 queries per pass on the f32 matrix cores (scan_mfma.hip)
 static bool mfma_scan_ok(const qmx_segment *s) {
@@ -439,3 +456,12 @@ int32_t fold_split_counters(qmx_query *q, qmx_counters *c);
 TqRotationHost tq_rotation(const qmx_segment *s);
 TqRotationHost tq_rotation_inverse(const qmx_segment *s);
 }
+// sparse vectors (api_sparse.hip)
+void sparse_segment_free(qmx_segment *s);
+void sparse_query_free(qmx_query *q);
+int32_t sparse_query_create_internal(const qmx_segment *seg, const uint32_t *point_ids, uint32_t nq, qmx_query **out);
+int32_t sparse_score_matrix(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride);
+int32_t sparse_score_pairs(qmx_query *q, const PairSel &sel, const uint32_t *d_ids, uint64_t n_items, float *d_scores);
+int32_t sparse_score_internal(const qmx_segment *seg, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t n, float *out);
+int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64_t n_ids, qmx_scored_point *d_out, uint32_t *d_counts,
+                              const volatile uint8_t *is_stopped, qmx_counters *counters, bool timed);

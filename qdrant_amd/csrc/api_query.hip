@@ -99,6 +99,7 @@ static int32_t query_encode(qmx_query *q, const float *queries) {
 int32_t qmx_query_create(const qmx_segment *seg, const float *queries, uint32_t nq, qmx_query **out) {
     QMX_REQUIRE(seg && out && (nq == 0 || queries), QMX_ERR_BAD_ARG, "NULL argument");
     *out = nullptr;
+    QMX_REFUSE_SPARSE(seg);      // (dense floats: a sparse batch comes from qmx_sparse_query_create)
     QMX_HIP(hipSetDevice(seg->device));
     qmx_query *q = nullptr;
     QMX_TRY(query_alloc(seg, nq, &q));
@@ -117,6 +118,7 @@ int32_t qmx_query_create(const qmx_segment *seg, const float *queries, uint32_t 
 
 int32_t qmx_query_update(qmx_query *q, const float *queries) {
     QMX_REQUIRE(q && (q->nq == 0 || queries), QMX_ERR_BAD_ARG, "NULL argument");
+    QMX_REFUSE_SPARSE(q);
     QMX_HIP(hipSetDevice(q->seg->device));
     return query_encode(q, queries);
 }
@@ -125,6 +127,7 @@ int32_t qmx_query_create_internal(const qmx_segment *seg, const uint32_t *point_
     QMX_REQUIRE(seg && out && (nq == 0 || point_ids), QMX_ERR_BAD_ARG, "NULL argument");
     *out = nullptr;
     QMX_HIP(hipSetDevice(seg->device));
+    if (is_sparse(seg)) return sparse_query_create_internal(seg, point_ids, nq, out);
     QMX_REQUIRE(seg->dtype <= QMX_DTYPE_SQ_U8 || seg->dtype == QMX_DTYPE_BQ, QMX_ERR_NOT_SUPPORTED,
                 "dtype %u has no internal encoding (EncodedVectorsPQ::encode_internal_vector returns None): pass the original vector to qmx_query_create",
                 seg->dtype);
@@ -204,6 +207,7 @@ int32_t qmx_query_destroy(qmx_query *q) {
         if (p.a) (void)hipEventDestroy(p.a);
         if (p.b) (void)hipEventDestroy(p.b);
     }
+    sparse_query_free(q);
     if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
     delete q;
     return QMX_OK;
@@ -274,6 +278,7 @@ int32_t qmx_query_synchronize(qmx_query *q) {
 int32_t qmx_query_read_encoded(const qmx_query *q, uint32_t query_index, void *out, uint64_t out_bytes, uint64_t *written) {
     QMX_REQUIRE(q && out, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(query_index < q->nq, QMX_ERR_OUT_OF_BOUNDS, "query index %u >= %u", query_index, q->nq);
+    QMX_REFUSE_SPARSE(q);
     QMX_HIP(hipSetDevice(q->seg->device));
     const bool sq = q->seg->dtype == QMX_DTYPE_SQ_U8;
     const uint64_t ebytes = q->seg->dtype == QMX_DTYPE_PQ ? (uint64_t)q->seg->pq_m * q->seg->pq.n_centroids * sizeof(float)
@@ -399,6 +404,10 @@ int32_t tq_l1_scores_device(qmx_query *q, uint32_t q0, uint32_t nq, const uint32
 int32_t score_matrix_enqueue(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride,
                                     uint32_t *launches) {
     const qmx_segment *s = q->seg;
+    if (is_sparse(s)) {
+        if (launches) ++*launches;
+        return sparse_score_matrix(q, tile0, nq_tile, d_ids, n, d_scores, stride);
+    }
     if (tq_l1(s)) {
         if (launches) *launches += 3 * (uint32_t)((n + 65535) / 65536);
         return tq_l1_scores_device(const_cast<qmx_query *>(q), tile0, nq_tile, d_ids, n, d_scores, stride, nullptr);
@@ -491,6 +500,8 @@ int32_t score_pairs_device(qmx_query *q, const PairSel &sel, const uint32_t *d_i
         rc = launch_pairs_tq(q->stream, a, sel, n_items, s->num_cus);
     } else if (s->dtype == QMX_DTYPE_BQ) {
         rc = launch_pairs_bq(q->stream, a, sel, n_items, s->num_cus);
+    } else if (is_sparse(s)) {
+        rc = sparse_score_pairs(q, sel, d_ids, n_items, d_scores);
     } else {
         set_error("dtype %u not built yet", s->dtype);
         rc = QMX_ERR_NOT_SUPPORTED;
@@ -542,6 +553,7 @@ int32_t qmx_rescore(qmx_query *q, const uint32_t *ids, const uint32_t *counts, u
                     qmx_scored_point *out, uint32_t *out_counts) {
     QMX_REQUIRE(q && ids && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
+    QMX_REFUSE_SPARSE(q);
     QMX_HIP(hipSetDevice(q->device));
     if (q->nq == 0) return QMX_OK;
     if (n_per_query == 0) {
@@ -572,6 +584,7 @@ int32_t qmx_rescore(qmx_query *q, const uint32_t *ids, const uint32_t *counts, u
 int32_t qmx_score_internal(const qmx_segment *seg, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t n, float *out) {
     QMX_REQUIRE(seg && (n == 0 || (a_ids && b_ids && out)), QMX_ERR_BAD_ARG, "NULL argument");
     if (n == 0) return QMX_OK;
+    if (is_sparse(seg)) return sparse_score_internal(seg, a_ids, b_ids, n, out);
     if (seg->dtype == QMX_DTYPE_PQ || seg->dtype == QMX_DTYPE_TQ) {   // centroid <-> centroid (encoded_vectors_pq.rs:574-618 | TurboQuantizer::score_symmetric); no query involved
         QMX_HIP(hipSetDevice(seg->device));
         DevBuf ba, bb, bo, be;
@@ -650,6 +663,7 @@ int32_t qmx_score_internal(const qmx_segment *seg, const uint32_t *a_ids, const 
 
 int32_t qmx_score_bytes(qmx_query *q, const void *rows, uint32_t n, uint64_t stride_bytes, float *scores) {
     QMX_REQUIRE(q && (n == 0 || (rows && scores)), QMX_ERR_BAD_ARG, "NULL argument");
+    QMX_REFUSE_SPARSE(q);        // (the reference has no byte scoring for sparse vectors either)
     QMX_HIP(hipSetDevice(q->device));
     if (n == 0 || q->nq == 0) return QMX_OK;
     const qmx_segment *s = q->seg;

@@ -317,6 +317,7 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
                               qmx_scored_point *d_out, uint32_t *d_counts, const volatile uint8_t *is_stopped,
                               qmx_counters *counters, bool timed) {
     const qmx_segment *s = q->seg;
+    if (is_sparse(s)) return sparse_search_enqueue(q, top, d_ids, n_ids, d_out, d_counts, is_stopped, counters, timed);
     const uint64_t n_cand = d_ids ? n_ids : s->scan_rows();
     if (tq_l1(s)) {     // the score matrix (tiles of queries: at most 256 MiB of scores at a time), then one block per query selects its k best live candidates
         q->last_counters = qmx_counters{};
@@ -674,6 +675,17 @@ int32_t fold_split_counters(qmx_query *q, qmx_counters *c) {
 int32_t qmx_search_topk(qmx_query *q, uint32_t top, const uint32_t *ids, uint64_t n_ids, qmx_scored_point *out,
                         uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
     QMX_REQUIRE(q && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
+    if (top == 0 && is_sparse(q)) {     // the sparse search returns an empty list for top 0 (TopK, lib/common/common/src/top_k.rs)
+        if (counters) memset(counters, 0, sizeof(*counters));
+        QMX_HIP(hipSetDevice(q->device));
+        if (is_device_ptr(out_counts)) {
+            QMX_HIP(hipMemsetAsync(out_counts, 0, (size_t)q->nq * 4, q->stream));
+            QMX_HIP(hipStreamSynchronize(q->stream));
+        } else {
+            for (uint32_t i = 0; i < q->nq; ++i) out_counts[i] = 0;
+        }
+        return QMX_OK;
+    }
     QMX_REQUIRE(top >= 1, QMX_ERR_BAD_ARG, "top must be > 0 (FixedLengthPriorityQueue::new panics on 0)");
     QMX_REQUIRE(top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u > %u not supported yet", top, MAX_TOP);
     QMX_HIP(hipSetDevice(q->seg->device));
@@ -808,6 +820,8 @@ int32_t qmx_merge_topk_packed_async(int32_t device_id, void *hip_stream, const v
 int32_t qmx_search_quantized(const qmx_hnsw *g, qmx_query *quantized, qmx_query *raw, const qmx_search_params *p, const uint32_t *ids,
                              uint64_t n_ids, qmx_scored_point *out, uint32_t *out_counts, const volatile uint8_t *is_stopped,
                              qmx_counters *counters) {
+    QMX_REFUSE_SPARSE(quantized);
+    QMX_REFUSE_SPARSE(raw);
     QMX_REQUIRE(quantized && p && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(p->top >= 1, QMX_ERR_BAD_ARG, "top must be > 0");
     const bool rescore = p->rescore != 0;

@@ -30,6 +30,7 @@ static void segment_free(qmx_segment *seg) {
     if (seg->d_tq_tables) (void)hipFree(seg->d_tq_tables);
     if (seg->d_tq_l1) (void)hipFree(seg->d_tq_l1);
     if (seg->d_tq_norms) (void)hipFree(seg->d_tq_norms);
+    sparse_segment_free(seg);
     delete seg;
 }
 
@@ -859,12 +860,14 @@ int32_t qmx_segment_set_deleted(qmx_segment *seg, const uint64_t *point_deleted,
 }
 
 int32_t qmx_segment_row_bytes(const qmx_segment *seg, uint64_t *out) {
+    QMX_REFUSE_SPARSE(seg);
     QMX_REQUIRE(seg && out, QMX_ERR_BAD_ARG, "NULL argument");
     *out = seg->row_bytes;
     return QMX_OK;
 }
 
 int32_t qmx_segment_get_info(const qmx_segment *seg, qmx_segment_info *out) {
+    QMX_REFUSE_SPARSE(seg);
     QMX_REQUIRE(seg && out, QMX_ERR_BAD_ARG, "NULL argument");
     memset(out, 0, sizeof(*out));
     out->derived_copy = !seg->d_rows_split ? 0u : seg->split_i8 ? QMX_SEG_I8_COPY : seg->split_half ? QMX_SEG_HALF_COPY : QMX_SEG_SPLIT_COPY;
@@ -879,6 +882,7 @@ int32_t qmx_segment_get_info(const qmx_segment *seg, qmx_segment_info *out) {
 }
 
 int32_t qmx_segment_read_rows(const qmx_segment *seg, const uint32_t *ids, uint32_t n, void *out_rows) {
+    QMX_REFUSE_SPARSE(seg);
     QMX_REQUIRE(seg && (n == 0 || (ids && out_rows)), QMX_ERR_BAD_ARG, "NULL argument");
     QMX_HIP(hipSetDevice(seg->device));
     if (seg->dtype == QMX_DTYPE_SQ_U8) {

@@ -139,22 +139,26 @@ static int32_t sharded_sync(qmx_query *const *queries, const qmx_hnsw *const *gr
 
 int32_t qmx_sharded_search_topk(qmx_query *const *queries, uint32_t n_segments, uint32_t top, const uint32_t *id_bases, qmx_scored_point *out,
                                 uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
+    for (uint32_t i = 0; queries && i < n_segments; ++i) QMX_REFUSE_SPARSE(queries[i]);
     return sharded_sync(queries, nullptr, n_segments, top, 0, id_bases, out, out_counts, is_stopped, counters);
 }
 int32_t qmx_sharded_hnsw_search(const qmx_hnsw *const *graphs, qmx_query *const *queries, uint32_t n_segments, uint32_t top, uint32_t ef,
                                 const uint32_t *id_bases, qmx_scored_point *out, uint32_t *out_counts, const volatile uint8_t *is_stopped,
                                 qmx_counters *counters) {
+    for (uint32_t i = 0; queries && i < n_segments; ++i) QMX_REFUSE_SPARSE(queries[i]);
     QMX_REQUIRE(graphs, QMX_ERR_BAD_ARG, "NULL argument");
     return sharded_sync(queries, graphs, n_segments, top, ef, id_bases, out, out_counts, is_stopped, counters);
 }
 int32_t qmx_sharded_search_topk_async(qmx_query *const *queries, uint32_t n_segments, uint32_t top, const uint32_t *id_bases, qmx_scored_point *out_dev,
                                       uint32_t *out_counts_dev) {
+    for (uint32_t i = 0; queries && i < n_segments; ++i) QMX_REFUSE_SPARSE(queries[i]);
     QMX_REQUIRE(queries && n_segments >= 1 && queries[0] && out_dev && out_counts_dev, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     if (queries[0]->nq == 0) return QMX_OK;
     return sharded_enqueue(queries, nullptr, n_segments, top, 0, id_bases, out_dev, out_counts_dev, nullptr, nullptr);
 }
 int32_t qmx_sharded_query_update(qmx_query *const *queries, uint32_t n_segments, const float *batch) {
+    for (uint32_t i = 0; queries && i < n_segments; ++i) QMX_REFUSE_SPARSE(queries[i]);
     QMX_REQUIRE(queries && n_segments >= 1 && batch, QMX_ERR_BAD_ARG, "NULL argument");
     for (uint32_t i = 0; i < n_segments; ++i) {
         QMX_REQUIRE(queries[i], QMX_ERR_BAD_ARG, "segment %u: NULL batch", i);

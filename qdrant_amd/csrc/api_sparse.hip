@@ -1,0 +1,415 @@
+// api_sparse.hip — the C-ABI of include/qdrant_amd.h, sparse vectors (QMX_DTYPE_SPARSE): segment and query creation, and the sparse arms of
+// score_points / score_internal / search_topk that api_query.hip and api_search.hip dispatch to.  The kernels are in sparse.hip.
+// (One of the api_*.hip translation units; what they share: api_internal.hpp.)
+#include "api_internal.hpp"
+
+// the segment: CSR rows sorted by (remapped) index, the dimension-major posting layout, and on the host the row offsets, the directory of the
+// posting layout (distinct dimensions ascending, where each one's postings start) and the IndicesTracker map
+struct SparseSeg {
+    uint64_t nnz = 0;
+    uint64_t *d_off = nullptr;
+    uint32_t *d_idx = nullptr;
+    float *d_val = nullptr;
+    uint64_t *d_post = nullptr;              // [nnz]: (f32 weight bits << 32) | point id, grouped by dimension, ids ascending
+    std::vector<uint64_t> h_off;             // [n + 1]
+    std::vector<uint32_t> dir_dims;          // [D]
+    std::vector<uint64_t> dir_start;         // [D + 1]
+    std::vector<uint32_t> map_keys, map_vals;   // sorted by key; empty = identity
+    bool has_map = false;
+};
+
+// a query batch: CSR lists sorted by (remapped) index, and the posting plan of every query (its dimensions that have postings, ascending)
+struct SparseQuery {
+    uint64_t *d_off = nullptr;
+    uint32_t *d_idx = nullptr;
+    float *d_val = nullptr;
+    uint32_t *d_poff = nullptr;
+    uint64_t *d_pstart = nullptr, *d_pend = nullptr;
+    float *d_pw = nullptr;
+    uint64_t posting_entries = 0;            // sum over the queries of the posting lengths of their dimensions
+};
+
+static SparseRows rows_of(const qmx_segment *s) {
+    const SparseSeg *sp = s->sparse;
+    return SparseRows{sp->d_off, sp->d_idx, sp->d_val, s->n};
+}
+static SparseQueries queries_of(const qmx_query *q) {
+    const SparseQuery *sq = q->sparse;
+    return SparseQueries{sq->d_off, sq->d_idx, sq->d_val};
+}
+
+void sparse_segment_free(qmx_segment *s) {
+    SparseSeg *sp = s->sparse;
+    if (!sp) return;
+    if (sp->d_off) (void)hipFree(sp->d_off);
+    if (sp->d_idx) (void)hipFree(sp->d_idx);
+    if (sp->d_val) (void)hipFree(sp->d_val);
+    if (sp->d_post) (void)hipFree(sp->d_post);
+    delete sp;
+    s->sparse = nullptr;
+}
+
+void sparse_query_free(qmx_query *q) {
+    SparseQuery *sq = q->sparse;
+    if (!sq) return;
+    for (void *p : {(void *)sq->d_off, (void *)sq->d_idx, (void *)sq->d_val, (void *)sq->d_poff, (void *)sq->d_pstart, (void *)sq->d_pend, (void *)sq->d_pw})
+        if (p) (void)hipFree(p);
+    delete sq;
+    q->sparse = nullptr;
+}
+
+template <typename T>
+static int32_t upload(T **dst, const T *src, size_t count) {
+    QMX_HIP(hipMalloc((void **)dst, std::max<size_t>(count, 1) * sizeof(T)));
+    if (count) QMX_HIP(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyDefault));
+    return QMX_OK;
+}
+
+// (index, value) pairs of one vector sorted by index; false on a duplicate index (validate_sparse_vector_impl, sparse_vector.rs:302-323)
+static bool sort_pairs(std::vector<std::pair<uint32_t, float>> &v) {
+    std::sort(v.begin(), v.end(), [](const std::pair<uint32_t, float> &a, const std::pair<uint32_t, float> &b) { return a.first < b.first; });
+    for (size_t i = 1; i < v.size(); ++i)
+        if (v[i - 1].first == v[i].first) return false;
+    return true;
+}
+
+// the batch's device arrays from host CSR lists that are sorted and remapped already, and the posting plan from the segment's directory
+static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, const std::vector<uint32_t> &idx, const std::vector<float> &val) {
+    const SparseSeg *sp = q->seg->sparse;
+    SparseQuery *sq = q->sparse;
+    std::vector<uint32_t> poff(q->nq + 1, 0);
+    std::vector<uint64_t> pstart, pend;
+    std::vector<float> pw;
+    for (uint32_t qi = 0; qi < q->nq; ++qi) {
+        for (uint64_t k = off[qi]; k < off[qi + 1]; ++k) {
+            auto it = std::lower_bound(sp->dir_dims.begin(), sp->dir_dims.end(), idx[k]);
+            if (it == sp->dir_dims.end() || *it != idx[k]) continue;      // no stored point has this dimension
+            const size_t d = (size_t)(it - sp->dir_dims.begin());
+            pstart.push_back(sp->dir_start[d]);
+            pend.push_back(sp->dir_start[d + 1]);
+            pw.push_back(val[k]);
+            sq->posting_entries += sp->dir_start[d + 1] - sp->dir_start[d];
+        }
+        poff[qi + 1] = (uint32_t)pstart.size();
+    }
+    QMX_TRY(upload(&sq->d_off, off.data(), off.size()));
+    QMX_TRY(upload(&sq->d_idx, idx.data(), idx.size()));
+    QMX_TRY(upload(&sq->d_val, val.data(), val.size()));
+    QMX_TRY(upload(&sq->d_poff, poff.data(), poff.size()));
+    QMX_TRY(upload(&sq->d_pstart, pstart.data(), pstart.size()));
+    QMX_TRY(upload(&sq->d_pend, pend.data(), pend.size()));
+    QMX_TRY(upload(&sq->d_pw, pw.data(), pw.size()));
+    return QMX_OK;
+}
+
+static int32_t sparse_query_alloc(const qmx_segment *seg, uint32_t nq, qmx_query **out) {
+    qmx_query *q = new (std::nothrow) qmx_query();
+    QMX_REQUIRE(q, QMX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    q->seg = seg;
+    q->device = seg->device;
+    q->nq = nq;
+    q->nq_padded = nq;
+    q->sparse = new (std::nothrow) SparseQuery();
+    hipError_t e = q->sparse ? hipStreamCreateWithFlags(&q->own_stream, hipStreamNonBlocking) : hipErrorOutOfMemory;
+    if (e == hipSuccess) {
+        q->stream = q->own_stream;
+        e = hipMalloc((void **)&q->d_err, sizeof(int));
+    }
+    if (e == hipSuccess) e = hipMemset(q->d_err, 0, sizeof(int));
+    if (e != hipSuccess) {
+        const int32_t rc = hip_status(e, "sparse query allocation", __FILE__, __LINE__);
+        qmx_query_destroy(q);
+        return rc;
+    }
+    *out = q;
+    return QMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the sparse arms of the shared entry points
+// ---------------------------------------------------------------------------------------------
+int32_t sparse_query_create_internal(const qmx_segment *seg, const uint32_t *point_ids, uint32_t nq, qmx_query **out) {
+    const SparseSeg *sp = seg->sparse;
+    std::vector<uint32_t> ids(nq);
+    if (nq) QMX_HIP(hipMemcpy(ids.data(), point_ids, (size_t)nq * 4, hipMemcpyDefault));
+    std::vector<uint64_t> off(nq + 1, 0);
+    for (uint32_t i = 0; i < nq; ++i) {
+        QMX_REQUIRE(ids[i] < seg->n, QMX_ERR_OUT_OF_BOUNDS, "point offset %u out of range for this segment (the reference panics here)", ids[i]);
+        off[i + 1] = off[i] + sp->h_off[ids[i] + 1] - sp->h_off[ids[i]];
+    }
+    // the stored rows ARE the queries (FilteredScorer::new_internal): already sorted and remapped
+    std::vector<uint32_t> idx(off[nq]);
+    std::vector<float> val(off[nq]);
+    for (uint32_t i = 0; i < nq; ++i) {
+        const uint64_t len = off[i + 1] - off[i], src = sp->h_off[ids[i]];
+        if (!len) continue;
+        QMX_HIP(hipMemcpy(idx.data() + off[i], sp->d_idx + src, len * 4, hipMemcpyDeviceToHost));
+        QMX_HIP(hipMemcpy(val.data() + off[i], sp->d_val + src, len * 4, hipMemcpyDeviceToHost));
+    }
+    qmx_query *q = nullptr;
+    QMX_TRY(sparse_query_alloc(seg, nq, &q));
+    const int32_t rc = query_finish(q, off, idx, val);
+    if (rc != QMX_OK) {
+        qmx_query_destroy(q);
+        return rc;
+    }
+    *out = q;
+    return QMX_OK;
+}
+
+int32_t sparse_score_matrix(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride) {
+    QMX_REQUIRE(q->sparse, QMX_ERR_NOT_SUPPORTED, "a sparse segment is scored with a sparse query batch (qmx_sparse_query_create)");
+    QMX_TRY(launch_sparse_score_matrix(q->stream, rows_of(q->seg), queries_of(q), tile0, nq_tile, d_ids, n, d_scores, stride, q->d_err));
+    const_cast<qmx_query *>(q)->last_kernel = last_noted_kernel();
+    return QMX_OK;
+}
+
+int32_t sparse_score_pairs(qmx_query *q, const PairSel &sel, const uint32_t *d_ids, uint64_t n_items, float *d_scores) {
+    QMX_REQUIRE(q->sparse, QMX_ERR_NOT_SUPPORTED, "a sparse segment is scored with a sparse query batch (qmx_sparse_query_create)");
+    QMX_TRY(launch_sparse_score_pairs(q->stream, rows_of(q->seg), queries_of(q), sel, d_ids, n_items, d_scores, q->d_err));
+    q->last_kernel = last_noted_kernel();
+    return QMX_OK;
+}
+
+int32_t sparse_score_internal(const qmx_segment *seg, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t n, float *out) {
+    QMX_HIP(hipSetDevice(seg->device));
+    DevBuf ba, bb, bo, be;
+    int32_t rc = QMX_OK;
+    do {
+        if ((rc = ba.reserve((size_t)n * 4)) != QMX_OK || (rc = bb.reserve((size_t)n * 4)) != QMX_OK || (rc = bo.reserve((size_t)n * 4)) != QMX_OK ||
+            (rc = be.reserve(4)) != QMX_OK)
+            break;
+        hipError_t e = hipMemcpy(ba.p, a_ids, (size_t)n * 4, hipMemcpyDefault);
+        if (e == hipSuccess) e = hipMemcpy(bb.p, b_ids, (size_t)n * 4, hipMemcpyDefault);
+        if (e == hipSuccess) e = hipMemset(be.p, 0, 4);
+        if (e != hipSuccess) { rc = hip_status(e, "stage ids", __FILE__, __LINE__); break; }
+        if ((rc = launch_sparse_score_internal(nullptr, rows_of(seg), (const uint32_t *)ba.p, (const uint32_t *)bb.p, n, (float *)bo.p, (int *)be.p)) != QMX_OK) break;
+        int flag = 0;
+        e = hipMemcpy(&flag, be.p, 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * 4, hipMemcpyDefault);
+        if (e != hipSuccess) { rc = hip_status(e, "copy scores", __FILE__, __LINE__); break; }
+        if (flag) { set_error("point offset out of range for this segment"); rc = QMX_ERR_OUT_OF_BOUNDS; }
+    } while (0);
+    ba.release(); bb.release(); bo.release(); be.release();
+    return rc;
+}
+
+// Nearest: the posting top-k over every point (sparse_topk_postings_kernel), or plain_search over an id list (sparse_topk_ids_kernel); both write
+// one key list of `top` (<= 64) per work-group and query, merged by launch_merge_keys.  top > 64 runs in passes of 64, each below the last key of
+// the pass before.  Queries go in tiles of 128 (the key lists of a tile: lists x 128 x 64 keys).
+int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64_t n_ids, qmx_scored_point *d_out, uint32_t *d_counts,
+                              const volatile uint8_t *is_stopped, qmx_counters *counters, bool timed) {
+    const qmx_segment *s = q->seg;
+    QMX_REQUIRE(q->sparse, QMX_ERR_NOT_SUPPORTED, "a sparse segment is searched with a sparse query batch (qmx_sparse_query_create)");
+    const SparseQuery *sq = q->sparse;
+    DeletedView del = s->deleted_view();
+    if (q->has_filter) {
+        del.allowed = (const uint64_t *)q->filter.p;
+        del.n_allowed_bits = q->n_filter_bits;
+    }
+    const uint64_t n_scan = s->scan_rows();
+    const uint32_t n_lists_max = d_ids ? sparse_ids_lists(n_ids) : (uint32_t)((n_scan + sparse_tile_ids() - 1) / sparse_tile_ids());
+    q->last_counters = qmx_counters{};
+    q->last_split = false;
+    if (n_lists_max == 0) {      // no rows: every list is empty
+        QMX_HIP(hipMemsetAsync(d_counts, 0, (size_t)q->nq * 4, q->stream));
+        if (counters) *counters = q->last_counters;
+        return QMX_OK;
+    }
+    const uint32_t QT = 128;
+    const uint32_t ptop_max = std::min<uint32_t>(top, MAX_TOP_FAST);
+    const uint32_t n_pass = (top + MAX_TOP_FAST - 1) / MAX_TOP_FAST;
+    QMX_TRY(q->partial.reserve((size_t)n_lists_max * std::min<uint32_t>(q->nq, QT) * ptop_max * sizeof(uint64_t)));
+    if (n_pass > 1) QMX_TRY(q->bounds.reserve((size_t)QT * sizeof(uint64_t)));
+    const SparsePlan plan{sq->d_poff, sq->d_pstart, sq->d_pend, sq->d_pw};
+    uint32_t launches = 0;
+    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += QT) {
+        const uint32_t nq_tile = std::min<uint32_t>(QT, q->nq - tile0);
+        for (uint32_t pass = 0; pass < n_pass; ++pass) {
+            if (is_stopped && *is_stopped) {
+                set_error("search cancelled");
+                return QMX_ERR_CANCELLED;
+            }
+            const uint32_t off = pass * MAX_TOP_FAST;
+            const uint32_t ptop = std::min<uint32_t>(MAX_TOP_FAST, top - off);
+            const uint64_t *bound = pass ? (const uint64_t *)q->bounds.p : nullptr;
+            uint32_t n_lists = 0;
+            size_t slot = 0;
+            if (timed) QMX_TRY(timing_begin(q, &slot));
+            if (d_ids)
+                QMX_TRY(launch_sparse_topk_ids(q->stream, rows_of(s), queries_of(q), tile0, nq_tile, d_ids, n_ids, del, ptop, bound, (uint64_t *)q->partial.p,
+                                               &n_lists));
+            else
+                QMX_TRY(launch_sparse_topk_postings(q->stream, s->sparse->d_post, plan, tile0, nq_tile, n_scan, del, ptop, bound, (uint64_t *)q->partial.p,
+                                                    &n_lists));
+            q->last_kernel = last_noted_kernel();
+            if (timed) QMX_TRY(timing_end(q, slot));
+            QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, n_lists, nq_tile, nq_tile, ptop, d_out + (size_t)tile0 * top,
+                                      d_counts + tile0, top, off, n_pass > 1 ? (uint64_t *)q->bounds.p : nullptr));
+            launches += 2;
+        }
+    }
+    qmx_counters &c = q->last_counters;
+    const uint64_t entries = d_ids ? (uint64_t)q->nq * n_ids : sq->posting_entries;
+    c.vectors_scored = entries * n_pass;
+    c.bytes_read = d_ids ? 0 : entries * 8 * n_pass;      // posting entries (id, weight); the id-list path reads rows of unknown length
+    c.kernel_launches = launches;
+    if (counters) *counters = c;
+    return QMX_OK;
+}
+
+extern "C" {
+
+int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment **out) {
+    QMX_REQUIRE(d && out, QMX_ERR_BAD_ARG, "NULL argument");
+    *out = nullptr;
+    QMX_REQUIRE(d->n <= 0xFFFFFFFFull, QMX_ERR_BAD_ARG, "PointOffsetType is u32: n=%llu too large", (unsigned long long)d->n);
+    QMX_REQUIRE(d->offsets || d->n == 0, QMX_ERR_BAD_ARG, "offsets is NULL");
+    QMX_REQUIRE((d->map_keys == nullptr) == (d->map_values == nullptr), QMX_ERR_BAD_ARG, "map_keys and map_values go together");
+    QMX_REQUIRE(d->flags == 0, QMX_ERR_BAD_ARG, "flags must be 0");
+    hipDeviceProp_t prop;
+    QMX_TRY(check_device(d->device_id, &prop));
+    std::vector<uint64_t> h_off(d->n + 1, 0);
+    if (d->offsets) QMX_HIP(hipMemcpy(h_off.data(), d->offsets, h_off.size() * 8, hipMemcpyDefault));
+    QMX_REQUIRE(h_off[0] == 0, QMX_ERR_BAD_ARG, "offsets[0] must be 0");
+    for (uint64_t i = 0; i < d->n; ++i)
+        QMX_REQUIRE(h_off[i] <= h_off[i + 1], QMX_ERR_BAD_ARG, "offsets must be non-decreasing (row %llu)", (unsigned long long)i);
+    const uint64_t nnz = h_off[d->n];
+    QMX_REQUIRE(nnz == 0 || (d->indices && d->values), QMX_ERR_BAD_ARG, "indices / values are NULL");
+    QMX_REQUIRE(nnz <= 0xFFFFFFFFull, QMX_ERR_NOT_SUPPORTED, "a sparse segment holds at most 2^32 - 1 non-zeros (got %llu)", (unsigned long long)nnz);
+
+    qmx_segment *s = new (std::nothrow) qmx_segment();
+    QMX_REQUIRE(s, QMX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    s->device = d->device_id;
+    s->num_cus = prop.multiProcessorCount;
+    s->dtype = QMX_DTYPE_SPARSE;
+    s->distance = QMX_DISTANCE_DOT;
+    s->n = d->n;
+    s->sparse = new (std::nothrow) SparseSeg();
+    SparseSeg *sp = s->sparse;
+    uint32_t *d_flag = nullptr, *d_keys = nullptr, *d_vals = nullptr, *d_dims = nullptr, *d_counts = nullptr;
+    int32_t rc = QMX_OK;
+    auto hip = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == QMX_OK) rc = hip_status(e, what, __FILE__, __LINE__);
+        return rc == QMX_OK;
+    };
+    do {
+        if (!sp) { set_error("host allocation failed"); rc = QMX_ERR_OUT_OF_MEMORY; break; }
+        sp->nnz = nnz;
+        sp->h_off = std::move(h_off);
+        if ((rc = upload(&sp->d_off, sp->h_off.data(), sp->h_off.size())) != QMX_OK) break;
+        if ((rc = upload(&sp->d_idx, d->indices, nnz)) != QMX_OK) break;
+        if ((rc = upload(&sp->d_val, d->values, nnz)) != QMX_OK) break;
+        if (!hip(hipMalloc((void **)&d_flag, 4), "hipMalloc(flag)") || !hip(hipMemset(d_flag, 0, 4), "hipMemset(flag)")) break;
+        if (d->map_keys) {      // IndicesTracker: every stored index is remapped, then every row re-sorted
+            std::vector<std::pair<uint32_t, uint32_t>> m(d->n_map);
+            std::vector<uint32_t> k(d->n_map), v(d->n_map);
+            if (d->n_map && (!hip(hipMemcpy(k.data(), d->map_keys, d->n_map * 4, hipMemcpyDefault), "map keys") ||
+                             !hip(hipMemcpy(v.data(), d->map_values, d->n_map * 4, hipMemcpyDefault), "map values")))
+                break;
+            for (uint64_t i = 0; i < d->n_map; ++i) m[i] = {k[i], v[i]};
+            std::sort(m.begin(), m.end());
+            bool dup = false;
+            for (uint64_t i = 1; i < d->n_map; ++i) dup = dup || m[i - 1].first == m[i].first;
+            if (dup) { set_error("the dimension map holds a key twice"); rc = QMX_ERR_BAD_ARG; break; }
+            sp->has_map = true;
+            for (auto &p : m) {
+                sp->map_keys.push_back(p.first);
+                sp->map_vals.push_back(p.second);
+            }
+            if ((rc = upload(&d_keys, sp->map_keys.data(), sp->map_keys.size())) != QMX_OK) break;
+            if ((rc = upload(&d_vals, sp->map_vals.data(), sp->map_vals.size())) != QMX_OK) break;
+            if ((rc = launch_sparse_remap(nullptr, sp->d_idx, nnz, d_keys, d_vals, d->n_map, d_flag)) != QMX_OK) break;
+            uint32_t missing = 0;
+            if (!hip(hipMemcpy(&missing, d_flag, 4, hipMemcpyDeviceToHost), "remap flag")) break;
+            if (missing) { set_error("a stored index is not in the dimension map"); rc = QMX_ERR_BAD_ARG; break; }
+        }
+        // sorted by index on the way in; duplicates refused
+        if ((rc = launch_sparse_check_rows(nullptr, sp->d_off, sp->d_idx, s->n, d_flag)) != QMX_OK) break;
+        uint32_t flags = 0;
+        if (!hip(hipMemcpy(&flags, d_flag, 4, hipMemcpyDeviceToHost), "row check")) break;
+        if (flags & 1u) {
+            if ((rc = launch_sparse_sort_rows(nullptr, sp->d_off, sp->d_idx, sp->d_val, s->n)) != QMX_OK) break;
+            if (!hip(hipMemset(d_flag, 0, 4), "hipMemset(flag)")) break;
+            if ((rc = launch_sparse_check_rows(nullptr, sp->d_off, sp->d_idx, s->n, d_flag)) != QMX_OK) break;
+            if (!hip(hipMemcpy(&flags, d_flag, 4, hipMemcpyDeviceToHost), "row check")) break;
+        }
+        if (flags & 2u) { set_error("a sparse vector holds an index twice"); rc = QMX_ERR_BAD_ARG; break; }
+        // the posting layout and its directory
+        if (!hip(hipMalloc((void **)&sp->d_post, std::max<uint64_t>(nnz, 1) * 8), "hipMalloc(postings)")) break;
+        if (!hip(hipMalloc((void **)&d_dims, std::max<uint64_t>(nnz, 1) * 4), "hipMalloc(dims)")) break;
+        if (!hip(hipMalloc((void **)&d_counts, std::max<uint64_t>(nnz, 1) * 4), "hipMalloc(counts)")) break;
+        if ((rc = sparse_build_postings(nullptr, sp->d_off, sp->d_idx, sp->d_val, s->n, nnz, sp->d_post, d_dims, d_counts, d_flag)) != QMX_OK) break;
+        uint32_t n_dims = 0;
+        if (!hip(hipMemcpy(&n_dims, d_flag, 4, hipMemcpyDeviceToHost), "directory size")) break;
+        sp->dir_dims.resize(n_dims);
+        std::vector<uint32_t> counts(n_dims);
+        if (n_dims && (!hip(hipMemcpy(sp->dir_dims.data(), d_dims, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "directory") ||
+                       !hip(hipMemcpy(counts.data(), d_counts, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "directory")))
+            break;
+        sp->dir_start.assign(n_dims + 1, 0);
+        for (uint32_t i = 0; i < n_dims; ++i) sp->dir_start[i + 1] = sp->dir_start[i] + counts[i];
+    } while (0);
+    for (void *p : {(void *)d_flag, (void *)d_keys, (void *)d_vals, (void *)d_dims, (void *)d_counts})
+        if (p) (void)hipFree(p);
+    if (rc != QMX_OK) {
+        qmx_segment_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return QMX_OK;
+}
+
+int32_t qmx_sparse_query_create(const qmx_segment *seg, const uint64_t *offsets, const uint32_t *indices, const float *values, uint32_t nq, qmx_query **out) {
+    QMX_REQUIRE(seg && out && (nq == 0 || offsets), QMX_ERR_BAD_ARG, "NULL argument");
+    *out = nullptr;
+    QMX_REQUIRE(is_sparse(seg), QMX_ERR_NOT_SUPPORTED, "qmx_sparse_query_create needs a sparse segment (qmx_sparse_segment_create)");
+    QMX_HIP(hipSetDevice(seg->device));
+    const SparseSeg *sp = seg->sparse;
+    std::vector<uint64_t> in_off(nq + 1, 0);
+    if (nq) QMX_HIP(hipMemcpy(in_off.data(), offsets, in_off.size() * 8, hipMemcpyDefault));
+    QMX_REQUIRE(in_off[0] == 0, QMX_ERR_BAD_ARG, "offsets[0] must be 0");
+    for (uint32_t i = 0; i < nq; ++i) QMX_REQUIRE(in_off[i] <= in_off[i + 1], QMX_ERR_BAD_ARG, "offsets must be non-decreasing (query %u)", i);
+    const uint64_t total = in_off[nq];
+    QMX_REQUIRE(total == 0 || (indices && values), QMX_ERR_BAD_ARG, "indices / values are NULL");
+    std::vector<uint32_t> in_idx(total);
+    std::vector<float> in_val(total);
+    if (total) {
+        QMX_HIP(hipMemcpy(in_idx.data(), indices, total * 4, hipMemcpyDefault));
+        QMX_HIP(hipMemcpy(in_val.data(), values, total * 4, hipMemcpyDefault));
+    }
+    std::vector<uint64_t> off(nq + 1, 0);
+    std::vector<uint32_t> idx;
+    std::vector<float> val;
+    std::vector<std::pair<uint32_t, float>> v;
+    for (uint32_t qi = 0; qi < nq; ++qi) {
+        v.clear();
+        for (uint64_t k = in_off[qi]; k < in_off[qi + 1]; ++k) v.push_back({in_idx[k], in_val[k]});
+        QMX_REQUIRE(sort_pairs(v), QMX_ERR_BAD_ARG, "query %u holds an index twice", qi);
+        if (sp->has_map) {      // remap_vector: dimensions the tracker does not know are dropped, the rest re-sorted
+            std::vector<std::pair<uint32_t, float>> r;
+            for (auto &p : v) {
+                auto it = std::lower_bound(sp->map_keys.begin(), sp->map_keys.end(), p.first);
+                if (it != sp->map_keys.end() && *it == p.first) r.push_back({sp->map_vals[(size_t)(it - sp->map_keys.begin())], p.second});
+            }
+            QMX_REQUIRE(sort_pairs(r), QMX_ERR_BAD_ARG, "query %u maps two indices to one", qi);
+            v.swap(r);
+        }
+        for (auto &p : v) {
+            idx.push_back(p.first);
+            val.push_back(p.second);
+        }
+        off[qi + 1] = idx.size();
+    }
+    qmx_query *q = nullptr;
+    QMX_TRY(sparse_query_alloc(seg, nq, &q));
+    const int32_t rc = query_finish(q, off, idx, val);
+    if (rc != QMX_OK) {
+        qmx_query_destroy(q);
+        return rc;
+    }
+    *out = q;
+    return QMX_OK;
+}
+
+}  // extern "C"

@@ -181,6 +181,16 @@ __device__ __forceinline__ void wave_list_insert(uint64_t &list, uint64_t nk, in
     uint64_t up = shfl_up1_u64(list);
     list = lane < p ? list : (lane == p ? nk : up);
 }
+// offer one key per lane to the wave's list of `top` (wave-uniform): the keys that beat the current last entry go in, in lane order
+__device__ __forceinline__ void wave_offer(uint64_t &list, uint64_t key, int top, int lane) {
+    uint64_t m = __ballot(key > readlane_u64(list, top - 1));
+    while (m) {
+        const int src = __builtin_ctzll(m);
+        m &= m - 1;
+        const uint64_t nk = readlane_u64(key, src);
+        if (nk > readlane_u64(list, top - 1)) wave_list_insert(list, nk, lane);
+    }
+}
 
 #endif  // __HIPCC__
 }  // namespace qmx

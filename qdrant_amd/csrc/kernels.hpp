@@ -479,4 +479,39 @@ int32_t launch_minmax_f32(hipStream_t st, const float *in, uint64_t count, float
 int32_t launch_gather_rows(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t row_bytes,
                            const uint32_t *ids, uint32_t n, uint64_t n_rows, void *out, int *err_flag);
 
+// sparse vectors (sparse.hip): CSR rows sorted by index, CSR query lists, and per query the posting ranges of its dimensions (ascending)
+struct SparseRows {
+    const uint64_t *off;
+    const uint32_t *idx;
+    const float *val;
+    uint64_t n;
+};
+struct SparseQueries {
+    const uint64_t *off;
+    const uint32_t *idx;
+    const float *val;
+};
+struct SparsePlan {
+    const uint32_t *off;      // [nq + 1]: query q's dimensions are entries off[q] .. off[q + 1]
+    const uint64_t *start;    // posting range of the dimension in the segment's posting layout
+    const uint64_t *end;
+    const float *w;           // the query's weight of the dimension
+};
+uint32_t sparse_tile_ids();
+uint32_t sparse_ids_lists(uint64_t n_ids);
+int32_t launch_sparse_check_rows(hipStream_t st, const uint64_t *offsets, const uint32_t *idx, uint64_t n, uint32_t *flags);
+int32_t launch_sparse_sort_rows(hipStream_t st, const uint64_t *offsets, uint32_t *idx, float *val, uint64_t n);
+int32_t launch_sparse_remap(hipStream_t st, uint32_t *idx, uint64_t nnz, const uint32_t *keys, const uint32_t *vals, uint64_t m, uint32_t *missing);
+int32_t sparse_build_postings(hipStream_t st, const uint64_t *offsets, const uint32_t *idx, const float *val, uint64_t n, uint64_t nnz, uint64_t *post,
+                              uint32_t *dims, uint32_t *counts, uint32_t *n_dims_dev);
+int32_t launch_sparse_score_matrix(hipStream_t st, const SparseRows &r, const SparseQueries &qs, uint32_t q0, uint32_t nq, const uint32_t *ids, uint64_t n,
+                                   float *scores, uint64_t stride, int *err);
+int32_t launch_sparse_score_pairs(hipStream_t st, const SparseRows &r, const SparseQueries &qs, const PairSel &sel, const uint32_t *ids, uint64_t n_items,
+                                  float *scores, int *err);
+int32_t launch_sparse_score_internal(hipStream_t st, const SparseRows &r, const uint32_t *a, const uint32_t *b, uint64_t n, float *out, int *err);
+int32_t launch_sparse_topk_postings(hipStream_t st, const uint64_t *post, const SparsePlan &plan, uint32_t q0, uint32_t nq_tile, uint64_t n_scan,
+                                    const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists);
+int32_t launch_sparse_topk_ids(hipStream_t st, const SparseRows &r, const SparseQueries &qs, uint32_t q0, uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids,
+                               const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists);
+
 }  // namespace qmx

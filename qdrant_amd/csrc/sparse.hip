@@ -1,0 +1,430 @@
+// sparse.hip — sparse vectors (QMX_DTYPE_SPARSE) on the device: the create-time preparation of a segment (row checks, row sort, remap,
+// the dimension-major posting layout), the gather scorer of RawScorer (`score_vectors`, lib/sparse/src/common/sparse_vector.rs:66-90)
+// and the posting-list top-k of Nearest search (the GPU form of `advance_batch`, lib/sparse/src/index/search_context.rs:146-187).
+//
+// Every score is the reference's sum: the products of the shared dimensions, each rounded (`__fmul_rn`), added in ascending dimension
+// order from 0.0, each add rounded (`__fadd_rn`).  No fused multiply-add, no atomics on scores.
+#include "kernels.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_run_length_encode.hpp>
+
+namespace qmx {
+
+constexpr int SP_BLOCK = 256;
+constexpr uint32_t SP_LDS_Q = 4096;           // query entries staged in LDS (32 KiB); longer queries are read from global memory
+constexpr uint32_t SPT_SUB = 2048;            // point ids per wave in the posting top-k
+constexpr uint32_t SPT_WAVES = SP_BLOCK / WAVE;
+constexpr uint32_t SPT_TILE = SPT_SUB * SPT_WAVES;   // ids per work-group: 32 KiB of accumulators + 1 KiB overlap bitmap
+constexpr uint32_t SPT_CHUNK = WAVE;          // query dimensions whose posting sub-ranges one wave finds at once (one per lane)
+
+uint32_t sparse_tile_ids() { return SPT_TILE; }
+
+// score_vectors: both lists ascending; *overlap = at least one shared dimension
+__device__ __forceinline__ float sparse_dot(const uint32_t *ai, const float *av, uint32_t na, const uint32_t *bi, const float *bv, uint32_t nb,
+                                            bool *overlap) {
+    float s = 0.0f;
+    bool ov = false;
+    uint32_t i = 0, j = 0;
+    while (i < na && j < nb) {
+        const uint32_t x = ai[i], y = bi[j];
+        if (x < y) {
+            ++i;
+        } else if (x > y) {
+            ++j;
+        } else {
+            s = __fadd_rn(s, __fmul_rn(av[i], bv[j]));
+            ov = true;
+            ++i;
+            ++j;
+        }
+    }
+    *overlap = ov;
+    return s;
+}
+
+// ---- create ----
+
+// flags bit 0: a row is not strictly ascending; bit 1: a row holds an index twice
+__global__ void sparse_check_rows_kernel(const uint64_t *offsets, const uint32_t *idx, uint64_t n, uint32_t *flags) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint64_t a = offsets[r], b = offsets[r + 1];
+    uint32_t f = 0;
+    for (uint64_t i = a + 1; i < b; ++i) {
+        const uint32_t x = idx[i - 1], y = idx[i];
+        if (x > y) f |= 1u;
+        if (x == y) f |= 2u;
+    }
+    if (f) atomicOr(flags, f);
+}
+
+// insertion sort of each unsorted row by index, values along (rows are short: ~100 entries; a row of L entries costs O(L^2) on one thread)
+__global__ void sparse_sort_rows_kernel(const uint64_t *offsets, uint32_t *idx, float *val, uint64_t n) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint64_t a = offsets[r], b = offsets[r + 1];
+    bool sorted = true;
+    for (uint64_t i = a + 1; i < b && sorted; ++i) sorted = idx[i - 1] <= idx[i];
+    if (sorted) return;
+    for (uint64_t i = a + 1; i < b; ++i) {
+        const uint32_t k = idx[i];
+        const float v = val[i];
+        uint64_t j = i;
+        while (j > a && idx[j - 1] > k) {
+            idx[j] = idx[j - 1];
+            val[j] = val[j - 1];
+            --j;
+        }
+        idx[j] = k;
+        val[j] = v;
+    }
+}
+
+// IndicesTracker::remap_index over every stored index: keys sorted ascending; a key the map lacks sets *missing
+__global__ void sparse_remap_kernel(uint32_t *idx, uint64_t nnz, const uint32_t *keys, const uint32_t *vals, uint64_t m, uint32_t *missing) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nnz) return;
+    const uint32_t k = idx[i];
+    uint64_t lo = 0, hi = m;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) / 2;
+        if (keys[mid] < k) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < m && keys[lo] == k) idx[i] = vals[lo];
+    else atomicOr(missing, 1u);
+}
+
+// posting payload of every entry: (f32 bits of the weight << 32) | row id, in row order (the stable sort by dimension keeps ids ascending)
+__global__ void sparse_post_payload_kernel(const uint64_t *offsets, const float *val, uint64_t n, uint64_t *out) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    for (uint64_t i = offsets[r]; i < offsets[r + 1]; ++i) out[i] = ((uint64_t)__float_as_uint(val[i]) << 32) | (uint32_t)r;
+}
+
+static uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + SP_BLOCK - 1) / SP_BLOCK); }
+
+int32_t launch_sparse_check_rows(hipStream_t st, const uint64_t *offsets, const uint32_t *idx, uint64_t n, uint32_t *flags) {
+    if (n == 0) return QMX_OK;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_check_rows_kernel, dim3(blocks_of(n)), dim3(SP_BLOCK), 0, st, offsets, idx, n, flags);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_sort_rows(hipStream_t st, const uint64_t *offsets, uint32_t *idx, float *val, uint64_t n) {
+    if (n == 0) return QMX_OK;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_sort_rows_kernel, dim3(blocks_of(n)), dim3(SP_BLOCK), 0, st, offsets, idx, val, n);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_remap(hipStream_t st, uint32_t *idx, uint64_t nnz, const uint32_t *keys, const uint32_t *vals, uint64_t m, uint32_t *missing) {
+    if (nnz == 0) return QMX_OK;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_remap_kernel, dim3(blocks_of(nnz)), dim3(SP_BLOCK), 0, st, idx, nnz, keys, vals, m, missing);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+
+// The dimension-major layout: post[] = the (id, weight) payloads grouped by dimension, ids ascending inside a group; dims[] / counts[] = the
+// distinct dimensions ascending and their posting lengths, *n_dims of them.  Stable radix sort of the payloads by dimension, then a run-length
+// encoding of the sorted dimensions.  Scratch is allocated and freed here.
+int32_t sparse_build_postings(hipStream_t st, const uint64_t *offsets, const uint32_t *idx, const float *val, uint64_t n, uint64_t nnz, uint64_t *post,
+                              uint32_t *dims, uint32_t *counts, uint32_t *n_dims_dev) {
+    if (nnz == 0) {
+        QMX_HIP(hipMemsetAsync(n_dims_dev, 0, 4, st));
+        return QMX_OK;
+    }
+    QMX_REQUIRE(nnz <= 0xFFFFFFFFull, QMX_ERR_NOT_SUPPORTED, "a sparse segment holds at most 2^32 - 1 non-zeros (got %llu)", (unsigned long long)nnz);
+    uint64_t *payload = nullptr;
+    uint32_t *keys_sorted = nullptr;
+    void *tmp = nullptr;
+    int32_t rc = QMX_OK;
+    auto fail = [&](hipError_t e, const char *what) { rc = hip_status(e, what, __FILE__, __LINE__); };
+    do {
+        hipError_t e = hipMalloc(&payload, nnz * 8);
+        if (e != hipSuccess) { fail(e, "hipMalloc(payload)"); break; }
+        e = hipMalloc(&keys_sorted, nnz * 4);
+        if (e != hipSuccess) { fail(e, "hipMalloc(keys)"); break; }
+        ::qmx::clear_stale_error();
+        hipLaunchKernelGGL(sparse_post_payload_kernel, dim3(blocks_of(n)), dim3(SP_BLOCK), 0, st, offsets, val, n, payload);
+        if ((e = hipGetLastError()) != hipSuccess) { fail(e, "sparse_post_payload_kernel"); break; }
+        size_t sort_bytes = 0, rle_bytes = 0;
+        e = rocprim::radix_sort_pairs(nullptr, sort_bytes, idx, keys_sorted, payload, post, (size_t)nnz, 0, 32, st);
+        if (e == hipSuccess) e = rocprim::run_length_encode(nullptr, rle_bytes, keys_sorted, (unsigned int)nnz, dims, counts, n_dims_dev, st);
+        if (e != hipSuccess) { fail(e, "rocprim temporary storage"); break; }
+        size_t tmp_bytes = std::max(sort_bytes, rle_bytes);
+        e = hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 16));
+        if (e != hipSuccess) { fail(e, "hipMalloc(sort scratch)"); break; }
+        e = rocprim::radix_sort_pairs(tmp, sort_bytes, idx, keys_sorted, payload, post, (size_t)nnz, 0, 32, st);
+        if (e != hipSuccess) { fail(e, "rocprim::radix_sort_pairs"); break; }
+        e = rocprim::run_length_encode(tmp, rle_bytes, keys_sorted, (unsigned int)nnz, dims, counts, n_dims_dev, st);
+        if (e != hipSuccess) { fail(e, "rocprim::run_length_encode"); break; }
+        e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { fail(e, "posting build"); break; }
+    } while (0);
+    if (payload) (void)hipFree(payload);
+    if (keys_sorted) (void)hipFree(keys_sorted);
+    if (tmp) (void)hipFree(tmp);
+    return rc;
+}
+
+// ---- gather scoring (RawScorer) ----
+
+// scores[(q - q0) * stride + i] = score_vectors(query q, row ids[i]) (0.0 without overlap); block (x, y) = a slice of the ids for query q0 + y,
+// whose sorted list is staged in LDS
+__global__ __launch_bounds__(SP_BLOCK) void sparse_score_matrix_kernel(SparseRows r, SparseQueries qs, uint32_t q0, const uint32_t *ids, uint64_t n,
+                                                                       float *scores, uint64_t stride, int *err) {
+    __shared__ uint32_t s_idx[SP_LDS_Q];
+    __shared__ float s_val[SP_LDS_Q];
+    const uint32_t qi = q0 + blockIdx.y;
+    const uint64_t qo = qs.off[qi];
+    const uint32_t qn = (uint32_t)(qs.off[qi + 1] - qo);
+    const bool staged = qn <= SP_LDS_Q;
+    if (staged)
+        for (uint32_t k = threadIdx.x; k < qn; k += SP_BLOCK) {
+            s_idx[k] = qs.idx[qo + k];
+            s_val[k] = qs.val[qo + k];
+        }
+    __syncthreads();
+    const uint32_t *qidx = staged ? s_idx : qs.idx + qo;
+    const float *qval = staged ? s_val : qs.val + qo;
+    for (uint64_t i = (uint64_t)blockIdx.x * SP_BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * SP_BLOCK) {
+        const uint32_t id = ids ? ids[i] : (uint32_t)i;
+        float s = 0.0f;
+        if (id >= r.n) {
+            *err = 1;
+        } else {
+            bool ov;
+            const uint64_t ro = r.off[id];
+            s = sparse_dot(r.idx + ro, r.val + ro, (uint32_t)(r.off[id + 1] - ro), qidx, qval, qn, &ov);
+        }
+        scores[(uint64_t)blockIdx.y * stride + i] = s;
+    }
+}
+
+// one (query, row) item per thread: ragged score_points, rescoring
+__global__ __launch_bounds__(SP_BLOCK) void sparse_score_pairs_kernel(SparseRows r, SparseQueries qs, PairSel sel, const uint32_t *ids, uint64_t n_items,
+                                                                      float *scores, int *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (i >= n_items) return;
+    const uint32_t qi = sel.query_of(i);
+    if (!sel.live(i, qi)) {
+        scores[i] = 0.0f;
+        return;
+    }
+    const uint32_t id = ids[i];
+    float s = 0.0f;
+    if (id >= r.n) {
+        *err = 1;
+    } else {
+        bool ov;
+        const uint64_t ro = r.off[id], qo = qs.off[qi];
+        s = sparse_dot(r.idx + ro, r.val + ro, (uint32_t)(r.off[id + 1] - ro), qs.idx + qo, qs.val + qo, (uint32_t)(qs.off[qi + 1] - qo), &ov);
+    }
+    scores[i] = s;
+}
+
+// score_internal: pair i = (stored row a[i], stored row b[i])
+__global__ __launch_bounds__(SP_BLOCK) void sparse_score_internal_kernel(SparseRows r, const uint32_t *a, const uint32_t *b, uint64_t n, float *out, int *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t x = a[i], y = b[i];
+    float s = 0.0f;
+    if (x >= r.n || y >= r.n) {
+        *err = 1;
+    } else {
+        bool ov;
+        const uint64_t xo = r.off[x], yo = r.off[y];
+        s = sparse_dot(r.idx + xo, r.val + xo, (uint32_t)(r.off[x + 1] - xo), r.idx + yo, r.val + yo, (uint32_t)(r.off[y + 1] - yo), &ov);
+    }
+    out[i] = s;
+}
+
+int32_t launch_sparse_score_matrix(hipStream_t st, const SparseRows &r, const SparseQueries &qs, uint32_t q0, uint32_t nq, const uint32_t *ids, uint64_t n,
+                                   float *scores, uint64_t stride, int *err) {
+    if (n == 0 || nq == 0) return QMX_OK;
+    const uint32_t gx = (uint32_t)std::min<uint64_t>(blocks_of(n), 4096);
+    ::qmx::clear_stale_error();
+    for (uint32_t y0 = 0; y0 < nq; y0 += 65535) {
+        const uint32_t ny = std::min<uint32_t>(65535, nq - y0);
+        hipLaunchKernelGGL(sparse_score_matrix_kernel, dim3(gx, ny), dim3(SP_BLOCK), 0, st, r, qs, q0 + y0, ids, n, scores + (uint64_t)y0 * stride, stride, err);
+        QMX_NOTE_KERNEL(sparse_score_matrix_kernel);
+    }
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_score_pairs(hipStream_t st, const SparseRows &r, const SparseQueries &qs, const PairSel &sel, const uint32_t *ids, uint64_t n_items,
+                                  float *scores, int *err) {
+    if (n_items == 0) return QMX_OK;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_score_pairs_kernel, dim3(blocks_of(n_items)), dim3(SP_BLOCK), 0, st, r, qs, sel, ids, n_items, scores, err);
+    QMX_NOTE_KERNEL(sparse_score_pairs_kernel);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_score_internal(hipStream_t st, const SparseRows &r, const uint32_t *a, const uint32_t *b, uint64_t n, float *out, int *err) {
+    if (n == 0) return QMX_OK;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_score_internal_kernel, dim3(blocks_of(n)), dim3(SP_BLOCK), 0, st, r, a, b, n, out, err);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+// ---- top-k ----
+
+// the work-group's end of a pass: the four wave lists merged into the best `top` keys, written as list `list` of query ql
+__device__ __forceinline__ void sparse_block_emit(uint64_t list, int top, uint32_t list_idx, uint32_t ql, uint32_t nq_tile, uint64_t *partial) {
+    __shared__ uint64_t sh[SPT_WAVES][WAVE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    sh[wave][lane] = list;
+    __syncthreads();
+    if (wave == 0) {
+        uint64_t merged = sh[0][lane];
+        for (uint32_t w = 1; w < SPT_WAVES; ++w) wave_offer(merged, sh[w][lane], top, lane);
+        if (lane < top) partial[((uint64_t)list_idx * nq_tile + ql) * top + lane] = merged;
+    }
+}
+
+// Nearest over the posting layout.  Work-group (x, y): point ids [x * SPT_TILE, (x + 1) * SPT_TILE) for query q0 + y; wave w owns the
+// SPT_SUB ids from x * SPT_TILE + w * SPT_SUB with its accumulators and overlap bits in LDS.  The query's dimensions are visited in ascending
+// order; for each, the lanes of the wave first find the posting sub-range of their dimension (64 dimensions at a time, one binary search per
+// lane), then the wave adds weight x query weight of the dimension's entries into the accumulators, 64 entries per step.  Ids are distinct inside
+// one posting list and a wave's LDS operations complete in order, so every point's sum is score_vectors' sum, dimension after dimension.
+// Then each wave offers its overlapping, live, allowed ids (below the bound of the previous pass) to a list of `top`, and the work-group
+// writes the best `top` of its four lists as one key list of launch_merge_keys.
+__global__ __launch_bounds__(SP_BLOCK) void sparse_topk_postings_kernel(const uint64_t *post, SparsePlan plan, uint32_t q0, uint32_t nq_tile, uint64_t n_scan,
+                                                                        DeletedView del, uint32_t top, const uint64_t *key_bound, uint64_t *partial) {
+    __shared__ float acc[SPT_TILE];
+    __shared__ uint32_t hit[SPT_TILE / 32];
+    const uint32_t tile = blockIdx.x, ql = blockIdx.y, qi = q0 + ql;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t bound = key_bound ? key_bound[ql] : 0;
+    if (key_bound && bound == 0) {   // the query was exhausted by an earlier pass
+        if (threadIdx.x < top) partial[((uint64_t)tile * nq_tile + ql) * top + threadIdx.x] = 0;
+        return;
+    }
+    const uint64_t sub_lo = (uint64_t)tile * SPT_TILE + (uint64_t)wave * SPT_SUB;
+    const uint64_t sub_hi = sub_lo + SPT_SUB < n_scan ? sub_lo + SPT_SUB : n_scan;
+    float *wacc = acc + wave * SPT_SUB;
+    uint32_t *whit = hit + wave * (SPT_SUB / 32);
+    for (uint32_t k = lane; k < SPT_SUB; k += WAVE) wacc[k] = 0.0f;
+    for (uint32_t k = lane; k < SPT_SUB / 32; k += WAVE) whit[k] = 0u;
+    const uint32_t d0 = plan.off[qi], d1 = plan.off[qi + 1];
+    for (uint32_t c = d0; c < d1 && sub_lo < sub_hi; c += SPT_CHUNK) {
+        const uint32_t nc = d1 - c < SPT_CHUNK ? d1 - c : SPT_CHUNK;
+        uint64_t lo = 0, hi = 0;
+        float w = 0.0f;
+        if ((uint32_t)lane < nc) {   // lower_bound(sub_lo) in the dimension's posting list
+            uint64_t a = plan.start[c + lane], b = plan.end[c + lane];
+            hi = b;
+            w = plan.w[c + lane];
+            while (a < b) {
+                const uint64_t m = (a + b) >> 1;
+                if ((uint32_t)post[m] < sub_lo) a = m + 1;
+                else b = m;
+            }
+            lo = a;
+        }
+        for (uint32_t j = 0; j < nc; ++j) {
+            uint64_t p = readlane_u64(lo, (int)j);
+            const uint64_t e = readlane_u64(hi, (int)j);
+            const float qv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), (int)j));
+            while (p < e) {
+                const uint64_t i = p + lane;
+                uint64_t ent = ~0ull;
+                if (i < e) ent = post[i];
+                const uint32_t id = (uint32_t)ent;
+                const bool in = i < e && id < sub_hi;
+                if (in) {
+                    const uint32_t k = id - (uint32_t)sub_lo;
+                    wacc[k] = __fadd_rn(wacc[k], __fmul_rn(__uint_as_float((uint32_t)(ent >> 32)), qv));
+                    atomicOr(&whit[k >> 5], 1u << (k & 31));
+                }
+                if (__ballot(in) != ~0ull) break;
+                p += WAVE;
+            }
+        }
+    }
+    uint64_t list = 0;
+    for (uint32_t k0 = 0; k0 < SPT_SUB; k0 += WAVE) {
+        const uint32_t k = k0 + lane;
+        const uint64_t id = sub_lo + k;
+        uint64_t key = 0;
+        if (id < sub_hi && ((whit[k >> 5] >> (k & 31)) & 1u) && del.live((uint32_t)id)) key = make_key(wacc[k], (uint32_t)id);
+        if (key_bound && key >= bound) key = 0;
+        wave_offer(list, key, (int)top, lane);
+    }
+    sparse_block_emit(list, (int)top, tile, ql, nq_tile, partial);
+}
+
+// plain_search over an id list: block (x, y) scores a grid-strided slice of the ids against query q0 + y (staged in LDS) and keeps the
+// overlapping, live, allowed ones
+__global__ __launch_bounds__(SP_BLOCK) void sparse_topk_ids_kernel(SparseRows r, SparseQueries qs, uint32_t q0, uint32_t nq_tile, const uint32_t *ids,
+                                                                   uint64_t n_ids, DeletedView del, uint32_t top, const uint64_t *key_bound, uint64_t *partial) {
+    __shared__ uint32_t s_idx[SP_LDS_Q];
+    __shared__ float s_val[SP_LDS_Q];
+    const uint32_t ql = blockIdx.y, qi = q0 + ql;
+    const int lane = threadIdx.x & 63;
+    const uint64_t bound = key_bound ? key_bound[ql] : 0;
+    if (key_bound && bound == 0) {
+        if (threadIdx.x < top) partial[((uint64_t)blockIdx.x * nq_tile + ql) * top + threadIdx.x] = 0;
+        return;
+    }
+    const uint64_t qo = qs.off[qi];
+    const uint32_t qn = (uint32_t)(qs.off[qi + 1] - qo);
+    const bool staged = qn <= SP_LDS_Q;
+    if (staged)
+        for (uint32_t k = threadIdx.x; k < qn; k += SP_BLOCK) {
+            s_idx[k] = qs.idx[qo + k];
+            s_val[k] = qs.val[qo + k];
+        }
+    __syncthreads();
+    const uint32_t *qidx = staged ? s_idx : qs.idx + qo;
+    const float *qval = staged ? s_val : qs.val + qo;
+    uint64_t list = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * SP_BLOCK; base < n_ids; base += (uint64_t)gridDim.x * SP_BLOCK) {
+        const uint64_t i = base + threadIdx.x;
+        uint64_t key = 0;
+        if (i < n_ids) {
+            const uint32_t id = ids[i];
+            if (id < r.n && del.live(id)) {
+                bool ov;
+                const uint64_t ro = r.off[id];
+                const float s = sparse_dot(r.idx + ro, r.val + ro, (uint32_t)(r.off[id + 1] - ro), qidx, qval, qn, &ov);
+                if (ov) key = make_key(s, id);
+            }
+        }
+        if (key_bound && key >= bound) key = 0;
+        wave_offer(list, key, (int)top, lane);
+    }
+    sparse_block_emit(list, (int)top, blockIdx.x, ql, nq_tile, partial);
+}
+
+int32_t launch_sparse_topk_postings(hipStream_t st, const uint64_t *post, const SparsePlan &plan, uint32_t q0, uint32_t nq_tile, uint64_t n_scan,
+                                    const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists) {
+    const uint64_t tiles = (n_scan + SPT_TILE - 1) / SPT_TILE;
+    *n_lists = (uint32_t)tiles;
+    if (tiles == 0 || nq_tile == 0) return QMX_OK;
+    QMX_REQUIRE(nq_tile <= 65535, QMX_ERR_OTHER, "query tile too large");
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_topk_postings_kernel, dim3((uint32_t)tiles, nq_tile), dim3(SP_BLOCK), 0, st, post, plan, q0, nq_tile, n_scan, del, top, key_bound,
+                       partial);
+    QMX_NOTE_KERNEL(sparse_topk_postings_kernel);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+uint32_t sparse_ids_lists(uint64_t n_ids) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_ids + SP_BLOCK - 1) / SP_BLOCK, 1), 1024); }
+int32_t launch_sparse_topk_ids(hipStream_t st, const SparseRows &r, const SparseQueries &qs, uint32_t q0, uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids,
+                               const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists) {
+    *n_lists = sparse_ids_lists(n_ids);
+    if (nq_tile == 0) return QMX_OK;
+    QMX_REQUIRE(nq_tile <= 65535, QMX_ERR_OTHER, "query tile too large");
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_topk_ids_kernel, dim3(*n_lists, nq_tile), dim3(SP_BLOCK), 0, st, r, qs, q0, nq_tile, ids, n_ids, del, top, key_bound, partial);
+    QMX_NOTE_KERNEL(sparse_topk_ids_kernel);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+
+}  // namespace qmx

@@ -14,16 +14,6 @@ namespace qmx {
 constexpr int MERGE_BLOCK = 256;
 constexpr int MERGE_NW = MERGE_BLOCK / WAVE;
 
-__device__ __forceinline__ void wave_offer(uint64_t &list, uint64_t key, int top, int lane) {
-    uint64_t m = __ballot(key > readlane_u64(list, top - 1));
-    while (m) {
-        const int src = __builtin_ctzll(m);
-        m &= m - 1;
-        const uint64_t nk = readlane_u64(key, src);
-        if (nk > readlane_u64(list, top - 1)) wave_list_insert(list, nk, lane);
-    }
-}
-
 // block-level finish of one pass: merge the MERGE_NW wave lists, write ScoredPointOffset entries
 // out[q * out_stride + out_offset .. + top), add to / set the count, and return (to every thread) the key bound
 // of the next pass: the last key written, or 0 when fewer than `top` were found (nothing is left).

@@ -785,7 +785,10 @@ class RawScorer:
 
 def new_raw_scorer(query, storage: VectorStorage) -> RawScorer:
     """`new_raw_scorer(QueryVector::Nearest(query), storage, hc)` (raw_scorer.rs:60-114).
-    `query`: [dim] or [nq, dim] f32 ORIGINAL vectors; preprocessing + cast happen on device."""
+    `query`: [dim] or [nq, dim] f32 ORIGINAL vectors; preprocessing + cast happen on device.
+    Over a SparseVectorStorage: sparse queries, a list of (indices, values) pairs or CSR arrays (offsets, indices, values)."""
+    if isinstance(storage, SparseVectorStorage):
+        return storage._raw_scorer(query)
     if hasattr(query, "data_ptr") and getattr(query, "is_cuda", False):    # a contiguous [nq, dim] f32 torch CUDA tensor: no host copy
         q = query
         assert q.dim() == 2 and q.is_contiguous() and str(q.dtype) == "torch.float32"
@@ -921,6 +924,9 @@ class BatchFilteredSearcher:
     def __init__(self, queries, vectors: VectorStorage, top: int, quantized_vectors=None):
         if top == 0:
             raise ValueError("length must be greater than zero")  # FixedLengthPriorityQueue::new panics
+        if isinstance(vectors, SparseVectorStorage):
+            # peek_top_iter over a sparse raw scorer keeps non-overlapping points at 0.0; the device top-k returns overlapping points only
+            raise NotImplementedError("BatchFilteredSearcher over sparse vectors is not supported: use SparseVectorStorage.search")
         self.top = int(top)
         self.storage = quantized_vectors if quantized_vectors is not None else vectors
         self.scorer = new_raw_scorer(queries, self.storage)
@@ -950,3 +956,102 @@ class BatchFilteredSearcher:
     def peek_top_iter(self, points: Iterable[int], is_stopped=None) -> List[np.ndarray]:
         """Candidate stream given explicitly (point_scorer.rs:423-472)."""
         return self._run(points, is_stopped)
+
+
+def _sparse_csr(vectors):
+    """Sparse vectors as CSR arrays (u64 offsets, u32 indices, f32 values): from a list of (indices, values) pairs, or from CSR arrays as given."""
+    if isinstance(vectors, tuple) and len(vectors) == 3 and not isinstance(vectors[0], tuple):
+        off, idx, val = vectors
+        return (np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(idx, dtype=np.uint32),
+                np.ascontiguousarray(val, dtype=np.float32))
+    vectors = list(vectors)
+    off = np.zeros(len(vectors) + 1, dtype=np.uint64)
+    for i, (ix, vx) in enumerate(vectors):
+        if len(ix) != len(vx):
+            raise ValueError("sparse vector %d: values must be the same length as indices" % i)     # sparse_vector.rs:309-314
+        off[i + 1] = off[i] + len(ix)
+    idx = np.concatenate([np.asarray(v[0], dtype=np.uint32) for v in vectors]) if off[-1] else np.zeros(0, dtype=np.uint32)
+    val = np.concatenate([np.asarray(v[1], dtype=np.float32) for v in vectors]) if off[-1] else np.zeros(0, dtype=np.float32)
+    return off, np.ascontiguousarray(idx), np.ascontiguousarray(val)
+
+
+class SparseVectorStorage:
+    """Sparse vectors (lib/sparse, `SparseVectorIndex` over a sparse vector storage) on the device: rows sorted by index at create, the
+    dimension-major posting layout beside them.  `vectors`: a list of (indices, values) pairs or CSR arrays (offsets, indices, values), host
+    arrays or torch device tensors.  `dim_map`: the IndicesTracker as (keys, remapped ids) or a dict; rows and queries are remapped and re-sorted.
+    Scores are `score_vectors` (sparse_vector.rs:66-90); 0.0 where a query shares no dimension with a point."""
+
+    def __init__(self, offsets, indices=None, values=None, dim_map=None, device_id: int = 0):
+        self._h = C.c_void_p()
+        if indices is None:      # SparseVectorStorage([(indices, values), ...])
+            offsets, indices, values = _sparse_csr(offsets)
+        if not hasattr(offsets, "data_ptr"):
+            offsets, indices, values = _sparse_csr((offsets, indices, values))
+        self._keep = (offsets, indices, values)
+        n = len(offsets) - 1
+        desc = F.SparseSegmentDesc()
+        desc.n = n
+        desc.offsets, desc.indices, desc.values = F.ptr(offsets), F.ptr(indices), F.ptr(values)
+        if dim_map is not None:
+            if isinstance(dim_map, dict):
+                dim_map = (list(dim_map.keys()), list(dim_map.values()))
+            keys = np.ascontiguousarray(dim_map[0], dtype=np.uint32)
+            vals = np.ascontiguousarray(dim_map[1], dtype=np.uint32)
+            if len(keys) != len(vals):
+                raise ValueError("dim_map: keys and remapped ids differ in length")
+            desc.map_keys, desc.map_values, desc.n_map = F.ptr(keys), F.ptr(vals), len(keys)
+        desc.device_id = device_id
+        self.n = n
+        self.dim_map = dim_map
+        F.check(F.lib().qmx_sparse_segment_create(C.byref(desc), C.byref(self._h)))
+        self._keep = None
+
+    def total_vector_count(self) -> int:
+        return self.n
+
+    def set_deleted(self, point_deleted=None, vec_deleted=None):
+        pw = _bits_to_words(point_deleted)
+        vw = _bits_to_words(vec_deleted)
+        F.check(F.lib().qmx_segment_set_deleted(
+            self._h, F.ptr(pw), 0 if point_deleted is None else len(point_deleted),
+            F.ptr(vw), 0 if vec_deleted is None else len(vec_deleted)))
+
+    def _raw_scorer(self, queries) -> RawScorer:
+        off, idx, val = _sparse_csr(queries)
+        h = C.c_void_p()
+        nq = len(off) - 1
+        F.check(F.lib().qmx_sparse_query_create(self._h, F.ptr(off), F.ptr(idx), F.ptr(val), nq, C.byref(h)))
+        return RawScorer(h, self, nq)
+
+    def search(self, queries, top: int, ids=None, allowed=None) -> List[np.ndarray]:
+        """`search_nearest_query` (sparse_vector_index/read_view/search.rs:258-300): per query the `top` best points that share at least one
+        dimension with it, score descending (lower offset first among equal scores).  `ids`: the prefiltered candidates (plain_search);
+        `allowed`: a payload-filter allow mask over point ids.  top == 0 gives empty lists."""
+        scorer = self._raw_scorer(queries)
+        try:
+            nq = scorer.nq
+            if top == 0 or nq == 0:
+                return [np.zeros(0, dtype=ScoredPointOffset) for _ in range(nq)]
+            if allowed is not None:
+                scorer.set_filter(allowed)
+            if ids is not None:
+                ids = np.ascontiguousarray(list(ids) if not isinstance(ids, np.ndarray) else ids, dtype=np.uint32)
+            out = np.zeros((nq, top), dtype=ScoredPointOffset)
+            counts = np.zeros(nq, dtype=np.uint32)
+            self.counters = F.Counters()
+            F.check(F.lib().qmx_search_topk(scorer._h, top, F.ptr(ids), 0 if ids is None else len(ids), F.ptr(out), F.ptr(counts), None,
+                                            C.byref(self.counters)))
+            return [out[i, :counts[i]].copy() for i in range(nq)]
+        finally:
+            scorer.close()
+
+    def close(self):
+        if self._h:
+            F.lib().qmx_segment_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""Sparse-vector Nearest search on the device (qmx_search_topk over a QMX_DTYPE_SPARSE segment) on deterministic SPLADE-like data.
+
+Data (generated on the device with torch, seeded): `--points` rows of about `--nnz` non-zeros over `--dims` dimensions, dimensions drawn from
+a Zipf law (p(rank k) ~ 1 / k), duplicates per row dropped, positive log-normal weights; queries of about `--qnnz` non-zeros from the same law.
+Reports, per batch size Q: ms per batch and QPS; the posting bytes the batch touches (sum over the queries of len(d) x 8 B for each of their
+dimensions d) with their GB/s and the fraction of 8 TB/s; the CSR block size; the segment create time (row checks + the posting transpose).
+One JSON line per run on stdout; `--out` also writes it to a file."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402  (before the library: one HIP runtime for both)
+
+import qdrant_amd as qa  # noqa: E402
+from qdrant_amd import _ffi as F  # noqa: E402
+
+HBM_BYTES_PER_S = 8.0e12
+
+
+def zipf_cdf(n_dims, dev):
+    p = 1.0 / torch.arange(1, n_dims + 1, dtype=torch.float64, device=dev)
+    c = torch.cumsum(p, 0)
+    return (c / c[-1]).to(torch.float64)
+
+
+def sample_rows(gen, cdf, perm, n_rows, nnz, dev):
+    """CSR (lengths, dims, weights) of n_rows rows: ~nnz Zipf draws each, repeats within a row dropped, dims ascending."""
+    n_dims = len(perm)
+    lens = torch.randint(nnz - nnz // 4, nnz + nnz // 4 + 1, (n_rows,), generator=gen, device=dev)
+    total = int(lens.sum())
+    u = torch.rand(total, generator=gen, device=dev, dtype=torch.float64)
+    dims = perm[torch.searchsorted(cdf, u).clamp_(max=n_dims - 1)]
+    row = torch.repeat_interleave(torch.arange(n_rows, device=dev, dtype=torch.int64), lens)
+    key = torch.unique(row * n_dims + dims)      # sorted: by row, then dimension
+    row, dims = key // n_dims, (key % n_dims).to(torch.int32)
+    lens = torch.bincount(row, minlength=n_rows)
+    w = torch.exp(torch.randn(len(dims), generator=gen, device=dev) * 0.75 - 0.5).to(torch.float32)
+    return lens, dims, w
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--points", type=int, default=10_000_000)
+    ap.add_argument("--dims", type=int, default=30522)
+    ap.add_argument("--nnz", type=int, default=120)
+    ap.add_argument("--qnnz", type=int, default=25)
+    ap.add_argument("--batches", default="1,8,32,128")
+    ap.add_argument("--top", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=20241016)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed)
+    cdf = zipf_cdf(args.dims, dev)
+    perm = torch.randperm(args.dims, generator=gen, device=dev).to(torch.int64)     # Zipf rank -> dimension id
+    chunk = 1_000_000
+    lens_l, dims_l, w_l = [], [], []
+    for r0 in range(0, args.points, chunk):
+        lens, dims, w = sample_rows(gen, cdf, perm, min(chunk, args.points - r0), args.nnz, dev)
+        lens_l.append(lens)
+        dims_l.append(dims)
+        w_l.append(w)
+    lens = torch.cat(lens_l)
+    offsets = torch.zeros(args.points + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(lens, 0)
+    indices = torch.cat(dims_l)
+    values = torch.cat(w_l)
+    del lens_l, dims_l, w_l
+    nnz = int(offsets[-1])
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    st = qa.SparseVectorStorage(offsets, indices, values)
+    create_s = time.perf_counter() - t0
+    del indices, values
+    torch.cuda.empty_cache()
+    csr_bytes = nnz * 8 + (args.points + 1) * 8
+    qgen = torch.Generator(device=dev)
+    qgen.manual_seed(args.seed + 1)
+    results = []
+    for nq in [int(x) for x in args.batches.split(",")]:
+        ql, qd, qw = sample_rows(qgen, cdf, perm, nq, args.qnnz, dev)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum(ql.cpu().numpy())
+        qidx = qd.cpu().numpy().astype(np.uint32)
+        qval = qw.cpu().numpy()
+        h = C.c_void_p()
+        F.check(F.lib().qmx_sparse_query_create(st._h, F.ptr(qoff), F.ptr(qidx), F.ptr(qval), nq, C.byref(h)))
+        out = np.zeros((nq, args.top), dtype=qa.ScoredPointOffset)
+        counts = np.zeros(nq, dtype=np.uint32)
+        ctr = F.Counters()
+        for _ in range(args.warmup):
+            F.check(F.lib().qmx_search_topk(h, args.top, None, 0, F.ptr(out), F.ptr(counts), None, C.byref(ctr)))
+        times = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            F.check(F.lib().qmx_search_topk(h, args.top, None, 0, F.ptr(out), F.ptr(counts), None, C.byref(ctr)))
+            times.append(time.perf_counter() - t0)
+        F.lib().qmx_query_destroy(h)
+        ms = 1e3 * float(np.median(times))
+        post_bytes = int(ctr.bytes_read)
+        gbs = post_bytes / (ms * 1e-3) / 1e9
+        results.append({"queries": nq, "ms_per_batch": round(ms, 3), "qps": round(nq / (ms * 1e-3), 1), "posting_bytes": post_bytes,
+                        "posting_gb_per_s": round(gbs, 1), "hbm_fraction": round(gbs * 1e9 / HBM_BYTES_PER_S, 4),
+                        "mean_results": float(counts.mean())})
+    rec = {"tool": "bench_sparse", "points": args.points, "dims": args.dims, "nnz": nnz, "mean_row_nnz": round(nnz / args.points, 2),
+           "qnnz": args.qnnz, "top": args.top, "csr_bytes": csr_bytes, "posting_layout_bytes": nnz * 8, "create_s": round(create_s, 3),
+           "device": torch.cuda.get_device_name(0), "batches": results}
+    line = json.dumps(rec)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
