@@ -360,7 +360,8 @@ QMX_API int32_t qmx_segment_row_bytes(const qmx_segment *seg, uint64_t *out);
  * rounding per multiply and per add; 0.0 for no shared dimension (the raw scorer, sparse_metric_query_scorer.rs:43).
  * Served on a sparse segment / query: qmx_query_create_internal, qmx_score_points(_ragged), qmx_score_point, qmx_score_internal,
  * qmx_search_topk(_async) (Nearest: only points that share a dimension with the query, search_context.rs:92-143; `ids`, filters and
- * deleted flags as for dense; top = 0 gives empty lists), qmx_query_set_filter / set_stream / destroy, qmx_segment_set_deleted / destroy.
+ * deleted flags as for dense; top = 0 gives empty lists), qmx_query_set_filter / set_stream / destroy, qmx_segment_set_deleted / destroy,
+ * and for custom queries qmx_sparse_custom_score_points / qmx_sparse_custom_search_topk / qmx_custom_set_coefficients.
  * Every other entry point handed one: QMX_ERR_NOT_SUPPORTED. */
 typedef struct qmx_sparse_segment_desc {
     uint64_t n;                   /* rows */
@@ -624,6 +625,27 @@ QMX_API int32_t qmx_custom_score_points(qmx_query *examples, const qmx_custom_qu
  * `ids` or every live point; deleted flags and the batch's payload filter apply; out [n_queries][top]. */
 QMX_API int32_t qmx_custom_search_topk(qmx_query *examples, const qmx_custom_query *queries, uint32_t n_queries, uint32_t top,
                                        const uint32_t *ids, uint64_t n_ids, qmx_scored_point *out, uint32_t *out_counts);
+
+/* Custom queries over SPARSE vectors (`SparseCustomQueryScorer`, query_scorer/sparse_custom_query_scorer.rs; what `SparseVectorIndex::search_query`
+ * sends every non-Nearest query to, sparse_vector_index/read_view/search.rs:99-151, 302-341).  `examples` = a batch made by qmx_sparse_query_create over
+ * the sparse segment: the example vectors of all custom queries, back to back, flat_iter() order; descriptors and validation as for
+ * qmx_custom_score_points.  A batch from qmx_query_create_internal, a dense batch or a dense segment: QMX_ERR_NOT_SUPPORTED.
+ * score(point) = query.score_by(|example| score_vectors(example, point).unwrap_or(0.0)): a point that shares no dimension with any example still
+ * has a score and may be returned (unlike Nearest).  The scorer works on the vector storage, not on the index: under an `IndicesTracker` map each
+ * example's sum runs in ascending ORIGINAL index order (Nearest sums in remapped order); example dimensions the map lacks contribute nothing.
+ * qmx_custom_set_coefficients on the example batch first for feedback queries.
+ * qmx_sparse_custom_score_points: `RawScorer::score_points`, scores[qi * n + i] = custom query qi against stored point ids[i]; an id past the
+ * segment: QMX_ERR_OUT_OF_BOUNDS. */
+QMX_API int32_t qmx_sparse_custom_score_points(qmx_query *examples, const qmx_custom_query *queries, uint32_t n_queries,
+                                               const uint32_t *ids, uint32_t n, float *scores);
+/* `search_scored`: candidates = `ids` (ids past the segment are skipped) or every live point; deleted flags and the example batch's payload filter
+ * (qmx_query_set_filter) apply; descending score, lower offset first among equal scores; out [n_queries][top] and out_counts [n_queries] in host or
+ * device memory; top in 1..65 536 (passes of 64); is_stopped is read between launches.  counters: over every point vectors_scored = posting entries
+ * visited (all examples of all queries, times passes) and bytes_read = 8 x that; over an id list vectors_scored = examples x ids (times passes),
+ * bytes_read = 0. */
+QMX_API int32_t qmx_sparse_custom_search_topk(qmx_query *examples, const qmx_custom_query *queries, uint32_t n_queries, uint32_t top,
+                                              const uint32_t *ids, uint64_t n_ids, qmx_scored_point *out, uint32_t *out_counts,
+                                              const volatile uint8_t *is_stopped, qmx_counters *counters);
 
 /* `GraphLayers::search` with a custom query as the points scorer: raw_scorer.rs:228-333 builds a CustomQueryScorer (dense storages), a
  * QuantizedCustomQueryScorer (SQ / PQ / BQ: quantized/quantized_custom_query_scorer.rs:13-113) or a TurboCustomQueryScorer

@@ -8,7 +8,7 @@ extern "C" {
 // custom queries (custom_query.hip)
 // ---------------------------------------------------------------------------------------------
 // `n_examples`: how many examples the batch holds (for multi-vector examples: the number of example multi-vectors, not of inner vectors)
-static int32_t custom_validate(const qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t n_examples, uint32_t *max_examples) {
+int32_t custom_validate(const qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t n_examples, uint32_t *max_examples) {
     QMX_REQUIRE(!is_device_ptr(queries), QMX_ERR_BAD_ARG, "the custom query descriptors are a host array (they are validated here)");
     if (max_examples) *max_examples = 0;
     for (uint32_t i = 0; i < n_queries; ++i) {
@@ -39,8 +39,7 @@ static int32_t custom_prepare(qmx_query *ex, const qmx_custom_query *queries, ui
                                  (float *)ex->cq_scores.p);
 }
 
-int32_t qmx_custom_set_coefficients(qmx_query *ex, const float *coefs, uint32_t n) {
-    QMX_REFUSE_SPARSE(ex);
+int32_t qmx_custom_set_coefficients(qmx_query *ex, const float *coefs, uint32_t n) {      // (sparse example batches too: qmx_sparse_custom_*)
     QMX_REQUIRE(ex && (n == 0 || coefs), QMX_ERR_BAD_ARG, "NULL argument");
     QMX_HIP(hipSetDevice(ex->device));
     ex->n_cq_coefs = 0;

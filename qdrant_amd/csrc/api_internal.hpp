@@ -453,6 +453,8 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
                               qmx_scored_point *d_out, uint32_t *d_counts, const volatile uint8_t *is_stopped,
                               qmx_counters *counters, bool timed);
 int32_t fold_split_counters(qmx_query *q, qmx_counters *c);
+// api_custom.hip: the descriptors of a custom-query request against a batch of `n_examples` examples
+int32_t custom_validate(const qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t n_examples, uint32_t *max_examples);
 TqRotationHost tq_rotation(const qmx_segment *s);
 TqRotationHost tq_rotation_inverse(const qmx_segment *s);
 }

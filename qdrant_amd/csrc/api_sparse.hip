@@ -1,5 +1,6 @@
-// api_sparse.hip — the C-ABI of include/qdrant_amd.h, sparse vectors (QMX_DTYPE_SPARSE): segment and query creation, and the sparse arms of
-// score_points / score_internal / search_topk that api_query.hip and api_search.hip dispatch to.  The kernels are in sparse.hip.
+// api_sparse.hip — the C-ABI of include/qdrant_amd.h, sparse vectors (QMX_DTYPE_SPARSE): segment and query creation, the sparse arms of
+// score_points / score_internal / search_topk that api_query.hip and api_search.hip dispatch to, and the custom queries over sparse vectors
+// (qmx_sparse_custom_*).  The kernels are in sparse.hip.
 // (One of the api_*.hip translation units; what they share: api_internal.hpp.)
 #include "api_internal.hpp"
 
@@ -27,6 +28,15 @@ struct SparseQuery {
     uint64_t *d_pstart = nullptr, *d_pend = nullptr;
     float *d_pw = nullptr;
     uint64_t posting_entries = 0;            // sum over the queries of the posting lengths of their dimensions
+    // the custom queries (SparseCustomQueryScorer) sum each example in ascending ORIGINAL index order: the lists (remapped ids, weights) and the
+    // posting plan once more in that order, under the same offsets.  Without a map they ARE the arrays above (not owned twice).
+    uint32_t *d_oidx = nullptr;
+    float *d_oval = nullptr;
+    uint64_t *d_opstart = nullptr, *d_opend = nullptr;
+    float *d_opw = nullptr;
+    bool own_original = false;
+    bool internal = false;                   // made by qmx_query_create_internal: stored rows, whose original order is not known
+    std::vector<uint64_t> h_entries;         // [nq]: posting entries of each query
 };
 
 static SparseRows rows_of(const qmx_segment *s) {
@@ -54,6 +64,9 @@ void sparse_query_free(qmx_query *q) {
     if (!sq) return;
     for (void *p : {(void *)sq->d_off, (void *)sq->d_idx, (void *)sq->d_val, (void *)sq->d_poff, (void *)sq->d_pstart, (void *)sq->d_pend, (void *)sq->d_pw})
         if (p) (void)hipFree(p);
+    if (sq->own_original)
+        for (void *p : {(void *)sq->d_oidx, (void *)sq->d_oval, (void *)sq->d_opstart, (void *)sq->d_opend, (void *)sq->d_opw})
+            if (p) (void)hipFree(p);
     delete sq;
     q->sparse = nullptr;
 }
@@ -73,14 +86,13 @@ static bool sort_pairs(std::vector<std::pair<uint32_t, float>> &v) {
     return true;
 }
 
-// the batch's device arrays from host CSR lists that are sorted and remapped already, and the posting plan from the segment's directory
-static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, const std::vector<uint32_t> &idx, const std::vector<float> &val) {
-    const SparseSeg *sp = q->seg->sparse;
-    SparseQuery *sq = q->sparse;
-    std::vector<uint32_t> poff(q->nq + 1, 0);
-    std::vector<uint64_t> pstart, pend;
-    std::vector<float> pw;
-    for (uint32_t qi = 0; qi < q->nq; ++qi) {
+// the posting plan of lists `idx` / `val` under offsets `off`: per list, its dimensions that have postings, in the list's order
+static void posting_plan(const SparseSeg *sp, uint32_t nq, const std::vector<uint64_t> &off, const std::vector<uint32_t> &idx, const std::vector<float> &val,
+                         std::vector<uint32_t> &poff, std::vector<uint64_t> &pstart, std::vector<uint64_t> &pend, std::vector<float> &pw,
+                         std::vector<uint64_t> *entries) {
+    poff.assign(nq + 1, 0);
+    for (uint32_t qi = 0; qi < nq; ++qi) {
+        uint64_t sum = 0;
         for (uint64_t k = off[qi]; k < off[qi + 1]; ++k) {
             auto it = std::lower_bound(sp->dir_dims.begin(), sp->dir_dims.end(), idx[k]);
             if (it == sp->dir_dims.end() || *it != idx[k]) continue;      // no stored point has this dimension
@@ -88,10 +100,24 @@ static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, cons
             pstart.push_back(sp->dir_start[d]);
             pend.push_back(sp->dir_start[d + 1]);
             pw.push_back(val[k]);
-            sq->posting_entries += sp->dir_start[d + 1] - sp->dir_start[d];
+            sum += sp->dir_start[d + 1] - sp->dir_start[d];
         }
         poff[qi + 1] = (uint32_t)pstart.size();
+        if (entries) entries->push_back(sum);
     }
+}
+
+// the batch's device arrays from host CSR lists that are sorted and remapped already, and the posting plan from the segment's directory.
+// oidx / oval: the same lists (remapped ids, weights) in ascending original index order, or null where that is the order of idx / val
+static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, const std::vector<uint32_t> &idx, const std::vector<float> &val,
+                            const std::vector<uint32_t> *oidx = nullptr, const std::vector<float> *oval = nullptr) {
+    const SparseSeg *sp = q->seg->sparse;
+    SparseQuery *sq = q->sparse;
+    std::vector<uint32_t> poff;
+    std::vector<uint64_t> pstart, pend;
+    std::vector<float> pw;
+    posting_plan(sp, q->nq, off, idx, val, poff, pstart, pend, pw, &sq->h_entries);
+    for (uint64_t e : sq->h_entries) sq->posting_entries += e;
     QMX_TRY(upload(&sq->d_off, off.data(), off.size()));
     QMX_TRY(upload(&sq->d_idx, idx.data(), idx.size()));
     QMX_TRY(upload(&sq->d_val, val.data(), val.size()));
@@ -99,6 +125,25 @@ static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, cons
     QMX_TRY(upload(&sq->d_pstart, pstart.data(), pstart.size()));
     QMX_TRY(upload(&sq->d_pend, pend.data(), pend.size()));
     QMX_TRY(upload(&sq->d_pw, pw.data(), pw.size()));
+    if (!oidx) {
+        sq->d_oidx = sq->d_idx;
+        sq->d_oval = sq->d_val;
+        sq->d_opstart = sq->d_pstart;
+        sq->d_opend = sq->d_pend;
+        sq->d_opw = sq->d_pw;
+        return QMX_OK;
+    }
+    // (the same dimensions in another order: the plan's offsets are those above)
+    std::vector<uint32_t> opoff;
+    std::vector<uint64_t> opstart, opend;
+    std::vector<float> opw;
+    posting_plan(sp, q->nq, off, *oidx, *oval, opoff, opstart, opend, opw, nullptr);
+    sq->own_original = true;
+    QMX_TRY(upload(&sq->d_oidx, oidx->data(), oidx->size()));
+    QMX_TRY(upload(&sq->d_oval, oval->data(), oval->size()));
+    QMX_TRY(upload(&sq->d_opstart, opstart.data(), opstart.size()));
+    QMX_TRY(upload(&sq->d_opend, opend.data(), opend.size()));
+    QMX_TRY(upload(&sq->d_opw, opw.data(), opw.size()));
     return QMX_OK;
 }
 
@@ -148,6 +193,7 @@ int32_t sparse_query_create_internal(const qmx_segment *seg, const uint32_t *poi
     }
     qmx_query *q = nullptr;
     QMX_TRY(sparse_query_alloc(seg, nq, &q));
+    q->sparse->internal = true;
     const int32_t rc = query_finish(q, off, idx, val);
     if (rc != QMX_OK) {
         qmx_query_destroy(q);
@@ -379,8 +425,8 @@ int32_t qmx_sparse_query_create(const qmx_segment *seg, const uint64_t *offsets,
         QMX_HIP(hipMemcpy(in_val.data(), values, total * 4, hipMemcpyDefault));
     }
     std::vector<uint64_t> off(nq + 1, 0);
-    std::vector<uint32_t> idx;
-    std::vector<float> val;
+    std::vector<uint32_t> idx, oidx;
+    std::vector<float> val, oval;
     std::vector<std::pair<uint32_t, float>> v;
     for (uint32_t qi = 0; qi < nq; ++qi) {
         v.clear();
@@ -391,6 +437,10 @@ int32_t qmx_sparse_query_create(const qmx_segment *seg, const uint64_t *offsets,
             for (auto &p : v) {
                 auto it = std::lower_bound(sp->map_keys.begin(), sp->map_keys.end(), p.first);
                 if (it != sp->map_keys.end() && *it == p.first) r.push_back({sp->map_vals[(size_t)(it - sp->map_keys.begin())], p.second});
+            }
+            for (auto &p : r) {      // still in ascending original index: the order of the custom queries' sums
+                oidx.push_back(p.first);
+                oval.push_back(p.second);
             }
             QMX_REQUIRE(sort_pairs(r), QMX_ERR_BAD_ARG, "query %u maps two indices to one", qi);
             v.swap(r);
@@ -403,12 +453,145 @@ int32_t qmx_sparse_query_create(const qmx_segment *seg, const uint64_t *offsets,
     }
     qmx_query *q = nullptr;
     QMX_TRY(sparse_query_alloc(seg, nq, &q));
-    const int32_t rc = query_finish(q, off, idx, val);
+    const int32_t rc = sp->has_map ? query_finish(q, off, idx, val, &oidx, &oval) : query_finish(q, off, idx, val);
     if (rc != QMX_OK) {
         qmx_query_destroy(q);
         return rc;
     }
     *out = q;
+    return QMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// custom queries over sparse vectors (SparseCustomQueryScorer; sparse_custom_*_kernel in sparse.hip)
+// ---------------------------------------------------------------------------------------------
+// the example batch of a sparse custom query: made by qmx_sparse_query_create over a sparse segment
+static int32_t sparse_custom_check(const qmx_query *ex, const char *fn) {
+    if (!is_sparse(ex) || !ex->sparse || ex->sparse->internal) {
+        set_error("%s needs an example batch made by qmx_sparse_query_create over a sparse segment", fn);
+        return QMX_ERR_NOT_SUPPORTED;
+    }
+    return QMX_OK;
+}
+
+// descriptors to the device; *n_examples_total = the examples of all queries, *entries = their posting entries
+static int32_t sparse_custom_stage(qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint64_t *n_examples_total, uint64_t *entries) {
+    QMX_TRY(custom_validate(ex, queries, n_queries, ex->nq, nullptr));
+    *n_examples_total = *entries = 0;
+    for (uint32_t i = 0; i < n_queries; ++i) {
+        const qmx_custom_query &c = queries[i];
+        const uint32_t ne = c.kind <= QMX_CUSTOM_RECO_SUM_SCORES ? c.n_a + c.n_b : c.n_a + 2 * c.n_b;
+        *n_examples_total += ne;
+        for (uint32_t e = 0; e < ne; ++e) *entries += ex->sparse->h_entries[c.first + e];
+    }
+    QMX_TRY(ex->cq_desc.reserve((size_t)n_queries * sizeof(qmx_custom_query)));
+    QMX_HIP(hipMemcpyAsync(ex->cq_desc.p, queries, (size_t)n_queries * sizeof(qmx_custom_query), hipMemcpyHostToDevice, ex->stream));
+    return QMX_OK;
+}
+
+int32_t qmx_sparse_custom_score_points(qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, const uint32_t *ids, uint32_t n, float *scores) {
+    QMX_REQUIRE(ex && (n_queries == 0 || queries) && (n == 0 || (ids && scores)), QMX_ERR_BAD_ARG, "NULL argument");
+    QMX_TRY(sparse_custom_check(ex, __func__));
+    QMX_HIP(hipSetDevice(ex->device));
+    if (n == 0 || n_queries == 0) return QMX_OK;
+    const SparseQuery *sq = ex->sparse;
+    uint64_t n_examples = 0, entries = 0;
+    QMX_TRY(sparse_custom_stage(ex, queries, n_queries, &n_examples, &entries));
+    const void *d_ids = nullptr;
+    QMX_TRY(stage_in(ex, ex->ids, ids, (size_t)n * 4, &d_ids));
+    QMX_TRY(ex->cq_scores.reserve((size_t)n_queries * n * 4));
+    QMX_TRY(launch_sparse_custom_score(ex->stream, rows_of(ex->seg), SparseQueries{sq->d_off, sq->d_oidx, sq->d_oval}, (const qmx_custom_query *)ex->cq_desc.p,
+                                       (const float *)ex->cq_coefs.p, n_queries, (const uint32_t *)d_ids, n, (float *)ex->cq_scores.p, ex->d_err));
+    ex->last_kernel = last_noted_kernel();
+    QMX_TRY(copy_out(ex->stream, scores, ex->cq_scores.p, (size_t)n_queries * n * 4));
+    return check_err_flag(ex);      // synchronises (the caller's descriptors may go away)
+}
+
+// search_scored: the fused posting scan over every point (sparse_custom_topk_postings_kernel) or the id list (sparse_custom_topk_ids_kernel); key lists,
+// passes of 64 and query tiles of 128 as sparse_search_enqueue
+int32_t qmx_sparse_custom_search_topk(qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t top, const uint32_t *ids, uint64_t n_ids,
+                                      qmx_scored_point *out, uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
+    QMX_REQUIRE(ex && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
+    QMX_TRY(sparse_custom_check(ex, __func__));
+    QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
+    QMX_HIP(hipSetDevice(ex->device));
+    if (counters) memset(counters, 0, sizeof(*counters));
+    if (n_queries == 0) return QMX_OK;
+    const qmx_segment *s = ex->seg;
+    const SparseQuery *sq = ex->sparse;
+    uint64_t n_examples = 0, entries = 0;
+    QMX_TRY(sparse_custom_stage(ex, queries, n_queries, &n_examples, &entries));
+    const void *d_ids = nullptr;
+    if (ids && n_ids) QMX_TRY(stage_in(ex, ex->ids, ids, (size_t)n_ids * 4, &d_ids));
+    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
+    qmx_scored_point *d_out = out;
+    uint32_t *d_counts = out_counts;
+    if (!out_dev) { QMX_TRY(ex->out.reserve((size_t)n_queries * top * sizeof(qmx_scored_point))); d_out = (qmx_scored_point *)ex->out.p; }
+    if (!cnt_dev) { QMX_TRY(ex->counts.reserve((size_t)n_queries * 4)); d_counts = (uint32_t *)ex->counts.p; }
+    DeletedView del = s->deleted_view();
+    if (ex->has_filter) {
+        del.allowed = (const uint64_t *)ex->filter.p;
+        del.n_allowed_bits = ex->n_filter_bits;
+    }
+    const uint64_t n_scan = s->scan_rows();
+    const uint32_t n_lists_max = ids ? (n_ids ? sparse_ids_lists(n_ids) : 0) : (uint32_t)((n_scan + sparse_custom_tile_ids() - 1) / sparse_custom_tile_ids());
+    const bool timed = ex->timing || (s->flags & QMX_SEG_TIME_KERNELS) != 0;
+    ex->last_counters = qmx_counters{};
+    ex->last_split = false;
+    uint32_t launches = 0;
+    const uint32_t n_pass = (top + MAX_TOP_FAST - 1) / MAX_TOP_FAST;
+    if (n_lists_max == 0) {      // no candidates: every list is empty
+        QMX_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_queries * 4, ex->stream));
+    } else {
+        const uint32_t QT = 128;
+        const uint32_t ptop_max = std::min<uint32_t>(top, MAX_TOP_FAST);
+        QMX_TRY(ex->partial.reserve((size_t)n_lists_max * std::min<uint32_t>(n_queries, QT) * ptop_max * sizeof(uint64_t)));
+        if (n_pass > 1) QMX_TRY(ex->bounds.reserve((size_t)QT * sizeof(uint64_t)));
+        const SparsePlan plan{sq->d_poff, sq->d_opstart, sq->d_opend, sq->d_opw};
+        const SparseQueries exq{sq->d_off, sq->d_oidx, sq->d_oval};
+        const qmx_custom_query *d_desc = (const qmx_custom_query *)ex->cq_desc.p;
+        const float *d_coefs = (const float *)ex->cq_coefs.p;
+        for (uint32_t tile0 = 0; tile0 < n_queries; tile0 += QT) {
+            const uint32_t nq_tile = std::min<uint32_t>(QT, n_queries - tile0);
+            for (uint32_t pass = 0; pass < n_pass; ++pass) {
+                if (is_stopped && *is_stopped) {
+                    QMX_HIP(hipStreamSynchronize(ex->stream));      // (the caller's descriptors may go away)
+                    set_error("search cancelled");
+                    return QMX_ERR_CANCELLED;
+                }
+                const uint32_t off = pass * MAX_TOP_FAST;
+                const uint32_t ptop = std::min<uint32_t>(MAX_TOP_FAST, top - off);
+                const uint64_t *bound = pass ? (const uint64_t *)ex->bounds.p : nullptr;
+                uint32_t n_lists = 0;
+                size_t slot = 0;
+                if (timed) QMX_TRY(timing_begin(ex, &slot));
+                if (d_ids)
+                    QMX_TRY(launch_sparse_custom_topk_ids(ex->stream, rows_of(s), exq, d_desc, d_coefs, tile0, nq_tile, (const uint32_t *)d_ids, n_ids, del, ptop,
+                                                          bound, (uint64_t *)ex->partial.p, &n_lists));
+                else
+                    QMX_TRY(launch_sparse_custom_topk_postings(ex->stream, s->sparse->d_post, plan, d_desc, d_coefs, tile0, nq_tile, n_scan, del, ptop, bound,
+                                                               (uint64_t *)ex->partial.p, &n_lists));
+                ex->last_kernel = last_noted_kernel();
+                if (timed) QMX_TRY(timing_end(ex, slot));
+                QMX_TRY(launch_merge_keys(ex->stream, (const uint64_t *)ex->partial.p, n_lists, nq_tile, nq_tile, ptop, d_out + (size_t)tile0 * top,
+                                          d_counts + tile0, top, off, n_pass > 1 ? (uint64_t *)ex->bounds.p : nullptr));
+                launches += 2;
+            }
+        }
+    }
+    qmx_counters &c = ex->last_counters;
+    c.vectors_scored = (d_ids ? n_examples * n_ids : entries) * n_pass;
+    c.bytes_read = d_ids ? 0 : entries * 8 * n_pass;      // posting entries (id, weight) of every example; the id-list path reads rows of unknown length
+    c.kernel_launches = launches;
+    if (!out_dev) QMX_TRY(copy_out(ex->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
+    if (!cnt_dev) QMX_TRY(copy_out(ex->stream, out_counts, d_counts, (size_t)n_queries * 4));
+    QMX_TRY(check_err_flag(ex));      // synchronises
+    if (counters) *counters = c;
+    if (timed) {
+        const float before = ex->timing_ms;
+        QMX_TRY(timing_fold(ex));
+        if (counters) counters->kernel_ms = ex->timing_ms - before;
+    }
     return QMX_OK;
 }
 

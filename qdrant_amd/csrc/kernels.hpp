@@ -513,5 +513,16 @@ int32_t launch_sparse_topk_postings(hipStream_t st, const uint64_t *post, const 
                                     const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists);
 int32_t launch_sparse_topk_ids(hipStream_t st, const SparseRows &r, const SparseQueries &qs, uint32_t q0, uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids,
                                const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists);
+// custom queries over sparse vectors: `ex` / `plan` are the example batch's lists and posting plan in ascending ORIGINAL index order, `desc` and
+// `coefs` device arrays (descriptors of the whole request, the feedback coefficients)
+uint32_t sparse_custom_tile_ids();
+int32_t launch_sparse_custom_score(hipStream_t st, const SparseRows &r, const SparseQueries &ex, const qmx_custom_query *desc, const float *coefs, uint32_t nq,
+                                   const uint32_t *ids, uint64_t n, float *scores, int *err);
+int32_t launch_sparse_custom_topk_postings(hipStream_t st, const uint64_t *post, const SparsePlan &plan, const qmx_custom_query *desc, const float *coefs,
+                                           uint32_t q0, uint32_t nq_tile, uint64_t n_scan, const DeletedView &del, uint32_t top, const uint64_t *key_bound,
+                                           uint64_t *partial, uint32_t *n_lists);
+int32_t launch_sparse_custom_topk_ids(hipStream_t st, const SparseRows &r, const SparseQueries &ex, const qmx_custom_query *desc, const float *coefs, uint32_t q0,
+                                      uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids, const DeletedView &del, uint32_t top, const uint64_t *key_bound,
+                                      uint64_t *partial, uint32_t *n_lists);
 
 }  // namespace qmx

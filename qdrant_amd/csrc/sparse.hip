@@ -1,9 +1,11 @@
 // sparse.hip — sparse vectors (QMX_DTYPE_SPARSE) on the device: the create-time preparation of a segment (row checks, row sort, remap,
 // the dimension-major posting layout), the gather scorer of RawScorer (`score_vectors`, lib/sparse/src/common/sparse_vector.rs:66-90)
-// and the posting-list top-k of Nearest search (the GPU form of `advance_batch`, lib/sparse/src/index/search_context.rs:146-187).
+// the posting-list top-k of Nearest search (the GPU form of `advance_batch`, lib/sparse/src/index/search_context.rs:146-187), and the custom
+// queries (recommend / discover / context / feedback) over the same rows and postings (`SparseCustomQueryScorer`).
 //
 // Every score is the reference's sum: the products of the shared dimensions, each rounded (`__fmul_rn`), added in ascending dimension
 // order from 0.0, each add rounded (`__fadd_rn`).  No fused multiply-add, no atomics on scores.
+#include "custom_combine.hpp"
 #include "kernels.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -286,6 +288,48 @@ __device__ __forceinline__ void sparse_block_emit(uint64_t list, int top, uint32
     }
 }
 
+// The posting walk of one wave over one chunk of a plan: entries c .. c + nc (nc <= SPT_CHUNK) of `plan`, in that order.  The lanes first find the
+// posting sub-range of their entry's dimension (one binary search per lane), then the wave adds weight x query weight of each dimension's entries that
+// fall into [sub_lo, sub_hi) into the accumulators wacc[id - sub_lo], 64 entries per step; HIT: the overlap bit of every touched id is set in whit.
+// Ids are distinct inside one posting list and a wave's LDS operations complete in order, so every accumulator sees the plan's dimensions one after
+// the other.
+template <bool HIT>
+__device__ __forceinline__ void sparse_walk_chunk(const uint64_t *post, const SparsePlan &plan, uint32_t c, uint32_t nc, uint64_t sub_lo, uint64_t sub_hi,
+                                                  float *wacc, uint32_t *whit, int lane) {
+    uint64_t lo = 0, hi = 0;
+    float w = 0.0f;
+    if ((uint32_t)lane < nc) {   // lower_bound(sub_lo) in the dimension's posting list
+        uint64_t a = plan.start[c + lane], b = plan.end[c + lane];
+        hi = b;
+        w = plan.w[c + lane];
+        while (a < b) {
+            const uint64_t m = (a + b) >> 1;
+            if ((uint32_t)post[m] < sub_lo) a = m + 1;
+            else b = m;
+        }
+        lo = a;
+    }
+    for (uint32_t j = 0; j < nc; ++j) {
+        uint64_t p = readlane_u64(lo, (int)j);
+        const uint64_t e = readlane_u64(hi, (int)j);
+        const float qv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), (int)j));
+        while (p < e) {
+            const uint64_t i = p + lane;
+            uint64_t ent = ~0ull;
+            if (i < e) ent = post[i];
+            const uint32_t id = (uint32_t)ent;
+            const bool in = i < e && id < sub_hi;
+            if (in) {
+                const uint32_t k = id - (uint32_t)sub_lo;
+                wacc[k] = __fadd_rn(wacc[k], __fmul_rn(__uint_as_float((uint32_t)(ent >> 32)), qv));
+                if (HIT) atomicOr(&whit[k >> 5], 1u << (k & 31));
+            }
+            if (__ballot(in) != ~0ull) break;
+            p += WAVE;
+        }
+    }
+}
+
 // Nearest over the posting layout.  Work-group (x, y): point ids [x * SPT_TILE, (x + 1) * SPT_TILE) for query q0 + y; wave w owns the
 // SPT_SUB ids from x * SPT_TILE + w * SPT_SUB with its accumulators and overlap bits in LDS.  The query's dimensions are visited in ascending
 // order; for each, the lanes of the wave first find the posting sub-range of their dimension (64 dimensions at a time, one binary search per
@@ -311,41 +355,8 @@ __global__ __launch_bounds__(SP_BLOCK) void sparse_topk_postings_kernel(const ui
     for (uint32_t k = lane; k < SPT_SUB; k += WAVE) wacc[k] = 0.0f;
     for (uint32_t k = lane; k < SPT_SUB / 32; k += WAVE) whit[k] = 0u;
     const uint32_t d0 = plan.off[qi], d1 = plan.off[qi + 1];
-    for (uint32_t c = d0; c < d1 && sub_lo < sub_hi; c += SPT_CHUNK) {
-        const uint32_t nc = d1 - c < SPT_CHUNK ? d1 - c : SPT_CHUNK;
-        uint64_t lo = 0, hi = 0;
-        float w = 0.0f;
-        if ((uint32_t)lane < nc) {   // lower_bound(sub_lo) in the dimension's posting list
-            uint64_t a = plan.start[c + lane], b = plan.end[c + lane];
-            hi = b;
-            w = plan.w[c + lane];
-            while (a < b) {
-                const uint64_t m = (a + b) >> 1;
-                if ((uint32_t)post[m] < sub_lo) a = m + 1;
-                else b = m;
-            }
-            lo = a;
-        }
-        for (uint32_t j = 0; j < nc; ++j) {
-            uint64_t p = readlane_u64(lo, (int)j);
-            const uint64_t e = readlane_u64(hi, (int)j);
-            const float qv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), (int)j));
-            while (p < e) {
-                const uint64_t i = p + lane;
-                uint64_t ent = ~0ull;
-                if (i < e) ent = post[i];
-                const uint32_t id = (uint32_t)ent;
-                const bool in = i < e && id < sub_hi;
-                if (in) {
-                    const uint32_t k = id - (uint32_t)sub_lo;
-                    wacc[k] = __fadd_rn(wacc[k], __fmul_rn(__uint_as_float((uint32_t)(ent >> 32)), qv));
-                    atomicOr(&whit[k >> 5], 1u << (k & 31));
-                }
-                if (__ballot(in) != ~0ull) break;
-                p += WAVE;
-            }
-        }
-    }
+    for (uint32_t c = d0; c < d1 && sub_lo < sub_hi; c += SPT_CHUNK)
+        sparse_walk_chunk<true>(post, plan, c, d1 - c < SPT_CHUNK ? d1 - c : SPT_CHUNK, sub_lo, sub_hi, wacc, whit, lane);
     uint64_t list = 0;
     for (uint32_t k0 = 0; k0 < SPT_SUB; k0 += WAVE) {
         const uint32_t k = k0 + lane;
@@ -401,6 +412,130 @@ __global__ __launch_bounds__(SP_BLOCK) void sparse_topk_ids_kernel(SparseRows r,
     sparse_block_emit(list, (int)top, blockIdx.x, ql, nq_tile, partial);
 }
 
+// ---- custom queries (SparseCustomQueryScorer, lib/segment/src/vector_storage/query_scorer/sparse_custom_query_scorer.rs) ----
+// score(point) = query.score_by(|example| score_vectors(example, point).unwrap_or(0.0)): every live candidate has a score, overlap or not.  The
+// scorer works on the vector STORAGE, not on the index: each example's sum runs in ascending ORIGINAL index order, whatever the IndicesTracker
+// made of the ids.  The example batch therefore carries its lists and its posting plan a second time in that order (SparseQueries / SparsePlan
+// handed to the kernels below are those).
+
+// score_vectors of an example with a stored row, the example's dimensions in the order its list has them: `ei` holds the remapped ids, the row is
+// sorted by remapped id, so each example dimension is looked up by binary search.  The sum starts at +0.0 and is never assigned: it cannot be -0.0.
+__device__ __forceinline__ float sparse_dot_lookup(const uint32_t *ri, const float *rv, uint32_t rn, const uint32_t *ei, const float *ev, uint32_t en) {
+    float s = 0.0f;
+    for (uint32_t k = 0; k < en; ++k) {
+        const uint32_t d = ei[k];
+        uint32_t a = 0, b = rn;
+        while (a < b) {
+            const uint32_t m = (a + b) >> 1;
+            if (ri[m] < d) a = m + 1;
+            else b = m;
+        }
+        if (a < rn && ri[a] == d) s = __fadd_rn(s, __fmul_rn(rv[a], ev[k]));
+    }
+    return s;
+}
+
+// one custom query against one stored row (id < r.n)
+__device__ __forceinline__ float sparse_custom_score(const SparseRows &r, const SparseQueries &ex, const qmx_custom_query &cq, const float *coefs, uint32_t id) {
+    const uint64_t ro = r.off[id];
+    const uint32_t rn = (uint32_t)(r.off[id + 1] - ro);
+    return custom_score_by(cq.kind, cq.n_a, cq.n_b, coefs + cq.coef_first, [&](uint32_t e) {
+        const uint64_t eo = ex.off[cq.first + e];
+        return sparse_dot_lookup(r.idx + ro, r.val + ro, rn, ex.idx + eo, ex.val + eo, (uint32_t)(ex.off[cq.first + e + 1] - eo));
+    });
+}
+
+// RawScorer::score_points: scores[qi * n + i] = custom query qi against row ids[i]; one thread per (query, id)
+__global__ __launch_bounds__(SP_BLOCK) void sparse_custom_score_kernel(SparseRows r, SparseQueries ex, const qmx_custom_query *desc, const float *coefs,
+                                                                       const uint32_t *ids, uint64_t n, float *scores, int *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t qi = blockIdx.y, id = ids[i];
+    float s = 0.0f;
+    if (id >= r.n) *err = 1;
+    else s = sparse_custom_score(r, ex, desc[qi], coefs, id);
+    scores[(uint64_t)qi * n + i] = s;
+}
+
+// search_scored over an id list: block (x, y) scores a grid-strided slice of the ids against custom query q0 + y and keeps the live, allowed ones
+__global__ __launch_bounds__(SP_BLOCK) void sparse_custom_topk_ids_kernel(SparseRows r, SparseQueries ex, const qmx_custom_query *desc, const float *coefs,
+                                                                          uint32_t q0, uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids, DeletedView del,
+                                                                          uint32_t top, const uint64_t *key_bound, uint64_t *partial) {
+    const uint32_t ql = blockIdx.y, qi = q0 + ql;
+    const int lane = threadIdx.x & 63;
+    const uint64_t bound = key_bound ? key_bound[ql] : 0;
+    if (key_bound && bound == 0) {
+        if (threadIdx.x < top) partial[((uint64_t)blockIdx.x * nq_tile + ql) * top + threadIdx.x] = 0;
+        return;
+    }
+    const qmx_custom_query cq = desc[qi];
+    uint64_t list = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * SP_BLOCK; base < n_ids; base += (uint64_t)gridDim.x * SP_BLOCK) {
+        const uint64_t i = base + threadIdx.x;
+        uint64_t key = 0;
+        if (i < n_ids) {
+            const uint32_t id = ids[i];
+            if (id < r.n && del.live(id)) key = make_key(sparse_custom_score(r, ex, cq, coefs, id), id);
+        }
+        if (key_bound && key >= bound) key = 0;
+        wave_offer(list, key, (int)top, lane);
+    }
+    sparse_block_emit(list, (int)top, blockIdx.x, ql, nq_tile, partial);
+}
+
+// search_scored over every point, fused on the posting layout.  Work-group (x, y) and its waves own point ids as in sparse_topk_postings_kernel
+// (SPC_SUB ids per wave).  For each example of custom query q0 + y, in flat_iter() order: the wave zeroes its accumulators, walks the example's
+// posting plan (sparse_walk_chunk: the similarity of the example with every point of the sub-range), and folds the finished similarities into the
+// points' score_by states (custom_step).  Lane l folds the points l, l + 64, ... of the sub-range - a static mapping, so the SPC_SUB / 64 states of
+// a lane stay in registers through fully unrolled loops and the LDS holds the accumulators only.  After the last example the scores are finished,
+// and every live, allowed point (no overlap needed) below the pass's bound is offered to the wave's key list.
+constexpr uint32_t SPC_SUB = 1024;                        // point ids per wave: half the Nearest kernel's (measured: DESIGN 3.9)
+constexpr uint32_t SPC_TILE = SPC_SUB * SPT_WAVES;        // ids per work-group: 16 KiB of accumulators
+constexpr uint32_t SPC_LANE_IDS = SPC_SUB / WAVE;
+uint32_t sparse_custom_tile_ids() { return SPC_TILE; }
+__global__ __launch_bounds__(SP_BLOCK) void sparse_custom_topk_postings_kernel(const uint64_t *post, SparsePlan plan, const qmx_custom_query *desc,
+                                                                               const float *coefs, uint32_t q0, uint32_t nq_tile, uint64_t n_scan,
+                                                                               DeletedView del, uint32_t top, const uint64_t *key_bound, uint64_t *partial) {
+    __shared__ float acc[SPC_TILE];
+    const uint32_t tile = blockIdx.x, ql = blockIdx.y, qi = q0 + ql;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t bound = key_bound ? key_bound[ql] : 0;
+    if (key_bound && bound == 0) {   // the query was exhausted by an earlier pass
+        if (threadIdx.x < top) partial[((uint64_t)tile * nq_tile + ql) * top + threadIdx.x] = 0;
+        return;
+    }
+    const uint64_t sub_lo = (uint64_t)tile * SPC_TILE + (uint64_t)wave * SPC_SUB;
+    const uint64_t sub_hi = sub_lo + SPC_SUB < n_scan ? sub_lo + SPC_SUB : n_scan;
+    float *wacc = acc + wave * SPC_SUB;
+    const qmx_custom_query cq = desc[qi];
+    const float *cf = coefs + cq.coef_first;
+    const uint32_t ne = custom_examples(cq.kind, cq.n_a, cq.n_b);
+    CustomState st[SPC_LANE_IDS];
+#pragma unroll
+    for (uint32_t u = 0; u < SPC_LANE_IDS; ++u) st[u] = custom_init(cq.kind);
+    for (uint32_t e = 0; e < ne && sub_lo < sub_hi; ++e) {
+#pragma unroll
+        for (uint32_t u = 0; u < SPC_LANE_IDS; ++u) wacc[u * WAVE + lane] = 0.0f;
+        const uint32_t d0 = plan.off[cq.first + e], d1 = plan.off[cq.first + e + 1];
+        for (uint32_t c = d0; c < d1; c += SPT_CHUNK)
+            sparse_walk_chunk<false>(post, plan, c, d1 - c < SPT_CHUNK ? d1 - c : SPT_CHUNK, sub_lo, sub_hi, wacc, nullptr, lane);
+#pragma unroll
+        for (uint32_t u = 0; u < SPC_LANE_IDS; ++u) custom_step(cq.kind, cq.n_a, cf, st[u], e, wacc[u * WAVE + lane]);
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < SPC_LANE_IDS; ++u) wacc[u * WAVE + lane] = custom_finish(cq.kind, st[u]);
+    uint64_t list = 0;
+    for (uint32_t k0 = 0; k0 < SPC_SUB; k0 += WAVE) {
+        const uint32_t k = k0 + lane;
+        const uint64_t id = sub_lo + k;
+        uint64_t key = 0;
+        if (id < sub_hi && del.live((uint32_t)id)) key = make_key(wacc[k], (uint32_t)id);
+        if (key_bound && key >= bound) key = 0;
+        wave_offer(list, key, (int)top, lane);
+    }
+    sparse_block_emit(list, (int)top, tile, ql, nq_tile, partial);
+}
+
 int32_t launch_sparse_topk_postings(hipStream_t st, const uint64_t *post, const SparsePlan &plan, uint32_t q0, uint32_t nq_tile, uint64_t n_scan,
                                     const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists) {
     const uint64_t tiles = (n_scan + SPT_TILE - 1) / SPT_TILE;
@@ -423,6 +558,46 @@ int32_t launch_sparse_topk_ids(hipStream_t st, const SparseRows &r, const Sparse
     ::qmx::clear_stale_error();
     hipLaunchKernelGGL(sparse_topk_ids_kernel, dim3(*n_lists, nq_tile), dim3(SP_BLOCK), 0, st, r, qs, q0, nq_tile, ids, n_ids, del, top, key_bound, partial);
     QMX_NOTE_KERNEL(sparse_topk_ids_kernel);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+
+int32_t launch_sparse_custom_score(hipStream_t st, const SparseRows &r, const SparseQueries &ex, const qmx_custom_query *desc, const float *coefs, uint32_t nq,
+                                   const uint32_t *ids, uint64_t n, float *scores, int *err) {
+    if (n == 0 || nq == 0) return QMX_OK;
+    ::qmx::clear_stale_error();
+    for (uint32_t y0 = 0; y0 < nq; y0 += 65535) {
+        const uint32_t ny = std::min<uint32_t>(65535, nq - y0);
+        hipLaunchKernelGGL(sparse_custom_score_kernel, dim3(blocks_of(n), ny), dim3(SP_BLOCK), 0, st, r, ex, desc + y0, coefs, ids, n, scores + (uint64_t)y0 * n, err);
+        QMX_NOTE_KERNEL(sparse_custom_score_kernel);
+    }
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_custom_topk_postings(hipStream_t st, const uint64_t *post, const SparsePlan &plan, const qmx_custom_query *desc, const float *coefs,
+                                           uint32_t q0, uint32_t nq_tile, uint64_t n_scan, const DeletedView &del, uint32_t top, const uint64_t *key_bound,
+                                           uint64_t *partial, uint32_t *n_lists) {
+    const uint64_t tiles = (n_scan + SPC_TILE - 1) / SPC_TILE;
+    *n_lists = (uint32_t)tiles;
+    if (tiles == 0 || nq_tile == 0) return QMX_OK;
+    QMX_REQUIRE(nq_tile <= 65535, QMX_ERR_OTHER, "query tile too large");
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_custom_topk_postings_kernel, dim3((uint32_t)tiles, nq_tile), dim3(SP_BLOCK), 0, st, post, plan, desc, coefs, q0, nq_tile, n_scan, del,
+                       top, key_bound, partial);
+    QMX_NOTE_KERNEL(sparse_custom_topk_postings_kernel);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_custom_topk_ids(hipStream_t st, const SparseRows &r, const SparseQueries &ex, const qmx_custom_query *desc, const float *coefs, uint32_t q0,
+                                      uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids, const DeletedView &del, uint32_t top, const uint64_t *key_bound,
+                                      uint64_t *partial, uint32_t *n_lists) {
+    *n_lists = sparse_ids_lists(n_ids);
+    if (nq_tile == 0) return QMX_OK;
+    QMX_REQUIRE(nq_tile <= 65535, QMX_ERR_OTHER, "query tile too large");
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_custom_topk_ids_kernel, dim3(*n_lists, nq_tile), dim3(SP_BLOCK), 0, st, r, ex, desc, coefs, q0, nq_tile, ids, n_ids, del, top, key_bound,
+                       partial);
+    QMX_NOTE_KERNEL(sparse_custom_topk_ids_kernel);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }

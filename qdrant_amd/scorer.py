@@ -811,12 +811,27 @@ def new_raw_scorer_internal(point_ids, storage: VectorStorage) -> RawScorer:
     return scorer
 
 
+def _is_sparse_example(v) -> bool:
+    """An (indices, values) pair - two sequences - where a dense example is one sequence of numbers."""
+    return isinstance(v, (tuple, list)) and len(v) == 2 and np.ndim(v[0]) == 1 and np.ndim(v[1]) == 1
+
+
 class CustomQuery:
     """One `QueryVector::{RecommendBestScore, RecommendSumScores, Discover, Context}` (vector_storage/query/*.rs);
-    vectors are ORIGINAL (un-preprocessed) f32, as for `new_raw_scorer`."""
+    vectors are ORIGINAL (un-preprocessed) f32, as for `new_raw_scorer`.  Over a SparseVectorStorage the examples are sparse vectors:
+    (indices, values) pairs where dense examples are vectors.  `sparse`: True / False, None for a query without examples."""
 
     def __init__(self, kind: int, examples, n_a: int, n_b: int, coefs=None):
-        self.kind, self.examples, self.n_a, self.n_b = kind, [np.asarray(v, dtype=np.float32) for v in examples], n_a, n_b
+        examples = list(examples)
+        kinds = {_is_sparse_example(v) for v in examples}
+        if len(kinds) > 1:
+            raise ValueError("a custom query mixes dense and sparse examples")
+        self.sparse = kinds.pop() if kinds else None
+        if self.sparse:
+            examples = [(np.asarray(ix, dtype=np.uint32), np.asarray(vx, dtype=np.float32)) for ix, vx in examples]
+        else:
+            examples = [np.asarray(v, dtype=np.float32) for v in examples]
+        self.kind, self.examples, self.n_a, self.n_b = kind, examples, n_a, n_b
         self.coefs = None if coefs is None else np.asarray(coefs, dtype=np.float32)
 
     @classmethod
@@ -855,10 +870,18 @@ class CustomQuery:
 
 class CustomRawScorer:
     """`new_raw_scorer(QueryVector::<custom>, storage)` for a batch of custom queries (raw_scorer.rs:60-114 ->
-    CustomQueryScorer): all example vectors form one device query batch, every custom query is a slice of it."""
+    CustomQueryScorer): all example vectors form one device query batch, every custom query is a slice of it.
+    Over a SparseVectorStorage (raw_sparse_scorer_impl -> SparseCustomQueryScorer) the examples are sparse vectors and `peek_top` is
+    `search_scored` (sparse_vector_index/read_view/search.rs:99-151): every live point is a candidate, overlap or not."""
 
     def __init__(self, queries: Sequence[CustomQuery], storage: VectorStorage):
         self.storage = storage
+        self.sparse = isinstance(storage, SparseVectorStorage)
+        kinds = {q.sparse for q in queries if q.sparse is not None}
+        if len(kinds) > 1:
+            raise ValueError("dense and sparse examples in one scorer")
+        if kinds and kinds.pop() != self.sparse:
+            raise ValueError("sparse examples need a SparseVectorStorage, dense examples a dense storage")
         flat, descs, first, coefs = [], (F.CustomQuery * len(queries))(), 0, []
         for i, q in enumerate(queries):
             descs[i].kind, descs[i].first, descs[i].n_a, descs[i].n_b, descs[i].coef_first = q.kind, first, q.n_a, q.n_b, len(coefs)
@@ -867,7 +890,10 @@ class CustomRawScorer:
             if q.coefs is not None:
                 coefs += q.coefs.tolist()
         self._descs, self.nq = descs, len(queries)
-        self.examples = new_raw_scorer(np.stack(flat) if flat else np.zeros((0, storage.dim), dtype=np.float32), storage)
+        if self.sparse:
+            self.examples = storage._raw_scorer(flat)
+        else:
+            self.examples = new_raw_scorer(np.stack(flat) if flat else np.zeros((0, storage.dim), dtype=np.float32), storage)
         if coefs:
             cf = np.asarray(coefs, dtype=np.float32)
             F.check(F.lib().qmx_custom_set_coefficients(self.examples._h, F.ptr(cf), len(cf)))
@@ -875,13 +901,19 @@ class CustomRawScorer:
     def score_points(self, points: Sequence[int]) -> np.ndarray:
         ids = np.ascontiguousarray(points, dtype=np.uint32)
         out = np.empty((self.nq, len(ids)), dtype=np.float32)
-        F.check(F.lib().qmx_custom_score_points(self.examples._h, self._descs, self.nq, F.ptr(ids), len(ids), F.ptr(out)))
+        score = F.lib().qmx_sparse_custom_score_points if self.sparse else F.lib().qmx_custom_score_points
+        F.check(score(self.examples._h, self._descs, self.nq, F.ptr(ids), len(ids), F.ptr(out)))
         return out
 
     def peek_top(self, top: int, points=None) -> List[np.ndarray]:
         out = np.zeros((self.nq, top), dtype=ScoredPointOffset)
         counts = np.zeros(self.nq, dtype=np.uint32)
         ids = None if points is None else np.ascontiguousarray(points, dtype=np.uint32)
+        if self.sparse:
+            self.counters = F.Counters()
+            F.check(F.lib().qmx_sparse_custom_search_topk(self.examples._h, self._descs, self.nq, top, F.ptr(ids), 0 if ids is None else len(ids),
+                                                          F.ptr(out), F.ptr(counts), None, C.byref(self.counters)))
+            return [out[i, :counts[i]].copy() for i in range(self.nq)]
         F.check(F.lib().qmx_custom_search_topk(self.examples._h, self._descs, self.nq, top, F.ptr(ids), 0 if ids is None else len(ids),
                                                F.ptr(out), F.ptr(counts)))
         return [out[i, :counts[i]].copy() for i in range(self.nq)]
@@ -889,6 +921,8 @@ class CustomRawScorer:
     def search_hnsw(self, graph, top: int, ef: int, with_scored: bool = False):
         """`GraphLayers::search(top, ef, Hnsw, points_scorer = the custom scorer)` for every custom query of the batch, on device
         (qmx_custom_hnsw_search): dense, SQ, PQ, BQ and TurboQuant storages."""
+        if self.sparse:
+            raise NotImplementedError("no HNSW over sparse vectors (the reference has none either)")
         out = np.zeros((self.nq, max(top, 1)), dtype=ScoredPointOffset)
         counts = np.zeros(self.nq, dtype=np.uint32)
         ctr = F.Counters()

@@ -5,7 +5,12 @@ Data (generated on the device with torch, seeded): `--points` rows of about `--n
 a Zipf law (p(rank k) ~ 1 / k), duplicates per row dropped, positive log-normal weights; queries of about `--qnnz` non-zeros from the same law.
 Reports, per batch size Q: ms per batch and QPS; the posting bytes the batch touches (sum over the queries of len(d) x 8 B for each of their
 dimensions d) with their GB/s and the fraction of 8 TB/s; the CSR block size; the segment create time (row checks + the posting transpose).
-One JSON line per run on stdout; `--out` also writes it to a file."""
+One JSON line per run on stdout; `--out` also writes it to a file.
+
+`--custom KIND:EXAMPLES` (reco_best, reco_sum, discover, context, feedback; for instance `reco_best:7`, `discover:7`): per batch size Q, Q custom
+queries of that many examples each through qmx_sparse_custom_search_topk over the same segment - ms per batch, QPS, the posting bytes of all
+examples with their GB/s and fraction of 8 TB/s - and beside them the Nearest search of the same Q x EXAMPLES example vectors as plain queries
+(same process, same segment): a custom query of E examples reads the postings E plain queries read."""
 import argparse
 import ctypes as C
 import json
@@ -46,6 +51,44 @@ def sample_rows(gen, cdf, perm, n_rows, nnz, dev):
     return lens, dims, w
 
 
+CUSTOM_KINDS = {"reco_best": F.CUSTOM_RECO_BEST_SCORE, "reco_sum": F.CUSTOM_RECO_SUM_SCORES, "discover": F.CUSTOM_DISCOVER,
+                "context": F.CUSTOM_CONTEXT, "feedback": F.CUSTOM_FEEDBACK}
+
+
+def custom_descriptors(spec, nq):
+    """`KIND:EXAMPLES` -> (descriptors of nq queries over nq x EXAMPLES examples back to back, EXAMPLES, feedback coefficients or None)."""
+    name, _, count = spec.partition(":")
+    if name not in CUSTOM_KINDS or not count.isdigit() or int(count) < 1:
+        raise SystemExit("--custom wants KIND:EXAMPLES with KIND one of %s" % ", ".join(CUSTOM_KINDS))
+    kind, ne = CUSTOM_KINDS[name], int(count)
+    if kind <= F.CUSTOM_RECO_SUM_SCORES:
+        n_a, n_b = (ne + 1) // 2, ne // 2
+    elif kind == F.CUSTOM_CONTEXT:
+        if ne % 2:
+            raise SystemExit("a context query has pairs only: an even number of examples")
+        n_a, n_b = 0, ne // 2
+    else:
+        if ne % 2 == 0:
+            raise SystemExit("a %s query has a target and pairs: an odd number of examples" % name)
+        n_a, n_b = 1, ne // 2
+    descs = (F.CustomQuery * nq)()
+    for i in range(nq):
+        descs[i].kind, descs[i].first, descs[i].n_a, descs[i].n_b, descs[i].coef_first = kind, i * ne, n_a, n_b, i * (1 + n_b)
+    coefs = np.tile(np.array([0.5] + [0.1] * n_b, dtype=np.float32), nq) if kind == F.CUSTOM_FEEDBACK else None
+    return descs, ne, coefs
+
+
+def timed(call, warmup, steps):
+    for _ in range(warmup):
+        call()
+    times = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        call()
+        times.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(times))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -57,6 +100,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=20241016)
+    ap.add_argument("--custom", default=None, metavar="KIND:EXAMPLES", help="custom queries instead of Nearest, e.g. reco_best:7, discover:7")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -89,6 +133,36 @@ def main():
     qgen.manual_seed(args.seed + 1)
     results = []
     for nq in [int(x) for x in args.batches.split(",")]:
+        if args.custom:
+            descs, ne, coefs = custom_descriptors(args.custom, nq)
+            ql, qd, qw = sample_rows(qgen, cdf, perm, nq * ne, args.qnnz, dev)
+            qoff = np.zeros(nq * ne + 1, dtype=np.uint64)
+            qoff[1:] = np.cumsum(ql.cpu().numpy())
+            qidx = qd.cpu().numpy().astype(np.uint32)
+            qval = qw.cpu().numpy()
+            h = C.c_void_p()
+            F.check(F.lib().qmx_sparse_query_create(st._h, F.ptr(qoff), F.ptr(qidx), F.ptr(qval), nq * ne, C.byref(h)))
+            if coefs is not None:
+                F.check(F.lib().qmx_custom_set_coefficients(h, F.ptr(coefs), len(coefs)))
+            out = np.zeros((nq, args.top), dtype=qa.ScoredPointOffset)
+            counts = np.zeros(nq, dtype=np.uint32)
+            ctr = F.Counters()
+            ms = timed(lambda: F.check(F.lib().qmx_sparse_custom_search_topk(h, descs, nq, args.top, None, 0, F.ptr(out), F.ptr(counts), None,
+                                                                             C.byref(ctr))), args.warmup, args.steps)
+            # the same example vectors as plain queries: what the fusion is measured against
+            nout = np.zeros((nq * ne, args.top), dtype=qa.ScoredPointOffset)
+            ncounts = np.zeros(nq * ne, dtype=np.uint32)
+            nctr = F.Counters()
+            nms = timed(lambda: F.check(F.lib().qmx_search_topk(h, args.top, None, 0, F.ptr(nout), F.ptr(ncounts), None, C.byref(nctr))),
+                        args.warmup, args.steps)
+            F.lib().qmx_query_destroy(h)
+            post_bytes = int(ctr.bytes_read)
+            gbs = post_bytes / (ms * 1e-3) / 1e9
+            results.append({"queries": nq, "examples_per_query": ne, "ms_per_batch": round(ms, 3), "qps": round(nq / (ms * 1e-3), 1),
+                            "posting_bytes": post_bytes, "posting_gb_per_s": round(gbs, 1), "hbm_fraction": round(gbs * 1e9 / HBM_BYTES_PER_S, 4),
+                            "mean_results": float(counts.mean()), "nearest_queries": nq * ne, "nearest_ms_per_batch": round(nms, 3),
+                            "nearest_posting_bytes": int(nctr.bytes_read), "custom_over_nearest": round(ms / nms, 3)})
+            continue
         ql, qd, qw = sample_rows(qgen, cdf, perm, nq, args.qnnz, dev)
         qoff = np.zeros(nq + 1, dtype=np.uint64)
         qoff[1:] = np.cumsum(ql.cpu().numpy())
@@ -116,6 +190,8 @@ def main():
     rec = {"tool": "bench_sparse", "points": args.points, "dims": args.dims, "nnz": nnz, "mean_row_nnz": round(nnz / args.points, 2),
            "qnnz": args.qnnz, "top": args.top, "csr_bytes": csr_bytes, "posting_layout_bytes": nnz * 8, "create_s": round(create_s, 3),
            "device": torch.cuda.get_device_name(0), "batches": results}
+    if args.custom:
+        rec["custom"] = args.custom
     line = json.dumps(rec)
     print(line)
     if args.out:
