@@ -731,6 +731,71 @@ QMX_API int32_t qmx_sharded_hnsw_search(const qmx_hnsw *const *graphs, qmx_query
  * segment's device). */
 QMX_API int32_t qmx_sharded_query_update(qmx_query *const *queries, uint32_t n_segments, const float *batch);
 
+/* ---- hybrid queries: fusion of prefetch lists, MMR re-ranking ---------------------------------- */
+
+typedef enum qmx_fusion_kind {
+    QMX_FUSION_RRF = 0,  /* rrf_scoring (lib/segment/src/common/reciprocal_rank_fusion.rs:54-99) */
+    QMX_FUSION_DBSF = 1  /* score_fusion(ScoreFusion::dbsf()) (lib/segment/src/common/score_fusion.rs:23-94) */
+} qmx_fusion_kind;
+
+typedef struct qmx_fusion_params {
+    uint32_t kind;         /* qmx_fusion_kind */
+    uint32_t rrf_k;        /* RRF: the K parameter (DEFAULT_RRF_K = 2, reciprocal_rank_fusion.rs:14); unused by DBSF */
+    const float *weights;  /* host memory, n_weights entries, or NULL */
+    uint32_t n_weights;    /* RRF: 0 or n_sources (anything else: QMX_ERR_BAD_ARG, the invalid-argument status, as rrf_scoring rejects a length
+                              mismatch, :62-69); DBSF: missing weights are 1.0 (`chain(iter::repeat(1.0))`, score_fusion.rs:57), those past n_sources unused */
+    uint32_t top;          /* entries kept per query, 1..65536 */
+} qmx_fusion_params;
+
+/* Fusion of `n_sources` prefetch lists per query into one list (the Query API's `Fusion::Rrf` / `Fusion::Dbsf`):
+ *   lists  : [n_sources][nq][stride] ScoredPointOffset, each list as qmx_search_topk / the sparse searches return it; counts : [n_sources][nq] live
+ *            entries (clamped to stride).  Offsets are point offsets of ONE id space (the named vectors of a segment share the id tracker).
+ *   RRF    : `rrf_scoring` (reciprocal_rank_fusion.rs:54-99) with `position_score` (:32-39): 1.0 / ((pos + 1) as f32 / weight + k as f32 - 1.0), 0.0 when
+ *            weight <= 0; the input scores are not read.
+ *   DBSF   : `score_fusion` (score_fusion.rs:46-94) over `distr_norm` (:149-164): per list Welford's mean and sample variance in list order
+ *            (`welfords_mean_variance`, :126-145), extremes mean -+ 3 * sqrt(variance), `norm` (:97-109): (s - min) / (max - min), 0.5 for every
+ *            entry when min == max or the list has one entry; then * weight.
+ *   Both sum a point's contributions in source order (then list order) starting FROM its first contribution, and a duplicate id inside one list
+ *   contributes twice, as the reference's hash-map fold does.  Every step is one correctly rounded f32 operation in the reference's order: the
+ *   scores are the reference's bits.
+ *   out    : [nq][top] sorted by score descending in OrderedFloat order (NaN greatest, -0.0 == 0.0), the LOWER offset first among equal scores -
+ *            the rule of qmx_search_topk.  (The reference "does not break ties": its order among equals is the hash map's iteration order, so any
+ *            fixed rule conforms.)  out_counts : [nq] = min(top, distinct ids).
+ * n_sources <= 64 and n_sources * stride <= 8192 entries per query (they are deduplicated in LDS); beyond: QMX_ERR_NOT_SUPPORTED.  Lists of several
+ * segments are merged with qmx_merge_topk* first.  Host or device memory; runs on `device_id`. */
+QMX_API int32_t qmx_fuse_topk(int32_t device_id, const qmx_scored_point *lists, const uint32_t *counts, uint32_t n_sources, uint32_t nq,
+                              uint32_t stride, const qmx_fusion_params *params, qmx_scored_point *out, uint32_t *out_counts);
+/* Same, but only enqueues on `hip_stream`; every list / count / output buffer in device memory (`params` and its weights are read before the
+ * call returns). */
+QMX_API int32_t qmx_fuse_topk_async(int32_t device_id, void *hip_stream, const qmx_scored_point *lists_dev, const uint32_t *counts_dev,
+                                    uint32_t n_sources, uint32_t nq, uint32_t stride, const qmx_fusion_params *params,
+                                    qmx_scored_point *out_dev, uint32_t *out_counts_dev);
+
+/* Maximal marginal relevance re-ranking = `mmr_from_points_with_vector` (lib/shard/src/query/mmr/mod.rs:42-100) + `maximal_marginal_relevance`
+ * (:198-279) for every request of a batch in one launch.  `q` = a Nearest batch over a dense f32 / f16 / u8 segment: query qi is the
+ * `mmr.vector` of request qi; candidates : [nq][stride] ScoredPointOffset, counts : [nq].
+ *   1. candidates are made unique by id (first occurrence stays, order kept; `unique_by`, :50-52); zero or one candidate: returned as it is (:77-80).
+ *   2. relevance of a candidate = the score of query qi for its row, the bits of the gather path (qmx_score_points_ragged / qmx_rescore; =
+ *      qmx_score_points of a batch of fewer than 8 queries).
+ *   3. sim(c, s) = candidate c as the query against stored row s (`LazyMatrix::compute_similarity`, lazy_matrix.rs:65-67), with the rows as stored:
+ *      on an f32 segment the bits of qmx_query_create_internal([c]) + qmx_score_points([s]); f16 / u8 rows are widened to f32 exactly and the
+ *      f32 metric applied, the reference's temporary storage being f32 whatever the collection's datatype (`new_volatile_dense_vector_storage`,
+ *      :113; Cosine = the dot product of the stored rows).
+ *   4. the first pick is the candidate of greatest relevance; then, while fewer than `limit` are picked and any remain, the one of greatest
+ *      lambda * relevance - (1.0 - lambda) * max over the picked s of sim(c, s) (two multiplies and one subtract, each rounded).
+ *   5. every maximum is OrderedFloat's (NaN greatest, -0.0 == 0.0) and ties go as in the reference: `max_by_key` returns the LAST maximal element
+ *      in the order of `remaining_indices`, an IndexSet filled 0..C from which every pick is taken by `swap_remove` (the last element moves
+ *      into the freed slot).
+ *   out : [nq][limit] the picked candidates in selection order with their INPUT scores (`candidates[idx].clone()`, :263-278); out_counts : [nq].
+ * stride <= 4096 candidates per request, limit >= 1; sparse and quantized segments (and multi-vector points): QMX_ERR_NOT_SUPPORTED; a candidate id
+ * past the segment's rows: QMX_ERR_OUT_OF_BOUNDS.  Host or device memory; synchronises. */
+QMX_API int32_t qmx_mmr_select(qmx_query *q, const qmx_scored_point *candidates, const uint32_t *counts, uint32_t stride, float lambda,
+                               uint32_t limit, qmx_scored_point *out, uint32_t *out_counts);
+/* Same, but only enqueues on the query's stream (qmx_query_set_stream); device memory; complete with qmx_query_synchronize.  An out-of-range id
+ * empties its request's list and is reported by the next synchronous call on this batch. */
+QMX_API int32_t qmx_mmr_select_async(qmx_query *q, const qmx_scored_point *candidates_dev, const uint32_t *counts_dev, uint32_t stride,
+                                     float lambda, uint32_t limit, qmx_scored_point *out_dev, uint32_t *out_counts_dev);
+
 /* ---- HNSW search on device -------------------------------------------------------------------- */
 
 /* One built graph = `GraphLayers` (lib/segment/src/index/hnsw_index/graph_layers.rs:58-72): the

@@ -132,6 +132,15 @@ class CustomQuery(C.Structure):
 CUSTOM_RECO_BEST_SCORE, CUSTOM_RECO_SUM_SCORES, CUSTOM_DISCOVER, CUSTOM_CONTEXT, CUSTOM_FEEDBACK = range(5)
 
 
+class FusionParams(C.Structure):
+    """qmx_fusion_params: RRF / DBSF fusion of prefetch lists (weights: host memory)."""
+    _fields_ = [("kind", C.c_uint32), ("rrf_k", C.c_uint32), ("weights", C.c_void_p), ("n_weights", C.c_uint32), ("top", C.c_uint32)]
+
+
+FUSION_RRF, FUSION_DBSF = range(2)
+FUSE_MAX_SOURCES, FUSE_MAX_ENTRIES, MMR_MAX_CANDIDATES = 64, 8192, 4096
+
+
 class QmxError(RuntimeError):
     def __init__(self, status, message):
         self.status = status
@@ -197,6 +206,10 @@ SIGNATURES = {
     "qmx_merge_topk_async": (C.c_int32, [C.c_int32, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "qmx_topk_record_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
     "qmx_merge_topk_packed_async": (C.c_int32, [C.c_int32, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
+    "qmx_fuse_topk": (C.c_int32, [C.c_int32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(FusionParams), _P, _P]),
+    "qmx_fuse_topk_async": (C.c_int32, [C.c_int32, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(FusionParams), _P, _P]),
+    "qmx_mmr_select": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
+    "qmx_mmr_select_async": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
     "qmx_sharded_search_topk": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),
     "qmx_sharded_search_topk_async": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "qmx_sharded_hnsw_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),

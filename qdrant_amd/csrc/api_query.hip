@@ -196,6 +196,8 @@ int32_t qmx_query_destroy(qmx_query *q) {
     q->cand.release();
     q->cand_cnt.release();
     q->cand_ids.release();
+    q->mmr_ids.release();
+    q->mmr_rel.release();
     q->hnsw_vis.release();
     q->hnsw_log.release();
     q->hnsw_scored.release();

@@ -525,4 +525,36 @@ int32_t launch_sparse_custom_topk_ids(hipStream_t st, const SparseRows &r, const
                                       uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids, const DeletedView &del, uint32_t top, const uint64_t *key_bound,
                                       uint64_t *partial, uint32_t *n_lists);
 
+// hybrid queries (fusion.hip): RRF / DBSF fusion of n_sources top lists per query, one work-group per query
+constexpr uint32_t FUSE_MAX_SOURCES = 64;      // the weights travel as a kernel argument
+constexpr uint32_t FUSE_MAX_ENTRIES = 8192;    // n_sources * stride per query: two u64 key arrays of that many entries in LDS (128 KiB)
+struct FuseArgs {
+    const qmx_scored_point *lists;   // [n_sources][nq][stride]
+    const uint32_t *counts;          // [n_sources][nq]
+    uint32_t n_sources, nq, stride;
+    uint32_t kind, rrf_k, n_weights, top;
+    float weights[FUSE_MAX_SOURCES];
+    qmx_scored_point *out;           // [nq][top]
+    uint32_t *out_counts;            // [nq]
+};
+int32_t launch_fuse_topk(hipStream_t st, const FuseArgs &a);
+
+// MMR re-ranking (mmr.hip): one work-group per request, `limit` selection steps inside one launch
+constexpr uint32_t MMR_MAX_CANDIDATES = 4096;  // candidates per request (20 bytes of LDS each, beside the selected row as f32)
+struct MmrArgs {
+    const void *rows;                // dense f32 / f16 / u8 block
+    uint64_t n_rows, row_stride;
+    uint32_t dim;
+    const qmx_scored_point *cand;    // [nq][stride]
+    const uint32_t *counts;          // [nq]
+    uint32_t stride;
+    const float *rel;                // [nq][stride]: relevance of the candidate at every input position
+    float lambda;
+    uint32_t limit;
+    qmx_scored_point *out;           // [nq][limit]
+    uint32_t *out_counts;            // [nq]
+    int *err_flag;                   // set to 1 on an out-of-range candidate id
+};
+int32_t launch_mmr_select(hipStream_t st, int dtype, int distance, const MmrArgs &a, uint32_t nq);
+
 }  // namespace qmx

@@ -1,0 +1,203 @@
+#!/usr/bin/env python3
+"""Hybrid queries on the device against what a caller of the previous C-ABI had to do on the host.
+
+Data: `--points` x `--dim` f32 cosine rows (the generator of bench.py) and the SPLADE-like sparse segment of tools/bench_sparse.py over the same
+points.  Per batch size Q:
+
+ (a) fused pipeline: dense search + sparse search (prefetch `--prefetch` each) + fusion to `--top`, all enqueued on one stream and synchronised
+     once (qdrant_amd.hybrid_search), against the same two searches returning their lists to the host and the numpy restatement of the fusion
+     (tests/fusion_reference.py) there.  `host_search_ms` is the host path's share spent in the two searches and their copies.
+ (b) MMR over the dense top-`--mmr-candidates` list, `limit` in `--mmr-limits`: qmx_mmr_select (one launch) against the same selection driven from
+     the host, one round per pick: new_raw_scorer_internal over the picks of all requests, score_points_ragged of the remaining candidates, the
+     arg-max in numpy.  `model_bytes` = rows the selection has to read (per request and step: the remaining candidates' rows), `effective_gb_per_s`
+     = that over the device time.
+
+One JSON line on stdout; `--out` also writes it to a file."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402  (before the library: one HIP runtime for both)
+
+import qdrant_amd as qa  # noqa: E402
+from qdrant_amd import _ffi as F  # noqa: E402
+import bench_sparse as BS  # noqa: E402
+import fusion_reference as FR  # noqa: E402  (the host side of comparison (a))
+
+
+def timed(call, warmup, steps):
+    for _ in range(warmup):
+        call()
+    times = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        call()
+        times.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(times))
+
+
+def sparse_queries(gen, cdf, perm, nq, qnnz, dev):
+    ql, qd, qw = BS.sample_rows(gen, cdf, perm, nq, qnnz, dev)
+    off = np.zeros(nq + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(ql.cpu().numpy())
+    return off, qd.cpu().numpy().astype(np.uint32), qw.cpu().numpy()
+
+
+def host_mmr(storage, scorer, cand, lambda_, limit):
+    """The selection of maximal_marginal_relevance driven from the host with the entry points the library had before qmx_mmr_select: per pick one
+    batch of internal queries (the picks of all requests) and one ragged score_points over every request's remaining candidates.  Candidate
+    lists hold distinct ids (a search result)."""
+    nq, c = cand.shape
+    ids = np.ascontiguousarray(cand["idx"])
+    rel = np.stack(scorer.score_points_ragged(list(ids)))
+    order = np.tile(np.arange(c), (nq, 1))
+    remaining = c
+    max_sim = np.zeros((nq, c), dtype=np.float32)
+    picks = np.zeros((nq, limit), dtype=np.int64)
+    rows = np.arange(nq)
+    lam, one_minus = np.float32(lambda_), np.float32(1.0) - np.float32(lambda_)
+
+    def take(scores):      # the last maximal element in the current order, then swap_remove
+        pos = remaining - 1 - np.argmax(scores[:, ::-1], axis=1)
+        chosen = order[rows, pos]
+        order[rows, pos] = order[rows, remaining - 1]
+        return chosen
+
+    picks[:, 0] = take(rel[rows[:, None], order[:, :remaining]])
+    remaining -= 1
+    for step in range(1, min(limit, c)):
+        internal = qa.new_raw_scorer_internal(ids[rows, picks[:, step - 1]], storage)
+        live = order[:, :remaining]
+        sims = np.stack(internal.score_points_ragged(list(ids[rows[:, None], live])))
+        internal.close()
+        cur = max_sim[rows[:, None], live]
+        cur = sims if step == 1 else np.where(sims >= cur, sims, cur)
+        max_sim[rows[:, None], live] = cur
+        picks[:, step] = take(lam * rel[rows[:, None], live] - one_minus * cur)
+        remaining -= 1
+    return cand[rows[:, None], picks[:, :min(limit, c)]]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--points", type=int, default=10_000_000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--sparse-dims", type=int, default=30522)
+    ap.add_argument("--nnz", type=int, default=120)
+    ap.add_argument("--qnnz", type=int, default=25)
+    ap.add_argument("--batches", default="1,32,128")
+    ap.add_argument("--prefetch", type=int, default=1000)
+    ap.add_argument("--top", type=int, default=10)
+    ap.add_argument("--mmr-candidates", type=int, default=1000)
+    ap.add_argument("--mmr-limits", default="10,100")
+    ap.add_argument("--mmr-lambda", type=float, default=0.5)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=20241016)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    lib = F.lib()
+    n, dim = args.points, args.dim
+    rows = torch.empty((n, dim), dtype=torch.float32, device=dev)
+    F.check(lib.qmx_synth_fill_f32(0, args.seed, 0, n, dim, F.ptr(rows)))
+    F.check(lib.qmx_preprocess_f32(0, int(qa.Distance.Cosine), F.ptr(rows), n, dim, F.ptr(rows)))
+    dense = qa.VectorStorage(rows, qa.Distance.Cosine)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed)
+    cdf = BS.zipf_cdf(args.sparse_dims, dev)
+    perm = torch.randperm(args.sparse_dims, generator=gen, device=dev).to(torch.int64)
+    parts = [BS.sample_rows(gen, cdf, perm, min(1_000_000, n - r0), args.nnz, dev) for r0 in range(0, n, 1_000_000)]
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(torch.cat([p[0] for p in parts]), 0)
+    sparse = qa.SparseVectorStorage(offsets, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]))
+    del parts
+    torch.cuda.empty_cache()
+    qgen = torch.Generator(device=dev)
+    qgen.manual_seed(args.seed + 1)
+    row_bytes = dim * 4
+    results = []
+    for nq in [int(x) for x in args.batches.split(",")]:
+        queries = torch.empty((nq, dim), dtype=torch.float32, device=dev)
+        F.check(lib.qmx_synth_fill_f32(0, args.seed + 2, 0, nq, dim, F.ptr(queries)))
+        queries = queries.cpu().numpy()
+        dq = qa.new_raw_scorer(queries, dense)
+        sq = qa.new_raw_scorer(sparse_queries(qgen, cdf, perm, nq, args.qnnz, dev), sparse)
+        rec = {"queries": nq}
+        # ---- (a) search + search + fuse ----
+        sources = [(dq, args.prefetch), (sq, args.prefetch)]
+        d_out = np.zeros((nq, args.prefetch), dtype=qa.ScoredPointOffset)
+        s_out = np.zeros((nq, args.prefetch), dtype=qa.ScoredPointOffset)
+        d_cnt, s_cnt = np.zeros(nq, dtype=np.uint32), np.zeros(nq, dtype=np.uint32)
+
+        def host_searches():
+            F.check(lib.qmx_search_topk(dq._h, args.prefetch, None, 0, F.ptr(d_out), F.ptr(d_cnt), None, None))
+            F.check(lib.qmx_search_topk(sq._h, args.prefetch, None, 0, F.ptr(s_out), F.ptr(s_cnt), None, None))
+            return [[d_out[i, :d_cnt[i]] for i in range(nq)], [s_out[i, :s_cnt[i]] for i in range(nq)]]
+
+        rec["host_search_ms"] = round(timed(host_searches, args.warmup, args.steps), 3)
+        for name, fusion, host_fuse in (("rrf", qa.Rrf(), lambda r: FR.rrf_scoring(r, 2, None, args.top)),
+                                        ("dbsf", qa.Dbsf(), lambda r: FR.score_fusion(r, (), args.top))):
+            got = []
+
+            def device():
+                got[:] = qa.hybrid_search(sources, fusion, args.top)
+
+            def host():
+                lists = host_searches()
+                return [host_fuse([lists[0][i], lists[1][i]]) for i in range(nq)]
+
+            dms = timed(device, args.warmup, args.steps)
+            hms = timed(host, 0, max(1, args.steps // 2))
+            want = host()
+            same = all(g["idx"].tolist() == w["idx"].tolist() and np.array_equal(g["score"].view(np.uint32), w["score"].view(np.uint32))
+                       for g, w in zip(got, want))
+            rec[name] = {"device_ms": round(dms, 3), "host_ms": round(hms, 3), "host_over_device": round(hms / dms, 2), "same_lists": bool(same)}
+        # ---- (b) MMR over the dense top list ----
+        c = args.mmr_candidates
+        cand = np.zeros((nq, c), dtype=qa.ScoredPointOffset)
+        ccnt = np.zeros(nq, dtype=np.uint32)
+        F.check(lib.qmx_search_topk(dq._h, c, None, 0, F.ptr(cand), F.ptr(ccnt), None, None))
+        assert ccnt.min() == c
+        rec["mmr"] = []
+        for limit in [int(x) for x in args.mmr_limits.split(",")]:
+            out = np.zeros((nq, limit), dtype=qa.ScoredPointOffset)
+            oc = np.zeros(nq, dtype=np.uint32)
+            dms = timed(lambda: F.check(lib.qmx_mmr_select(dq._h, F.ptr(cand), F.ptr(ccnt), c, args.mmr_lambda, limit, F.ptr(out), F.ptr(oc))),
+                        args.warmup, args.steps)
+            kernel = F.last_kernel(dq._h)
+            want = []
+
+            def host():
+                want[:] = [host_mmr(dense, dq, cand, args.mmr_lambda, limit)]
+
+            hms = timed(host, 0, max(1, args.steps // 2))
+            same = bool(np.array_equal(out["idx"], want[0]["idx"]))
+            model = nq * sum(c - i for i in range(1, limit)) * row_bytes
+            rec["mmr"].append({"candidates": c, "limit": limit, "device_ms": round(dms, 3), "host_ms": round(hms, 3), "host_over_device": round(hms / dms, 2),
+                               "same_selection": same, "model_bytes": model, "model_bytes_per_step": nq * c * row_bytes,
+                               "effective_gb_per_s": round(model / (dms * 1e-3) / 1e9, 1), "us_per_step": round(1e3 * dms / limit, 1),
+                               "kernel": kernel.split("(")[0]})
+        dq.close()
+        sq.close()
+        results.append(rec)
+    line = json.dumps({"tool": "bench_query", "points": n, "dim": dim, "sparse_dims": args.sparse_dims, "nnz": args.nnz, "qnnz": args.qnnz,
+                       "prefetch": args.prefetch, "top": args.top, "mmr_lambda": args.mmr_lambda, "device": torch.cuda.get_device_name(0),
+                       "batches": results})
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
