@@ -361,8 +361,18 @@ QMX_API int32_t qmx_segment_row_bytes(const qmx_segment *seg, uint64_t *out);
  * Served on a sparse segment / query: qmx_query_create_internal, qmx_score_points(_ragged), qmx_score_point, qmx_score_internal,
  * qmx_search_topk(_async) (Nearest: only points that share a dimension with the query, search_context.rs:92-143; `ids`, filters and
  * deleted flags as for dense; top = 0 gives empty lists), qmx_query_set_filter / set_stream / destroy, qmx_segment_set_deleted / destroy,
- * and for custom queries qmx_sparse_custom_score_points / qmx_sparse_custom_search_topk / qmx_custom_set_coefficients.
- * Every other entry point handed one: QMX_ERR_NOT_SUPPORTED. */
+ * for custom queries qmx_sparse_custom_score_points / qmx_sparse_custom_search_topk / qmx_custom_set_coefficients, and for the IDF modifier
+ * qmx_sparse_idf_statistics / qmx_sparse_query_create_idf.
+ * Every other entry point handed one: QMX_ERR_NOT_SUPPORTED.
+ *
+ * Index weights (`SparseIndexConfig.datatype`, the low bits of `flags`): the posting layout holds the weights as f32, as f16
+ * (`half::f16::from_f32`, exact widening back) or as u8 codes with (min, diff256) per posting list (`QuantizedU8`,
+ * lib/sparse/src/common/types.rs:122-165).  Nearest search - all points or an id list - reads the index and scores the DECODED weights, as
+ * `SearchContext` does; the raw scorer (qmx_score_*, rescoring) and the custom queries read the vector storage, which stays f32. */
+#define QMX_SPARSE_WEIGHT_F32 0u
+#define QMX_SPARSE_WEIGHT_F16 1u
+#define QMX_SPARSE_WEIGHT_U8 2u
+#define QMX_SPARSE_WEIGHT_MASK 3u
 typedef struct qmx_sparse_segment_desc {
     uint64_t n;                   /* rows */
     const uint64_t *offsets;      /* [n + 1] */
@@ -372,13 +382,25 @@ typedef struct qmx_sparse_segment_desc {
     const uint32_t *map_values;   /* [n_map] or NULL */
     uint64_t n_map;
     int32_t device_id;
-    uint32_t flags;               /* 0 (reserved) */
+    uint32_t flags;               /* QMX_SPARSE_WEIGHT_F32 (0) / _F16 / _U8; any other bit: QMX_ERR_BAD_ARG */
 } qmx_sparse_segment_desc;
 QMX_API int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *desc, qmx_segment **out);
 /* A batch of nq sparse queries in CSR form (host or device arrays), each sorted by index; under the segment's map each is remapped and
  * dimensions the map lacks are dropped (`remap_vector`).  Duplicate indices => QMX_ERR_BAD_ARG. */
 QMX_API int32_t qmx_sparse_query_create(const qmx_segment *seg, const uint64_t *offsets, const uint32_t *indices, const float *values, uint32_t nq,
                                         qmx_query **out);
+/* `Modifier::Idf`.  qmx_sparse_idf_statistics = `fill_idf_statistics` (sparse_vector_index/read_view/idf.rs) for this segment: df_out[i] = the
+ * document frequency of ORIGINAL dimension dims[i] (0 for one the map or the segment lacks), *n_docs_out = the document count.
+ * corpus_words == NULL: global - the whole posting length, deleted points included, and the non-empty vectors indexed.  Otherwise a corpus mask
+ * of n_corpus_bits bits over point ids (host or device): the posting entries of, and the number of, corpus points that are neither point- nor
+ * vector-deleted (empty vectors count as documents); counted on the device.  A caller sums the statistics of several segments before use.
+ * qmx_sparse_query_create_idf = `remap_idf_weights` (data_types/query_context.rs:275-299), then qmx_sparse_query_create: every value is
+ * multiplied by ln((n_docs - df + 0.5) / (df + 0.5) + 1) in f32 (libm logf on the host), df looked up by original index in stat_dims / stat_df
+ * (host arrays; a missing one is 0).  It scales every vector of the batch, so a custom query's examples too. */
+QMX_API int32_t qmx_sparse_idf_statistics(const qmx_segment *seg, const uint32_t *dims, uint32_t n, const uint64_t *corpus_words, uint64_t n_corpus_bits,
+                                          uint64_t *df_out, uint64_t *n_docs_out);
+QMX_API int32_t qmx_sparse_query_create_idf(const qmx_segment *seg, const uint64_t *offsets, const uint32_t *indices, const float *values, uint32_t nq,
+                                            const uint32_t *stat_dims, const uint64_t *stat_df, uint32_t n_stats, uint64_t n_docs, qmx_query **out);
 /* What a segment holds beside its rows: the derived copy of an f32 dot / cosine block (QMX_SEG_*_COPY flags) and, under QMX_SEG_AUTO_COPY, what the
  * trial at create measured.  (The reference's counterpart is the segment telemetry, `VectorIndexSearchesTelemetry` / `SegmentInfo`: which index and
  * quantization serve a segment is reported, not guessed.) */

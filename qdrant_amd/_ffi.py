@@ -80,6 +80,9 @@ class SegmentDesc(C.Structure):
                 ("pq", C.POINTER(PqParams)), ("bq", C.POINTER(BqParams)), ("tq", C.POINTER(TqParams))]
 
 
+SPARSE_WEIGHT_F32, SPARSE_WEIGHT_F16, SPARSE_WEIGHT_U8 = range(3)      # qmx_sparse_segment_desc.flags: the index weights' datatype
+
+
 class SparseSegmentDesc(C.Structure):
     """qmx_sparse_segment_desc: CSR rows (u64 offsets, u32 indices, f32 values) and the optional IndicesTracker map."""
     _fields_ = [("n", C.c_uint64), ("offsets", C.c_void_p), ("indices", C.c_void_p), ("values", C.c_void_p),
@@ -170,6 +173,8 @@ SIGNATURES = {
     "qmx_segment_get_info": (C.c_int32, [_P, C.POINTER(SegmentInfo)]),
     "qmx_sparse_segment_create": (C.c_int32, [C.POINTER(SparseSegmentDesc), C.POINTER(_P)]),
     "qmx_sparse_query_create": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.POINTER(_P)]),
+    "qmx_sparse_idf_statistics": (C.c_int32, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "qmx_sparse_query_create_idf": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint64, C.POINTER(_P)]),
     "qmx_preprocess_f32": (C.c_int32, [C.c_int32, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P]),
     "qmx_cast_f32": (C.c_int32, [C.c_int32, C.c_uint32, _P, C.c_uint64, _P]),
     "qmx_query_create": (C.c_int32, [_P, _P, C.c_uint32, C.POINTER(_P)]),

@@ -8,10 +8,15 @@
 // posting layout (distinct dimensions ascending, where each one's postings start) and the IndicesTracker map
 struct SparseSeg {
     uint64_t nnz = 0;
+    uint64_t n_nonempty = 0;                 // rows with at least one entry: InvertedIndex::vector_count
     uint64_t *d_off = nullptr;
     uint32_t *d_idx = nullptr;
     float *d_val = nullptr;
-    uint64_t *d_post = nullptr;              // [nnz]: (f32 weight bits << 32) | point id, grouped by dimension, ids ascending
+    uint64_t *d_post = nullptr;              // [nnz]: (f32 weight bits << 32) | point id, grouped by dimension, ids ascending (f32 index weights)
+    uint32_t wtype = QMX_SPARSE_WEIGHT_F32;  // f16 / u8 index weights: the two arrays below instead of d_post
+    uint32_t *d_post_id = nullptr;           // [nnz]
+    void *d_post_w = nullptr;                // [nnz] u16 (f16 bits) / u8 (QuantizedU8 codes)
+    std::vector<float> dir_min, dir_d256;    // [D]: QuantizedU8Params of every posting list (u8 only)
     std::vector<uint64_t> h_off;             // [n + 1]
     std::vector<uint32_t> dir_dims;          // [D]
     std::vector<uint64_t> dir_start;         // [D + 1]
@@ -27,6 +32,7 @@ struct SparseQuery {
     uint32_t *d_poff = nullptr;
     uint64_t *d_pstart = nullptr, *d_pend = nullptr;
     float *d_pw = nullptr;
+    float *d_pmn = nullptr, *d_pd256 = nullptr;   // u8 index weights: the QuantizedU8Params of every plan entry's posting list
     uint64_t posting_entries = 0;            // sum over the queries of the posting lengths of their dimensions
     // the custom queries (SparseCustomQueryScorer) sum each example in ascending ORIGINAL index order: the lists (remapped ids, weights) and the
     // posting plan once more in that order, under the same offsets.  Without a map they ARE the arrays above (not owned twice).
@@ -55,6 +61,8 @@ void sparse_segment_free(qmx_segment *s) {
     if (sp->d_idx) (void)hipFree(sp->d_idx);
     if (sp->d_val) (void)hipFree(sp->d_val);
     if (sp->d_post) (void)hipFree(sp->d_post);
+    if (sp->d_post_id) (void)hipFree(sp->d_post_id);
+    if (sp->d_post_w) (void)hipFree(sp->d_post_w);
     delete sp;
     s->sparse = nullptr;
 }
@@ -62,7 +70,8 @@ void sparse_segment_free(qmx_segment *s) {
 void sparse_query_free(qmx_query *q) {
     SparseQuery *sq = q->sparse;
     if (!sq) return;
-    for (void *p : {(void *)sq->d_off, (void *)sq->d_idx, (void *)sq->d_val, (void *)sq->d_poff, (void *)sq->d_pstart, (void *)sq->d_pend, (void *)sq->d_pw})
+    for (void *p : {(void *)sq->d_off, (void *)sq->d_idx, (void *)sq->d_val, (void *)sq->d_poff, (void *)sq->d_pstart, (void *)sq->d_pend, (void *)sq->d_pw,
+                    (void *)sq->d_pmn, (void *)sq->d_pd256})
         if (p) (void)hipFree(p);
     if (sq->own_original)
         for (void *p : {(void *)sq->d_oidx, (void *)sq->d_oval, (void *)sq->d_opstart, (void *)sq->d_opend, (void *)sq->d_opw})
@@ -89,7 +98,7 @@ static bool sort_pairs(std::vector<std::pair<uint32_t, float>> &v) {
 // the posting plan of lists `idx` / `val` under offsets `off`: per list, its dimensions that have postings, in the list's order
 static void posting_plan(const SparseSeg *sp, uint32_t nq, const std::vector<uint64_t> &off, const std::vector<uint32_t> &idx, const std::vector<float> &val,
                          std::vector<uint32_t> &poff, std::vector<uint64_t> &pstart, std::vector<uint64_t> &pend, std::vector<float> &pw,
-                         std::vector<uint64_t> *entries) {
+                         std::vector<uint64_t> *entries, std::vector<float> *pmn = nullptr, std::vector<float> *pd256 = nullptr) {
     poff.assign(nq + 1, 0);
     for (uint32_t qi = 0; qi < nq; ++qi) {
         uint64_t sum = 0;
@@ -100,6 +109,10 @@ static void posting_plan(const SparseSeg *sp, uint32_t nq, const std::vector<uin
             pstart.push_back(sp->dir_start[d]);
             pend.push_back(sp->dir_start[d + 1]);
             pw.push_back(val[k]);
+            if (pmn) {
+                pmn->push_back(sp->dir_min[d]);
+                pd256->push_back(sp->dir_d256[d]);
+            }
             sum += sp->dir_start[d + 1] - sp->dir_start[d];
         }
         poff[qi + 1] = (uint32_t)pstart.size();
@@ -115,8 +128,9 @@ static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, cons
     SparseQuery *sq = q->sparse;
     std::vector<uint32_t> poff;
     std::vector<uint64_t> pstart, pend;
-    std::vector<float> pw;
-    posting_plan(sp, q->nq, off, idx, val, poff, pstart, pend, pw, &sq->h_entries);
+    std::vector<float> pw, pmn, pd256;
+    const bool u8 = sp->wtype == QMX_SPARSE_WEIGHT_U8;
+    posting_plan(sp, q->nq, off, idx, val, poff, pstart, pend, pw, &sq->h_entries, u8 ? &pmn : nullptr, u8 ? &pd256 : nullptr);
     for (uint64_t e : sq->h_entries) sq->posting_entries += e;
     QMX_TRY(upload(&sq->d_off, off.data(), off.size()));
     QMX_TRY(upload(&sq->d_idx, idx.data(), idx.size()));
@@ -125,6 +139,10 @@ static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, cons
     QMX_TRY(upload(&sq->d_pstart, pstart.data(), pstart.size()));
     QMX_TRY(upload(&sq->d_pend, pend.data(), pend.size()));
     QMX_TRY(upload(&sq->d_pw, pw.data(), pw.size()));
+    if (u8) {
+        QMX_TRY(upload(&sq->d_pmn, pmn.data(), pmn.size()));
+        QMX_TRY(upload(&sq->d_pd256, pd256.data(), pd256.size()));
+    }
     if (!oidx) {
         sq->d_oidx = sq->d_idx;
         sq->d_oval = sq->d_val;
@@ -240,7 +258,8 @@ int32_t sparse_score_internal(const qmx_segment *seg, const uint32_t *a_ids, con
     return rc;
 }
 
-// Nearest: the posting top-k over every point (sparse_topk_postings_kernel), or plain_search over an id list (sparse_topk_ids_kernel); both write
+// Nearest: the posting top-k over every point (sparse_topk_postings_kernel), or plain_search over an id list (sparse_topk_ids_kernel); over f16 / u8
+// index weights their counterparts on the two-array layout (sparse_topk_postings_q_kernel, sparse_topk_ids_q_kernel).  All write
 // one key list of `top` (<= 64) per work-group and query, merged by launch_merge_keys.  top > 64 runs in passes of 64, each below the last key of
 // the pass before.  Queries go in tiles of 128 (the key lists of a tile: lists x 128 x 64 keys).
 int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64_t n_ids, qmx_scored_point *d_out, uint32_t *d_counts,
@@ -268,6 +287,10 @@ int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids,
     QMX_TRY(q->partial.reserve((size_t)n_lists_max * std::min<uint32_t>(q->nq, QT) * ptop_max * sizeof(uint64_t)));
     if (n_pass > 1) QMX_TRY(q->bounds.reserve((size_t)QT * sizeof(uint64_t)));
     const SparsePlan plan{sq->d_poff, sq->d_pstart, sq->d_pend, sq->d_pw};
+    const SparseSeg *sp = s->sparse;
+    const bool quantized = sp->wtype != QMX_SPARSE_WEIGHT_F32;
+    const SparsePlanQ plan_q{sq->d_poff, sq->d_pstart, sq->d_pend, sq->d_pw, sq->d_pmn, sq->d_pd256};
+    const SparsePostQ post_q{sp->d_post_id, sp->d_post_w, sp->wtype};
     uint32_t launches = 0;
     for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += QT) {
         const uint32_t nq_tile = std::min<uint32_t>(QT, q->nq - tile0);
@@ -282,7 +305,12 @@ int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids,
             uint32_t n_lists = 0;
             size_t slot = 0;
             if (timed) QMX_TRY(timing_begin(q, &slot));
-            if (d_ids)
+            if (quantized && d_ids)
+                QMX_TRY(launch_sparse_topk_ids_q(q->stream, post_q, plan_q, tile0, nq_tile, d_ids, n_ids, s->n, del, ptop, bound, (uint64_t *)q->partial.p,
+                                                 &n_lists));
+            else if (quantized)
+                QMX_TRY(launch_sparse_topk_postings_q(q->stream, post_q, plan_q, tile0, nq_tile, n_scan, del, ptop, bound, (uint64_t *)q->partial.p, &n_lists));
+            else if (d_ids)
                 QMX_TRY(launch_sparse_topk_ids(q->stream, rows_of(s), queries_of(q), tile0, nq_tile, d_ids, n_ids, del, ptop, bound, (uint64_t *)q->partial.p,
                                                &n_lists));
             else
@@ -298,7 +326,8 @@ int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids,
     qmx_counters &c = q->last_counters;
     const uint64_t entries = d_ids ? (uint64_t)q->nq * n_ids : sq->posting_entries;
     c.vectors_scored = entries * n_pass;
-    c.bytes_read = d_ids ? 0 : entries * 8 * n_pass;      // posting entries (id, weight); the id-list path reads rows of unknown length
+    // posting entries (id, weight): 8 / 6 / 5 bytes each; the id-list paths read rows, or probe postings, of unknown length
+    c.bytes_read = d_ids ? 0 : entries * (sp->wtype == QMX_SPARSE_WEIGHT_U8 ? 5 : sp->wtype == QMX_SPARSE_WEIGHT_F16 ? 6 : 8) * n_pass;
     c.kernel_launches = launches;
     if (counters) *counters = c;
     return QMX_OK;
@@ -312,7 +341,8 @@ int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment 
     QMX_REQUIRE(d->n <= 0xFFFFFFFFull, QMX_ERR_BAD_ARG, "PointOffsetType is u32: n=%llu too large", (unsigned long long)d->n);
     QMX_REQUIRE(d->offsets || d->n == 0, QMX_ERR_BAD_ARG, "offsets is NULL");
     QMX_REQUIRE((d->map_keys == nullptr) == (d->map_values == nullptr), QMX_ERR_BAD_ARG, "map_keys and map_values go together");
-    QMX_REQUIRE(d->flags == 0, QMX_ERR_BAD_ARG, "flags must be 0");
+    QMX_REQUIRE((d->flags & ~QMX_SPARSE_WEIGHT_MASK) == 0 && d->flags <= QMX_SPARSE_WEIGHT_U8, QMX_ERR_BAD_ARG,
+                "flags 0x%x: QMX_SPARSE_WEIGHT_F32 / _F16 / _U8 only", d->flags);
     hipDeviceProp_t prop;
     QMX_TRY(check_device(d->device_id, &prop));
     std::vector<uint64_t> h_off(d->n + 1, 0);
@@ -334,6 +364,8 @@ int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment 
     s->sparse = new (std::nothrow) SparseSeg();
     SparseSeg *sp = s->sparse;
     uint32_t *d_flag = nullptr, *d_keys = nullptr, *d_vals = nullptr, *d_dims = nullptr, *d_counts = nullptr;
+    uint64_t *d_dir = nullptr;
+    float *d_mn = nullptr, *d_d256 = nullptr;
     int32_t rc = QMX_OK;
     auto hip = [&](hipError_t e, const char *what) {
         if (e != hipSuccess && rc == QMX_OK) rc = hip_status(e, what, __FILE__, __LINE__);
@@ -343,6 +375,7 @@ int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment 
         if (!sp) { set_error("host allocation failed"); rc = QMX_ERR_OUT_OF_MEMORY; break; }
         sp->nnz = nnz;
         sp->h_off = std::move(h_off);
+        for (uint64_t r = 0; r < d->n; ++r) sp->n_nonempty += sp->h_off[r + 1] > sp->h_off[r];
         if ((rc = upload(&sp->d_off, sp->h_off.data(), sp->h_off.size())) != QMX_OK) break;
         if ((rc = upload(&sp->d_idx, d->indices, nnz)) != QMX_OK) break;
         if ((rc = upload(&sp->d_val, d->values, nnz)) != QMX_OK) break;
@@ -395,8 +428,32 @@ int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment 
             break;
         sp->dir_start.assign(n_dims + 1, 0);
         for (uint32_t i = 0; i < n_dims; ++i) sp->dir_start[i + 1] = sp->dir_start[i] + counts[i];
+        sp->wtype = d->flags & QMX_SPARSE_WEIGHT_MASK;
+        if (sp->wtype == QMX_SPARSE_WEIGHT_F32) break;
+        // f16 / u8 index weights: the packed layout is encoded into (post_id, post_w) and freed - 8 B per entry become 6 B / 5 B.  The u8
+        // parameters of every posting list stay on the host beside the directory.
+        const bool u8 = sp->wtype == QMX_SPARSE_WEIGHT_U8;
+        if ((rc = upload(&d_dir, sp->dir_start.data(), sp->dir_start.size())) != QMX_OK) break;
+        if (!hip(hipMalloc((void **)&sp->d_post_id, std::max<uint64_t>(nnz, 1) * 4), "hipMalloc(posting ids)")) break;
+        if (!hip(hipMalloc(&sp->d_post_w, std::max<uint64_t>(nnz, 1) * (u8 ? 1 : 2)), "hipMalloc(posting weights)")) break;
+        if (u8) {
+            if (!hip(hipMalloc((void **)&d_mn, std::max<size_t>(n_dims, 1) * 4), "hipMalloc(min)")) break;
+            if (!hip(hipMalloc((void **)&d_d256, std::max<size_t>(n_dims, 1) * 4), "hipMalloc(diff256)")) break;
+            if ((rc = launch_sparse_post_params(nullptr, sp->d_post, d_dir, n_dims, d_mn, d_d256)) != QMX_OK) break;
+        }
+        if ((rc = launch_sparse_post_encode(nullptr, sp->d_post, d_dir, n_dims, d_mn, d_d256, sp->wtype, sp->d_post_id, sp->d_post_w)) != QMX_OK) break;
+        if (u8) {
+            sp->dir_min.resize(n_dims);
+            sp->dir_d256.resize(n_dims);
+            if (n_dims && (!hip(hipMemcpy(sp->dir_min.data(), d_mn, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "posting parameters") ||
+                           !hip(hipMemcpy(sp->dir_d256.data(), d_d256, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "posting parameters")))
+                break;
+        }
+        if (!hip(hipDeviceSynchronize(), "posting encode")) break;
+        (void)hipFree(sp->d_post);
+        sp->d_post = nullptr;
     } while (0);
-    for (void *p : {(void *)d_flag, (void *)d_keys, (void *)d_vals, (void *)d_dims, (void *)d_counts})
+    for (void *p : {(void *)d_flag, (void *)d_keys, (void *)d_vals, (void *)d_dims, (void *)d_counts, (void *)d_dir, (void *)d_mn, (void *)d_d256})
         if (p) (void)hipFree(p);
     if (rc != QMX_OK) {
         qmx_segment_destroy(s);
@@ -460,6 +517,99 @@ int32_t qmx_sparse_query_create(const qmx_segment *seg, const uint64_t *offsets,
     }
     *out = q;
     return QMX_OK;
+}
+
+// fill_idf_statistics (sparse_vector_index/read_view/idf.rs:51-140)
+int32_t qmx_sparse_idf_statistics(const qmx_segment *seg, const uint32_t *dims, uint32_t n, const uint64_t *corpus_words, uint64_t n_corpus_bits,
+                                  uint64_t *df_out, uint64_t *n_docs_out) {
+    QMX_REQUIRE(seg && n_docs_out && (n == 0 || (dims && df_out)), QMX_ERR_BAD_ARG, "NULL argument");
+    QMX_REQUIRE(is_sparse(seg), QMX_ERR_NOT_SUPPORTED, "qmx_sparse_idf_statistics needs a sparse segment (qmx_sparse_segment_create)");
+    QMX_HIP(hipSetDevice(seg->device));
+    const SparseSeg *sp = seg->sparse;
+    // the posting range of every requested dimension: remap_index, then the directory; none = df 0
+    std::vector<uint32_t> h_dims(n);
+    if (n) QMX_HIP(hipMemcpy(h_dims.data(), dims, (size_t)n * 4, hipMemcpyDefault));
+    std::vector<uint64_t> start(n, 0), end(n, 0);
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t d = h_dims[i];
+        if (sp->has_map) {
+            auto it = std::lower_bound(sp->map_keys.begin(), sp->map_keys.end(), d);
+            if (it == sp->map_keys.end() || *it != d) continue;
+            d = sp->map_vals[(size_t)(it - sp->map_keys.begin())];
+        }
+        auto it = std::lower_bound(sp->dir_dims.begin(), sp->dir_dims.end(), d);
+        if (it == sp->dir_dims.end() || *it != d) continue;
+        const size_t k = (size_t)(it - sp->dir_dims.begin());
+        start[i] = sp->dir_start[k];
+        end[i] = sp->dir_start[k + 1];
+        longest = std::max(longest, end[i] - start[i]);
+    }
+    if (!corpus_words) {      // global: whole posting lengths (deleted points included) and InvertedIndex::vector_count, the non-empty vectors
+        for (uint32_t i = 0; i < n; ++i) df_out[i] = end[i] - start[i];
+        *n_docs_out = sp->n_nonempty;
+        return QMX_OK;
+    }
+    const uint64_t n_words = (n_corpus_bits + 63) / 64;
+    DevBuf mask, ranges, cnt;
+    int32_t rc = QMX_OK;
+    do {
+        if ((rc = mask.reserve(std::max<size_t>(n_words, 1) * 8)) != QMX_OK || (rc = ranges.reserve(std::max<size_t>(n, 1) * 16)) != QMX_OK ||
+            (rc = cnt.reserve(((size_t)n + 1) * 8)) != QMX_OK)
+            break;
+        uint64_t *d_start = (uint64_t *)ranges.p, *d_end = d_start + n;
+        unsigned long long *d_cnt = (unsigned long long *)cnt.p;
+        hipError_t e = n_words ? hipMemcpy(mask.p, corpus_words, n_words * 8, hipMemcpyDefault) : hipSuccess;
+        if (e == hipSuccess && n) e = hipMemcpy(d_start, start.data(), (size_t)n * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && n) e = hipMemcpy(d_end, end.data(), (size_t)n * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(d_cnt, 0, ((size_t)n + 1) * 8);
+        if (e != hipSuccess) { rc = hip_status(e, "stage corpus statistics", __FILE__, __LINE__); break; }
+        DeletedView del = seg->deleted_view();
+        del.allowed = (const uint64_t *)mask.p;
+        del.n_allowed_bits = n_corpus_bits;
+        if ((rc = launch_sparse_idf_corpus(nullptr, sp->d_post, sp->d_post_id, d_start, d_end, n, longest, del, seg->scan_rows(), d_cnt, d_cnt + n)) != QMX_OK)
+            break;
+        std::vector<unsigned long long> h_cnt((size_t)n + 1);
+        e = hipMemcpy(h_cnt.data(), d_cnt, h_cnt.size() * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { rc = hip_status(e, "corpus statistics", __FILE__, __LINE__); break; }
+        for (uint32_t i = 0; i < n; ++i) df_out[i] = h_cnt[i];
+        *n_docs_out = h_cnt[n];
+    } while (0);
+    mask.release(); ranges.release(); cnt.release();
+    return rc;
+}
+
+// VectorQueryContext::fancy_idf: f32 throughout, f32::ln = libm logf (computed here on the host: the device's logf rounds differently)
+static float fancy_idf(float n, float df) { return logf((n - df + 0.5f) / (df + 0.5f) + 1.0f); }
+
+int32_t qmx_sparse_query_create_idf(const qmx_segment *seg, const uint64_t *offsets, const uint32_t *indices, const float *values, uint32_t nq,
+                                    const uint32_t *stat_dims, const uint64_t *stat_df, uint32_t n_stats, uint64_t n_docs, qmx_query **out) {
+    QMX_REQUIRE(seg && out && (nq == 0 || offsets) && (n_stats == 0 || (stat_dims && stat_df)), QMX_ERR_BAD_ARG, "NULL argument");
+    *out = nullptr;
+    QMX_REQUIRE(is_sparse(seg), QMX_ERR_NOT_SUPPORTED, "qmx_sparse_query_create_idf needs a sparse segment (qmx_sparse_segment_create)");
+    QMX_HIP(hipSetDevice(seg->device));
+    std::vector<uint64_t> off(nq + 1, 0);
+    if (nq) QMX_HIP(hipMemcpy(off.data(), offsets, off.size() * 8, hipMemcpyDefault));
+    QMX_REQUIRE(off[0] == 0, QMX_ERR_BAD_ARG, "offsets[0] must be 0");
+    for (uint32_t i = 0; i < nq; ++i) QMX_REQUIRE(off[i] <= off[i + 1], QMX_ERR_BAD_ARG, "offsets must be non-decreasing (query %u)", i);
+    const uint64_t total = off[nq];
+    QMX_REQUIRE(total == 0 || (indices && values), QMX_ERR_BAD_ARG, "indices / values are NULL");
+    std::vector<uint32_t> idx(total);
+    std::vector<float> val(total);
+    if (total) {
+        QMX_HIP(hipMemcpy(idx.data(), indices, total * 4, hipMemcpyDefault));
+        QMX_HIP(hipMemcpy(val.data(), values, total * 4, hipMemcpyDefault));
+    }
+    std::vector<std::pair<uint32_t, uint64_t>> stats(n_stats);
+    for (uint32_t i = 0; i < n_stats; ++i) stats[i] = {stat_dims[i], stat_df[i]};
+    std::sort(stats.begin(), stats.end());
+    const float n = (float)n_docs;
+    for (uint64_t k = 0; k < total; ++k) {      // remap_idf_weights: by ORIGINAL index, before any remap
+        auto it = std::lower_bound(stats.begin(), stats.end(), std::make_pair(idx[k], (uint64_t)0));
+        const uint64_t df = it != stats.end() && it->first == idx[k] ? it->second : 0;
+        val[k] *= fancy_idf(n, (float)df);
+    }
+    return qmx_sparse_query_create(seg, off.data(), idx.data(), val.data(), nq, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -534,7 +684,12 @@ int32_t qmx_sparse_custom_search_topk(qmx_query *ex, const qmx_custom_query *que
         del.n_allowed_bits = ex->n_filter_bits;
     }
     const uint64_t n_scan = s->scan_rows();
-    const uint32_t n_lists_max = ids ? (n_ids ? sparse_ids_lists(n_ids) : 0) : (uint32_t)((n_scan + sparse_custom_tile_ids() - 1) / sparse_custom_tile_ids());
+    // over f16 / u8 index weights no f32 postings exist and the custom scorer reads the vector storage: the full scan is the row kernel over the
+    // implicit identity id list
+    const bool rows_scan = !ids && s->sparse->wtype != QMX_SPARSE_WEIGHT_F32;
+    const uint32_t n_lists_max = ids        ? (n_ids ? sparse_ids_lists(n_ids) : 0)
+                                 : rows_scan ? (n_scan ? sparse_ids_lists(n_scan) : 0)
+                                             : (uint32_t)((n_scan + sparse_custom_tile_ids() - 1) / sparse_custom_tile_ids());
     const bool timed = ex->timing || (s->flags & QMX_SEG_TIME_KERNELS) != 0;
     ex->last_counters = qmx_counters{};
     ex->last_split = false;
@@ -565,9 +720,9 @@ int32_t qmx_sparse_custom_search_topk(qmx_query *ex, const qmx_custom_query *que
                 uint32_t n_lists = 0;
                 size_t slot = 0;
                 if (timed) QMX_TRY(timing_begin(ex, &slot));
-                if (d_ids)
-                    QMX_TRY(launch_sparse_custom_topk_ids(ex->stream, rows_of(s), exq, d_desc, d_coefs, tile0, nq_tile, (const uint32_t *)d_ids, n_ids, del, ptop,
-                                                          bound, (uint64_t *)ex->partial.p, &n_lists));
+                if (d_ids || rows_scan)
+                    QMX_TRY(launch_sparse_custom_topk_ids(ex->stream, rows_of(s), exq, d_desc, d_coefs, tile0, nq_tile, (const uint32_t *)d_ids,
+                                                          d_ids ? n_ids : n_scan, del, ptop, bound, (uint64_t *)ex->partial.p, &n_lists));
                 else
                     QMX_TRY(launch_sparse_custom_topk_postings(ex->stream, s->sparse->d_post, plan, d_desc, d_coefs, tile0, nq_tile, n_scan, del, ptop, bound,
                                                                (uint64_t *)ex->partial.p, &n_lists));
@@ -580,8 +735,8 @@ int32_t qmx_sparse_custom_search_topk(qmx_query *ex, const qmx_custom_query *que
         }
     }
     qmx_counters &c = ex->last_counters;
-    c.vectors_scored = (d_ids ? n_examples * n_ids : entries) * n_pass;
-    c.bytes_read = d_ids ? 0 : entries * 8 * n_pass;      // posting entries (id, weight) of every example; the id-list path reads rows of unknown length
+    c.vectors_scored = (d_ids ? n_examples * n_ids : rows_scan ? n_examples * n_scan : entries) * n_pass;
+    c.bytes_read = d_ids || rows_scan ? 0 : entries * 8 * n_pass;      // posting entries (id, weight) of every example; the id-list path reads rows of unknown length
     c.kernel_launches = launches;
     if (!out_dev) QMX_TRY(copy_out(ex->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
     if (!cnt_dev) QMX_TRY(copy_out(ex->stream, out_counts, d_counts, (size_t)n_queries * 4));

@@ -497,8 +497,38 @@ struct SparsePlan {
     const uint64_t *end;
     const float *w;           // the query's weight of the dimension
 };
+// the posting layout of a segment whose index weights are f16 / u8 (SparseIndexConfig.datatype): structure of arrays, ids[nnz] and weights[nnz]
+// (u16 = f16 bits, or u8 codes of QuantizedU8), grouped by dimension, ids ascending inside a group
+struct SparsePostQ {
+    const uint32_t *id;
+    const void *w;
+    uint32_t wtype;           // QMX_SPARSE_WEIGHT_F16 / QMX_SPARSE_WEIGHT_U8
+};
+// ... and the plan of a batch over it: beside each query weight the QuantizedU8Params (min, diff256) of the dimension's posting list (u8 only)
+struct SparsePlanQ {
+    const uint32_t *off;
+    const uint64_t *start;
+    const uint64_t *end;
+    const float *w;
+    const float *mn;
+    const float *d256;
+};
 uint32_t sparse_tile_ids();
 uint32_t sparse_ids_lists(uint64_t n_ids);
+// quantized index weights: (min, diff256) of every posting list of the packed layout `post` (dir_start: [n_dims + 1] device), then the encode into
+// the structure of arrays
+int32_t launch_sparse_post_params(hipStream_t st, const uint64_t *post, const uint64_t *dir_start, uint32_t n_dims, float *mn, float *d256);
+int32_t launch_sparse_post_encode(hipStream_t st, const uint64_t *post, const uint64_t *dir_start, uint32_t n_dims, const float *mn, const float *d256,
+                                  uint32_t wtype, uint32_t *post_id, void *post_w);
+int32_t launch_sparse_topk_postings_q(hipStream_t st, const SparsePostQ &post, const SparsePlanQ &plan, uint32_t q0, uint32_t nq_tile, uint64_t n_scan,
+                                      const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists);
+int32_t launch_sparse_topk_ids_q(hipStream_t st, const SparsePostQ &post, const SparsePlanQ &plan, uint32_t q0, uint32_t nq_tile, const uint32_t *ids,
+                                 uint64_t n_ids, uint64_t n_rows, const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial,
+                                 uint32_t *n_lists);
+// IDF corpus statistics: df[d] += the entries of posting range [start[d], end[d]) whose point `del` lets through (post: the packed u64 layout, or
+// post_id when that is null); *n_docs += the points below n_scan that `del` lets through.  df / n_docs are zeroed by the caller.
+int32_t launch_sparse_idf_corpus(hipStream_t st, const uint64_t *post, const uint32_t *post_id, const uint64_t *start, const uint64_t *end, uint32_t n_dims,
+                                 uint64_t longest, const DeletedView &del, uint64_t n_scan, unsigned long long *df, unsigned long long *n_docs);
 int32_t launch_sparse_check_rows(hipStream_t st, const uint64_t *offsets, const uint32_t *idx, uint64_t n, uint32_t *flags);
 int32_t launch_sparse_sort_rows(hipStream_t st, const uint64_t *offsets, uint32_t *idx, float *val, uint64_t n);
 int32_t launch_sparse_remap(hipStream_t st, uint32_t *idx, uint64_t nnz, const uint32_t *keys, const uint32_t *vals, uint64_t m, uint32_t *missing);

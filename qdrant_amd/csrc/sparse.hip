@@ -457,7 +457,8 @@ __global__ __launch_bounds__(SP_BLOCK) void sparse_custom_score_kernel(SparseRow
     scores[(uint64_t)qi * n + i] = s;
 }
 
-// search_scored over an id list: block (x, y) scores a grid-strided slice of the ids against custom query q0 + y and keeps the live, allowed ones
+// search_scored over an id list: block (x, y) scores a grid-strided slice of the ids against custom query q0 + y and keeps the live, allowed ones.
+// ids == nullptr: the identity list (id = i), nothing materialised - the full scan of a segment whose postings hold no f32 weights
 __global__ __launch_bounds__(SP_BLOCK) void sparse_custom_topk_ids_kernel(SparseRows r, SparseQueries ex, const qmx_custom_query *desc, const float *coefs,
                                                                           uint32_t q0, uint32_t nq_tile, const uint32_t *ids, uint64_t n_ids, DeletedView del,
                                                                           uint32_t top, const uint64_t *key_bound, uint64_t *partial) {
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(SP_BLOCK) void sparse_custom_topk_ids_kernel(Sparse
         const uint64_t i = base + threadIdx.x;
         uint64_t key = 0;
         if (i < n_ids) {
-            const uint32_t id = ids[i];
+            const uint32_t id = ids ? ids[i] : (uint32_t)i;
             if (id < r.n && del.live(id)) key = make_key(sparse_custom_score(r, ex, cq, coefs, id), id);
         }
         if (key_bound && key >= bound) key = 0;
@@ -598,6 +599,307 @@ int32_t launch_sparse_custom_topk_ids(hipStream_t st, const SparseRows &r, const
     hipLaunchKernelGGL(sparse_custom_topk_ids_kernel, dim3(*n_lists, nq_tile), dim3(SP_BLOCK), 0, st, r, ex, desc, coefs, q0, nq_tile, ids, n_ids, del, top, key_bound,
                        partial);
     QMX_NOTE_KERNEL(sparse_custom_topk_ids_kernel);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+
+// ---- f16 / u8 index weights (SparseIndexConfig.datatype; lib/sparse/src/common/types.rs, compressed_posting_list.rs:361-407) ----
+// The posting layout as a structure of arrays: post_id[nnz] and post_w[nnz] (u16 = the bits of half::f16, or u8 = QuantizedU8 with (min, diff256)
+// per posting list).  The f32 kernels above are left as they are; the kernels below are their counterparts over the two arrays and score the
+// DECODED weight, as SearchContext does over a CompressedPostingList<W>.
+
+// Weight::to_f32: exact widening of f16; min + f32(code) * diff256 with the multiply and the add rounded separately
+template <typename W>
+__device__ __forceinline__ float sparse_decode(W c, float mn, float d256);
+template <>
+__device__ __forceinline__ float sparse_decode<uint16_t>(uint16_t c, float, float) { return __half2float(__ushort_as_half(c)); }
+template <>
+__device__ __forceinline__ float sparse_decode<uint8_t>(uint8_t c, float mn, float d256) { return __fadd_rn(mn, __fmul_rn((float)c, d256)); }
+
+// Weight::from_f32: f16 rounds to nearest even and overflows to inf; u8 = ((v - min) / diff256).round().clamp(0, 255) as u8 - IEEE division, round
+// half away from zero, NaN (0 / 0 of a list whose weights are all equal) becomes 0
+template <typename W>
+__device__ __forceinline__ W sparse_encode(float v, float mn, float d256);
+template <>
+__device__ __forceinline__ uint16_t sparse_encode<uint16_t>(float v, float, float) { return __half_as_ushort(__float2half_rn(v)); }
+template <>
+__device__ __forceinline__ uint8_t sparse_encode<uint8_t>(float v, float mn, float d256) {
+    const float r = roundf(__fdiv_rn(__fsub_rn(v, mn), d256));
+    return r >= 255.0f ? (uint8_t)255 : r > 0.0f ? (uint8_t)r : (uint8_t)0;      // (every comparison with NaN is false: 0)
+}
+
+// QuantizedU8::quantization_params_for of every posting list: work-group d (grid-strided) reduces the weights of dimension d
+__global__ __launch_bounds__(SP_BLOCK) void sparse_post_params_kernel(const uint64_t *post, const uint64_t *dir_start, uint32_t n_dims, float *mn, float *d256) {
+    __shared__ float s_lo[SP_BLOCK], s_hi[SP_BLOCK];
+    for (uint32_t d = blockIdx.x; d < n_dims; d += gridDim.x) {
+        const uint64_t a = dir_start[d], b = dir_start[d + 1];
+        float lo = INFINITY, hi = -INFINITY;
+        for (uint64_t i = a + threadIdx.x; i < b; i += SP_BLOCK) {
+            const float v = __uint_as_float((uint32_t)(post[i] >> 32));
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+        s_lo[threadIdx.x] = lo;
+        s_hi[threadIdx.x] = hi;
+        __syncthreads();
+        for (uint32_t s = SP_BLOCK / 2; s > 0; s >>= 1) {
+            if (threadIdx.x < s) {
+                s_lo[threadIdx.x] = fminf(s_lo[threadIdx.x], s_lo[threadIdx.x + s]);
+                s_hi[threadIdx.x] = fmaxf(s_hi[threadIdx.x], s_hi[threadIdx.x + s]);
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            mn[d] = s_lo[0];
+            d256[d] = __fdiv_rn(__fsub_rn(s_hi[0], s_lo[0]), 255.0f);
+        }
+        __syncthreads();
+    }
+}
+
+// the packed layout into the two arrays; work-group d (grid-strided) encodes the posting list of dimension d with its parameters
+template <typename W>
+__global__ __launch_bounds__(SP_BLOCK) void sparse_post_encode_kernel(const uint64_t *post, const uint64_t *dir_start, uint32_t n_dims, const float *mn,
+                                                                      const float *d256, uint32_t *post_id, W *post_w) {
+    for (uint32_t d = blockIdx.x; d < n_dims; d += gridDim.x) {
+        const uint64_t a = dir_start[d], b = dir_start[d + 1];
+        const float lo = mn ? mn[d] : 0.0f, dd = d256 ? d256[d] : 0.0f;
+        for (uint64_t i = a + threadIdx.x; i < b; i += SP_BLOCK) {
+            const uint64_t ent = post[i];
+            post_id[i] = (uint32_t)ent;
+            post_w[i] = sparse_encode<W>(__uint_as_float((uint32_t)(ent >> 32)), lo, dd);
+        }
+    }
+}
+
+// sparse_walk_chunk over the two arrays: the binary search runs over post_id, id and code come from their arrays, and the u8 parameters of a plan
+// entry are broadcast with its query weight
+template <typename W>
+__device__ __forceinline__ void sparse_walk_chunk_q(const uint32_t *pid, const W *pw, const SparsePlanQ &plan, uint32_t c, uint32_t nc, uint64_t sub_lo,
+                                                    uint64_t sub_hi, float *wacc, uint32_t *whit, int lane) {
+    uint64_t lo = 0, hi = 0;
+    float w = 0.0f, mn = 0.0f, dd = 0.0f;
+    if ((uint32_t)lane < nc) {   // lower_bound(sub_lo) in the dimension's posting list
+        uint64_t a = plan.start[c + lane], b = plan.end[c + lane];
+        hi = b;
+        w = plan.w[c + lane];
+        if (sizeof(W) == 1) {
+            mn = plan.mn[c + lane];
+            dd = plan.d256[c + lane];
+        }
+        while (a < b) {
+            const uint64_t m = (a + b) >> 1;
+            if (pid[m] < sub_lo) a = m + 1;
+            else b = m;
+        }
+        lo = a;
+    }
+    for (uint32_t j = 0; j < nc; ++j) {
+        uint64_t p = readlane_u64(lo, (int)j);
+        const uint64_t e = readlane_u64(hi, (int)j);
+        const float qv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), (int)j));
+        const float qmn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mn), (int)j));
+        const float qdd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dd), (int)j));
+        while (p < e) {
+            const uint64_t i = p + lane;
+            uint32_t id = ~0u;
+            W code = 0;
+            if (i < e) {
+                id = pid[i];
+                code = pw[i];
+            }
+            const bool in = i < e && id < sub_hi;
+            if (in) {
+                const uint32_t k = id - (uint32_t)sub_lo;
+                wacc[k] = __fadd_rn(wacc[k], __fmul_rn(sparse_decode<W>(code, qmn, qdd), qv));
+                atomicOr(&whit[k >> 5], 1u << (k & 31));
+            }
+            if (__ballot(in) != ~0ull) break;
+            p += WAVE;
+        }
+    }
+}
+
+// sparse_topk_postings_kernel over the two arrays: tiles, LDS, emit and merge are the f32 kernel's
+template <typename W>
+__global__ __launch_bounds__(SP_BLOCK) void sparse_topk_postings_q_kernel(const uint32_t *pid, const W *pw, SparsePlanQ plan, uint32_t q0, uint32_t nq_tile,
+                                                                          uint64_t n_scan, DeletedView del, uint32_t top, const uint64_t *key_bound,
+                                                                          uint64_t *partial) {
+    __shared__ float acc[SPT_TILE];
+    __shared__ uint32_t hit[SPT_TILE / 32];
+    const uint32_t tile = blockIdx.x, ql = blockIdx.y, qi = q0 + ql;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t bound = key_bound ? key_bound[ql] : 0;
+    if (key_bound && bound == 0) {   // the query was exhausted by an earlier pass
+        if (threadIdx.x < top) partial[((uint64_t)tile * nq_tile + ql) * top + threadIdx.x] = 0;
+        return;
+    }
+    const uint64_t sub_lo = (uint64_t)tile * SPT_TILE + (uint64_t)wave * SPT_SUB;
+    const uint64_t sub_hi = sub_lo + SPT_SUB < n_scan ? sub_lo + SPT_SUB : n_scan;
+    float *wacc = acc + wave * SPT_SUB;
+    uint32_t *whit = hit + wave * (SPT_SUB / 32);
+    for (uint32_t k = lane; k < SPT_SUB; k += WAVE) wacc[k] = 0.0f;
+    for (uint32_t k = lane; k < SPT_SUB / 32; k += WAVE) whit[k] = 0u;
+    const uint32_t d0 = plan.off[qi], d1 = plan.off[qi + 1];
+    for (uint32_t c = d0; c < d1 && sub_lo < sub_hi; c += SPT_CHUNK)
+        sparse_walk_chunk_q<W>(pid, pw, plan, c, d1 - c < SPT_CHUNK ? d1 - c : SPT_CHUNK, sub_lo, sub_hi, wacc, whit, lane);
+    uint64_t list = 0;
+    for (uint32_t k0 = 0; k0 < SPT_SUB; k0 += WAVE) {
+        const uint32_t k = k0 + lane;
+        const uint64_t id = sub_lo + k;
+        uint64_t key = 0;
+        if (id < sub_hi && ((whit[k >> 5] >> (k & 31)) & 1u) && del.live((uint32_t)id)) key = make_key(wacc[k], (uint32_t)id);
+        if (key_bound && key >= bound) key = 0;
+        wave_offer(list, key, (int)top, lane);
+    }
+    sparse_block_emit(list, (int)top, tile, ql, nq_tile, partial);
+}
+
+// plain_search over an id list on the index (search_context.rs:92-143): one thread per id; for each dimension of the query's plan, in ascending
+// remapped order, the id is looked up in the dimension's posting ids (`skip_to`: a lower bound), and a hit adds decode(weight) x query weight.
+// No decoded copy of the row exists.  Grid, key lists and passes as sparse_topk_ids_kernel.
+template <typename W>
+__global__ __launch_bounds__(SP_BLOCK) void sparse_topk_ids_q_kernel(const uint32_t *pid, const W *pw, SparsePlanQ plan, uint32_t q0, uint32_t nq_tile,
+                                                                     const uint32_t *ids, uint64_t n_ids, uint64_t n_rows, DeletedView del, uint32_t top,
+                                                                     const uint64_t *key_bound, uint64_t *partial) {
+    const uint32_t ql = blockIdx.y, qi = q0 + ql;
+    const int lane = threadIdx.x & 63;
+    const uint64_t bound = key_bound ? key_bound[ql] : 0;
+    if (key_bound && bound == 0) {
+        if (threadIdx.x < top) partial[((uint64_t)blockIdx.x * nq_tile + ql) * top + threadIdx.x] = 0;
+        return;
+    }
+    const uint32_t d0 = plan.off[qi], d1 = plan.off[qi + 1];
+    uint64_t list = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * SP_BLOCK; base < n_ids; base += (uint64_t)gridDim.x * SP_BLOCK) {
+        const uint64_t i = base + threadIdx.x;
+        uint64_t key = 0;
+        if (i < n_ids) {
+            const uint32_t id = ids[i];
+            if (id < n_rows && del.live(id)) {
+                float s = 0.0f;
+                bool ov = false;
+                for (uint32_t c = d0; c < d1; ++c) {
+                    uint64_t a = plan.start[c], b = plan.end[c];
+                    const uint64_t e = b;
+                    while (a < b) {
+                        const uint64_t m = (a + b) >> 1;
+                        if (pid[m] < id) a = m + 1;
+                        else b = m;
+                    }
+                    if (a < e && pid[a] == id) {
+                        const float mn = sizeof(W) == 1 ? plan.mn[c] : 0.0f, dd = sizeof(W) == 1 ? plan.d256[c] : 0.0f;
+                        s = __fadd_rn(s, __fmul_rn(sparse_decode<W>(pw[a], mn, dd), plan.w[c]));
+                        ov = true;
+                    }
+                }
+                if (ov) key = make_key(s, id);
+            }
+        }
+        if (key_bound && key >= bound) key = 0;
+        wave_offer(list, key, (int)top, lane);
+    }
+    sparse_block_emit(list, (int)top, blockIdx.x, ql, nq_tile, partial);
+}
+
+int32_t launch_sparse_post_params(hipStream_t st, const uint64_t *post, const uint64_t *dir_start, uint32_t n_dims, float *mn, float *d256) {
+    if (n_dims == 0) return QMX_OK;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_post_params_kernel, dim3(std::min<uint32_t>(n_dims, 65535)), dim3(SP_BLOCK), 0, st, post, dir_start, n_dims, mn, d256);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_post_encode(hipStream_t st, const uint64_t *post, const uint64_t *dir_start, uint32_t n_dims, const float *mn, const float *d256,
+                                  uint32_t wtype, uint32_t *post_id, void *post_w) {
+    if (n_dims == 0) return QMX_OK;
+    const dim3 grid(std::min<uint32_t>(n_dims, 65535));
+    ::qmx::clear_stale_error();
+    if (wtype == QMX_SPARSE_WEIGHT_U8)
+        hipLaunchKernelGGL(sparse_post_encode_kernel<uint8_t>, grid, dim3(SP_BLOCK), 0, st, post, dir_start, n_dims, mn, d256, post_id, (uint8_t *)post_w);
+    else
+        hipLaunchKernelGGL(sparse_post_encode_kernel<uint16_t>, grid, dim3(SP_BLOCK), 0, st, post, dir_start, n_dims, nullptr, nullptr, post_id,
+                           (uint16_t *)post_w);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_topk_postings_q(hipStream_t st, const SparsePostQ &post, const SparsePlanQ &plan, uint32_t q0, uint32_t nq_tile, uint64_t n_scan,
+                                      const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial, uint32_t *n_lists) {
+    const uint64_t tiles = (n_scan + SPT_TILE - 1) / SPT_TILE;
+    *n_lists = (uint32_t)tiles;
+    if (tiles == 0 || nq_tile == 0) return QMX_OK;
+    QMX_REQUIRE(nq_tile <= 65535, QMX_ERR_OTHER, "query tile too large");
+    ::qmx::clear_stale_error();
+    const dim3 grid((uint32_t)tiles, nq_tile);
+    if (post.wtype == QMX_SPARSE_WEIGHT_U8) {
+        hipLaunchKernelGGL(sparse_topk_postings_q_kernel<uint8_t>, grid, dim3(SP_BLOCK), 0, st, post.id, (const uint8_t *)post.w, plan, q0, nq_tile, n_scan, del,
+                           top, key_bound, partial);
+        QMX_NOTE_KERNEL(sparse_topk_postings_q_kernel<uint8_t>);
+    } else {
+        hipLaunchKernelGGL(sparse_topk_postings_q_kernel<uint16_t>, grid, dim3(SP_BLOCK), 0, st, post.id, (const uint16_t *)post.w, plan, q0, nq_tile, n_scan, del,
+                           top, key_bound, partial);
+        QMX_NOTE_KERNEL(sparse_topk_postings_q_kernel<uint16_t>);
+    }
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_sparse_topk_ids_q(hipStream_t st, const SparsePostQ &post, const SparsePlanQ &plan, uint32_t q0, uint32_t nq_tile, const uint32_t *ids,
+                                 uint64_t n_ids, uint64_t n_rows, const DeletedView &del, uint32_t top, const uint64_t *key_bound, uint64_t *partial,
+                                 uint32_t *n_lists) {
+    *n_lists = sparse_ids_lists(n_ids);
+    if (nq_tile == 0) return QMX_OK;
+    QMX_REQUIRE(nq_tile <= 65535, QMX_ERR_OTHER, "query tile too large");
+    ::qmx::clear_stale_error();
+    const dim3 grid(*n_lists, nq_tile);
+    if (post.wtype == QMX_SPARSE_WEIGHT_U8) {
+        hipLaunchKernelGGL(sparse_topk_ids_q_kernel<uint8_t>, grid, dim3(SP_BLOCK), 0, st, post.id, (const uint8_t *)post.w, plan, q0, nq_tile, ids, n_ids, n_rows,
+                           del, top, key_bound, partial);
+        QMX_NOTE_KERNEL(sparse_topk_ids_q_kernel<uint8_t>);
+    } else {
+        hipLaunchKernelGGL(sparse_topk_ids_q_kernel<uint16_t>, grid, dim3(SP_BLOCK), 0, st, post.id, (const uint16_t *)post.w, plan, q0, nq_tile, ids, n_ids,
+                           n_rows, del, top, key_bound, partial);
+        QMX_NOTE_KERNEL(sparse_topk_ids_q_kernel<uint16_t>);
+    }
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+
+// ---- IDF corpus statistics (sparse_vector_index/read_view/idf.rs: the posting walk against a corpus mask) ----
+// Work-groups (x, d) stride the posting ids of requested dimension d with coalesced loads; each wave counts the entries whose point the mask and
+// the deleted flags let through by ballot + popcount and adds its count to df[d] once.
+template <typename E>
+__global__ __launch_bounds__(SP_BLOCK) void sparse_idf_corpus_kernel(const E *post, const uint64_t *start, const uint64_t *end, DeletedView del,
+                                                                     unsigned long long *df) {
+    const uint32_t d = blockIdx.y;
+    const uint64_t a = start[d], e = end[d];
+    uint32_t count = 0;      // wave-uniform
+    for (uint64_t base = a + (uint64_t)blockIdx.x * SP_BLOCK; base < e; base += (uint64_t)gridDim.x * SP_BLOCK) {
+        const uint64_t i = base + threadIdx.x;
+        const bool in = i < e && del.live((uint32_t)post[i]);
+        count += (uint32_t)__popcll(__ballot(in));
+    }
+    if ((threadIdx.x & 63) == 0 && count) atomicAdd(&df[d], (unsigned long long)count);
+}
+// the document count of a corpus: the points below n_scan that the mask and the deleted flags let through
+__global__ __launch_bounds__(SP_BLOCK) void sparse_idf_docs_kernel(DeletedView del, uint64_t n_scan, unsigned long long *n_docs) {
+    uint32_t count = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * SP_BLOCK; base < n_scan; base += (uint64_t)gridDim.x * SP_BLOCK) {
+        const uint64_t i = base + threadIdx.x;
+        const bool in = i < n_scan && del.live((uint32_t)i);
+        count += (uint32_t)__popcll(__ballot(in));
+    }
+    if ((threadIdx.x & 63) == 0 && count) atomicAdd(n_docs, (unsigned long long)count);
+}
+int32_t launch_sparse_idf_corpus(hipStream_t st, const uint64_t *post, const uint32_t *post_id, const uint64_t *start, const uint64_t *end, uint32_t n_dims,
+                                 uint64_t longest, const DeletedView &del, uint64_t n_scan, unsigned long long *df, unsigned long long *n_docs) {
+    ::qmx::clear_stale_error();
+    const uint32_t gx = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(blocks_of(longest), 1), 256);
+    for (uint32_t y0 = 0; y0 < n_dims && longest; y0 += 65535) {
+        const dim3 grid(gx, std::min<uint32_t>(65535, n_dims - y0));
+        if (post) hipLaunchKernelGGL(sparse_idf_corpus_kernel<uint64_t>, grid, dim3(SP_BLOCK), 0, st, post, start + y0, end + y0, del, df + y0);
+        else hipLaunchKernelGGL(sparse_idf_corpus_kernel<uint32_t>, grid, dim3(SP_BLOCK), 0, st, post_id, start + y0, end + y0, del, df + y0);
+    }
+    if (n_scan)
+        hipLaunchKernelGGL(sparse_idf_docs_kernel, dim3((uint32_t)std::min<uint64_t>(blocks_of(n_scan), 1024)), dim3(SP_BLOCK), 0, st, del, n_scan, n_docs);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }

@@ -95,15 +95,25 @@ class Mmr:
         self.scorer, self.lambda_, self.limit = scorer, float(lambda_), int(limit)
 
 
-def hybrid_search(sources, fusion, top: int, mmr: Optional[Mmr] = None, device_id: int = 0) -> List[np.ndarray]:
+def hybrid_search(sources, fusion, top: int, mmr: Optional[Mmr] = None, device_id: int = 0, sparse_idf=None) -> List[np.ndarray]:
     """One hybrid request batch without a host round trip between its stages.  `sources`: (scorer, prefetch limit) pairs - query batches of the
     same size made by new_raw_scorer over a dense VectorStorage or a SparseVectorStorage on one device; `fusion`: Rrf(...) or Dbsf(...); `mmr`:
     an optional Mmr stage over the fused list.  Every search, the fusion and the MMR selection are enqueued on one stream, which is synchronised
     once.  (All sources search the largest prefetch limit; a source with a smaller one has its counts clamped - a top list's head is the shorter
-    top list.)"""
+    top list.)  A sparse source may be given as ((SparseVectorStorage, queries), prefetch limit): its query batch is then made here, with
+    `sparse_idf` as the IDF modifier (True, a corpus mask or merged statistics, as SparseVectorStorage.search takes them)."""
     import torch
     if not sources:
         raise ValueError("no sources")
+    made = []
+    for i, (s, limit) in enumerate(sources):
+        if isinstance(s, tuple):
+            storage, queries = s
+            made.append(new_raw_scorer(queries, storage, idf=sparse_idf))
+            sources = list(sources)
+            sources[i] = (made[-1], limit)
+    if sparse_idf is not None and not made:
+        raise ValueError("sparse_idf needs a sparse source given as ((storage, queries), limit)")
     nq = sources[0][0].nq
     if any(s.nq != nq for s, _ in sources) or (mmr is not None and mmr.scorer.nq != nq):
         raise ValueError("every stage needs the same number of queries")
@@ -141,6 +151,8 @@ def hybrid_search(sources, fusion, top: int, mmr: Optional[Mmr] = None, device_i
             stream.synchronize()      # the one synchronisation of the request batch
             for s in scorers:
                 lib.qmx_query_set_stream(s._h, None)
+            for s in made:
+                s.close()
     del keep
     # (a fused id past the dense storage's rows empties that request's MMR list; the next synchronous call on mmr.scorer reports it)
     out = out.numpy().view(ScoredPointOffset).reshape(nq, -1)

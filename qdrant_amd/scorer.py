@@ -783,12 +783,15 @@ class RawScorer:
             pass
 
 
-def new_raw_scorer(query, storage: VectorStorage) -> RawScorer:
+def new_raw_scorer(query, storage: VectorStorage, idf=None) -> RawScorer:
     """`new_raw_scorer(QueryVector::Nearest(query), storage, hc)` (raw_scorer.rs:60-114).
     `query`: [dim] or [nq, dim] f32 ORIGINAL vectors; preprocessing + cast happen on device.
-    Over a SparseVectorStorage: sparse queries, a list of (indices, values) pairs or CSR arrays (offsets, indices, values)."""
+    Over a SparseVectorStorage: sparse queries, a list of (indices, values) pairs or CSR arrays (offsets, indices, values); `idf`: the IDF
+    modifier, as for SparseVectorStorage.search."""
     if isinstance(storage, SparseVectorStorage):
-        return storage._raw_scorer(query)
+        return storage._raw_scorer(query, idf=idf)
+    if idf is not None:
+        raise ValueError("the IDF modifier belongs to sparse vectors")
     if hasattr(query, "data_ptr") and getattr(query, "is_cuda", False):    # a contiguous [nq, dim] f32 torch CUDA tensor: no host copy
         q = query
         assert q.dim() == 2 and q.is_contiguous() and str(q.dtype) == "torch.float32"
@@ -872,9 +875,10 @@ class CustomRawScorer:
     """`new_raw_scorer(QueryVector::<custom>, storage)` for a batch of custom queries (raw_scorer.rs:60-114 ->
     CustomQueryScorer): all example vectors form one device query batch, every custom query is a slice of it.
     Over a SparseVectorStorage (raw_sparse_scorer_impl -> SparseCustomQueryScorer) the examples are sparse vectors and `peek_top` is
-    `search_scored` (sparse_vector_index/read_view/search.rs:99-151): every live point is a candidate, overlap or not."""
+    `search_scored` (sparse_vector_index/read_view/search.rs:99-151): every live point is a candidate, overlap or not.  `idf` (sparse only, as for
+    SparseVectorStorage.search): the modifier scales every example vector (`QueryVector::transform`, read_view/search.rs:46-60)."""
 
-    def __init__(self, queries: Sequence[CustomQuery], storage: VectorStorage):
+    def __init__(self, queries: Sequence[CustomQuery], storage: VectorStorage, idf=None):
         self.storage = storage
         self.sparse = isinstance(storage, SparseVectorStorage)
         kinds = {q.sparse for q in queries if q.sparse is not None}
@@ -891,7 +895,9 @@ class CustomRawScorer:
                 coefs += q.coefs.tolist()
         self._descs, self.nq = descs, len(queries)
         if self.sparse:
-            self.examples = storage._raw_scorer(flat)
+            self.examples = storage._raw_scorer(flat, idf=idf)
+        elif idf is not None:
+            raise ValueError("the IDF modifier belongs to sparse vectors")
         else:
             self.examples = new_raw_scorer(np.stack(flat) if flat else np.zeros((0, storage.dim), dtype=np.float32), storage)
         if coefs:
@@ -1013,10 +1019,18 @@ class SparseVectorStorage:
     """Sparse vectors (lib/sparse, `SparseVectorIndex` over a sparse vector storage) on the device: rows sorted by index at create, the
     dimension-major posting layout beside them.  `vectors`: a list of (indices, values) pairs or CSR arrays (offsets, indices, values), host
     arrays or torch device tensors.  `dim_map`: the IndicesTracker as (keys, remapped ids) or a dict; rows and queries are remapped and re-sorted.
-    Scores are `score_vectors` (sparse_vector.rs:66-90); 0.0 where a query shares no dimension with a point."""
+    Scores are `score_vectors` (sparse_vector.rs:66-90); 0.0 where a query shares no dimension with a point.
+    `index_datatype` (`SparseIndexConfig.datatype`): Float16 / Uint8 keep the posting layout's weights as f16 / as u8 codes with (min, diff256)
+    per posting list; `search` then scores the decoded weights, as the reference's index does, while the raw scorer and the custom queries keep
+    reading the f32 rows."""
 
-    def __init__(self, offsets, indices=None, values=None, dim_map=None, device_id: int = 0):
+    _WEIGHTS = {VectorStorageDatatype.Float32: F.SPARSE_WEIGHT_F32, VectorStorageDatatype.Float16: F.SPARSE_WEIGHT_F16,
+                VectorStorageDatatype.Uint8: F.SPARSE_WEIGHT_U8}
+
+    def __init__(self, offsets, indices=None, values=None, dim_map=None, device_id: int = 0,
+                 index_datatype: VectorStorageDatatype = VectorStorageDatatype.Float32):
         self._h = C.c_void_p()
+        self.index_datatype = VectorStorageDatatype(index_datatype)
         if indices is None:      # SparseVectorStorage([(indices, values), ...])
             offsets, indices, values = _sparse_csr(offsets)
         if not hasattr(offsets, "data_ptr"):
@@ -1035,6 +1049,7 @@ class SparseVectorStorage:
                 raise ValueError("dim_map: keys and remapped ids differ in length")
             desc.map_keys, desc.map_values, desc.n_map = F.ptr(keys), F.ptr(vals), len(keys)
         desc.device_id = device_id
+        desc.flags = self._WEIGHTS[self.index_datatype]
         self.n = n
         self.dim_map = dim_map
         F.check(F.lib().qmx_sparse_segment_create(C.byref(desc), C.byref(self._h)))
@@ -1050,18 +1065,49 @@ class SparseVectorStorage:
             self._h, F.ptr(pw), 0 if point_deleted is None else len(point_deleted),
             F.ptr(vw), 0 if vec_deleted is None else len(vec_deleted)))
 
-    def _raw_scorer(self, queries) -> RawScorer:
+    def idf_statistics(self, dims, corpus=None):
+        """`fill_idf_statistics` (sparse_vector_index/read_view/idf.rs): (df, n_docs) for the ORIGINAL dimensions `dims` - df[i] = 0 for one the
+        map or the segment lacks.  `corpus` None: global statistics (whole posting lengths, the non-empty vectors indexed); a bool mask over
+        point ids: the corpus points that are neither point- nor vector-deleted, counted on the device.  Statistics of several segments are
+        added by the caller and handed to `search(idf=(dims, df, n_docs))`."""
+        dims = np.ascontiguousarray(dims, dtype=np.uint32)
+        df = np.zeros(len(dims), dtype=np.uint64)
+        n_docs = C.c_uint64(0)
+        words = _bits_to_words(corpus)
+        F.check(F.lib().qmx_sparse_idf_statistics(self._h, F.ptr(dims), len(dims), F.ptr(words), 0 if corpus is None else len(corpus), F.ptr(df),
+                                                  C.byref(n_docs)))
+        return df, int(n_docs.value)
+
+    def _raw_scorer(self, queries, idf=None) -> RawScorer:
+        """`idf`: None; True = this segment's global statistics; a bool mask over point ids = this segment's corpus statistics; or
+        (dims, df, n_docs) = statistics the caller merged."""
         off, idx, val = _sparse_csr(queries)
         h = C.c_void_p()
         nq = len(off) - 1
-        F.check(F.lib().qmx_sparse_query_create(self._h, F.ptr(off), F.ptr(idx), F.ptr(val), nq, C.byref(h)))
+        if idf is None or idf is False:
+            F.check(F.lib().qmx_sparse_query_create(self._h, F.ptr(off), F.ptr(idx), F.ptr(val), nq, C.byref(h)))
+            return RawScorer(h, self, nq)
+        if hasattr(off, "data_ptr"):
+            off, idx, val = _sparse_csr((off.cpu().numpy(), idx.cpu().numpy(), val.cpu().numpy()))
+        if isinstance(idf, tuple) and len(idf) == 3:
+            dims, df, n_docs = idf
+        else:
+            dims = np.unique(idx)
+            df, n_docs = self.idf_statistics(dims, None if idf is True else idf)
+        dims = np.ascontiguousarray(dims, dtype=np.uint32)
+        df = np.ascontiguousarray(df, dtype=np.uint64)
+        if len(dims) != len(df):
+            raise ValueError("idf: dims and df differ in length")
+        F.check(F.lib().qmx_sparse_query_create_idf(self._h, F.ptr(off), F.ptr(idx), F.ptr(val), nq, F.ptr(dims), F.ptr(df), len(dims), int(n_docs),
+                                                    C.byref(h)))
         return RawScorer(h, self, nq)
 
-    def search(self, queries, top: int, ids=None, allowed=None) -> List[np.ndarray]:
+    def search(self, queries, top: int, ids=None, allowed=None, idf=None) -> List[np.ndarray]:
         """`search_nearest_query` (sparse_vector_index/read_view/search.rs:258-300): per query the `top` best points that share at least one
         dimension with it, score descending (lower offset first among equal scores).  `ids`: the prefiltered candidates (plain_search);
-        `allowed`: a payload-filter allow mask over point ids.  top == 0 gives empty lists."""
-        scorer = self._raw_scorer(queries)
+        `allowed`: a payload-filter allow mask over point ids.  top == 0 gives empty lists.  `idf` (`Modifier::Idf`): True, a corpus mask or
+        merged (dims, df, n_docs) - every query weight is multiplied by ln((n - df + 0.5) / (df + 0.5) + 1) first."""
+        scorer = self._raw_scorer(queries, idf=idf)
         try:
             nq = scorer.nq
             if top == 0 or nq == 0:

@@ -10,7 +10,12 @@ One JSON line per run on stdout; `--out` also writes it to a file.
 `--custom KIND:EXAMPLES` (reco_best, reco_sum, discover, context, feedback; for instance `reco_best:7`, `discover:7`): per batch size Q, Q custom
 queries of that many examples each through qmx_sparse_custom_search_topk over the same segment - ms per batch, QPS, the posting bytes of all
 examples with their GB/s and fraction of 8 TB/s - and beside them the Nearest search of the same Q x EXAMPLES example vectors as plain queries
-(same process, same segment): a custom query of E examples reads the postings E plain queries read."""
+(same process, same segment): a custom query of E examples reads the postings E plain queries read.
+
+`--weights f32|f16|u8`: the index weights' datatype (`SparseIndexConfig.datatype`); the record carries the posting layout's bytes (8 / 6 / 5 B per
+entry) and the device memory the segment took at create.  Over f16 / u8 weights `--custom` measures the row scan that serves the full scan there.
+`--idf`: the queries are created with the IDF modifier (global statistics of the segment), and per batch size the record also times
+`qmx_sparse_idf_statistics` for the batch's dimensions under a 50 % corpus mask (the mask resident on the device)."""
 import argparse
 import ctypes as C
 import json
@@ -101,6 +106,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=20241016)
     ap.add_argument("--custom", default=None, metavar="KIND:EXAMPLES", help="custom queries instead of Nearest, e.g. reco_best:7, discover:7")
+    ap.add_argument("--weights", default="f32", choices=["f32", "f16", "u8"], help="datatype of the index weights")
+    ap.add_argument("--idf", action="store_true", help="IDF-scaled queries, and time the corpus statistics of each batch's dimensions")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -123,9 +130,18 @@ def main():
     del lens_l, dims_l, w_l
     nnz = int(offsets[-1])
     torch.cuda.synchronize()
+    datatype = {"f32": qa.VectorStorageDatatype.Float32, "f16": qa.VectorStorageDatatype.Float16, "u8": qa.VectorStorageDatatype.Uint8}[args.weights]
+    entry_bytes = {"f32": 8, "f16": 6, "u8": 5}[args.weights]
+    free_before = torch.cuda.mem_get_info(dev)[0]
     t0 = time.perf_counter()
-    st = qa.SparseVectorStorage(offsets, indices, values)
+    st = qa.SparseVectorStorage(offsets, indices, values, index_datatype=datatype)
     create_s = time.perf_counter() - t0
+    segment_bytes = free_before - torch.cuda.mem_get_info(dev)[0]
+    corpus_words = None
+    if args.idf:
+        mgen = torch.Generator(device=dev)
+        mgen.manual_seed(args.seed + 2)
+        corpus_words = torch.randint(-2**63, 2**63 - 1, ((args.points + 63) // 64,), generator=mgen, device=dev, dtype=torch.int64)      # ~50 % of the points
     del indices, values
     torch.cuda.empty_cache()
     csr_bytes = nnz * 8 + (args.points + 1) * 8
@@ -169,7 +185,20 @@ def main():
         qidx = qd.cpu().numpy().astype(np.uint32)
         qval = qw.cpu().numpy()
         h = C.c_void_p()
-        F.check(F.lib().qmx_sparse_query_create(st._h, F.ptr(qoff), F.ptr(qidx), F.ptr(qval), nq, C.byref(h)))
+        idf_rec = {}
+        if args.idf:
+            qdims = np.unique(qidx)
+            df = np.zeros(len(qdims), dtype=np.uint64)
+            n_docs = C.c_uint64(0)
+            stat_ms = timed(lambda: F.check(F.lib().qmx_sparse_idf_statistics(st._h, F.ptr(qdims), len(qdims), F.ptr(corpus_words), args.points, F.ptr(df),
+                                                                              C.byref(n_docs))), args.warmup, args.steps)
+            idf_rec = {"idf_corpus_statistics_ms": round(stat_ms, 3), "idf_dims": len(qdims), "idf_corpus_docs": int(n_docs.value),
+                       "idf_corpus_posting_entries": int(df.sum())}
+            df, n_docs = st.idf_statistics(qdims)
+            F.check(F.lib().qmx_sparse_query_create_idf(st._h, F.ptr(qoff), F.ptr(qidx), F.ptr(qval), nq, F.ptr(qdims), F.ptr(df), len(qdims), n_docs,
+                                                        C.byref(h)))
+        else:
+            F.check(F.lib().qmx_sparse_query_create(st._h, F.ptr(qoff), F.ptr(qidx), F.ptr(qval), nq, C.byref(h)))
         out = np.zeros((nq, args.top), dtype=qa.ScoredPointOffset)
         counts = np.zeros(nq, dtype=np.uint32)
         ctr = F.Counters()
@@ -182,13 +211,15 @@ def main():
             times.append(time.perf_counter() - t0)
         F.lib().qmx_query_destroy(h)
         ms = 1e3 * float(np.median(times))
+        idf_rec["ms_runs"] = [round(1e3 * t, 3) for t in times]
         post_bytes = int(ctr.bytes_read)
         gbs = post_bytes / (ms * 1e-3) / 1e9
         results.append({"queries": nq, "ms_per_batch": round(ms, 3), "qps": round(nq / (ms * 1e-3), 1), "posting_bytes": post_bytes,
                         "posting_gb_per_s": round(gbs, 1), "hbm_fraction": round(gbs * 1e9 / HBM_BYTES_PER_S, 4),
-                        "mean_results": float(counts.mean())})
+                        "mean_results": float(counts.mean()), **idf_rec})
     rec = {"tool": "bench_sparse", "points": args.points, "dims": args.dims, "nnz": nnz, "mean_row_nnz": round(nnz / args.points, 2),
-           "qnnz": args.qnnz, "top": args.top, "csr_bytes": csr_bytes, "posting_layout_bytes": nnz * 8, "create_s": round(create_s, 3),
+           "qnnz": args.qnnz, "top": args.top, "csr_bytes": csr_bytes, "weights": args.weights, "idf": bool(args.idf), "posting_layout_bytes": nnz * entry_bytes,
+           "segment_device_bytes": int(segment_bytes), "create_s": round(create_s, 3),
            "device": torch.cuda.get_device_name(0), "batches": results}
     if args.custom:
         rec["custom"] = args.custom
