@@ -818,6 +818,27 @@ QMX_API int32_t qmx_mmr_select(qmx_query *q, const qmx_scored_point *candidates,
 QMX_API int32_t qmx_mmr_select_async(qmx_query *q, const qmx_scored_point *candidates_dev, const uint32_t *counts_dev, uint32_t stride,
                                      float lambda, uint32_t limit, qmx_scored_point *out_dev, uint32_t *out_counts_dev);
 
+/* The same re-ranking over SPARSE vectors (the reference's temporary MMR storage of the `Sparse` kind, mmr/mod.rs:103-140).  `q` = a batch made by
+ * qmx_sparse_query_create / _create_idf over a sparse segment: query qi is the `mmr.vector` of request qi (a dense batch: QMX_ERR_BAD_ARG).
+ * Steps 1, 4 and 5, the arguments, the caps and the errors are those of qmx_mmr_select; what changes:
+ *   2./3. relevance(c) and sim(c, s) are both `SparseMetricQueryScorer::score_sparse` = a.score(b).unwrap_or_default()
+ *      (query_scorer/sparse_metric_query_scorer.rs:37-44): the products of the shared dimensions, each rounded, added from +0.0 in ascending
+ *      index order, each add rounded; 0.0 (never -0.0) without a shared dimension or for an empty vector.  The operands are the segment's f32 rows
+ *      whatever its index weights are (QMX_SPARSE_WEIGHT_*), and the request's query as given (IDF-scaled by _create_idf); deleted flags are not read.
+ *   The order of that sum is the ORIGINAL index order: the reference scores the vectors as they come off the points, the IndicesTracker never
+ *      sees them (the rule of qmx_sparse_custom_*).  Without a dimension map, or under a monotone one, that is the stored order and the relevance
+ *      has the bits of qmx_score_points; under any other map the sums run in another order than the Nearest scores of the same pairs.
+ *   A batch made by qmx_query_create_internal is accepted on a segment without a map; on a mapped one its rows have lost their original order:
+ *      QMX_ERR_NOT_SUPPORTED, as the sparse custom calls answer it.
+ * Rows and queries of any length are served.  qmx_mmr_select itself keeps refusing sparse batches (QMX_ERR_NOT_SUPPORTED).  Host or device memory;
+ * synchronises. */
+QMX_API int32_t qmx_sparse_mmr_select(qmx_query *q, const qmx_scored_point *candidates, const uint32_t *counts, uint32_t stride, float lambda,
+                                      uint32_t limit, qmx_scored_point *out, uint32_t *out_counts);
+/* Same, but only enqueues on the query's stream (qmx_query_set_stream); device memory; complete with qmx_query_synchronize.  An out-of-range id
+ * empties its request's list and is reported by the next synchronous call on this batch. */
+QMX_API int32_t qmx_sparse_mmr_select_async(qmx_query *q, const qmx_scored_point *candidates_dev, const uint32_t *counts_dev, uint32_t stride,
+                                            float lambda, uint32_t limit, qmx_scored_point *out_dev, uint32_t *out_counts_dev);
+
 /* ---- HNSW search on device -------------------------------------------------------------------- */
 
 /* One built graph = `GraphLayers` (lib/segment/src/index/hnsw_index/graph_layers.rs:58-72): the

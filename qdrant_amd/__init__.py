@@ -10,4 +10,4 @@ from .scorer import (BatchFilteredSearcher, Distance, EncodedVectorsPQ, EncodedV
                      new_raw_scorer_internal, pq_train, search_quantized, CustomQuery, CustomRawScorer, BinaryQuantizer, EncodedVectorsBin, load_quantizer, MultiDenseVectorStorage, QuantizedMultivectorStorage, TurboQuantizer, EncodedVectorsTQ, vector_stats,
                      SparseVectorStorage)
 from .hnsw import GraphLayers, decode_links_file  # noqa: F401
-from .query import Dbsf, Mmr, Rrf, dbsf, hybrid_search, mmr, rrf  # noqa: F401
+from .query import Dbsf, Mmr, Rrf, dbsf, hybrid_search, mmr, rrf, sparse_mmr  # noqa: F401

@@ -142,6 +142,7 @@ class FusionParams(C.Structure):
 
 FUSION_RRF, FUSION_DBSF = range(2)
 FUSE_MAX_SOURCES, FUSE_MAX_ENTRIES, MMR_MAX_CANDIDATES = 64, 8192, 4096
+SPARSE_MMR_STAGE_CAP = 6144      # entries of a query or picked row that qmx_sparse_mmr_select keeps in LDS; longer ones are read where they lie
 
 
 class QmxError(RuntimeError):
@@ -215,6 +216,8 @@ SIGNATURES = {
     "qmx_fuse_topk_async": (C.c_int32, [C.c_int32, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(FusionParams), _P, _P]),
     "qmx_mmr_select": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
     "qmx_mmr_select_async": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
+    "qmx_sparse_mmr_select": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
+    "qmx_sparse_mmr_select_async": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
     "qmx_sharded_search_topk": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),
     "qmx_sharded_search_topk_async": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "qmx_sharded_hnsw_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),

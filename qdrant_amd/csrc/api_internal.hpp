@@ -167,6 +167,7 @@ struct qmx_query {
     uint32_t n_cq_coefs = 0;
     DevBuf cand, cand_cnt, cand_ids;   // qmx_search_quantized: oversampled candidates of the quantized stage
     DevBuf mmr_ids, mmr_rel;           // qmx_mmr_select: the candidates' ids and their relevance, per input position
+    DevBuf mmr_spill;                  // qmx_sparse_mmr_select over a mapped segment: per request a picked row too long for LDS, in original order
     // split prefilter (scan_split.hip): split queries, per-query norms / thresholds / bands, scales, candidate and verification buffers, flag
     DevBuf sp_bq, sp_f32, sp_cand, sp_cnt, sp_ver, sp_vscores, sp_sample, sp_wl, xcnt, tq_rot;
     DevBuf sh_lists, sh_out;   // qmx_sharded_*: the segments' lists gathered on this (the first) batch's device, the merged lists of a host-output call

@@ -198,6 +198,7 @@ int32_t qmx_query_destroy(qmx_query *q) {
     q->cand_ids.release();
     q->mmr_ids.release();
     q->mmr_rel.release();
+    q->mmr_spill.release();
     q->hnsw_vis.release();
     q->hnsw_log.release();
     q->hnsw_scored.release();

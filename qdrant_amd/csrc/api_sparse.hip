@@ -1,6 +1,6 @@
 // api_sparse.hip — the C-ABI of include/qdrant_amd.h, sparse vectors (QMX_DTYPE_SPARSE): segment and query creation, the sparse arms of
 // score_points / score_internal / search_topk that api_query.hip and api_search.hip dispatch to, and the custom queries over sparse vectors
-// (qmx_sparse_custom_*).  The kernels are in sparse.hip.
+// (qmx_sparse_custom_*), and MMR re-ranking over them (qmx_sparse_mmr_select*).  The kernels are in sparse.hip and sparse_mmr.hip.
 // (One of the api_*.hip translation units; what they share: api_internal.hpp.)
 #include "api_internal.hpp"
 
@@ -22,6 +22,11 @@ struct SparseSeg {
     std::vector<uint64_t> dir_start;         // [D + 1]
     std::vector<uint32_t> map_keys, map_vals;   // sorted by key; empty = identity
     bool has_map = false;
+    uint64_t longest_row = 0;                // entries of the longest row
+    // a map under which ascending remapped id is NOT ascending original index: its remapped ids ascending and the original index of each, for the
+    // pair scores of qmx_sparse_mmr_select (sparse_mmr.hip); null under no map or a monotone one
+    uint32_t *d_inv_vals = nullptr, *d_inv_keys = nullptr;
+    uint32_t n_inv = 0;
 };
 
 // a query batch: CSR lists sorted by (remapped) index, and the posting plan of every query (its dimensions that have postings, ascending)
@@ -43,6 +48,7 @@ struct SparseQuery {
     bool own_original = false;
     bool internal = false;                   // made by qmx_query_create_internal: stored rows, whose original order is not known
     std::vector<uint64_t> h_entries;         // [nq]: posting entries of each query
+    uint64_t longest = 0;                    // entries of the longest list
 };
 
 static SparseRows rows_of(const qmx_segment *s) {
@@ -63,6 +69,8 @@ void sparse_segment_free(qmx_segment *s) {
     if (sp->d_post) (void)hipFree(sp->d_post);
     if (sp->d_post_id) (void)hipFree(sp->d_post_id);
     if (sp->d_post_w) (void)hipFree(sp->d_post_w);
+    if (sp->d_inv_vals) (void)hipFree(sp->d_inv_vals);
+    if (sp->d_inv_keys) (void)hipFree(sp->d_inv_keys);
     delete sp;
     s->sparse = nullptr;
 }
@@ -132,6 +140,7 @@ static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, cons
     const bool u8 = sp->wtype == QMX_SPARSE_WEIGHT_U8;
     posting_plan(sp, q->nq, off, idx, val, poff, pstart, pend, pw, &sq->h_entries, u8 ? &pmn : nullptr, u8 ? &pd256 : nullptr);
     for (uint64_t e : sq->h_entries) sq->posting_entries += e;
+    for (uint32_t qi = 0; qi < q->nq; ++qi) sq->longest = std::max(sq->longest, off[qi + 1] - off[qi]);
     QMX_TRY(upload(&sq->d_off, off.data(), off.size()));
     QMX_TRY(upload(&sq->d_idx, idx.data(), idx.size()));
     QMX_TRY(upload(&sq->d_val, val.data(), val.size()));
@@ -375,7 +384,10 @@ int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment 
         if (!sp) { set_error("host allocation failed"); rc = QMX_ERR_OUT_OF_MEMORY; break; }
         sp->nnz = nnz;
         sp->h_off = std::move(h_off);
-        for (uint64_t r = 0; r < d->n; ++r) sp->n_nonempty += sp->h_off[r + 1] > sp->h_off[r];
+        for (uint64_t r = 0; r < d->n; ++r) {
+            sp->n_nonempty += sp->h_off[r + 1] > sp->h_off[r];
+            sp->longest_row = std::max(sp->longest_row, sp->h_off[r + 1] - sp->h_off[r]);
+        }
         if ((rc = upload(&sp->d_off, sp->h_off.data(), sp->h_off.size())) != QMX_OK) break;
         if ((rc = upload(&sp->d_idx, d->indices, nnz)) != QMX_OK) break;
         if ((rc = upload(&sp->d_val, d->values, nnz)) != QMX_OK) break;
@@ -402,6 +414,23 @@ int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment 
             uint32_t missing = 0;
             if (!hip(hipMemcpy(&missing, d_flag, 4, hipMemcpyDeviceToHost), "remap flag")) break;
             if (missing) { set_error("a stored index is not in the dimension map"); rc = QMX_ERR_BAD_ARG; break; }
+            // the map by remapped id, kept where it changes the order (the first original index of a remapped id two of them share)
+            bool monotone = true;
+            for (size_t i = 1; i < sp->map_vals.size(); ++i) monotone = monotone && sp->map_vals[i - 1] < sp->map_vals[i];
+            if (!monotone) {
+                std::vector<std::pair<uint32_t, uint32_t>> inv;
+                for (size_t i = 0; i < sp->map_keys.size(); ++i) inv.push_back({sp->map_vals[i], sp->map_keys[i]});
+                std::sort(inv.begin(), inv.end());
+                std::vector<uint32_t> iv, ik;
+                for (size_t i = 0; i < inv.size(); ++i)
+                    if (i == 0 || inv[i].first != inv[i - 1].first) {
+                        iv.push_back(inv[i].first);
+                        ik.push_back(inv[i].second);
+                    }
+                sp->n_inv = (uint32_t)iv.size();
+                if ((rc = upload(&sp->d_inv_vals, iv.data(), iv.size())) != QMX_OK) break;
+                if ((rc = upload(&sp->d_inv_keys, ik.data(), ik.size())) != QMX_OK) break;
+            }
         }
         // sorted by index on the way in; duplicates refused
         if ((rc = launch_sparse_check_rows(nullptr, sp->d_off, sp->d_idx, s->n, d_flag)) != QMX_OK) break;
@@ -748,6 +777,80 @@ int32_t qmx_sparse_custom_search_topk(qmx_query *ex, const qmx_custom_query *que
         if (counters) counters->kernel_ms = ex->timing_ms - before;
     }
     return QMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// MMR re-ranking over sparse vectors (sparse_mmr_select_kernel in sparse_mmr.hip)
+// ---------------------------------------------------------------------------------------------
+static int32_t sparse_mmr_check(const qmx_query *q, const void *cand, const void *counts, uint32_t stride, uint32_t limit, const void *out, const void *oc,
+                                const char *fn) {
+    QMX_REQUIRE(q && out && oc && (q->nq == 0 || (counts && (stride == 0 || cand))), QMX_ERR_BAD_ARG, "NULL argument");
+    QMX_REQUIRE(is_sparse(q) && q->sparse, QMX_ERR_BAD_ARG, "%s needs a batch made by qmx_sparse_query_create over a sparse segment (dense segments: qmx_mmr_select)", fn);
+    // a batch of stored rows carries no original order under a map: the status of the sparse custom calls
+    QMX_REQUIRE(!(q->sparse->internal && q->seg->sparse->has_map), QMX_ERR_NOT_SUPPORTED,
+                "%s over a mapped segment needs a batch made by qmx_sparse_query_create (stored rows have lost their original order)", fn);
+    QMX_REQUIRE(limit >= 1, QMX_ERR_BAD_ARG, "limit must be > 0");
+    QMX_REQUIRE(limit <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "limit %u > %u", limit, MAX_TOP);
+    QMX_REQUIRE(stride <= MMR_MAX_CANDIDATES, QMX_ERR_NOT_SUPPORTED, "MMR over %u candidates per request (at most %u)", stride, MMR_MAX_CANDIDATES);
+    return QMX_OK;
+}
+
+static int32_t sparse_mmr_enqueue(qmx_query *q, const qmx_scored_point *d_cand, const uint32_t *d_counts, uint32_t stride, float lambda, uint32_t limit,
+                                  qmx_scored_point *d_out, uint32_t *d_oc) {
+    const SparseSeg *sp = q->seg->sparse;
+    const SparseQuery *sq = q->sparse;
+    SparseMmrArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rows = rows_of(q->seg);
+    a.qs = SparseQueries{sq->d_off, sq->d_oidx, sq->d_oval};
+    a.inv_vals = sp->d_inv_vals;
+    a.inv_keys = sp->d_inv_keys;
+    a.n_inv = sp->n_inv;
+    a.stage_cap = (uint32_t)std::min<uint64_t>(SPARSE_MMR_STAGE_CAP, std::max(sp->longest_row, sq->longest));
+    if (sp->d_inv_vals && sp->longest_row > SPARSE_MMR_STAGE_CAP) {      // a picked row that outgrows LDS is ranked into the request's slice
+        a.spill_stride = sp->longest_row;
+        QMX_TRY(q->mmr_spill.reserve((size_t)q->nq * 3 * a.spill_stride * 4));
+        a.spill = (uint32_t *)q->mmr_spill.p;
+    }
+    a.cand = d_cand;
+    a.counts = d_counts;
+    a.stride = stride;
+    a.lambda = lambda;
+    a.limit = limit;
+    a.out = d_out;
+    a.out_counts = d_oc;
+    a.err_flag = q->d_err;
+    QMX_TRY(launch_sparse_mmr_select(q->stream, a, q->nq));
+    q->last_kernel = last_noted_kernel();
+    return QMX_OK;
+}
+
+int32_t qmx_sparse_mmr_select(qmx_query *q, const qmx_scored_point *candidates, const uint32_t *counts, uint32_t stride, float lambda, uint32_t limit,
+                              qmx_scored_point *out, uint32_t *out_counts) {
+    QMX_TRY(sparse_mmr_check(q, candidates, counts, stride, limit, out, out_counts, __func__));
+    QMX_HIP(hipSetDevice(q->device));
+    if (q->nq == 0) return QMX_OK;
+    const void *d_cand = nullptr, *d_counts = nullptr;
+    QMX_TRY(stage_in(q, q->cand, candidates, (size_t)q->nq * stride * sizeof(qmx_scored_point), &d_cand));
+    QMX_TRY(stage_in(q, q->cand_cnt, counts, (size_t)q->nq * 4, &d_counts));
+    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
+    qmx_scored_point *d_out = out;
+    uint32_t *d_oc = out_counts;
+    if (!out_dev) { QMX_TRY(q->out.reserve((size_t)q->nq * limit * sizeof(qmx_scored_point))); d_out = (qmx_scored_point *)q->out.p; }
+    if (!cnt_dev) { QMX_TRY(q->counts.reserve((size_t)q->nq * 4)); d_oc = (uint32_t *)q->counts.p; }
+    QMX_TRY(sparse_mmr_enqueue(q, (const qmx_scored_point *)d_cand, (const uint32_t *)d_counts, stride, lambda, limit, d_out, d_oc));
+    if (!out_dev) QMX_TRY(copy_out(q->stream, out, d_out, (size_t)q->nq * limit * sizeof(qmx_scored_point)));
+    if (!cnt_dev) QMX_TRY(copy_out(q->stream, out_counts, d_oc, (size_t)q->nq * 4));
+    return check_err_flag(q);      // synchronises
+}
+
+int32_t qmx_sparse_mmr_select_async(qmx_query *q, const qmx_scored_point *candidates_dev, const uint32_t *counts_dev, uint32_t stride, float lambda,
+                                    uint32_t limit, qmx_scored_point *out_dev, uint32_t *out_counts_dev) {
+    QMX_TRY(sparse_mmr_check(q, candidates_dev, counts_dev, stride, limit, out_dev, out_counts_dev, __func__));
+    QMX_HIP(hipSetDevice(q->device));
+    if (q->nq == 0) return QMX_OK;
+    QMX_REQUIRE(stride == 0 || is_device_ptr(candidates_dev), QMX_ERR_BAD_ARG, "async MMR needs device candidates");
+    return sparse_mmr_enqueue(q, candidates_dev, counts_dev, stride, lambda, limit, out_dev, out_counts_dev);
 }
 
 }  // extern "C"

@@ -587,4 +587,26 @@ struct MmrArgs {
 };
 int32_t launch_mmr_select(hipStream_t st, int dtype, int distance, const MmrArgs &a, uint32_t nq);
 
+// MMR re-ranking over sparse vectors (sparse_mmr.hip): the same selection, pair scores in ascending ORIGINAL index order
+constexpr uint32_t SPARSE_MMR_STAGE_CAP = 6144;   // entries of the staged list (query or picked row) kept in LDS: 12 bytes each beside the 80 KiB of candidates
+struct SparseMmrArgs {
+    SparseRows rows;                 // the segment's f32 CSR rows (sorted by remapped id)
+    SparseQueries qs;                // the batch's lists in ascending original index order (remapped ids)
+    const uint32_t *inv_vals;        // non-monotone dimension map: its remapped ids ascending and ...
+    const uint32_t *inv_keys;        // ... the original index of each; both null where stored order IS original order
+    uint32_t n_inv;
+    uint32_t stage_cap;              // min(SPARSE_MMR_STAGE_CAP, the longest row or query)
+    uint32_t *spill;                 // [nq][3][spill_stride]: a picked row longer than stage_cap, ranked (mapped segments only), or null
+    uint64_t spill_stride;           // the segment's longest row
+    const qmx_scored_point *cand;    // [nq][stride]
+    const uint32_t *counts;          // [nq]
+    uint32_t stride;
+    float lambda;
+    uint32_t limit;
+    qmx_scored_point *out;           // [nq][limit]
+    uint32_t *out_counts;            // [nq]
+    int *err_flag;                   // set to 1 on an out-of-range candidate id
+};
+int32_t launch_sparse_mmr_select(hipStream_t st, const SparseMmrArgs &a, uint32_t nq);
+
 }  // namespace qmx

@@ -4,6 +4,8 @@
 //  maximal_marginal_relevance    lib/shard/src/query/mmr/mod.rs:198-279   (first pick by relevance, then lambda * rel - (1 - lambda) * max sim)
 //  LazyMatrix::get_similarity    lib/shard/src/query/mmr/lazy_matrix.rs:56-67 (scorers[c].score_point(s): candidate c as the query, row s stored)
 //
+// (The selection machinery - unique by id, the order array, OrderedFloat keys, the arg-max, the pick - is mmr_common.hpp's, shared with sparse_mmr.hip.)
+//
 // One work-group per request, every selection step inside the one launch.  The reference only ever asks for (candidate, selected) pairs, so a step
 // scores the remaining candidates against the ONE row selected last (staged in LDS as f32) and folds that column into a running maximum:
 // limit x C row scores per request, no C x C matrix.  In LDS per candidate: its input position, its id, its relevance, max_sim_to_selected and its
@@ -16,11 +18,9 @@
 // storage is always f32 (new_volatile_dense_vector_storage) - and the f32 metric applied.  The leaves are symmetric in their two vectors bit for bit
 // (a * b, (a - b)^2 and |a - b| are), so the selected row serves as the LDS-resident side.
 #include "dense_policies.hpp"
+#include "mmr_common.hpp"
 
 namespace qmx {
-
-constexpr int MMR_BLOCK = 1024;
-constexpr int MMR_NW = MMR_BLOCK / WAVE;
 
 // element types of the stored block, widened to f32 (exact)
 struct ElemF32 {
@@ -45,9 +45,6 @@ struct ElemU8 {
     }
     static __device__ __forceinline__ float load1(const unsigned char *row, uint32_t e) { return (float)row[e]; }
 };
-
-// OrderedFloat as one u32 (lib/common/common/src/types.rs: NaN greatest, -0.0 == 0.0)
-__device__ __forceinline__ uint32_t ordered_float(float s) { return score_to_ord(s == 0.0f ? 0.0f : s); }
 
 // rows of 32 elements and more: the AVX leaf (simple_avx.rs) by the 8 lanes of a group, candidate row `crow` as the query against the selected
 // row `sel` (f32, LDS).  Accumulators, step order and hsum are group_score<RowF32>'s; U row pieces in flight per lane.
@@ -88,33 +85,17 @@ __device__ __forceinline__ float mmr_group_score(const float *sel, const unsigne
     return result;
 }
 
-// block-wide maximum of one u64 key per thread (0 = none), returned to every thread
-__device__ __forceinline__ uint64_t mmr_block_max(uint64_t key, uint64_t *s_best) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = __shfl_xor((int)(uint32_t)key, off, 64), hi = __shfl_xor((int)(uint32_t)(key >> 32), off, 64);
-        const uint64_t other = ((uint64_t)hi << 32) | lo;
-        key = other > key ? other : key;
-    }
-    __syncthreads();      // the previous round's readers are done with s_best
-    if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = key;
-    __syncthreads();
-    uint64_t best = s_best[0];
-#pragma unroll
-    for (int w = 1; w < MMR_NW; ++w) best = s_best[w] > best ? s_best[w] : best;
-    return best;
-}
-
 template <int METRIC, class E>
 __global__ __launch_bounds__(MMR_BLOCK) void mmr_select_kernel(const MmrArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char mmr_smem[];
     const uint32_t S = (a.stride + 3) & ~3u;
-    uint32_t *s_id = reinterpret_cast<uint32_t *>(mmr_smem);      // [S] id of every input position
-    uint32_t *s_src = s_id + S;                                    // [S] input position of unique candidate c
-    uint32_t *s_order = s_src + S;                                 // [S] remaining_indices: candidate at every position of the current order
-    float *s_rel = reinterpret_cast<float *>(s_order + S);         // [S] relevance of candidate c
-    float *s_max = s_rel + S;                                      // [S] max_similarity_to_selected of candidate c
-    float *s_row = s_max + S;                                      // [dim] the row selected last, as f32
+    MmrLists l;
+    l.id = reinterpret_cast<uint32_t *>(mmr_smem);
+    l.src = l.id + S;
+    l.order = l.src + S;
+    l.rel = reinterpret_cast<float *>(l.order + S);
+    l.max = l.rel + S;
+    float *s_row = l.max + S;      // [dim] the row selected last, as f32
     __shared__ uint64_t s_best[MMR_NW];
     __shared__ uint32_t s_bad, s_n, s_sel;
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
@@ -124,54 +105,18 @@ __global__ __launch_bounds__(MMR_BLOCK) void mmr_select_kernel(const MmrArgs a) 
     const unsigned char *rows = reinterpret_cast<const unsigned char *>(a.rows);
     const uint32_t cnt = a.counts[q] < a.stride ? a.counts[q] : a.stride;
 
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    for (uint32_t j = tid; j < cnt; j += MMR_BLOCK) {
-        const uint32_t id = cand[j].idx;
-        s_id[j] = id;
-        if (id >= a.n_rows) s_bad = 1;
-    }
-    __syncthreads();
-    if (s_bad) {      // no row is read through an id the segment does not hold: the request is dropped, the caller gets QMX_ERR_OUT_OF_BOUNDS
-        if (tid == 0) {
-            *a.err_flag = 1;
-            a.out_counts[q] = 0;
-        }
-        for (uint32_t i = tid; i < a.limit; i += MMR_BLOCK) out[i] = qmx_scored_point{0u, 0.0f};
-        return;
-    }
-
-    // unique_by(|p| p.id): the first occurrence stays, the order is kept
-    for (uint32_t j = tid; j < cnt; j += MMR_BLOCK) {
-        const uint32_t id = s_id[j];
-        bool dup = false;
-        for (uint32_t e = 0; e < j; ++e) dup = dup || (s_id[e] == id);
-        s_order[j] = dup ? 0u : 1u;
-    }
-    __syncthreads();
-    if (tid < 64) {
-        uint32_t running = 0;
-        for (uint32_t base = 0; base < cnt; base += 64) {
-            const uint32_t j = base + (uint32_t)lane;
-            const bool keep = j < cnt && s_order[j] != 0u;
-            const uint64_t m = __ballot(keep);
-            if (keep) s_src[running + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = j;
-            running += (uint32_t)__popcll(m);
-        }
-        if (lane == 0) s_n = running;
-    }
-    __syncthreads();
-    const uint32_t C = s_n;
+    if (!mmr_load_ids(l, cand, cnt, a.n_rows, a.limit, out, a.out_counts + q, a.err_flag, &s_bad)) return;
+    const uint32_t C = mmr_unique(l, cnt, &s_n);
     for (uint32_t c = tid; c < C; c += MMR_BLOCK) {
-        s_order[c] = c;
-        s_rel[c] = a.rel[(uint64_t)q * a.stride + s_src[c]];
-        s_max[c] = 0.0f;
+        l.order[c] = c;
+        l.rel[c] = a.rel[(uint64_t)q * a.stride + l.src[c]];
+        l.max[c] = 0.0f;
     }
     __syncthreads();
 
     uint32_t n_sel = 0;
     if (C < 2) {      // "can't compute MMR for less than 2 points, return with original score" (mod.rs:77-80)
-        if (tid == 0 && C == 1) out[0] = cand[s_src[0]];
+        if (tid == 0 && C == 1) out[0] = cand[l.src[0]];
         n_sel = C;
     } else {
         const uint32_t L = a.limit < C ? a.limit : C;
@@ -183,11 +128,11 @@ __global__ __launch_bounds__(MMR_BLOCK) void mmr_select_kernel(const MmrArgs a) 
             uint64_t best = 0;
             if (n_sel == 0) {      // the candidate of greatest relevance
                 for (uint32_t p = tid; p < R; p += MMR_BLOCK) {
-                    const uint64_t key = ((uint64_t)ordered_float(s_rel[s_order[p]]) << 32) | p;
+                    const uint64_t key = mmr_key(l.rel[l.order[p]], p);
                     best = key > best ? key : best;
                 }
             } else {
-                const uint32_t sel_id = s_id[s_src[s_sel]];
+                const uint32_t sel_id = l.id[l.src[s_sel]];
                 const unsigned char *srow = rows + (uint64_t)sel_id * a.row_stride;
                 for (uint32_t e = tid; e < a.dim; e += MMR_BLOCK) s_row[e] = E::load1(srow, e);
                 __syncthreads();
@@ -196,38 +141,25 @@ __global__ __launch_bounds__(MMR_BLOCK) void mmr_select_kernel(const MmrArgs a) 
                     for (uint32_t base = 0; base < R; base += MMR_BLOCK / 8) {
                         const uint32_t p = base + g;
                         const bool valid = p < R;
-                        const uint32_t c = s_order[valid ? p : 0];
-                        const float sim = mmr_group_score<METRIC, E>(s_row, rows + (uint64_t)s_id[s_src[c]] * a.row_stride, a.dim, t);
+                        const uint32_t c = l.order[valid ? p : 0];
+                        const float sim = mmr_group_score<METRIC, E>(s_row, rows + (uint64_t)l.id[l.src[c]] * a.row_stride, a.dim, t);
                         if (valid && t == 0) {
-                            const float m = first || ordered_float(sim) >= ordered_float(s_max[c]) ? sim : s_max[c];
-                            s_max[c] = m;
-                            const float mmr = lambda * s_rel[c] - one_minus * m;
-                            const uint64_t key = ((uint64_t)ordered_float(mmr) << 32) | p;
+                            const uint64_t key = mmr_fold(l, c, p, sim, first, lambda, one_minus);
                             best = key > best ? key : best;
                         }
                     }
                 } else {      // below the AVX threshold: the SSE / scalar leaf, one lane per candidate
                     for (uint32_t p = tid; p < R; p += MMR_BLOCK) {
-                        const uint32_t c = s_order[p];
-                        const unsigned char *crow = rows + (uint64_t)s_id[s_src[c]] * a.row_stride;
+                        const uint32_t c = l.order[p];
+                        const unsigned char *crow = rows + (uint64_t)l.id[l.src[c]] * a.row_stride;
                         const float sim = small_f32_leaf<METRIC>(a.dim, [&](uint32_t i) { return E::load1(crow, i); }, [&](uint32_t i) { return s_row[i]; });
-                        const float m = first || ordered_float(sim) >= ordered_float(s_max[c]) ? sim : s_max[c];
-                        s_max[c] = m;
-                        const float mmr = lambda * s_rel[c] - one_minus * m;
-                        const uint64_t key = ((uint64_t)ordered_float(mmr) << 32) | p;
+                        const uint64_t key = mmr_fold(l, c, p, sim, first, lambda, one_minus);
                         best = key > best ? key : best;
                     }
                 }
             }
             best = mmr_block_max(best, s_best);
-            if (tid == 0) {      // swap_remove: the last element of the order moves into the freed slot
-                const uint32_t p = (uint32_t)best;
-                const uint32_t c = s_order[p];
-                s_order[p] = s_order[R - 1];
-                s_sel = c;
-                out[n_sel] = cand[s_src[c]];      // candidates[idx].clone(): the input score
-            }
-            __syncthreads();
+            mmr_pick(l, best, R, cand, out, n_sel, &s_sel);
             --R;
             ++n_sel;
         }
@@ -239,7 +171,7 @@ __global__ __launch_bounds__(MMR_BLOCK) void mmr_select_kernel(const MmrArgs a) 
 template <int METRIC, class E>
 static int32_t launch_mmr_inst(hipStream_t st, const MmrArgs &a, uint32_t nq) {
     const size_t S = ((size_t)a.stride + 3) & ~(size_t)3;
-    const size_t lds = S * 20 + (((size_t)a.dim + 3) & ~(size_t)3) * 4;
+    const size_t lds = S * MMR_CAND_BYTES + (((size_t)a.dim + 3) & ~(size_t)3) * 4;
     QMX_REQUIRE(lds <= 160 * 1024 - 256, QMX_ERR_NOT_SUPPORTED, "MMR over %u candidates of %u elements needs %zu B of LDS (> 160 KiB)", a.stride, a.dim, lds);
     auto kfn = mmr_select_kernel<METRIC, E>;
     static thread_local DeviceOnce attr_once;

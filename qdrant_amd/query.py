@@ -9,7 +9,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _ffi as F
-from .scorer import RawScorer, ScoredPointOffset, VectorStorage, new_raw_scorer
+from .scorer import RawScorer, ScoredPointOffset, SparseVectorStorage, VectorStorage, new_raw_scorer
 
 
 def _pack(lists):
@@ -57,18 +57,37 @@ def dbsf(lists, top: int, weights: Optional[Sequence[float]] = None, device_id: 
     return _fuse(lists, F.FUSION_DBSF, top, 0, weights, device_id)
 
 
+def _mmr(select, scorer, candidates, lambda_, limit):
+    if len(candidates) != scorer.nq:
+        raise ValueError("one candidate list per request")
+    packed, counts, nq, stride = _pack([candidates])
+    out = np.zeros((nq, limit), dtype=ScoredPointOffset)
+    oc = np.zeros(nq, dtype=np.uint32)
+    F.check(select(scorer._h, F.ptr(packed), F.ptr(counts), stride, float(lambda_), int(limit), F.ptr(out), F.ptr(oc)))
+    return [out[i, :oc[i]].copy() for i in range(nq)]
+
+
 def mmr(storage: VectorStorage, vectors, candidates, lambda_: float, limit: int) -> List[np.ndarray]:
     """`mmr_from_points_with_vector` (shard/src/query/mmr/mod.rs:42-100): request qi re-ranks candidates[qi] (a ScoredPointOffset list over
-    `storage`, a dense f32 / f16 / u8 storage) for diversity against `vectors[qi]`; the picked candidates in selection order, input scores kept."""
+    `storage`, a dense f32 / f16 / u8 storage) for diversity against `vectors[qi]`; the picked candidates in selection order, input scores kept.
+    (Sparse storages: `sparse_mmr`.)"""
     scorer = vectors if isinstance(vectors, RawScorer) else new_raw_scorer(vectors, storage)
     try:
-        if len(candidates) != scorer.nq:
-            raise ValueError("one candidate list per request")
-        packed, counts, nq, stride = _pack([candidates])
-        out = np.zeros((nq, limit), dtype=ScoredPointOffset)
-        oc = np.zeros(nq, dtype=np.uint32)
-        F.check(F.lib().qmx_mmr_select(scorer._h, F.ptr(packed), F.ptr(counts), stride, float(lambda_), int(limit), F.ptr(out), F.ptr(oc)))
-        return [out[i, :oc[i]].copy() for i in range(nq)]
+        return _mmr(F.lib().qmx_mmr_select, scorer, candidates, lambda_, limit)
+    finally:
+        if scorer is not vectors:
+            scorer.close()
+
+
+def sparse_mmr(storage: SparseVectorStorage, vectors, candidates, lambda_: float, limit: int, idf=None) -> List[np.ndarray]:
+    """`mmr` over a SparseVectorStorage: `vectors` are the requests' sparse mmr vectors, (indices, values) pairs (or CSR arrays), or a RawScorer
+    made over `storage`; `idf` as new_raw_scorer takes it.  Relevance and similarity are `score_vectors` sums in ascending ORIGINAL index order
+    (0.0 without a shared dimension), over the stored f32 rows whatever the index weights are."""
+    if not isinstance(storage, SparseVectorStorage):
+        raise ValueError("sparse_mmr needs a SparseVectorStorage (dense storages: mmr)")
+    scorer = vectors if isinstance(vectors, RawScorer) else new_raw_scorer(vectors, storage, idf=idf)
+    try:
+        return _mmr(F.lib().qmx_sparse_mmr_select, scorer, candidates, lambda_, limit)
     finally:
         if scorer is not vectors:
             scorer.close()
@@ -89,7 +108,8 @@ class Dbsf:
 
 
 class Mmr:
-    """The MMR stage of hybrid_search: `scorer` = the Nearest batch of the requests' mmr vectors over the dense storage (new_raw_scorer)."""
+    """The MMR stage of hybrid_search: `scorer` = the Nearest batch of the requests' mmr vectors (new_raw_scorer) over the dense storage, or over
+    the SparseVectorStorage when `mmr.using` names the sparse vector."""
 
     def __init__(self, scorer: RawScorer, lambda_: float, limit: int):
         self.scorer, self.lambda_, self.limit = scorer, float(lambda_), int(limit)
@@ -142,7 +162,8 @@ def hybrid_search(sources, fusion, top: int, mmr: Optional[Mmr] = None, device_i
             if mmr is not None:
                 result = torch.empty((nq, mmr.limit), dtype=torch.int64, device=dev)
                 rcounts = torch.zeros(nq, dtype=torch.int32, device=dev)
-                F.check(lib.qmx_mmr_select_async(mmr.scorer._h, F.ptr(fused), F.ptr(fcounts), top, mmr.lambda_, mmr.limit, F.ptr(result), F.ptr(rcounts)))
+                select = lib.qmx_sparse_mmr_select_async if isinstance(mmr.scorer.storage, SparseVectorStorage) else lib.qmx_mmr_select_async
+                F.check(select(mmr.scorer._h, F.ptr(fused), F.ptr(fcounts), top, mmr.lambda_, mmr.limit, F.ptr(result), F.ptr(rcounts)))
             out = torch.empty(result.shape, dtype=result.dtype, pin_memory=True)
             oc = torch.empty(rcounts.shape, dtype=rcounts.dtype, pin_memory=True)
             out.copy_(result, non_blocking=True)
@@ -154,7 +175,7 @@ def hybrid_search(sources, fusion, top: int, mmr: Optional[Mmr] = None, device_i
             for s in made:
                 s.close()
     del keep
-    # (a fused id past the dense storage's rows empties that request's MMR list; the next synchronous call on mmr.scorer reports it)
+    # (a fused id past the MMR storage's rows empties that request's MMR list; the next synchronous call on mmr.scorer reports it)
     out = out.numpy().view(ScoredPointOffset).reshape(nq, -1)
     oc = oc.numpy()
     return [out[i, :oc[i]].copy() for i in range(nq)]

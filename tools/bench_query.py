@@ -12,6 +12,11 @@ points.  Per batch size Q:
      arg-max in numpy.  `model_bytes` = rows the selection has to read (per request and step: the remaining candidates' rows), `effective_gb_per_s`
      = that over the device time.
 
+ (c) `--sparse-mmr` (instead of (a) and (b), on the sparse segment alone): MMR over the sparse top-`--mmr-candidates` list, qmx_sparse_mmr_select
+     against the same host-driven selection over the sparse batch (the segment has no dimension map, so new_raw_scorer_internal +
+     score_points_ragged give the kernel's bits; the leg asserts the same picks).  `--sparse-mmr-mapped` adds the device time of the same
+     selection on the same rows under a random permutation map (the kernel's other instantiation).
+
 One JSON line on stdout; `--out` also writes it to a file."""
 import argparse
 import json
@@ -86,6 +91,85 @@ def host_mmr(storage, scorer, cand, lambda_, limit):
     return cand[rows[:, None], picks[:, :min(limit, c)]]
 
 
+def sparse_segment(args, dev, gen, cdf, perm, dim_map=None):
+    n = args.points
+    parts = [BS.sample_rows(gen, cdf, perm, min(1_000_000, n - r0), args.nnz, dev) for r0 in range(0, n, 1_000_000)]
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(torch.cat([p[0] for p in parts]), 0)
+    sparse = qa.SparseVectorStorage(offsets, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), dim_map=dim_map)
+    del parts
+    torch.cuda.empty_cache()
+    return sparse
+
+
+def sparse_mmr_leg(args, dev):
+    """(c): see the module text."""
+    lib = F.lib()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed)
+    cdf = BS.zipf_cdf(args.sparse_dims, dev)
+    perm = torch.randperm(args.sparse_dims, generator=gen, device=dev).to(torch.int64)
+    state = gen.get_state()
+    sparse = sparse_segment(args, dev, gen, cdf, perm)
+    mapped = None
+    if args.sparse_mmr_mapped:      # the same rows (the generator rewound) under a random permutation of the dimensions
+        gen.set_state(state)
+        keys = np.arange(args.sparse_dims, dtype=np.uint32)
+        mapped = sparse_segment(args, dev, gen, cdf, perm, dim_map=(keys, np.random.default_rng(args.seed).permutation(keys)))
+    qgen = torch.Generator(device=dev)
+    qgen.manual_seed(args.seed + 1)
+    c = args.mmr_candidates
+    results = []
+    for nq in [int(x) for x in args.batches.split(",")]:
+        queries = sparse_queries(qgen, cdf, perm, nq, args.qnnz, dev)
+        sq = qa.new_raw_scorer(queries, sparse)
+        mq = qa.new_raw_scorer(queries, mapped) if mapped is not None else None
+        cand = np.zeros((nq, c), dtype=qa.ScoredPointOffset)
+        ccnt = np.zeros(nq, dtype=np.uint32)
+        F.check(lib.qmx_search_topk(sq._h, c, None, 0, F.ptr(cand), F.ptr(ccnt), None, None))
+        assert ccnt.min() == c, "a query overlaps fewer than --mmr-candidates points"
+        rec = {"queries": nq, "mmr": []}
+        for limit in [int(x) for x in args.mmr_limits.split(",")]:
+            out = np.zeros((nq, limit), dtype=qa.ScoredPointOffset)
+            oc = np.zeros(nq, dtype=np.uint32)
+
+            def device(scorer=sq):
+                F.check(lib.qmx_sparse_mmr_select(scorer._h, F.ptr(cand), F.ptr(ccnt), c, args.mmr_lambda, limit, F.ptr(out), F.ptr(oc)))
+
+            dms = timed(device, args.warmup, args.steps)
+            kernel = F.last_kernel(sq._h)
+            picks = out["idx"].copy()
+            want = []
+
+            def host():
+                want[:] = [host_mmr(sparse, sq, cand, args.mmr_lambda, limit)]
+
+            hms = timed(host, 0, max(1, args.steps // 2))
+            assert np.array_equal(picks, want[0]["idx"]), "device and host-driven selections differ"
+            r = {"candidates": c, "limit": limit, "device_ms": round(dms, 3), "host_ms": round(hms, 3), "host_over_device": round(hms / dms, 2),
+                 "same_selection": True, "us_per_step": round(1e3 * dms / limit, 1), "kernel": kernel.split("(")[0]}
+            if mq is not None:
+                r["mapped_device_ms"] = round(timed(lambda: device(mq), args.warmup, args.steps), 3)
+                r["mapped_us_per_step"] = round(1e3 * r["mapped_device_ms"] / limit, 1)
+                r["mapped_kernel"] = F.last_kernel(mq._h).split("(")[0]
+            rec["mmr"].append(r)
+        sq.close()
+        if mq is not None:
+            mq.close()
+        results.append(rec)
+    return {"tool": "bench_query", "leg": "sparse_mmr", "points": args.points, "sparse_dims": args.sparse_dims, "nnz": args.nnz, "qnnz": args.qnnz,
+            "mmr_lambda": args.mmr_lambda, "device": torch.cuda.get_device_name(0), "batches": results}
+
+
+def emit(record, out):
+    line = json.dumps(record)
+    print(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -103,8 +187,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=20241016)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sparse-mmr", action="store_true", help="leg (c) alone: MMR over the sparse top list")
+    ap.add_argument("--sparse-mmr-mapped", action="store_true", help="with --sparse-mmr: also time the same rows under a permutation map (device only)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.sparse_mmr:
+        emit(sparse_mmr_leg(args, dev), args.out)
+        return
     lib = F.lib()
     n, dim = args.points, args.dim
     rows = torch.empty((n, dim), dtype=torch.float32, device=dev)
@@ -115,12 +204,7 @@ def main():
     gen.manual_seed(args.seed)
     cdf = BS.zipf_cdf(args.sparse_dims, dev)
     perm = torch.randperm(args.sparse_dims, generator=gen, device=dev).to(torch.int64)
-    parts = [BS.sample_rows(gen, cdf, perm, min(1_000_000, n - r0), args.nnz, dev) for r0 in range(0, n, 1_000_000)]
-    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    offsets[1:] = torch.cumsum(torch.cat([p[0] for p in parts]), 0)
-    sparse = qa.SparseVectorStorage(offsets, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]))
-    del parts
-    torch.cuda.empty_cache()
+    sparse = sparse_segment(args, dev, gen, cdf, perm)
     qgen = torch.Generator(device=dev)
     qgen.manual_seed(args.seed + 1)
     row_bytes = dim * 4
@@ -189,14 +273,9 @@ def main():
         dq.close()
         sq.close()
         results.append(rec)
-    line = json.dumps({"tool": "bench_query", "points": n, "dim": dim, "sparse_dims": args.sparse_dims, "nnz": args.nnz, "qnnz": args.qnnz,
-                       "prefetch": args.prefetch, "top": args.top, "mmr_lambda": args.mmr_lambda, "device": torch.cuda.get_device_name(0),
-                       "batches": results})
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit({"tool": "bench_query", "points": n, "dim": dim, "sparse_dims": args.sparse_dims, "nnz": args.nnz, "qnnz": args.qnnz,
+          "prefetch": args.prefetch, "top": args.top, "mmr_lambda": args.mmr_lambda, "device": torch.cuda.get_device_name(0),
+          "batches": results}, args.out)
 
 
 if __name__ == "__main__":
