@@ -839,6 +839,133 @@ QMX_API int32_t qmx_sparse_mmr_select(qmx_query *q, const qmx_scored_point *cand
 QMX_API int32_t qmx_sparse_mmr_select_async(qmx_query *q, const qmx_scored_point *candidates_dev, const uint32_t *counts_dev, uint32_t stride,
                                             float lambda, uint32_t limit, qmx_scored_point *out_dev, uint32_t *out_counts_dev);
 
+/* ---- hybrid queries: formula rescoring ("score boosting") ------------------------------------- */
+
+/* The Query API's `Query::Formula` stage = `SegmentReadView::do_rescore_with_formula` (lib/segment/src/segment/read_view/formula_rescore.rs:29-104)
+ * over `FormulaScorer::score` (lib/segment/src/index/query_optimization/rescore_formula/formula_scorer.rs:76-343).  Payload reaches the device the
+ * way filters do: as arrays over point offsets which the caller's payload index evaluated. */
+
+typedef double qmx_precise_score;     /* PreciseScore = f64 (parsed_formula.rs) */
+
+typedef enum qmx_payload_kind {
+    QMX_PAYLOAD_NUMBER = 0,     /* data: double[n_points] */
+    QMX_PAYLOAD_GEO = 1,        /* data: double lat[n_points], data2: double lon[n_points] */
+    QMX_PAYLOAD_DATETIME = 2,   /* data: int64_t micros[n_points] = DateTimePayloadType::timestamp() */
+    QMX_PAYLOAD_CONDITION = 3   /* data: u64-word bitmap, bit id = what condition_checkers[c].check(id) returned (a qmx_query_set_filter bitmap) */
+} qmx_payload_kind;
+
+typedef struct qmx_payload_column {
+    uint32_t kind;             /* qmx_payload_kind */
+    uint32_t reserved;
+    const void *data;
+    const void *data2;
+    const uint64_t *present;   /* value columns: bit id = the point has exactly one value; NULL = every point has */
+    const uint64_t *invalid;   /* value columns: bit id = the point has a value of the wrong type, or several ("Value is not a number", the array
+                                  case: formula_scorer.rs:284-295); NULL = none.  Wins over `present`.  A point in neither has no value. */
+} qmx_payload_column;
+
+typedef struct qmx_payload_columns qmx_payload_columns;
+
+/* Device copies of `n_cols` columns over point offsets 0..n_points (bitmaps: (n_points + 63) / 64 words).  Host or device memory. */
+QMX_API int32_t qmx_payload_columns_create(int32_t device_id, uint64_t n_points, const qmx_payload_column *cols, uint32_t n_cols,
+                                           qmx_payload_columns **out);
+QMX_API int32_t qmx_payload_columns_destroy(qmx_payload_columns *columns);
+
+typedef enum qmx_formula_op {      /* ParsedExpression (parsed_formula.rs:55-92) */
+    QMX_FORMULA_CONSTANT = 0,      /* value */
+    QMX_FORMULA_SCORE = 1,         /* Variable(Score(var)) */
+    QMX_FORMULA_PAYLOAD = 2,       /* Variable(Payload(column var)): a NUMBER column */
+    QMX_FORMULA_CONDITION = 3,     /* Variable(Condition(column var)): a CONDITION column; 1.0 / 0.0 */
+    QMX_FORMULA_GEO_DISTANCE = 4,  /* origin (lat value, lon value2), GEO column var: Haversine metres */
+    QMX_FORMULA_DATETIME = 5,      /* Datetime(Constant(micros)): seconds */
+    QMX_FORMULA_DATETIME_KEY = 6,  /* Datetime(PayloadVariable(column var)): a DATETIME column; seconds */
+    QMX_FORMULA_MULT = 7,          /* children; folds from 1.0, returns 0.0 at the first factor == 0.0 without evaluating the rest */
+    QMX_FORMULA_SUM = 8,           /* children; folds from 0.0 */
+    QMX_FORMULA_DIV = 9,           /* children {left, right}; flags & 1: by_zero_default = value.  0.0 on a zero numerator (divisor not evaluated) */
+    QMX_FORMULA_NEG = 10,
+    QMX_FORMULA_SQRT = 11,
+    QMX_FORMULA_POW = 12,          /* children {base, exponent} */
+    QMX_FORMULA_EXP = 13,
+    QMX_FORMULA_LOG10 = 14,
+    QMX_FORMULA_LN = 15,
+    QMX_FORMULA_ABS = 16,
+    QMX_FORMULA_DECAY = 17         /* var = qmx_decay_kind, children {x} or {x, target} (no target: 0.0), value = lambda as
+                                      `decay_params_to_lambda` computes it (parsed_formula.rs:186-224) */
+} qmx_formula_op;
+
+typedef enum qmx_decay_kind { QMX_DECAY_LIN = 0, QMX_DECAY_GAUSS = 1, QMX_DECAY_EXP = 2 } qmx_decay_kind;
+
+typedef struct qmx_formula_node {
+    uint32_t op;                /* qmx_formula_op */
+    uint32_t var;
+    uint32_t n_children;
+    uint32_t flags;
+    const uint32_t *children;   /* n_children node indices */
+    double value;
+    double value2;
+    int64_t micros;
+} qmx_formula_node;
+
+typedef struct qmx_formula_default {
+    uint32_t is_column;   /* 0: the default of Score(index); 1: of payload column `index` */
+    uint32_t index;
+    uint32_t kind;        /* qmx_payload_kind of the value: NUMBER (value), GEO (lat value, lon value2), DATETIME (micros); Score: NUMBER */
+    uint32_t reserved;
+    double value;
+    double value2;
+    int64_t micros;
+} qmx_formula_default;
+
+typedef struct qmx_formula qmx_formula;
+
+/* Validates the array-encoded tree (indices in range, no cycle, arity per op, a default's kind against the ops that read its column) and compiles it
+ * to a linear program with jumps for the reference's short circuits.  At most 16 values on the evaluation stack and 4096 instructions:
+ * beyond, QMX_ERR_NOT_SUPPORTED; a malformed tree: QMX_ERR_BAD_ARG with a message.  Host memory; no device is touched. */
+QMX_API int32_t qmx_formula_create(const qmx_formula_node *nodes, uint32_t n_nodes, uint32_t root, const qmx_formula_default *defaults,
+                                   uint32_t n_defaults, qmx_formula **out);
+QMX_API int32_t qmx_formula_destroy(qmx_formula *formula);
+
+typedef enum qmx_formula_status {
+    QMX_FORMULA_OK = 0,
+    QMX_FORMULA_NON_FINITE = 1,  /* OperationError::NonFiniteNumber: Div, Sqrt, Pow, Exp, Log10, Ln, or the cast of the result to f32 */
+    QMX_FORMULA_NO_VALUE = 2,    /* VariableTypeError "No value found in a payload nor defaults" */
+    QMX_FORMULA_BAD_VALUE = 3    /* VariableTypeError for a value of the wrong type / several values (`invalid`) */
+} qmx_formula_status;
+
+/* Formula rescoring of `n_sources` prefetch lists per request (lists, counts, stride: as qmx_fuse_topk takes them):
+ *   candidates : the distinct ids of the request's lists (`points_to_rescore`).
+ *   $score[s]  : the candidate's score in list s - of its LAST entry there when the id repeats (`collect::<AHashMap>`); without an entry the default
+ *                of Score(s), else 0.0.
+ *   evaluation : `eval_expression` in f64, one rounded operation per step in the reference's order; sqrt and division are IEEE, exp / ln / log10 /
+ *                pow / sin / cos / asin the device library's f64 functions (within a few ulp of the host libm's).  A column is read at the
+ *                candidate's offset; an offset past n_points has no value and fails every condition.  `columns` may be NULL when the formula
+ *                names none.  A column whose kind does not fit the op that reads it: QMX_ERR_BAD_ARG.
+ *   result     : cast to f32, which must be finite; kept when score >= *score_threshold (NULL: no threshold); out : [nq][limit] the best `limit`,
+ *                score descending in OrderedFloat order, the lower offset first among equal scores (the reference's Ord is the score alone);
+ *                out_counts : [nq].
+ *   errors     : the reference fails the whole request.  out_status[q] = the qmx_formula_status of the first error in evaluation order of the
+ *                LOWEST failing offset, out_error_point[q] = that offset, out_counts[q] = 0; the batch's other requests are unaffected and the call
+ *                returns QMX_OK.  (out_status[q] = QMX_FORMULA_OK, out_error_point[q] = 0 otherwise.)
+ * n_sources <= 64, n_sources * stride <= 8192, 1 <= limit <= 65536; beyond: QMX_ERR_NOT_SUPPORTED.  Host or device memory; runs on the columns'
+ * device (device 0 without columns); synchronises. */
+QMX_API int32_t qmx_formula_rescore(const qmx_formula *formula, const qmx_payload_columns *columns, const qmx_scored_point *lists,
+                                    const uint32_t *counts, uint32_t n_sources, uint32_t nq, uint32_t stride, uint32_t limit,
+                                    const float *score_threshold, qmx_scored_point *out, uint32_t *out_counts, uint32_t *out_status,
+                                    uint32_t *out_error_point);
+/* Same, but only enqueues on `hip_stream`; every list / count / output buffer in device memory (`score_threshold` is read before the call
+ * returns).  The handles must outlive the work. */
+QMX_API int32_t qmx_formula_rescore_async(const qmx_formula *formula, const qmx_payload_columns *columns, void *hip_stream,
+                                          const qmx_scored_point *lists_dev, const uint32_t *counts_dev, uint32_t n_sources, uint32_t nq,
+                                          uint32_t stride, uint32_t limit, const float *score_threshold, qmx_scored_point *out_dev,
+                                          uint32_t *out_counts_dev, uint32_t *out_status_dev, uint32_t *out_error_point_dev);
+/* `FormulaScorer::score` for `n` explicit points: scores : [n_score_vars][n] with n_score_vars = 1 + the greatest Score index the formula names
+ * (NULL: no point has a prefetch score); score_missing : the same shape, non-zero = the point is not in that prefetch (NULL: none missing).
+ * out_precise : [n] the f64 value before the cast (what was computed up to an error), out_scores : [n] its f32 cast (either may be NULL);
+ * out_status : [n] qmx_formula_status per point.  Host or device memory; synchronises. */
+QMX_API int32_t qmx_formula_eval(const qmx_formula *formula, const qmx_payload_columns *columns, const uint32_t *ids, uint64_t n,
+                                 const float *scores, const uint8_t *score_missing, qmx_precise_score *out_precise, float *out_scores,
+                                 uint32_t *out_status);
+
 /* ---- HNSW search on device -------------------------------------------------------------------- */
 
 /* One built graph = `GraphLayers` (lib/segment/src/index/hnsw_index/graph_layers.rs:58-72): the

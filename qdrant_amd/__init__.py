@@ -11,3 +11,6 @@ from .scorer import (BatchFilteredSearcher, Distance, EncodedVectorsPQ, EncodedV
                      SparseVectorStorage)
 from .hnsw import GraphLayers, decode_links_file  # noqa: F401
 from .query import Dbsf, Mmr, Rrf, dbsf, hybrid_search, mmr, rrf, sparse_mmr  # noqa: F401
+from .query import (CompiledFormula, Formula, FormulaError, PayloadColumns, abs_, condition, const, datetime, decay_params_to_lambda,  # noqa: F401
+                    div, exp, exp_decay, formula_eval, formula_rescore, gauss_decay, geo_distance, lin_decay, ln, log10, mult, neg, payload,
+                    pow_, score, sqrt, sum_)

@@ -141,6 +141,33 @@ class FusionParams(C.Structure):
 
 
 FUSION_RRF, FUSION_DBSF = range(2)
+
+
+class PayloadColumn(C.Structure):
+    """qmx_payload_column: one payload column over point offsets (values, optional `present` / `invalid` bitmaps) or a condition bitmap."""
+    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("data", C.c_void_p), ("data2", C.c_void_p), ("present", C.c_void_p),
+                ("invalid", C.c_void_p)]
+
+
+class FormulaNode(C.Structure):
+    """qmx_formula_node: one node of the array-encoded ParsedExpression tree."""
+    _fields_ = [("op", C.c_uint32), ("var", C.c_uint32), ("n_children", C.c_uint32), ("flags", C.c_uint32), ("children", C.c_void_p),
+                ("value", C.c_double), ("value2", C.c_double), ("micros", C.c_int64)]
+
+
+class FormulaDefault(C.Structure):
+    """qmx_formula_default: the default of Score(index) or of payload column `index`."""
+    _fields_ = [("is_column", C.c_uint32), ("index", C.c_uint32), ("kind", C.c_uint32), ("reserved", C.c_uint32), ("value", C.c_double),
+                ("value2", C.c_double), ("micros", C.c_int64)]
+
+
+PAYLOAD_NUMBER, PAYLOAD_GEO, PAYLOAD_DATETIME, PAYLOAD_CONDITION = range(4)
+(FORMULA_CONSTANT, FORMULA_SCORE, FORMULA_PAYLOAD, FORMULA_CONDITION, FORMULA_GEO_DISTANCE, FORMULA_DATETIME, FORMULA_DATETIME_KEY, FORMULA_MULT,
+ FORMULA_SUM, FORMULA_DIV, FORMULA_NEG, FORMULA_SQRT, FORMULA_POW, FORMULA_EXP, FORMULA_LOG10, FORMULA_LN, FORMULA_ABS, FORMULA_DECAY) = range(18)
+DECAY_LIN, DECAY_GAUSS, DECAY_EXP = range(3)
+FORMULA_OK, FORMULA_NON_FINITE, FORMULA_NO_VALUE, FORMULA_BAD_VALUE = range(4)
+FORMULA_STATUS_NAMES = ["OK", "NON_FINITE", "NO_VALUE", "BAD_VALUE"]
+FORMULA_MAX_DEPTH = 16
 FUSE_MAX_SOURCES, FUSE_MAX_ENTRIES, MMR_MAX_CANDIDATES = 64, 8192, 4096
 SPARSE_MMR_STAGE_CAP = 6144      # entries of a query or picked row that qmx_sparse_mmr_select keeps in LDS; longer ones are read where they lie
 
@@ -218,6 +245,13 @@ SIGNATURES = {
     "qmx_mmr_select_async": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
     "qmx_sparse_mmr_select": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
     "qmx_sparse_mmr_select_async": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_float, C.c_uint32, _P, _P]),
+    "qmx_payload_columns_create": (C.c_int32, [C.c_int32, C.c_uint64, C.POINTER(PayloadColumn), C.c_uint32, C.POINTER(_P)]),
+    "qmx_payload_columns_destroy": (C.c_int32, [_P]),
+    "qmx_formula_create": (C.c_int32, [C.POINTER(FormulaNode), C.c_uint32, C.c_uint32, C.POINTER(FormulaDefault), C.c_uint32, C.POINTER(_P)]),
+    "qmx_formula_destroy": (C.c_int32, [_P]),
+    "qmx_formula_rescore": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), _P, _P, _P, _P]),
+    "qmx_formula_rescore_async": (C.c_int32, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), _P, _P, _P, _P]),
+    "qmx_formula_eval": (C.c_int32, [_P, _P, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     "qmx_sharded_search_topk": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),
     "qmx_sharded_search_topk_async": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "qmx_sharded_hnsw_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),

@@ -12,31 +12,12 @@
 // best `top` written.  Every arithmetic step is one correctly rounded f32 operation in the reference's order (-ffp-contract=off; IEEE division and
 // square root).
 #include "kernels.hpp"
+#include "sort_lds.hpp"
 
 namespace qmx {
 
 constexpr int FUSE_BLOCK = 256;
 constexpr uint64_t FUSE_DEAD = ~0ull;      // a slot behind its list's count: sorts behind every live entry
-
-// ascending bitonic sort of n (a power of two >= 2) keys in LDS by the whole work-group
-__device__ __forceinline__ void bitonic_sort_lds(uint64_t *keys, uint32_t n) {
-    for (uint32_t k = 2; k <= n; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < n; i += FUSE_BLOCK) {
-                const uint32_t x = i ^ j;
-                if (x > i) {
-                    const uint64_t a = keys[i], b = keys[x];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) {
-                        keys[i] = b;
-                        keys[x] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
 
 // what list `s` of the query adds for its entry at position i (score `sc`)
 struct FuseSource {
@@ -124,7 +105,7 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_topk_kernel(const FuseArgs a,
         keys[j] = key;
     }
     __syncthreads();
-    bitonic_sort_lds(keys, n);
+    bitonic_sort_lds<FUSE_BLOCK>(keys, n);
 
     for (uint32_t x = tid; x < n; x += FUSE_BLOCK) {
         const uint64_t key = keys[x];
@@ -136,7 +117,7 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_topk_kernel(const FuseArgs a,
         fused[x] = f;
     }
     __syncthreads();
-    bitonic_sort_lds(fused, n);
+    bitonic_sort_lds<FUSE_BLOCK>(fused, n);
 
     const uint32_t found = n_distinct < a.top ? n_distinct : a.top;
     for (uint32_t r = tid; r < a.top; r += FUSE_BLOCK) {

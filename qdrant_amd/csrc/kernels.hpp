@@ -609,4 +609,62 @@ struct SparseMmrArgs {
 };
 int32_t launch_sparse_mmr_select(hipStream_t st, const SparseMmrArgs &a, uint32_t nq);
 
+// formula rescoring (formula.hip): the tree of a qmx_formula compiled by the host (api_formula.hip) to a linear program for a stack machine over
+// f64; jumps carry the reference's short circuits (Mult at a zero factor, Div at a zero numerator)
+constexpr uint32_t FORMULA_MAX_DEPTH = 16;     // values on the stack at once: the top in a register, the rest [depth - 1][lane] in LDS
+constexpr uint32_t FORMULA_MAX_INSTRS = 4096;
+enum FormulaInstrOp : uint32_t {
+    FI_CONST = 0,      // push c[0]
+    FI_SCORE,          // push $score[a], c[0] where the point has none
+    FI_PAYLOAD,        // push number column a; b = has default c[0]
+    FI_CONDITION,      // push 1.0 / 0.0 by the bit of condition column a
+    FI_GEO,            // push haversine(origin lat c[0] lon c[1], geo column a); b = has default lat c[2] lon c[3]
+    FI_DATETIME,       // push seconds of datetime column a; b = has default, c[0] = its seconds
+    FI_ADD,            // [x y] -> [x + y]
+    FI_MUL_SC,         // [p v] -> v == 0.0 ? [0.0], jump to a : [p * v]
+    FI_DIV_SC,         // [l] -> l == 0.0 ? [0.0], jump to a : [l]
+    FI_DIV,            // [l r] -> r == 0.0 and b ? [c[0]] : [l / r], which must be finite
+    FI_NEG, FI_SQRT, FI_POW, FI_EXP, FI_LOG10, FI_LN, FI_ABS,
+    FI_DECAY,          // [x target] -> decay of kind a (qmx_decay_kind) with lambda c[0]
+};
+struct FormulaInstr {
+    uint32_t op, a, b, pad_;
+    double c[4];
+};
+struct FormulaColumnDev {
+    uint32_t kind, pad_;              // qmx_payload_kind
+    const void *data, *data2;         // NUMBER f64 | GEO lat f64, lon f64 | DATETIME i64 micros | CONDITION u64 bitmap words
+    const uint64_t *present, *invalid;
+};
+struct FormulaProgram {
+    const FormulaInstr *instrs;       // device
+    uint32_t n_instrs, depth;
+    const FormulaColumnDev *cols;     // device
+    uint32_t n_cols;
+    uint64_t n_points;
+};
+struct FormulaRescoreArgs {
+    FormulaProgram prog;
+    const qmx_scored_point *lists;   // [n_sources][nq][stride]
+    const uint32_t *counts;          // [n_sources][nq]
+    uint32_t n_sources, nq, stride, limit;
+    uint32_t has_threshold;
+    float threshold;
+    qmx_scored_point *out;           // [nq][limit]
+    uint32_t *out_counts, *out_status, *out_error_point;   // [nq] each
+};
+int32_t launch_formula_rescore(hipStream_t st, const FormulaRescoreArgs &a);
+struct FormulaEvalArgs {
+    FormulaProgram prog;
+    const uint32_t *ids;             // [n]
+    uint64_t n;
+    const float *scores;             // [n_score_vars][n] or null
+    const uint8_t *score_missing;    // [n_score_vars][n] or null
+    uint32_t n_score_vars;
+    double *out_precise;             // [n] or null
+    float *out_scores;               // [n] or null
+    uint32_t *out_status;            // [n]
+};
+int32_t launch_formula_eval(hipStream_t st, const FormulaEvalArgs &a);
+
 }  // namespace qmx

@@ -17,6 +17,11 @@ points.  Per batch size Q:
      score_points_ragged give the kernel's bits; the leg asserts the same picks).  `--sparse-mmr-mapped` adds the device time of the same
      selection on the same rows under a random permutation map (the kernel's other instantiation).
 
+ (d) `--formula` (instead of (a) and (b)): the formula stage `$score[0] + 0.3 * $score[1] * gauss_decay(geo_distance) + condition` over the two
+     prefetch lists (a geo column and a condition bitmap over the same points) against the RRF fusion of the same lists, in the same process:
+     each stage alone on device lists (`stage_ms`: enqueue + one synchronisation, the lists already on the device) and inside the whole pipeline
+     (qdrant_amd.hybrid_search: both searches + the stage, `pipeline_ms`).  `formula_over_rrf` = the formula stage as a multiple of the fusion stage.
+
 One JSON line on stdout; `--out` also writes it to a file."""
 import argparse
 import json
@@ -161,6 +166,63 @@ def sparse_mmr_leg(args, dev):
             "mmr_lambda": args.mmr_lambda, "device": torch.cuda.get_device_name(0), "batches": results}
 
 
+def formula_leg(args, dev, dense, sparse, qgen, cdf, perm):
+    """(d): see the module text."""
+    import ctypes as C
+    lib = F.lib()
+    n = args.points
+    rng = np.random.default_rng(args.seed)
+    columns = qa.PayloadColumns(n, geo={"location": (rng.uniform(-60.0, 60.0, n), rng.uniform(-170.0, 170.0, n))}, conditions={"promoted": rng.random(n) < 0.2})
+    expr = qa.sum_(qa.score(0), qa.mult(qa.const(0.3), qa.score(1), qa.gauss_decay(qa.geo_distance((48.1, 11.5), "location"), scale=5e6)),
+                   qa.condition("promoted"))
+    stage = qa.Formula(expr, columns)
+    stream = torch.cuda.Stream(dev)
+    results = []
+    for nq in [int(x) for x in args.batches.split(",")]:
+        queries = torch.empty((nq, args.dim), dtype=torch.float32, device=dev)
+        F.check(lib.qmx_synth_fill_f32(0, args.seed + 2, 0, nq, args.dim, F.ptr(queries)))
+        dq = qa.new_raw_scorer(queries.cpu().numpy(), dense)
+        sq = qa.new_raw_scorer(sparse_queries(qgen, cdf, perm, nq, args.qnnz, dev), sparse)
+        sources = [(dq, args.prefetch), (sq, args.prefetch)]
+        rec = {"queries": nq}
+        # the two prefetch lists, once, on the device
+        lists = torch.zeros((2, nq, args.prefetch), dtype=torch.int64, device=dev)
+        counts = torch.zeros((2, nq), dtype=torch.int32, device=dev)
+        out = torch.zeros((nq, args.top), dtype=torch.int64, device=dev)
+        oc = torch.zeros((3, nq), dtype=torch.int32, device=dev)
+        for i, s in enumerate((dq, sq)):
+            F.check(lib.qmx_search_topk_async(s._h, args.prefetch, None, 0, F.ptr(lists[i]), F.ptr(counts[i])))
+            F.check(lib.qmx_query_synchronize(s._h))
+        params, keep = qa.query._fusion_params(F.FUSION_RRF, args.top, 2, None)
+        st = C.c_void_p(stream.cuda_stream)
+
+        def rrf_stage():
+            F.check(lib.qmx_fuse_topk_async(0, st, F.ptr(lists), F.ptr(counts), 2, nq, args.prefetch, C.byref(params), F.ptr(out), F.ptr(oc[0])))
+            stream.synchronize()
+
+        def formula_stage():
+            F.check(lib.qmx_formula_rescore_async(stage.compiled._h, columns._h, st, F.ptr(lists), F.ptr(counts), 2, nq, args.prefetch, args.top, None,
+                                                  F.ptr(out), F.ptr(oc[0]), F.ptr(oc[1]), F.ptr(oc[2])))
+            stream.synchronize()
+
+        reps = max(20, args.steps)
+        rrf_ms = timed(rrf_stage, 3, reps)
+        formula_ms = timed(formula_stage, 3, reps)
+        assert int(oc[1].max()) == 0, "a formula request failed"
+        rec["distinct_ids_per_request"] = round(float(np.mean([len(np.unique(lists[:, i].cpu().numpy().view(qa.ScoredPointOffset)["idx"])) for i in range(nq)])), 1)
+        rec["rrf"] = {"stage_ms": round(rrf_ms, 4), "pipeline_ms": round(timed(lambda: qa.hybrid_search(sources, qa.Rrf(), args.top), args.warmup, args.steps), 3)}
+        rec["formula"] = {"stage_ms": round(formula_ms, 4),
+                          "pipeline_ms": round(timed(lambda: qa.hybrid_search(sources, stage, args.top), args.warmup, args.steps), 3)}
+        rec["formula_over_rrf"] = round(formula_ms / rrf_ms, 2)
+        del keep
+        dq.close()
+        sq.close()
+        results.append(rec)
+    return {"tool": "bench_query", "leg": "formula", "points": n, "dim": args.dim, "sparse_dims": args.sparse_dims, "nnz": args.nnz, "qnnz": args.qnnz,
+            "prefetch": args.prefetch, "top": args.top, "formula": "$score[0] + 0.3 * $score[1] * gauss_decay(geo_distance, scale 5e6 m) + condition",
+            "device": torch.cuda.get_device_name(0), "batches": results}
+
+
 def emit(record, out):
     line = json.dumps(record)
     print(line)
@@ -188,6 +250,7 @@ def main():
     ap.add_argument("--seed", type=int, default=20241016)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sparse-mmr", action="store_true", help="leg (c) alone: MMR over the sparse top list")
+    ap.add_argument("--formula", action="store_true", help="leg (d) alone: the formula stage against the RRF fusion of the same lists")
     ap.add_argument("--sparse-mmr-mapped", action="store_true", help="with --sparse-mmr: also time the same rows under a permutation map (device only)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -207,6 +270,9 @@ def main():
     sparse = sparse_segment(args, dev, gen, cdf, perm)
     qgen = torch.Generator(device=dev)
     qgen.manual_seed(args.seed + 1)
+    if args.formula:
+        emit(formula_leg(args, dev, dense, sparse, qgen, cdf, perm), args.out)
+        return
     row_bytes = dim * 4
     results = []
     for nq in [int(x) for x in args.batches.split(",")]:
