@@ -300,7 +300,7 @@ QMX_API uint32_t qmx_abi_version(void);
  * both sides of every option - so they are tuning / triage switches, never correctness switches: "no_mfma_scan", "no_mfma16",
  * "no_prescan", "prescan_shift", "hnsw_log_cap", "no_split_scan", "split_min_queries", "no_split256", "no_pq_pair", "no_pq_prefilter",
  * "pq_prefilter_min_queries", "hnsw_pq_per_cu", "tq_rotate_block", "no_topk_small", "verify_max_per_query", "hnsw_pq_direct_walk",
- * "hnsw_pq_table_build", "hnsw_no_pq_prefilter", "hnsw_no_lds_visited", "pq_lut_no_lds", "hnsw_per_cu", "tq_wide_min_queries", "tq_wide_high_digit", "sq_wide_min_queries", "i8_resident", "debug"
+ * "hnsw_pq_table_build", "hnsw_no_pq_prefilter", "hnsw_no_lds_visited", "pq_lut_no_lds", "hnsw_per_cu", "tq_wide_min_queries", "tq_wide_high_digit", "sq_wide_min_queries", "i8_resident", "group_matrix_bytes", "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -
  * (qdrant_amd/csrc/common.hpp says what each selects; round 6 removed the experiments that had measured slower twice: their numbers stay under
  * profiles/).  Initial values come from the environment variables QMX_<NAME> read
@@ -965,6 +965,59 @@ QMX_API int32_t qmx_formula_rescore_async(const qmx_formula *formula, const qmx_
 QMX_API int32_t qmx_formula_eval(const qmx_formula *formula, const qmx_payload_columns *columns, const uint32_t *ids, uint64_t n,
                                  const float *scores, const uint8_t *score_missing, qmx_precise_score *out_precise, float *out_scores,
                                  uint32_t *out_status);
+
+/* ---- grouped search: search_groups / query_groups ------------------------------------------------ */
+
+/* "The best `limit` groups by a payload key, `group_size` hits each" = `group_by` (lib/collection/src/grouping/group_by.rs:263-356).  The reference's
+ * backend only returns a top-k, so its `GroupByDriver` (lib/shard/src/grouping/driver.rs) runs up to 5 + 5 whole searches under a growing filter
+ * (`must_not has_id(seen)`, `except` / `any` on the key) and feeds `GroupsAggregator` (lib/shard/src/grouping/aggregator.rs); when the request budget
+ * runs out it returns what it has.  Here the ranked stream stays on the device and one call returns what that loop converges to when its searches
+ * are exact and its budget suffices (DESIGN 3.12 has the argument) - also where the reference would run out of budget and return unfilled groups.
+ *
+ * The group key reaches the device as payload does for formulas: a column over point offsets which the caller's payload index evaluated, holding
+ * dense key indices 0 .. n_distinct - 1 (mapping strings and integers to indices is the caller's job). */
+
+#define QMX_GROUP_NONE 0xFFFFFFFFu   /* the point has no usable key: KeyNotFound / BadKeyType, which `add_points` ignores (aggregator.rs:57-105) */
+
+typedef struct qmx_group_keys qmx_group_keys;
+
+/* Device copy of the key column over point offsets 0..n_points.
+ *   offsets == NULL : keys[n_points], one key per point or QMX_GROUP_NONE.
+ *   offsets != NULL : CSR, the keys of point p are keys[offsets[p] .. offsets[p + 1]) - the reference's array values (aggregator.rs:63-85); offsets start
+ *                     at 0 and never decrease (QMX_ERR_BAD_ARG otherwise).  The keys of one point should be unique; a repeated key counts once and the
+ *                     order inside a point does not matter (they are taken in ascending key order).
+ * A key >= n_distinct other than QMX_GROUP_NONE: QMX_ERR_OUT_OF_BOUNDS (checked on the device, here).  Host or device memory. */
+QMX_API int32_t qmx_group_keys_create(int32_t device_id, uint64_t n_points, const uint32_t *keys, const uint64_t *offsets, uint32_t n_distinct,
+                                      qmx_group_keys **out);
+QMX_API int32_t qmx_group_keys_destroy(qmx_group_keys *keys);
+
+typedef struct qmx_group_counters {
+    uint64_t pages;             /* pages of 64 ranked hits the aggregator consumed, summed over queries (stage 0's page of every query included) */
+    uint32_t fallback_queries;  /* queries the first 64 hits did not finish: they took the score-matrix fallback */
+    uint32_t score_passes;      /* passes over the stored block that wrote the fallback's score rows */
+    uint32_t kernel_launches;
+    uint32_t reserved;
+} qmx_group_counters;
+
+/* Grouped search of a Nearest batch over the dense and quantized segments qmx_search_topk serves brute force (a sparse segment:
+ * QMX_ERR_NOT_SUPPORTED).  Per query, the candidates are those qmx_search_topk would search (`ids`, the deleted flags, the batch filter of
+ * qmx_query_set_filter) that carry at least one group key (`shape_candidates_query` adds `must_not is_empty(group_by)`, group_by.rs); scores are
+ * qmx_search_topk's bits.
+ *   hits of a group : the `group_size` best candidates carrying that key: score descending, the lower offset first among equal scores.
+ *   groups returned : the `limit` groups whose best hit is best, ordered by that best hit with the same comparison; two groups whose best hit is the same
+ *                     point (multi-valued keys only) by ascending key index.
+ *   score_threshold : optional; hits with score < *score_threshold do not exist (larger is better, as in the scores qmx_search_topk returns).
+ * Where the reference leaves the order unpinned - `ScoredPoint::cmp` is the score alone, `best_group_keys` runs `sort_unstable` over a hash map
+ * (aggregator.rs), hits are drained from a hash map - the rules above are this library's choice.
+ *   out_group_keys  : [nq][limit] key indices, QMX_GROUP_NONE behind the last group;  out_group_sizes : [nq][limit] hits per group;
+ *   out_hits        : [nq][limit][group_size], zeros behind a group's hits;           out_n_groups    : [nq].
+ * 1 <= limit <= 1024 and limit * group_size <= 65536 (QMX_ERR_NOT_SUPPORTED beyond); limit == 0 or group_size == 0 returns no groups (the driver's
+ * State::Done).  `keys` must cover the segment's points and live on its device (QMX_ERR_BAD_ARG).  An id past the segment's rows:
+ * QMX_ERR_OUT_OF_BOUNDS.  counters may be NULL.  Host or device memory; synchronises (between stages it reads a few bytes back: the unfinished
+ * queries).  Option "group_matrix_bytes" (qmx_set_option): the byte budget of the fallback's score matrix, default 1 GiB. */
+QMX_API int32_t qmx_group_search(qmx_query *q, const qmx_group_keys *keys, uint32_t limit, uint32_t group_size, const uint32_t *ids, uint64_t n_ids,
+                                 const float *score_threshold, uint32_t *out_group_keys, uint32_t *out_group_sizes, qmx_scored_point *out_hits,
+                                 uint32_t *out_n_groups, qmx_group_counters *counters);
 
 /* ---- HNSW search on device -------------------------------------------------------------------- */
 

@@ -166,6 +166,16 @@ PAYLOAD_NUMBER, PAYLOAD_GEO, PAYLOAD_DATETIME, PAYLOAD_CONDITION = range(4)
  FORMULA_SUM, FORMULA_DIV, FORMULA_NEG, FORMULA_SQRT, FORMULA_POW, FORMULA_EXP, FORMULA_LOG10, FORMULA_LN, FORMULA_ABS, FORMULA_DECAY) = range(18)
 DECAY_LIN, DECAY_GAUSS, DECAY_EXP = range(3)
 FORMULA_OK, FORMULA_NON_FINITE, FORMULA_NO_VALUE, FORMULA_BAD_VALUE = range(4)
+class GroupCounters(C.Structure):
+    """qmx_group_counters: what one qmx_group_search did."""
+    _fields_ = [("pages", C.c_uint64), ("fallback_queries", C.c_uint32), ("score_passes", C.c_uint32), ("kernel_launches", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+GROUP_NONE = 0xFFFFFFFF     # QMX_GROUP_NONE: the point has no usable group key
+GROUP_MAX_LIMIT = 1024
+GROUP_MAX_HITS = 65536
+
 FORMULA_STATUS_NAMES = ["OK", "NON_FINITE", "NO_VALUE", "BAD_VALUE"]
 FORMULA_MAX_DEPTH = 16
 FUSE_MAX_SOURCES, FUSE_MAX_ENTRIES, MMR_MAX_CANDIDATES = 64, 8192, 4096
@@ -252,6 +262,9 @@ SIGNATURES = {
     "qmx_formula_rescore": (C.c_int32, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), _P, _P, _P, _P]),
     "qmx_formula_rescore_async": (C.c_int32, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), _P, _P, _P, _P]),
     "qmx_formula_eval": (C.c_int32, [_P, _P, _P, C.c_uint64, _P, _P, _P, _P, _P]),
+    "qmx_group_keys_create": (C.c_int32, [C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(_P)]),
+    "qmx_group_keys_destroy": (C.c_int32, [_P]),
+    "qmx_group_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_float), _P, _P, _P, _P, C.POINTER(GroupCounters)]),
     "qmx_sharded_search_topk": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),
     "qmx_sharded_search_topk_async": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "qmx_sharded_hnsw_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),

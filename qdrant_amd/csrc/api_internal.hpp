@@ -167,6 +167,7 @@ struct qmx_query {
     uint32_t n_cq_coefs = 0;
     DevBuf cand, cand_cnt, cand_ids;   // qmx_search_quantized: oversampled candidates of the quantized stage
     DevBuf mmr_ids, mmr_rel;           // qmx_mmr_select: the candidates' ids and their relevance, per input position
+    DevBuf grp_state, grp_pages, grp_scores, grp_queries, grp_partial, grp_out;   // qmx_group_search: slots, pages, the fallback's score matrix / packed queries / partial lists, staged outputs
     DevBuf mmr_spill;                  // qmx_sparse_mmr_select over a mapped segment: per request a picked row too long for LDS, in original order
     // split prefilter (scan_split.hip): split queries, per-query norms / thresholds / bands, scales, candidate and verification buffers, flag
     DevBuf sp_bq, sp_f32, sp_cand, sp_cnt, sp_ver, sp_vscores, sp_sample, sp_wl, xcnt, tq_rot;

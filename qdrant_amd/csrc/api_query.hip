@@ -199,6 +199,7 @@ int32_t qmx_query_destroy(qmx_query *q) {
     q->mmr_ids.release();
     q->mmr_rel.release();
     q->mmr_spill.release();
+    q->grp_state.release(); q->grp_pages.release(); q->grp_scores.release(); q->grp_queries.release(); q->grp_partial.release(); q->grp_out.release();
     q->hnsw_vis.release();
     q->hnsw_log.release();
     q->hnsw_scored.release();

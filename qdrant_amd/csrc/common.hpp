@@ -54,6 +54,7 @@ enum Option {
     OPT_I8_RESIDENT,          // 1 (default): the int8-copy prefilter over rows of up to 1 024 coordinates keeps the queries' whole operand image resident in LDS
                               // (scan_i8copy_kernel_res: no stage barrier, 97 KiB of LDS at 768 coordinates); 0 = the staged kernel of rounds 3 - 6 (scan_i8copy_kernel:
                               // 144 KiB), which longer rows take anyway
+    OPT_GROUP_MATRIX_BYTES,   // qmx_group_search: byte budget of the fallback's score matrix, which tiles the unfinished queries (0 = 1 GiB)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT
 };

@@ -667,4 +667,38 @@ struct FormulaEvalArgs {
 };
 int32_t launch_formula_eval(hipStream_t st, const FormulaEvalArgs &a);
 
+// grouped search (groups.hip): the aggregator of qmx_group_search and the selection of its fallback pages; the logic both share with the host: group_logic.hpp
+struct GroupKeysDev {
+    const uint32_t *keys;            // one key per point (offsets == nullptr; padded to a multiple of 4 entries with QMX_GROUP_NONE), or the CSR values
+    const uint64_t *offsets;         // [n_points + 1] or nullptr
+    uint64_t n_points;
+};
+struct GroupStats {
+    unsigned long long pages;        // pages the aggregator consumed, summed over queries
+    uint32_t unfinished;             // queries the last aggregate launch left unfinished
+    uint32_t pad_;
+};
+struct GroupState {                  // per query of the batch
+    uint32_t *slot_key;              // [nq][limit]
+    uint32_t *slot_cnt;              // [nq][limit]
+    uint64_t *slot_hits;             // [nq][limit][group_size] keys (make_key), best first
+    uint32_t *n_slots, *n_full;      // [nq]
+    uint64_t *bound;                 // [nq] ~0: nothing consumed yet; the last key consumed; 0: the query is done
+    GroupStats *stats;
+    uint32_t limit, group_size;
+};
+constexpr uint32_t GROUP_PAGE = MAX_TOP_FAST;     // hits per page
+constexpr uint32_t GROUP_MAX_LIMIT = 1024;        // slots per query: what the aggregator and the selection keep in LDS
+constexpr uint32_t GROUP_MAX_HITS = 65536;        // limit * group_size
+// *bad |= 1 for a key >= n_distinct other than QMX_GROUP_NONE, |= 2 for offsets that decrease
+int32_t launch_group_keys_check(hipStream_t st, const uint32_t *keys, uint64_t n_keys, uint32_t n_distinct, const uint64_t *offsets, uint64_t n_points, uint32_t *bad);
+// pages : [nq][GROUP_PAGE] ranked hits, counts : [nq]; block b serves query list[b] (b without a list)
+int32_t launch_group_aggregate(hipStream_t st, const GroupKeysDev &gk, const GroupState &gs, const qmx_scored_point *pages, const uint32_t *counts,
+                               const uint32_t *list, uint32_t n_queries, const float *threshold);
+// partial : [blocks][n_queries][GROUP_PAGE] keys of the packed queries list[0 .. n_queries), whose score rows are scores[u * stride + i] for candidate i
+int32_t launch_group_select(hipStream_t st, const GroupKeysDev &gk, const GroupState &gs, const float *scores, uint64_t stride, uint64_t n_cand,
+                            const uint32_t *ids, const DeletedView &del, const uint32_t *list, uint32_t n_queries, uint32_t blocks, uint64_t *partial);
+int32_t launch_group_final(hipStream_t st, const GroupState &gs, uint32_t nq, uint32_t *out_keys, uint32_t *out_sizes, qmx_scored_point *out_hits,
+                           uint32_t *out_n_groups);
+
 }  // namespace qmx
