@@ -7,12 +7,18 @@ struct qmx_payload_columns {
     int device = 0;
     uint64_t n_points = 0;
     std::vector<uint32_t> kinds;
-    std::vector<void *> allocs;
+    std::vector<DevBuf> allocs;            // every column array and the descriptor table d_cols points into: freed with the handle
     FormulaColumnDev *d_cols = nullptr;
-    void release() {
-        for (void *p : allocs) (void)hipFree(p);
-        allocs.clear();
-        d_cols = nullptr;
+    // a column array (host or device memory) copied into an allocation of this handle; a null array stays null
+    int32_t upload(const void *src, size_t bytes, const void **dst) {
+        *dst = nullptr;
+        if (!src) return QMX_OK;
+        DevBuf b;
+        QMX_TRY(b.reserve(bytes));
+        if (bytes) QMX_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyDefault));
+        *dst = b.p;
+        allocs.push_back(std::move(b));
+        return QMX_OK;
     }
 };
 
@@ -24,6 +30,16 @@ struct qmx_formula {
     std::vector<Use> uses;                              // the columns the program reads and the kind each read expects
     mutable std::mutex mu;
     mutable FormulaInstr *d_prog[FORMULA_MAX_DEVICES] = {};   // the program on every device that ran it
+    qmx_formula() = default;
+    qmx_formula(const qmx_formula &) = delete;
+    qmx_formula &operator=(const qmx_formula &) = delete;
+    ~qmx_formula() {
+        int before = 0;
+        const bool have = hipGetDevice(&before) == hipSuccess;
+        for (int d = 0; d < FORMULA_MAX_DEVICES; ++d)
+            if (d_prog[d] && hipSetDevice(d) == hipSuccess) dev_free(d_prog[d]);
+        if (have) (void)hipSetDevice(before);
+    }
 };
 
 namespace {
@@ -197,17 +213,7 @@ struct FormulaCompiler {
 int32_t formula_on_device(const qmx_formula *f, int dev, const FormulaInstr **out) {
     QMX_REQUIRE(dev >= 0 && dev < FORMULA_MAX_DEVICES, QMX_ERR_NOT_SUPPORTED, "device %d", dev);
     std::lock_guard<std::mutex> lock(f->mu);
-    if (!f->d_prog[dev]) {
-        void *p = nullptr;
-        const size_t bytes = f->prog.size() * sizeof(FormulaInstr);
-        QMX_HIP(hipMalloc(&p, bytes));
-        const hipError_t e = hipMemcpy(p, f->prog.data(), bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return hip_status(e, "copy the formula's program", __FILE__, __LINE__);
-        }
-        f->d_prog[dev] = (FormulaInstr *)p;
-    }
+    if (!f->d_prog[dev]) QMX_TRY(dev_upload(&f->d_prog[dev], f->prog.data(), f->prog.size()));
     *out = f->d_prog[dev];
     return QMX_OK;
 }
@@ -252,34 +258,29 @@ int32_t rescore_args(const qmx_formula *f, const qmx_scored_point *lists, const 
     return QMX_OK;
 }
 
-// host memory staged through `buf` on the way in / out; device memory used where it lies
-struct Staged {
-    DevBuf buf;
-    void *host = nullptr;
-    size_t bytes = 0;
-    int32_t in(const void *p, size_t n, const void **dev) {
-        *dev = p;
-        if (!p || !n || is_device_ptr(p)) return QMX_OK;
-        QMX_TRY(buf.reserve(n));
-        QMX_HIP(hipMemcpy(buf.p, p, n, hipMemcpyHostToDevice));
-        *dev = buf.p;
-        return QMX_OK;
+int32_t columns_upload(qmx_payload_columns *h, const qmx_payload_column *cols, uint32_t n_cols) {
+    const uint64_t n_points = h->n_points;
+    const size_t words = (size_t)((n_points + 63) / 64) * 8;
+    std::vector<FormulaColumnDev> dev(n_cols);
+    for (uint32_t i = 0; i < n_cols; ++i) {
+        const qmx_payload_column &c = cols[i];
+        h->kinds.push_back(c.kind);
+        dev[i].kind = c.kind;
+        dev[i].pad_ = 0;
+        dev[i].data = dev[i].data2 = nullptr;
+        dev[i].present = dev[i].invalid = nullptr;
+        if (c.kind == QMX_PAYLOAD_CONDITION) {
+            QMX_TRY(h->upload(c.data, words, &dev[i].data));
+            continue;
+        }
+        QMX_TRY(h->upload(c.data, (size_t)n_points * 8, &dev[i].data));
+        if (c.kind == QMX_PAYLOAD_GEO) QMX_TRY(h->upload(c.data2, (size_t)n_points * 8, &dev[i].data2));
+        QMX_TRY(h->upload(c.present, words, (const void **)&dev[i].present));
+        QMX_TRY(h->upload(c.invalid, words, (const void **)&dev[i].invalid));
     }
-    int32_t out(void *p, size_t n, void **dev) {
-        *dev = p;
-        if (!p || !n || is_device_ptr(p)) return QMX_OK;
-        QMX_TRY(buf.reserve(n));
-        host = p;
-        bytes = n;
-        *dev = buf.p;
-        return QMX_OK;
-    }
-    int32_t back() {
-        if (host) QMX_HIP(hipMemcpy(host, buf.p, bytes, hipMemcpyDeviceToHost));
-        return QMX_OK;
-    }
-    ~Staged() { buf.release(); }
-};
+    if (n_cols) QMX_TRY(h->upload(dev.data(), dev.size() * sizeof(FormulaColumnDev), (const void **)&h->d_cols));
+    return QMX_OK;
+}
 
 }  // namespace
 
@@ -298,45 +299,11 @@ int32_t qmx_payload_columns_create(int32_t device_id, uint64_t n_points, const q
     QMX_REQUIRE(h, QMX_ERR_OUT_OF_MEMORY, "host allocation failed");
     h->device = device_id;
     h->n_points = n_points;
-    int32_t rc = QMX_OK;
-    auto upload = [&](const void *src, size_t bytes, const void **dst) {
-        *dst = nullptr;
-        if (!src || rc != QMX_OK) return;
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
-        if (e == hipSuccess) {
-            h->allocs.push_back(p);
-            if (bytes) e = hipMemcpy(p, src, bytes, hipMemcpyDefault);
-        }
-        if (e != hipSuccess) rc = hip_status(e, "copy a payload column", __FILE__, __LINE__);
-        *dst = p;
-    };
-    const size_t words = (size_t)((n_points + 63) / 64) * 8;
-    std::vector<FormulaColumnDev> dev(n_cols);
-    for (uint32_t i = 0; i < n_cols && rc == QMX_OK; ++i) {
-        const qmx_payload_column &c = cols[i];
-        h->kinds.push_back(c.kind);
-        dev[i].kind = c.kind;
-        dev[i].pad_ = 0;
-        dev[i].data2 = nullptr;
-        dev[i].present = dev[i].invalid = nullptr;
-        if (c.kind == QMX_PAYLOAD_CONDITION) {
-            upload(c.data, words, &dev[i].data);
-            continue;
-        }
-        upload(c.data, (size_t)n_points * 8, &dev[i].data);
-        if (c.kind == QMX_PAYLOAD_GEO) upload(c.data2, (size_t)n_points * 8, &dev[i].data2);
-        upload(c.present, words, (const void **)&dev[i].present);
-        upload(c.invalid, words, (const void **)&dev[i].invalid);
-    }
-    const void *d_cols = nullptr;
-    if (n_cols) upload(dev.data(), dev.size() * sizeof(FormulaColumnDev), &d_cols);
+    const int32_t rc = columns_upload(h, cols, n_cols);
     if (rc != QMX_OK) {
-        h->release();
         delete h;
         return rc;
     }
-    h->d_cols = (FormulaColumnDev *)d_cols;
     *out = h;
     return QMX_OK;
 }
@@ -344,7 +311,6 @@ int32_t qmx_payload_columns_create(int32_t device_id, uint64_t n_points, const q
 int32_t qmx_payload_columns_destroy(qmx_payload_columns *columns) {
     if (!columns) return QMX_OK;
     (void)hipSetDevice(columns->device);
-    columns->release();
     delete columns;
     return QMX_OK;
 }
@@ -371,11 +337,6 @@ int32_t qmx_formula_create(const qmx_formula_node *nodes, uint32_t n_nodes, uint
 
 int32_t qmx_formula_destroy(qmx_formula *formula) {
     if (!formula) return QMX_OK;
-    int before = 0;
-    const bool have = hipGetDevice(&before) == hipSuccess;
-    for (int d = 0; d < FORMULA_MAX_DEVICES; ++d)
-        if (formula->d_prog[d] && hipSetDevice(d) == hipSuccess) (void)hipFree(formula->d_prog[d]);
-    if (have) (void)hipSetDevice(before);
     delete formula;
     return QMX_OK;
 }
@@ -389,19 +350,16 @@ int32_t qmx_formula_rescore(const qmx_formula *formula, const qmx_payload_column
     QMX_TRY(check_device(dev, nullptr));
     QMX_TRY(formula_program(formula, columns, dev, a.prog));
     if (nq == 0) return QMX_OK;
-    Staged sl, sc, so, soc, sos, soe;
-    QMX_TRY(sl.in(lists, (size_t)n_sources * nq * stride * sizeof(qmx_scored_point), (const void **)&a.lists));
-    QMX_TRY(sc.in(counts, (size_t)n_sources * nq * 4, (const void **)&a.counts));
-    QMX_TRY(so.out(out, (size_t)nq * limit * sizeof(qmx_scored_point), (void **)&a.out));
-    QMX_TRY(soc.out(out_counts, (size_t)nq * 4, (void **)&a.out_counts));
-    QMX_TRY(sos.out(out_status, (size_t)nq * 4, (void **)&a.out_status));
-    QMX_TRY(soe.out(out_error_point, (size_t)nq * 4, (void **)&a.out_error_point));
+    Staging st;
+    QMX_TRY(st.in(lists, (size_t)n_sources * nq * stride * sizeof(qmx_scored_point), &a.lists));
+    QMX_TRY(st.in(counts, (size_t)n_sources * nq * 4, &a.counts));
+    QMX_TRY(st.out(out, (size_t)nq * limit * sizeof(qmx_scored_point), &a.out));
+    QMX_TRY(st.out(out_counts, (size_t)nq * 4, &a.out_counts));
+    QMX_TRY(st.out(out_status, (size_t)nq * 4, &a.out_status));
+    QMX_TRY(st.out(out_error_point, (size_t)nq * 4, &a.out_error_point));
     QMX_TRY(launch_formula_rescore(nullptr, a));
     QMX_HIP(hipDeviceSynchronize());
-    QMX_TRY(so.back());
-    QMX_TRY(soc.back());
-    QMX_TRY(sos.back());
-    return soe.back();
+    return st.back();
 }
 
 int32_t qmx_formula_rescore_async(const qmx_formula *formula, const qmx_payload_columns *columns, void *hip_stream, const qmx_scored_point *lists_dev,
@@ -429,17 +387,15 @@ int32_t qmx_formula_eval(const qmx_formula *formula, const qmx_payload_columns *
     if (n == 0) return QMX_OK;
     a.n = n;
     a.n_score_vars = formula->n_score_vars;
-    Staged si, ss, sm, sp, sf, st;
-    QMX_TRY(si.in(ids, (size_t)n * 4, (const void **)&a.ids));
-    QMX_TRY(ss.in(scores, (size_t)a.n_score_vars * n * 4, (const void **)&a.scores));
-    QMX_TRY(sm.in(score_missing, (size_t)a.n_score_vars * n, (const void **)&a.score_missing));
-    QMX_TRY(sp.out(out_precise, (size_t)n * 8, (void **)&a.out_precise));
-    QMX_TRY(sf.out(out_scores, (size_t)n * 4, (void **)&a.out_scores));
-    QMX_TRY(st.out(out_status, (size_t)n * 4, (void **)&a.out_status));
+    Staging st;
+    QMX_TRY(st.in(ids, (size_t)n * 4, &a.ids));
+    QMX_TRY(st.in(scores, (size_t)a.n_score_vars * n * 4, &a.scores));
+    QMX_TRY(st.in(score_missing, (size_t)a.n_score_vars * n, &a.score_missing));
+    QMX_TRY(st.out(out_precise, (size_t)n * 8, &a.out_precise));
+    QMX_TRY(st.out(out_scores, (size_t)n * 4, &a.out_scores));
+    QMX_TRY(st.out(out_status, (size_t)n * 4, &a.out_status));
     QMX_TRY(launch_formula_eval(nullptr, a));
     QMX_HIP(hipDeviceSynchronize());
-    QMX_TRY(sp.back());
-    QMX_TRY(sf.back());
     return st.back();
 }
 

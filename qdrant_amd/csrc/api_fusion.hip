@@ -81,31 +81,15 @@ int32_t qmx_fuse_topk(int32_t device_id, const qmx_scored_point *lists, const ui
     const size_t lbytes = (size_t)n_sources * nq * stride * sizeof(qmx_scored_point);
     const size_t cbytes = (size_t)n_sources * nq * sizeof(uint32_t);
     const size_t obytes = (size_t)nq * a.top * sizeof(qmx_scored_point);
-    DevBuf bl, bc, bo, boc;
-    int32_t rc = QMX_OK;
-    auto hip = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == QMX_OK) rc = hip_status(e, what, __FILE__, __LINE__);
-        return rc == QMX_OK;
-    };
-    do {
-        if (lbytes && !is_device_ptr(lists)) {
-            if ((rc = bl.reserve(lbytes)) != QMX_OK || !hip(hipMemcpy(bl.p, lists, lbytes, hipMemcpyHostToDevice), "copy lists")) break;
-            a.lists = (const qmx_scored_point *)bl.p;
-        }
-        if (cbytes && !is_device_ptr(counts)) {
-            if ((rc = bc.reserve(cbytes)) != QMX_OK || !hip(hipMemcpy(bc.p, counts, cbytes, hipMemcpyHostToDevice), "copy counts")) break;
-            a.counts = (const uint32_t *)bc.p;
-        }
-        const bool od = is_device_ptr(out), ocd = is_device_ptr(out_counts);
-        if (!od) { if ((rc = bo.reserve(obytes)) != QMX_OK) break; a.out = (qmx_scored_point *)bo.p; }
-        if (!ocd) { if ((rc = boc.reserve((size_t)nq * 4)) != QMX_OK) break; a.out_counts = (uint32_t *)boc.p; }
-        if ((rc = launch_fuse_topk(nullptr, a)) != QMX_OK) break;
-        if (!od && !hip(hipMemcpy(out, a.out, obytes, hipMemcpyDeviceToHost), "copy result")) break;
-        if (!ocd && !hip(hipMemcpy(out_counts, a.out_counts, (size_t)nq * 4, hipMemcpyDeviceToHost), "copy counts")) break;
-        hip(hipDeviceSynchronize(), "synchronize");
-    } while (0);
-    bl.release(); bc.release(); bo.release(); boc.release();
-    return rc;
+    Staging st;
+    QMX_TRY(st.in(lists, lbytes, &a.lists));
+    QMX_TRY(st.in(counts, cbytes, &a.counts));
+    QMX_TRY(st.out(out, obytes, &a.out));
+    QMX_TRY(st.out(out_counts, (size_t)nq * 4, &a.out_counts));
+    QMX_TRY(launch_fuse_topk(nullptr, a));
+    QMX_TRY(st.back());
+    QMX_HIP(hipDeviceSynchronize());
+    return QMX_OK;
 }
 
 int32_t qmx_fuse_topk_async(int32_t device_id, void *hip_stream, const qmx_scored_point *lists_dev, const uint32_t *counts_dev, uint32_t n_sources,

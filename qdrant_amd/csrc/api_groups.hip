@@ -9,11 +9,12 @@ struct qmx_group_keys {
     uint32_t n_distinct = 0;
     uint32_t *d_keys = nullptr;        // padded to a multiple of 4 entries with QMX_GROUP_NONE
     uint64_t *d_offsets = nullptr;     // CSR only
-    void release() {
-        if (d_keys) (void)hipFree(d_keys);
-        if (d_offsets) (void)hipFree(d_offsets);
-        d_keys = nullptr;
-        d_offsets = nullptr;
+    qmx_group_keys() = default;
+    qmx_group_keys(const qmx_group_keys &) = delete;
+    qmx_group_keys &operator=(const qmx_group_keys &) = delete;
+    ~qmx_group_keys() {
+        dev_free(d_keys);
+        dev_free(d_offsets);
     }
 };
 
@@ -25,8 +26,7 @@ int32_t keys_create(qmx_group_keys *h, const uint32_t *keys, const uint64_t *off
     const uint64_t n = h->n_points;
     h->n_keys = n;
     if (offsets) {
-        QMX_HIP(hipMalloc((void **)&h->d_offsets, (size_t)(n + 1) * 8));
-        QMX_HIP(hipMemcpy(h->d_offsets, offsets, (size_t)(n + 1) * 8, hipMemcpyDefault));
+        QMX_TRY(dev_upload(&h->d_offsets, offsets, (size_t)(n + 1)));
         uint64_t ends[2] = {0, 0};      // first and last offset
         QMX_HIP(hipMemcpy(&ends[0], h->d_offsets, 8, hipMemcpyDeviceToHost));
         QMX_HIP(hipMemcpy(&ends[1], h->d_offsets + n, 8, hipMemcpyDeviceToHost));
@@ -40,23 +40,19 @@ int32_t keys_create(qmx_group_keys *h, const uint32_t *keys, const uint64_t *off
     if (h->n_keys) QMX_REQUIRE(keys, QMX_ERR_BAD_ARG, "NULL keys");
     // offsets that decrease are found below, before anything reads keys through them; the copy trusts only the LAST offset, as the caller's array must hold that many
     if (h->n_keys) QMX_HIP(hipMemcpy(h->d_keys, keys, (size_t)h->n_keys * 4, hipMemcpyDefault));
-    uint32_t *d_bad = nullptr, bad = 0;
-    QMX_HIP(hipMalloc((void **)&d_bad, 4));
-    auto check = [&]() -> int32_t {
-        QMX_HIP(hipMemset(d_bad, 0, 4));
-        QMX_TRY(launch_group_keys_check(nullptr, h->d_keys, h->n_keys, n_distinct, h->d_offsets, n, d_bad));
-        QMX_HIP(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
-        return QMX_OK;
-    };
-    const int32_t rc = check();
-    (void)hipFree(d_bad);
-    QMX_TRY(rc);
+    DevBuf flag;
+    uint32_t bad = 0;
+    QMX_TRY(flag.reserve(4));
+    QMX_HIP(hipMemset(flag.p, 0, 4));
+    QMX_TRY(launch_group_keys_check(nullptr, h->d_keys, h->n_keys, n_distinct, h->d_offsets, n, (uint32_t *)flag.p));
+    QMX_HIP(hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost));
     QMX_REQUIRE(!(bad & 2u), QMX_ERR_BAD_ARG, "group key offsets must not decrease");
     QMX_REQUIRE(!(bad & 1u), QMX_ERR_OUT_OF_BOUNDS, "a group key is >= n_distinct (%u) and not QMX_GROUP_NONE", n_distinct);
     return QMX_OK;
 }
 
-// a possibly-host output: written on the device into `buf` at `*off`, copied back after the last kernel
+// a possibly-host output: written on the device into `buf` at `*off`, copied back after the last kernel.  Not a Staging (dev_mem.hpp): the four
+// outputs share ONE long-lived buffer of the query (grp_out, no allocation in steady state) and go back by stream-ordered copies on its stream.
 struct GroupOut {
     void *host = nullptr, *dev = nullptr;
     size_t bytes = 0;
@@ -101,7 +97,6 @@ int32_t qmx_group_keys_create(int32_t device_id, uint64_t n_points, const uint32
     h->n_distinct = n_distinct;
     const int32_t rc = keys_create(h, keys, offsets, n_distinct);
     if (rc != QMX_OK) {
-        h->release();
         delete h;
         return rc;
     }
@@ -112,7 +107,6 @@ int32_t qmx_group_keys_create(int32_t device_id, uint64_t n_points, const uint32
 int32_t qmx_group_keys_destroy(qmx_group_keys *keys) {
     if (!keys) return QMX_OK;
     (void)hipSetDevice(keys->device);
-    keys->release();
     delete keys;
     return QMX_OK;
 }

@@ -3,6 +3,7 @@
 #include "api_internal.hpp"
 #include <algorithm>
 #include <atomic>
+#include <functional>
 
 extern "C" {
 
@@ -10,22 +11,37 @@ extern "C" {
 int32_t qmx_hnsw_destroy(qmx_hnsw *g) {
     if (!g) return QMX_OK;
     (void)hipSetDevice(g->device);
-    void *ptrs[] = {g->d_reindex, g->d_neighbors, g->d_ep_ids, g->d_ep_levels, g->d_xp_ids, g->d_xp_levels, g->d_level_offsets, g->d_offsets, g->d_l0, g->d_l0x};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     delete g;
     return QMX_OK;
 }
 
-static int32_t upload_bytes(void **dst, const void *src, uint64_t count, size_t elem) {
-    *dst = nullptr;
-    const size_t bytes = std::max<size_t>((size_t)count * elem, elem);
-    QMX_HIP(hipMalloc(dst, bytes));
-    if (count) QMX_HIP(hipMemcpy(*dst, src, (size_t)count * elem, hipMemcpyDefault));
+// the graph's arrays on the device, and where every level-0 list fits it the packed level-0 table
+static int32_t hnsw_upload(qmx_hnsw *g, const qmx_hnsw_desc *d) {
+    QMX_TRY(dev_upload(&g->d_reindex, d->reindex, d->n_points));
+    QMX_TRY(dev_upload(&g->d_level_offsets, d->level_offsets, d->n_points ? (size_t)d->n_levels + 1 : 0));
+    QMX_TRY(dev_upload(&g->d_offsets, d->offsets, d->n_points ? d->n_offsets : 0));
+    QMX_TRY(dev_upload(&g->d_neighbors, d->neighbors, d->n_neighbors));
+    QMX_TRY(dev_upload(&g->d_ep_ids, d->entry_point_ids, d->n_entry_points));
+    QMX_TRY(dev_upload(&g->d_ep_levels, d->entry_point_levels, d->n_entry_points));
+    QMX_TRY(dev_upload(&g->d_xp_ids, d->extra_entry_point_ids, d->n_extra_entry_points));
+    QMX_TRY(dev_upload(&g->d_xp_levels, d->extra_entry_point_levels, d->n_extra_entry_points));
+    // packed level-0 table (one round trip per hop instead of two); lists longer than m0 or 63 keep the CSR path
+    if (!d->n_points || d->m0 > 63) return QMX_OK;
+    const uint32_t stride = d->m0 + 1;
+    bool fits = true;
+    if (!is_device_ptr(d->offsets))
+        for (uint64_t i = 0; i < d->n_points && fits; ++i) fits = d->offsets[i + 1] - d->offsets[i] <= d->m0;
+    else fits = false;   // device-side arrays are not inspected
+    if (fits && hipMalloc((void **)&g->d_l0, (size_t)d->n_points * stride * 4) == hipSuccess) {
+        g->l0_stride = stride;
+        QMX_TRY(launch_hnsw_pack_level0(nullptr, g->d_offsets, g->d_neighbors, d->n_points, stride, g->d_l0));
+        QMX_HIP(hipDeviceSynchronize());
+    } else {
+        (void)hipGetLastError();
+        g->d_l0 = nullptr;
+    }
     return QMX_OK;
 }
-static int32_t upload_array(uint32_t **dst, const uint32_t *src, uint64_t count) { return upload_bytes((void **)dst, src, count, 4); }
-static int32_t upload_array(uint64_t **dst, const uint64_t *src, uint64_t count) { return upload_bytes((void **)dst, src, count, 8); }
 
 int32_t qmx_hnsw_create(const qmx_hnsw_desc *d, qmx_hnsw **out) {
     QMX_REQUIRE(d && out, QMX_ERR_BAD_ARG, "NULL argument");
@@ -93,33 +109,7 @@ int32_t qmx_hnsw_create(const qmx_hnsw_desc *d, qmx_hnsw **out) {
     g->m = d->m; g->m0 = d->m0; g->n_points = d->n_points; g->n_levels = d->n_levels;
     g->n_ep = d->n_entry_points; g->n_xp = d->n_extra_entry_points;
     g->n_offsets = d->n_offsets; g->n_neighbors = d->n_neighbors;
-    int32_t rc = QMX_OK;
-    do {
-        if ((rc = upload_array(&g->d_reindex, d->reindex, d->n_points)) != QMX_OK) break;
-        if ((rc = upload_array(&g->d_level_offsets, d->level_offsets, d->n_points ? (uint64_t)d->n_levels + 1 : 0)) != QMX_OK) break;
-        if ((rc = upload_array(&g->d_offsets, d->offsets, d->n_points ? d->n_offsets : 0)) != QMX_OK) break;
-        if ((rc = upload_array(&g->d_neighbors, d->neighbors, d->n_neighbors)) != QMX_OK) break;
-        if ((rc = upload_array(&g->d_ep_ids, d->entry_point_ids, d->n_entry_points)) != QMX_OK) break;
-        if ((rc = upload_array(&g->d_ep_levels, d->entry_point_levels, d->n_entry_points)) != QMX_OK) break;
-        if ((rc = upload_array(&g->d_xp_ids, d->extra_entry_point_ids, d->n_extra_entry_points)) != QMX_OK) break;
-        if ((rc = upload_array(&g->d_xp_levels, d->extra_entry_point_levels, d->n_extra_entry_points)) != QMX_OK) break;
-    } while (0);
-    // packed level-0 table (one round trip per hop instead of two); lists longer than m0 or 63 keep the CSR path
-    if (rc == QMX_OK && d->n_points && d->m0 <= 63) {
-        const uint32_t stride = d->m0 + 1;
-        bool fits = true;
-        if (!is_device_ptr(d->offsets))
-            for (uint64_t i = 0; i < d->n_points && fits; ++i) fits = d->offsets[i + 1] - d->offsets[i] <= d->m0;
-        else fits = false;   // device-side arrays are not inspected
-        if (fits && hipMalloc((void **)&g->d_l0, (size_t)d->n_points * stride * 4) == hipSuccess) {
-            g->l0_stride = stride;
-            rc = launch_hnsw_pack_level0(nullptr, g->d_offsets, g->d_neighbors, d->n_points, stride, g->d_l0);
-            if (rc == QMX_OK && hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-        } else {
-            (void)hipGetLastError();
-            g->d_l0 = nullptr;
-        }
-    }
+    const int32_t rc = hnsw_upload(g, d);
     if (rc != QMX_OK) {
         qmx_hnsw_destroy(g);
         return rc;
@@ -392,6 +382,226 @@ int32_t qmx_multi_hnsw_build(const qmx_segment *inner, const uint64_t *point_off
     return qmx_multi_hnsw_build_quantized(inner, nullptr, point_offsets, n_points, point_deleted, n_deleted_bits, bp, out);
 }
 
+// what the device phase of a build leaves on the host: the fixed-capacity link lists and the entry points
+struct BuiltLinks {
+    std::vector<uint32_t> links0, cnt0, linksU, cntU;
+    bool have_ep = false;
+    uint32_t ep_id = 0, ep_level = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> extra;   // (level, id)
+};
+
+// the insertions of a build on the device; its scratch lives as long as this call
+static int32_t hnsw_build_links(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, const MultiBuild *mb, uint32_t n,
+                                uint32_t max_batch, const std::vector<uint8_t> &level, const std::vector<uint32_t> &up_off, uint64_t n_up,
+                                const std::vector<uint64_t> &pdel, const std::function<bool(uint32_t)> &live, BuiltLinks &r) {
+    const uint32_t m = bp->m, m0 = bp->m0;
+    const bool from_original = seg->dtype == QMX_DTYPE_PQ || seg->dtype == QMX_DTYPE_TQ;
+    DevBuf b_level, b_upoff, b_links0, b_cnt0, b_linksU, b_cntU, b_lock, b_vis, b_log, b_sel, b_sels, b_selc, b_normf, b_normi, b_bq, b_bqsrc, b_rot, b_next, b_mvoff,
+        b_mvdel;
+    const size_t nn = std::max<uint32_t>(n, 1);
+    QMX_TRY(b_level.reserve(nn)); QMX_TRY(b_upoff.reserve(nn * 4));
+    QMX_TRY(b_links0.reserve(nn * m0 * 4)); QMX_TRY(b_cnt0.reserve(nn * 4));
+    QMX_TRY(b_linksU.reserve(std::max<uint64_t>(n_up, 1) * m * 4)); QMX_TRY(b_cntU.reserve(std::max<uint64_t>(n_up, 1) * 4));
+    QMX_TRY(b_lock.reserve(nn * 4));
+    QMX_HIP(hipMemcpy(b_level.p, level.data(), nn, hipMemcpyHostToDevice));
+    QMX_HIP(hipMemcpy(b_upoff.p, up_off.data(), nn * 4, hipMemcpyHostToDevice));
+    QMX_HIP(hipMemset(b_cnt0.p, 0, nn * 4));
+    QMX_HIP(hipMemset(b_cntU.p, 0, std::max<uint64_t>(n_up, 1) * 4));
+    QMX_HIP(hipMemset(b_lock.p, 0, nn * 4));
+    QMX_TRY(b_sel.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * m0 * 4));
+    QMX_TRY(b_sels.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * m0 * 4));
+    QMX_TRY(b_selc.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * 4));
+
+    ScanArgs a;
+    fill_args_segment(seg, a);
+    if (mb) {   // the graph's points are multi-vectors: offsets into the inner rows, deletion per POINT (the inner rows carry no flags of their own)
+        QMX_TRY(b_mvoff.reserve((size_t)(n + 1) * 8));
+        QMX_HIP(hipMemcpy(b_mvoff.p, mb->h_offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+        a.mv_offsets = (const uint64_t *)b_mvoff.p;
+        DeletedView dv;
+        memset(&dv, 0, sizeof(dv));
+        dv.n_rows = n;
+        if (!pdel.empty()) {
+            QMX_TRY(b_mvdel.reserve(pdel.size() * 8));
+            QMX_HIP(hipMemcpy(b_mvdel.p, pdel.data(), pdel.size() * 8, hipMemcpyHostToDevice));
+            dv.point_deleted = (const uint64_t *)b_mvdel.p;
+            dv.n_point_bits = mb->n_deleted_bits;
+        }
+        a.del = dv;
+    }
+    HnswBuildArgs h;
+    memset(&h, 0, sizeof(h));
+    h.g.links0 = (uint32_t *)b_links0.p; h.g.cnt0 = (uint32_t *)b_cnt0.p; h.g.linksU = (uint32_t *)b_linksU.p; h.g.cntU = (uint32_t *)b_cntU.p;
+    h.g.up_off = (const uint32_t *)b_upoff.p; h.g.m = m; h.g.m0 = m0;
+    h.level = (const uint8_t *)b_level.p;
+    h.n_points = n;
+    h.ef_construct = bp->ef_construct;
+    h.sel_ids = (uint32_t *)b_sel.p; h.sel_scores = (float *)b_sels.p; h.sel_cnt = (uint32_t *)b_selc.p;
+    h.lock = (uint32_t *)b_lock.p;
+    // bytes of a row as it lies in HBM: the SQ block holds the codes only (the vector_offset column is separate)
+    const uint64_t dev_row_bytes = seg->dtype == QMX_DTYPE_SQ_U8 ? (uint64_t)seg->sq.actual_dim : seg->row_bytes;
+    h.row_bytes = (uint32_t)dev_row_bytes;
+    h.lds_query_bytes = (uint32_t)((dev_row_bytes + 127) / 128 * 128 + 128);
+    uint64_t lut_stride = 0;
+    uint64_t max_entries = max_batch;      // query entries a batch may need: one per point - or, multi-vector points, one per inner vector
+    bool pq_direct_build = false;
+    if (seg->dtype == QMX_DTYPE_PQ) {   // query entries = LUTs of the batch's original vectors, read through L2 (as the PQ walk does)
+        lut_stride = ((uint64_t)seg->pq_m * seg->pq.n_centroids * sizeof(float) + 15) & ~15ull;
+        if (mb) {   // at least the longest point, at most 1 GiB of LUTs (the insertion loop shortens a batch that would need more)
+            uint64_t longest = 1;
+            for (uint32_t p = 0; p < n; ++p) longest = std::max<uint64_t>(longest, mb->h_offsets[p + 1] - mb->h_offsets[p]);
+            max_entries = std::max<uint64_t>(longest, std::min<uint64_t>(mb->h_offsets[n] ? mb->h_offsets[n] : 1, (1ull << 30) / lut_stride));
+            a.q_stride = (uint32_t)lut_stride;
+        }
+        // the table-free build (pq.hip HopPQDirectBuild + HopPQInternalDirect; the default where the codebook allows, option hnsw_pq_table_build for the
+        // other): the entries are the preprocessed original vectors themselves, staged in LDS per insertion - no LUTs are made, and none are reserved
+        // (max_entries x lut_stride is 1.6 GB at m = 96: several builds on one device would multiply it for nothing)
+        pq_direct_build = !mb && !option(OPT_HNSW_PQ_TABLE_BUILD) && pq_direct_walk_ok(seg->dim, seg->pq_m, seg->pq.chunk_size, seg->pq.n_centroids);
+        if (!pq_direct_build) QMX_TRY(b_bq.reserve((size_t)max_entries * lut_stride));
+        QMX_TRY(b_bqsrc.reserve((size_t)max_entries * seg->dim * sizeof(float)));
+        h.batch_queries = (const unsigned char *)b_bq.p;
+        h.batch_q_stride = lut_stride;
+        h.lds_query_bytes = 0;
+        if (pq_direct_build) {
+            h.batch_queries = (const unsigned char *)b_bqsrc.p;
+            h.batch_q_stride = (uint64_t)seg->dim * 4;
+            h.lds_query_bytes = seg->dim * 4;
+            // (round 5 tried an 8-bit LUT image per new point behind its vector, to prefilter the hops of the insertion searches: the same graph,
+            // 25.6 s against 24.9 s at 2 M x 1536 points - gone from the code since round 6, profiles/r5_walk_variants_pq_hop_prefilter.jsonl)
+        }
+    }
+    if (seg->dtype == QMX_DTYPE_TQ) {   // query entries = precompute_query of the batch's original vectors, staged in LDS per insertion
+        if (mb) {   // one entry per inner vector of the batch: at least the longest point, at most 256 MiB of rotated vectors
+            uint64_t longest = 1;
+            for (uint32_t p = 0; p < n; ++p) longest = std::max<uint64_t>(longest, mb->h_offsets[p + 1] - mb->h_offsets[p]);
+            max_entries = std::max<uint64_t>(longest, std::min<uint64_t>(mb->h_offsets[n] ? mb->h_offsets[n] : 1,
+                                                                         (1ull << 28) / ((uint64_t)seg->tq_padded_dim * sizeof(double))));
+        }
+        QMX_TRY(b_bq.reserve((size_t)max_entries * a.q_stride));
+        QMX_TRY(b_bqsrc.reserve((size_t)max_entries * seg->dim * sizeof(float)));
+        QMX_TRY(b_rot.reserve((size_t)max_entries * seg->tq_padded_dim * sizeof(double)));
+        h.batch_queries = (const unsigned char *)b_bq.p;
+        h.batch_q_stride = a.q_stride;
+        h.lds_query_bytes = a.q_stride;
+        if (tq_l1(seg)) {   // over Manhattan the entry is the original vector as given (quantization.rs:532-535), its hop scratch behind it in LDS (tq_l1_policy.hpp)
+            a.tq_l1 = seg->d_tq_l1;
+            a.q_stride = tq_l1_query_bytes(seg->dim);
+            QMX_TRY(b_bq.reserve((size_t)max_batch * a.q_stride));
+            h.batch_queries = (const unsigned char *)b_bq.p;
+            h.batch_q_stride = a.q_stride;
+            h.lds_query_bytes = tq_l1_lds_bytes(seg->dim, seg->tq_rot_dim);
+        }
+    }
+    if (mb) h.lds_query_bytes = 0;      // nothing staged: the inner rows of the new point are read where they lie
+    if (seg->dtype == QMX_DTYPE_U8 && seg->distance == QMX_DISTANCE_COSINE && seg->dim >= 32) {   // the per-pair cosine's query norm of a stored row
+        QMX_TRY(b_normf.reserve(nn * 4)); QMX_TRY(b_normi.reserve(nn * 4));
+        QMX_TRY(launch_u8_row_norms(nullptr, seg->d_rows, seg->row_stride, n, seg->dim, seg->flags, (float *)b_normf.p, (int32_t *)b_normi.p));
+        a.row_norms_f = (const float *)b_normf.p;
+        a.row_norms_i = (const int32_t *)b_normi.p;
+    }
+    QMX_REQUIRE(h.lds_query_bytes <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "rows of %llu bytes do not fit the LDS query slot",
+                (unsigned long long)dev_row_bytes);
+    h.log_cap = 16384;
+    h.vis_words = ((uint64_t)n + 31) / 32;
+    if (h.vis_words == 0) h.vis_words = 1;
+    int per_cu1 = 1, per_cu2 = 1;
+    QMX_TRY(launch_hnsw_build_any(seg, a, h, 1, 0, &per_cu1));
+    QMX_TRY(launch_hnsw_build_any(seg, a, h, 2, 0, &per_cu2));
+    uint64_t slots1 = std::min<uint64_t>({(uint64_t)seg->num_cus * per_cu1, (uint64_t)HNSW_SLOT_CAP, (uint64_t)max_batch});
+    slots1 = std::max<uint64_t>(1, std::min<uint64_t>(slots1, HNSW_VIS_BUDGET / (h.vis_words * 4)));
+    const uint64_t slots2 = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)seg->num_cus * per_cu2, max_batch));
+    QMX_TRY(b_next.reserve(8));
+    h.next = (uint32_t *)b_next.p;
+    QMX_TRY(b_vis.reserve((size_t)slots1 * h.vis_words * 4));
+    QMX_TRY(b_log.reserve((size_t)slots1 * h.log_cap * 4));
+    QMX_HIP(hipMemset(b_vis.p, 0, (size_t)slots1 * h.vis_words * 4));
+    h.visited = (uint32_t *)b_vis.p;
+    h.vis_log = (uint32_t *)b_log.p;
+
+    // ---- insertion loop ----
+    // EntryPoints (entry_points.rs:46-94) kept on the host: the live point of the highest level seen first is the
+    // entry; the `entry_points_num` highest others are the extra entries
+    bool &have_ep = r.have_ep;
+    uint32_t &ep_id = r.ep_id, &ep_level = r.ep_level, inserted = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> &extra = r.extra;
+    auto note_point = [&](uint32_t id) {
+        const uint32_t lv = level[id];
+        if (!have_ep) { have_ep = true; ep_id = id; ep_level = lv; return; }
+        std::pair<uint32_t, uint32_t> other(lv, id);
+        if (lv > ep_level) { other = {ep_level, ep_id}; ep_id = id; ep_level = lv; }
+        if (bp->entry_points_num == 0) return;
+        if (extra.size() < bp->entry_points_num) { extra.push_back(other); return; }
+        size_t lo = 0;
+        for (size_t i = 1; i < extra.size(); ++i) if (extra[i].first < extra[lo].first) lo = i;
+        if (extra[lo].first < other.first) extra[lo] = other;
+    };
+    uint32_t next = 0;
+    while (next < n) {
+        if (!have_ep) {                      // the first live point: nothing to link to
+            if (live(next)) { note_point(next); ++inserted; }
+            ++next;
+            continue;
+        }
+        uint32_t count = std::min<uint32_t>({max_batch, std::max<uint32_t>(1, inserted / 32), n - next});
+        // a point above the current top level ends its batch: the next batch starts from it
+        for (uint32_t i = 0; i < count; ++i)
+            if (level[next + i] > ep_level && live(next + i)) { count = i + 1; break; }
+        if (mb && from_original)      // the batch's inner vectors must fit the entries (a single point always does)
+            while (count > 1 && mb->h_offsets[next + count] - mb->h_offsets[next] > max_entries) --count;
+        h.first = next; h.count = count; h.ep_id = ep_id; h.ep_level = ep_level;
+        if (seg->dtype == QMX_DTYPE_PQ) {
+            // quantized_vectors.raw_scorer(original vector): Metric::preprocess (quantized_query_scorer.rs:39-41; identity for a row
+            // normalised at insert, up to the reference's 1e-6 rule), then EncodedVectorsPQ::encode_query for every point of the batch
+            // (multi-vector points: for every inner vector of the batch's points, in storage order)
+            const uint64_t r0 = mb ? mb->h_offsets[next] : next, nr = mb ? mb->h_offsets[next + count] - r0 : count;
+            float *src = (float *)b_bqsrc.p;
+            if (nr) {
+                QMX_HIP(hipMemcpy2DAsync(src, (size_t)seg->dim * 4, (const char *)original->d_rows + r0 * original->row_stride, original->row_stride,
+                                    (size_t)seg->dim * 4, nr, hipMemcpyDeviceToDevice, nullptr));
+                if (seg->distance == QMX_DISTANCE_COSINE) QMX_TRY(launch_cosine_preprocess_f32(nullptr, src, src, nr, seg->dim));
+                if (!pq_direct_build) QMX_TRY(launch_pq_lut(nullptr, seg->distance, seg->dim, seg->pq, seg->d_centroids, src, (uint32_t)nr, (float *)b_bq.p));
+            }
+        }
+        if (tq_l1(seg)) {   // EncodedVectorsTQ over Manhattan: no preprocessing, no rotation - the rows themselves, zero padded to whole 16 bytes
+            QMX_HIP(hipMemsetAsync(b_bq.p, 0, (size_t)count * a.q_stride, nullptr));
+            QMX_HIP(hipMemcpy2DAsync(b_bq.p, a.q_stride, (const char *)original->d_rows + (uint64_t)next * original->row_stride, original->row_stride,
+                                (size_t)seg->dim * 4, count, hipMemcpyDeviceToDevice, nullptr));
+        } else if (seg->dtype == QMX_DTYPE_TQ) {   // the same for EncodedVectorsTQ: preprocess, rotate, TurboQuantizer::precompute_query
+            const uint64_t r0 = mb ? mb->h_offsets[next] : next, nr = mb ? mb->h_offsets[next + count] - r0 : count;      // (multi-vector points: every inner vector)
+            float *src = (float *)b_bqsrc.p;
+            if (nr) {
+                QMX_HIP(hipMemcpy2DAsync(src, (size_t)seg->dim * 4, (const char *)original->d_rows + r0 * original->row_stride, original->row_stride,
+                                    (size_t)seg->dim * 4, nr, hipMemcpyDeviceToDevice, nullptr));
+                if (seg->distance == QMX_DISTANCE_COSINE) QMX_TRY(launch_cosine_preprocess_f32(nullptr, src, src, nr, seg->dim));
+                QMX_TRY(launch_tq_rotate(nullptr, src, (uint32_t)nr, tq_rotation(seg), (double *)b_rot.p));
+                QMX_TRY(launch_tq_query_encode(nullptr, (double *)b_rot.p, (uint32_t)nr, seg->tq_padded_dim, seg->tq_value_bits, seg->distance == QMX_DISTANCE_EUCLID ? 1 : 0,
+                                          b_bq.p, a.q_stride, a.aux_off, seg->d_tq_shift, seg->d_tq_scale, a.tq_qbytes_off));
+            }
+        }
+        const uint32_t grid1 = (uint32_t)std::min<uint64_t>(slots1, count), grid2 = (uint32_t)std::min<uint64_t>(slots2, count);
+        if (h.next) {
+            const uint32_t start[2] = {grid1, grid2};
+            QMX_HIP(hipMemcpyAsync(h.next, start, sizeof(start), hipMemcpyHostToDevice, nullptr));      // (pageable source: the copy is staged before the call returns)
+        }
+        QMX_TRY(launch_hnsw_build_any(seg, a, h, 1, grid1, &per_cu1));
+        QMX_TRY(launch_hnsw_build_any(seg, a, h, 2, grid2, &per_cu2));
+        for (uint32_t i = 0; i < count; ++i)
+            if (live(next + i)) { note_point(next + i); ++inserted; }
+        next += count;
+    }
+    QMX_HIP(hipDeviceSynchronize());
+
+    r.links0.resize((size_t)nn * m0);
+    r.cnt0.resize(nn);
+    r.linksU.resize(std::max<uint64_t>(n_up, 1) * m);
+    r.cntU.resize(std::max<uint64_t>(n_up, 1));
+    QMX_HIP(hipMemcpy(r.links0.data(), b_links0.p, r.links0.size() * 4, hipMemcpyDeviceToHost));
+    QMX_HIP(hipMemcpy(r.cnt0.data(), b_cnt0.p, r.cnt0.size() * 4, hipMemcpyDeviceToHost));
+    QMX_HIP(hipMemcpy(r.linksU.data(), b_linksU.p, r.linksU.size() * 4, hipMemcpyDeviceToHost));
+    QMX_HIP(hipMemcpy(r.cntU.data(), b_cntU.p, r.cntU.size() * 4, hipMemcpyDeviceToHost));
+    return QMX_OK;
+}
+
 static int32_t hnsw_build_impl(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, qmx_hnsw **out, const MultiBuild *mb) {
     QMX_REQUIRE(seg && bp && out, QMX_ERR_BAD_ARG, "NULL argument");
     *out = nullptr;
@@ -446,293 +656,73 @@ static int32_t hnsw_build_impl(const qmx_segment *seg, const qmx_segment *origin
         return !vd && !pd;
     };
 
-    // ---- device state ----
-    DevBuf b_level, b_upoff, b_links0, b_cnt0, b_linksU, b_cntU, b_lock, b_vis, b_log, b_sel, b_sels, b_selc, b_normf, b_normi, b_bq, b_bqsrc, b_rot, b_next, b_mvoff,
-        b_mvdel;
-    auto release_all = [&]() {
-        for (DevBuf *b : {&b_level, &b_upoff, &b_links0, &b_cnt0, &b_linksU, &b_cntU, &b_lock, &b_vis, &b_log, &b_sel, &b_sels, &b_selc, &b_normf, &b_normi,
-                          &b_bq, &b_bqsrc, &b_rot, &b_next, &b_mvoff, &b_mvdel}) b->release();
-    };
-    int32_t rc = QMX_OK;
-    qmx_hnsw *g = nullptr;
-    do {
-#define QB(expr) if ((rc = (expr)) != QMX_OK) break
-#define QH(expr) if ((expr) != hipSuccess) { rc = hip_status(hipGetLastError(), #expr, __FILE__, __LINE__); if (rc == QMX_OK) rc = QMX_ERR_OTHER; break; }
-        const size_t nn = std::max<uint32_t>(n, 1);
-        QB(b_level.reserve(nn)); QB(b_upoff.reserve(nn * 4));
-        QB(b_links0.reserve(nn * m0 * 4)); QB(b_cnt0.reserve(nn * 4));
-        QB(b_linksU.reserve(std::max<uint64_t>(n_up, 1) * m * 4)); QB(b_cntU.reserve(std::max<uint64_t>(n_up, 1) * 4));
-        QB(b_lock.reserve(nn * 4));
-        QH(hipMemcpy(b_level.p, level.data(), nn, hipMemcpyHostToDevice));
-        QH(hipMemcpy(b_upoff.p, up_off.data(), nn * 4, hipMemcpyHostToDevice));
-        QH(hipMemset(b_cnt0.p, 0, nn * 4));
-        QH(hipMemset(b_cntU.p, 0, std::max<uint64_t>(n_up, 1) * 4));
-        QH(hipMemset(b_lock.p, 0, nn * 4));
-        QB(b_sel.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * m0 * 4));
-        QB(b_sels.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * m0 * 4));
-        QB(b_selc.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * 4));
+    // ---- device state and the insertion loop ----
+    BuiltLinks r;
+    QMX_TRY(hnsw_build_links(seg, original, bp, mb, n, max_batch, level, up_off, n_up, pdel, live, r));
+    const std::vector<uint32_t> &links0 = r.links0, &cnt0 = r.cnt0, &linksU = r.linksU, &cntU = r.cntU;
+    const bool have_ep = r.have_ep;
+    const uint32_t ep_id = r.ep_id, ep_level = r.ep_level;
+    const std::vector<std::pair<uint32_t, uint32_t>> &extra = r.extra;
+    const size_t nn = std::max<uint32_t>(n, 1);
 
-        ScanArgs a;
-        fill_args_segment(seg, a);
-        if (mb) {   // the graph's points are multi-vectors: offsets into the inner rows, deletion per POINT (the inner rows carry no flags of their own)
-            QB(b_mvoff.reserve((size_t)(n + 1) * 8));
-            QH(hipMemcpy(b_mvoff.p, mb->h_offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
-            a.mv_offsets = (const uint64_t *)b_mvoff.p;
-            DeletedView dv;
-            memset(&dv, 0, sizeof(dv));
-            dv.n_rows = n;
-            if (!pdel.empty()) {
-                QB(b_mvdel.reserve(pdel.size() * 8));
-                QH(hipMemcpy(b_mvdel.p, pdel.data(), pdel.size() * 8, hipMemcpyHostToDevice));
-                dv.point_deleted = (const uint64_t *)b_mvdel.p;
-                dv.n_point_bits = mb->n_deleted_bits;
-            }
-            a.del = dv;
-        }
-        HnswBuildArgs h;
-        memset(&h, 0, sizeof(h));
-        h.g.links0 = (uint32_t *)b_links0.p; h.g.cnt0 = (uint32_t *)b_cnt0.p; h.g.linksU = (uint32_t *)b_linksU.p; h.g.cntU = (uint32_t *)b_cntU.p;
-        h.g.up_off = (const uint32_t *)b_upoff.p; h.g.m = m; h.g.m0 = m0;
-        h.level = (const uint8_t *)b_level.p;
-        h.n_points = n;
-        h.ef_construct = bp->ef_construct;
-        h.sel_ids = (uint32_t *)b_sel.p; h.sel_scores = (float *)b_sels.p; h.sel_cnt = (uint32_t *)b_selc.p;
-        h.lock = (uint32_t *)b_lock.p;
-        // bytes of a row as it lies in HBM: the SQ block holds the codes only (the vector_offset column is separate)
-        const uint64_t dev_row_bytes = seg->dtype == QMX_DTYPE_SQ_U8 ? (uint64_t)seg->sq.actual_dim : seg->row_bytes;
-        h.row_bytes = (uint32_t)dev_row_bytes;
-        h.lds_query_bytes = (uint32_t)((dev_row_bytes + 127) / 128 * 128 + 128);
-        uint64_t lut_stride = 0;
-        uint64_t max_entries = max_batch;      // query entries a batch may need: one per point - or, multi-vector points, one per inner vector
-        bool pq_direct_build = false;
-        if (seg->dtype == QMX_DTYPE_PQ) {   // query entries = LUTs of the batch's original vectors, read through L2 (as the PQ walk does)
-            lut_stride = ((uint64_t)seg->pq_m * seg->pq.n_centroids * sizeof(float) + 15) & ~15ull;
-            if (mb) {   // at least the longest point, at most 1 GiB of LUTs (the insertion loop shortens a batch that would need more)
-                uint64_t longest = 1;
-                for (uint32_t p = 0; p < n; ++p) longest = std::max<uint64_t>(longest, mb->h_offsets[p + 1] - mb->h_offsets[p]);
-                max_entries = std::max<uint64_t>(longest, std::min<uint64_t>(mb->h_offsets[n] ? mb->h_offsets[n] : 1, (1ull << 30) / lut_stride));
-                a.q_stride = (uint32_t)lut_stride;
-            }
-            // the table-free build (pq.hip HopPQDirectBuild + HopPQInternalDirect; the default where the codebook allows, option hnsw_pq_table_build for the
-            // other): the entries are the preprocessed original vectors themselves, staged in LDS per insertion - no LUTs are made, and none are reserved
-            // (max_entries x lut_stride is 1.6 GB at m = 96: several builds on one device would multiply it for nothing)
-            pq_direct_build = !mb && !option(OPT_HNSW_PQ_TABLE_BUILD) && pq_direct_walk_ok(seg->dim, seg->pq_m, seg->pq.chunk_size, seg->pq.n_centroids);
-            if (!pq_direct_build) QB(b_bq.reserve((size_t)max_entries * lut_stride));
-            QB(b_bqsrc.reserve((size_t)max_entries * seg->dim * sizeof(float)));
-            h.batch_queries = (const unsigned char *)b_bq.p;
-            h.batch_q_stride = lut_stride;
-            h.lds_query_bytes = 0;
-            if (pq_direct_build) {
-                h.batch_queries = (const unsigned char *)b_bqsrc.p;
-                h.batch_q_stride = (uint64_t)seg->dim * 4;
-                h.lds_query_bytes = seg->dim * 4;
-                // (round 5 tried an 8-bit LUT image per new point behind its vector, to prefilter the hops of the insertion searches: the same graph,
-                // 25.6 s against 24.9 s at 2 M x 1536 points - gone from the code since round 6, profiles/r5_walk_variants_pq_hop_prefilter.jsonl)
-            }
-        }
-        if (seg->dtype == QMX_DTYPE_TQ) {   // query entries = precompute_query of the batch's original vectors, staged in LDS per insertion
-            if (mb) {   // one entry per inner vector of the batch: at least the longest point, at most 256 MiB of rotated vectors
-                uint64_t longest = 1;
-                for (uint32_t p = 0; p < n; ++p) longest = std::max<uint64_t>(longest, mb->h_offsets[p + 1] - mb->h_offsets[p]);
-                max_entries = std::max<uint64_t>(longest, std::min<uint64_t>(mb->h_offsets[n] ? mb->h_offsets[n] : 1,
-                                                                             (1ull << 28) / ((uint64_t)seg->tq_padded_dim * sizeof(double))));
-            }
-            QB(b_bq.reserve((size_t)max_entries * a.q_stride));
-            QB(b_bqsrc.reserve((size_t)max_entries * seg->dim * sizeof(float)));
-            QB(b_rot.reserve((size_t)max_entries * seg->tq_padded_dim * sizeof(double)));
-            h.batch_queries = (const unsigned char *)b_bq.p;
-            h.batch_q_stride = a.q_stride;
-            h.lds_query_bytes = a.q_stride;
-            if (tq_l1(seg)) {   // over Manhattan the entry is the original vector as given (quantization.rs:532-535), its hop scratch behind it in LDS (tq_l1_policy.hpp)
-                a.tq_l1 = seg->d_tq_l1;
-                a.q_stride = tq_l1_query_bytes(seg->dim);
-                QB(b_bq.reserve((size_t)max_batch * a.q_stride));
-                h.batch_queries = (const unsigned char *)b_bq.p;
-                h.batch_q_stride = a.q_stride;
-                h.lds_query_bytes = tq_l1_lds_bytes(seg->dim, seg->tq_rot_dim);
-            }
-        }
-        if (mb) h.lds_query_bytes = 0;      // nothing staged: the inner rows of the new point are read where they lie
-        if (seg->dtype == QMX_DTYPE_U8 && seg->distance == QMX_DISTANCE_COSINE && seg->dim >= 32) {   // the per-pair cosine's query norm of a stored row
-            QB(b_normf.reserve(nn * 4)); QB(b_normi.reserve(nn * 4));
-            QB(launch_u8_row_norms(nullptr, seg->d_rows, seg->row_stride, n, seg->dim, seg->flags, (float *)b_normf.p, (int32_t *)b_normi.p));
-            a.row_norms_f = (const float *)b_normf.p;
-            a.row_norms_i = (const int32_t *)b_normi.p;
-        }
-        if (h.lds_query_bytes > HNSW_LDS_QUERY_MAX) {
-            set_error("rows of %llu bytes do not fit the LDS query slot", (unsigned long long)dev_row_bytes);
-            rc = QMX_ERR_NOT_SUPPORTED;
-            break;
-        }
-        h.log_cap = 16384;
-        h.vis_words = ((uint64_t)n + 31) / 32;
-        if (h.vis_words == 0) h.vis_words = 1;
-        int per_cu1 = 1, per_cu2 = 1;
-        QB(launch_hnsw_build_any(seg, a, h, 1, 0, &per_cu1));
-        QB(launch_hnsw_build_any(seg, a, h, 2, 0, &per_cu2));
-        uint64_t slots1 = std::min<uint64_t>({(uint64_t)seg->num_cus * per_cu1, (uint64_t)HNSW_SLOT_CAP, (uint64_t)max_batch});
-        slots1 = std::max<uint64_t>(1, std::min<uint64_t>(slots1, HNSW_VIS_BUDGET / (h.vis_words * 4)));
-        const uint64_t slots2 = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)seg->num_cus * per_cu2, max_batch));
-        QB(b_next.reserve(8));
-        h.next = (uint32_t *)b_next.p;
-        QB(b_vis.reserve((size_t)slots1 * h.vis_words * 4));
-        QB(b_log.reserve((size_t)slots1 * h.log_cap * 4));
-        QH(hipMemset(b_vis.p, 0, (size_t)slots1 * h.vis_words * 4));
-        h.visited = (uint32_t *)b_vis.p;
-        h.vis_log = (uint32_t *)b_log.p;
-
-        // ---- insertion loop ----
-        // EntryPoints (entry_points.rs:46-94) kept on the host: the live point of the highest level seen first is the
-        // entry; the `entry_points_num` highest others are the extra entries
-        bool have_ep = false;
-        uint32_t ep_id = 0, ep_level = 0, inserted = 0;
-        std::vector<std::pair<uint32_t, uint32_t>> extra;   // (level, id)
-        auto note_point = [&](uint32_t id) {
-            const uint32_t lv = level[id];
-            if (!have_ep) { have_ep = true; ep_id = id; ep_level = lv; return; }
-            std::pair<uint32_t, uint32_t> other(lv, id);
-            if (lv > ep_level) { other = {ep_level, ep_id}; ep_id = id; ep_level = lv; }
-            if (bp->entry_points_num == 0) return;
-            if (extra.size() < bp->entry_points_num) { extra.push_back(other); return; }
-            size_t lo = 0;
-            for (size_t i = 1; i < extra.size(); ++i) if (extra[i].first < extra[lo].first) lo = i;
-            if (extra[lo].first < other.first) extra[lo] = other;
-        };
-        uint32_t next = 0;
-        while (next < n && rc == QMX_OK) {
-            if (!have_ep) {                      // the first live point: nothing to link to
-                if (live(next)) { note_point(next); ++inserted; }
-                ++next;
-                continue;
-            }
-            uint32_t count = std::min<uint32_t>({max_batch, std::max<uint32_t>(1, inserted / 32), n - next});
-            // a point above the current top level ends its batch: the next batch starts from it
-            for (uint32_t i = 0; i < count; ++i)
-                if (level[next + i] > ep_level && live(next + i)) { count = i + 1; break; }
-            if (mb && from_original)      // the batch's inner vectors must fit the entries (a single point always does)
-                while (count > 1 && mb->h_offsets[next + count] - mb->h_offsets[next] > max_entries) --count;
-            h.first = next; h.count = count; h.ep_id = ep_id; h.ep_level = ep_level;
-            if (seg->dtype == QMX_DTYPE_PQ) {
-                // quantized_vectors.raw_scorer(original vector): Metric::preprocess (quantized_query_scorer.rs:39-41; identity for a row
-                // normalised at insert, up to the reference's 1e-6 rule), then EncodedVectorsPQ::encode_query for every point of the batch
-                // (multi-vector points: for every inner vector of the batch's points, in storage order)
-                const uint64_t r0 = mb ? mb->h_offsets[next] : next, nr = mb ? mb->h_offsets[next + count] - r0 : count;
-                float *src = (float *)b_bqsrc.p;
-                if (nr) {
-                    QH(hipMemcpy2DAsync(src, (size_t)seg->dim * 4, (const char *)original->d_rows + r0 * original->row_stride, original->row_stride,
-                                        (size_t)seg->dim * 4, nr, hipMemcpyDeviceToDevice, nullptr));
-                    if (seg->distance == QMX_DISTANCE_COSINE) QB(launch_cosine_preprocess_f32(nullptr, src, src, nr, seg->dim));
-                    if (!pq_direct_build) QB(launch_pq_lut(nullptr, seg->distance, seg->dim, seg->pq, seg->d_centroids, src, (uint32_t)nr, (float *)b_bq.p));
-                }
-            }
-            if (tq_l1(seg)) {   // EncodedVectorsTQ over Manhattan: no preprocessing, no rotation - the rows themselves, zero padded to whole 16 bytes
-                QH(hipMemsetAsync(b_bq.p, 0, (size_t)count * a.q_stride, nullptr));
-                QH(hipMemcpy2DAsync(b_bq.p, a.q_stride, (const char *)original->d_rows + (uint64_t)next * original->row_stride, original->row_stride,
-                                    (size_t)seg->dim * 4, count, hipMemcpyDeviceToDevice, nullptr));
-            } else if (seg->dtype == QMX_DTYPE_TQ) {   // the same for EncodedVectorsTQ: preprocess, rotate, TurboQuantizer::precompute_query
-                const uint64_t r0 = mb ? mb->h_offsets[next] : next, nr = mb ? mb->h_offsets[next + count] - r0 : count;      // (multi-vector points: every inner vector)
-                float *src = (float *)b_bqsrc.p;
-                if (nr) {
-                    QH(hipMemcpy2DAsync(src, (size_t)seg->dim * 4, (const char *)original->d_rows + r0 * original->row_stride, original->row_stride,
-                                        (size_t)seg->dim * 4, nr, hipMemcpyDeviceToDevice, nullptr));
-                    if (seg->distance == QMX_DISTANCE_COSINE) QB(launch_cosine_preprocess_f32(nullptr, src, src, nr, seg->dim));
-                    QB(launch_tq_rotate(nullptr, src, (uint32_t)nr, tq_rotation(seg), (double *)b_rot.p));
-                    QB(launch_tq_query_encode(nullptr, (double *)b_rot.p, (uint32_t)nr, seg->tq_padded_dim, seg->tq_value_bits, seg->distance == QMX_DISTANCE_EUCLID ? 1 : 0,
-                                              b_bq.p, a.q_stride, a.aux_off, seg->d_tq_shift, seg->d_tq_scale, a.tq_qbytes_off));
-                }
-            }
-            const uint32_t grid1 = (uint32_t)std::min<uint64_t>(slots1, count), grid2 = (uint32_t)std::min<uint64_t>(slots2, count);
-            if (h.next) {
-                const uint32_t start[2] = {grid1, grid2};
-                QH(hipMemcpyAsync(h.next, start, sizeof(start), hipMemcpyHostToDevice, nullptr));      // (pageable source: the copy is staged before the call returns)
-            }
-            QB(launch_hnsw_build_any(seg, a, h, 1, grid1, &per_cu1));
-            QB(launch_hnsw_build_any(seg, a, h, 2, grid2, &per_cu2));
-            for (uint32_t i = 0; i < count; ++i)
-                if (live(next + i)) { note_point(next + i); ++inserted; }
-            next += count;
-        }
-        if (rc != QMX_OK) break;
-        QH(hipDeviceSynchronize());
-
-        // ---- export: fixed-capacity lists -> plain GraphLinks arrays (graph_links/serializer.rs:52-209) ----
-        std::vector<uint32_t> links0((size_t)nn * m0), cnt0(nn), linksU(std::max<uint64_t>(n_up, 1) * m), cntU(std::max<uint64_t>(n_up, 1));
-        QH(hipMemcpy(links0.data(), b_links0.p, links0.size() * 4, hipMemcpyDeviceToHost));
-        QH(hipMemcpy(cnt0.data(), b_cnt0.p, cnt0.size() * 4, hipMemcpyDeviceToHost));
-        QH(hipMemcpy(linksU.data(), b_linksU.p, linksU.size() * 4, hipMemcpyDeviceToHost));
-        QH(hipMemcpy(cntU.data(), b_cntU.p, cntU.size() * 4, hipMemcpyDeviceToHost));
-        release_all();
-        uint32_t maxl = 0;
-        for (uint32_t i = 0; i < n; ++i) maxl = std::max<uint32_t>(maxl, level[i]);
-        const uint32_t L = n ? maxl + 1 : 0;
-        g = new (std::nothrow) qmx_hnsw();
-        if (!g) { rc = QMX_ERR_OUT_OF_MEMORY; break; }
-        std::vector<uint64_t> count_ge(L + 1, 0);
-        for (uint32_t i = 0; i < n; ++i) for (uint32_t l = 0; l <= level[i]; ++l) count_ge[l]++;
-        // back_index: points by descending level, ties by id
-        std::vector<uint32_t> back(nn);
-        {
-            std::vector<uint64_t> start(L + 1, 0);
-            uint64_t acc = 0;
-            for (int32_t l = (int32_t)L - 1; l >= 0; --l) { start[l] = acc; acc += count_ge[l] - (l + 1 < (int32_t)L ? count_ge[l + 1] : 0); }
-            for (uint32_t i = 0; i < n; ++i) back[start[level[i]]++] = i;
-        }
-        g->h_reindex.resize(n);
-        for (uint32_t i = 0; i < n; ++i) g->h_reindex[back[i]] = i;
-        uint64_t total_slots = 0;
-        for (uint32_t l = 0; l < L; ++l) total_slots += count_ge[l];
-        g->h_level_offsets.assign(L + 1, 0);
-        g->h_offsets.assign(total_slots + 1, 0);
-        uint64_t nnb = 0;
-        for (uint32_t i = 0; i < n; ++i) { nnb += cnt0[i]; for (uint32_t l = 1; l <= level[i]; ++l) nnb += cntU[up_off[i] + l - 1]; }
-        g->h_neighbors.resize(nnb);
-        uint64_t off = 0, slot = 0;
-        for (uint32_t l = 0; l < L; ++l) {
-            g->h_level_offsets[l] = slot;
-            for (uint64_t j = 0; j < count_ge[l]; ++j) {
-                const uint32_t id = l == 0 ? (uint32_t)j : back[j];
-                g->h_offsets[slot++] = off;
-                const uint32_t len = l == 0 ? cnt0[id] : cntU[up_off[id] + l - 1];
-                const uint32_t *src = l == 0 ? &links0[(size_t)id * m0] : &linksU[((size_t)up_off[id] + l - 1) * m];
-                memcpy(g->h_neighbors.data() + off, src, (size_t)len * 4);
-                off += len;
-            }
-        }
-        g->h_level_offsets[L] = slot;
-        g->h_offsets[slot] = off;
-        if (have_ep) { g->h_ep_ids.push_back(ep_id); g->h_ep_levels.push_back(ep_level); }
-        for (auto &e : extra) { g->h_xp_ids.push_back(e.second); g->h_xp_levels.push_back(e.first); }
-        qmx_hnsw_desc d;
-        memset(&d, 0, sizeof(d));
-        d.m = m; d.m0 = m0; d.n_points = n; d.n_levels = L;
-        d.reindex = g->h_reindex.data(); d.level_offsets = g->h_level_offsets.data(); d.offsets = g->h_offsets.data();
-        d.n_offsets = g->h_offsets.size(); d.neighbors = g->h_neighbors.data(); d.n_neighbors = g->h_neighbors.size();
-        d.entry_point_ids = g->h_ep_ids.data(); d.entry_point_levels = g->h_ep_levels.data(); d.n_entry_points = (uint32_t)g->h_ep_ids.size();
-        d.extra_entry_point_ids = g->h_xp_ids.data(); d.extra_entry_point_levels = g->h_xp_levels.data();
-        d.n_extra_entry_points = (uint32_t)g->h_xp_ids.size();
-        d.device_id = seg->device;
-        qmx_hnsw *dev = nullptr;
-        QB(qmx_hnsw_create(&d, &dev));
-        // move the device arrays into g (which owns the host copy)
-        g->device = dev->device; g->m = dev->m; g->m0 = dev->m0; g->n_points = dev->n_points; g->n_levels = dev->n_levels;
-        g->n_ep = dev->n_ep; g->n_xp = dev->n_xp; g->n_offsets = dev->n_offsets; g->n_neighbors = dev->n_neighbors;
-        g->d_reindex = dev->d_reindex; g->d_neighbors = dev->d_neighbors; g->d_ep_ids = dev->d_ep_ids; g->d_ep_levels = dev->d_ep_levels;
-        g->d_xp_ids = dev->d_xp_ids; g->d_xp_levels = dev->d_xp_levels; g->d_level_offsets = dev->d_level_offsets; g->d_offsets = dev->d_offsets;
-        g->d_l0 = dev->d_l0; g->l0_stride = dev->l0_stride;
-        delete dev;
-#undef QB
-#undef QH
-    } while (0);
-    release_all();
-    if (rc != QMX_OK) {
-        if (g) qmx_hnsw_destroy(g);
-        return rc;
+    // ---- export: fixed-capacity lists -> plain GraphLinks arrays (graph_links/serializer.rs:52-209) ----
+    uint32_t maxl = 0;
+    for (uint32_t i = 0; i < n; ++i) maxl = std::max<uint32_t>(maxl, level[i]);
+    const uint32_t L = n ? maxl + 1 : 0;
+    qmx_hnsw host;      // (the plain arrays only: qmx_hnsw_create below makes the handle, which then takes them over for qmx_hnsw_export_plain)
+    qmx_hnsw *g = &host;
+    std::vector<uint64_t> count_ge(L + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) for (uint32_t l = 0; l <= level[i]; ++l) count_ge[l]++;
+    // back_index: points by descending level, ties by id
+    std::vector<uint32_t> back(nn);
+    {
+        std::vector<uint64_t> start(L + 1, 0);
+        uint64_t acc = 0;
+        for (int32_t l = (int32_t)L - 1; l >= 0; --l) { start[l] = acc; acc += count_ge[l] - (l + 1 < (int32_t)L ? count_ge[l + 1] : 0); }
+        for (uint32_t i = 0; i < n; ++i) back[start[level[i]]++] = i;
     }
-    *out = g;
+    g->h_reindex.resize(n);
+    for (uint32_t i = 0; i < n; ++i) g->h_reindex[back[i]] = i;
+    uint64_t total_slots = 0;
+    for (uint32_t l = 0; l < L; ++l) total_slots += count_ge[l];
+    g->h_level_offsets.assign(L + 1, 0);
+    g->h_offsets.assign(total_slots + 1, 0);
+    uint64_t nnb = 0;
+    for (uint32_t i = 0; i < n; ++i) { nnb += cnt0[i]; for (uint32_t l = 1; l <= level[i]; ++l) nnb += cntU[up_off[i] + l - 1]; }
+    g->h_neighbors.resize(nnb);
+    uint64_t off = 0, slot = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+        g->h_level_offsets[l] = slot;
+        for (uint64_t j = 0; j < count_ge[l]; ++j) {
+            const uint32_t id = l == 0 ? (uint32_t)j : back[j];
+            g->h_offsets[slot++] = off;
+            const uint32_t len = l == 0 ? cnt0[id] : cntU[up_off[id] + l - 1];
+            const uint32_t *src = l == 0 ? &links0[(size_t)id * m0] : &linksU[((size_t)up_off[id] + l - 1) * m];
+            memcpy(g->h_neighbors.data() + off, src, (size_t)len * 4);
+            off += len;
+        }
+    }
+    g->h_level_offsets[L] = slot;
+    g->h_offsets[slot] = off;
+    if (have_ep) { g->h_ep_ids.push_back(ep_id); g->h_ep_levels.push_back(ep_level); }
+    for (auto &e : extra) { g->h_xp_ids.push_back(e.second); g->h_xp_levels.push_back(e.first); }
+    qmx_hnsw_desc d;
+    memset(&d, 0, sizeof(d));
+    d.m = m; d.m0 = m0; d.n_points = n; d.n_levels = L;
+    d.reindex = g->h_reindex.data(); d.level_offsets = g->h_level_offsets.data(); d.offsets = g->h_offsets.data();
+    d.n_offsets = g->h_offsets.size(); d.neighbors = g->h_neighbors.data(); d.n_neighbors = g->h_neighbors.size();
+    d.entry_point_ids = g->h_ep_ids.data(); d.entry_point_levels = g->h_ep_levels.data(); d.n_entry_points = (uint32_t)g->h_ep_ids.size();
+    d.extra_entry_point_ids = g->h_xp_ids.data(); d.extra_entry_point_levels = g->h_xp_levels.data();
+    d.n_extra_entry_points = (uint32_t)g->h_xp_ids.size();
+    d.device_id = seg->device;
+    QMX_TRY(qmx_hnsw_create(&d, out));
+    qmx_hnsw *dev = *out;
+    dev->h_reindex = std::move(g->h_reindex); dev->h_neighbors = std::move(g->h_neighbors);
+    dev->h_ep_ids = std::move(g->h_ep_ids); dev->h_ep_levels = std::move(g->h_ep_levels);
+    dev->h_xp_ids = std::move(g->h_xp_ids); dev->h_xp_levels = std::move(g->h_xp_levels);
+    dev->h_level_offsets = std::move(g->h_level_offsets); dev->h_offsets = std::move(g->h_offsets);
     return QMX_OK;
 }
-
-
 
 static int32_t launch_hnsw(const qmx_query *q, const ScanArgs &a, const HnswArgs &h, uint32_t grid, int *per_cu) {
     const qmx_segment *s = q->seg;

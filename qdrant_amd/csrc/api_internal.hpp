@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "dev_mem.hpp"
 #include "tq_rotate.hpp"
 
 namespace qmx {
@@ -28,26 +29,6 @@ const void *last_noted_kernel();                             // the kernel the c
 bool is_device_ptr(const void *p);
 uint32_t elem_bytes(uint32_t dtype);
 int32_t check_device(int32_t device_id, hipDeviceProp_t *prop_out);
-// growable device scratch
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int32_t reserve(size_t bytes) {
-        if (bytes <= cap) return QMX_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(bytes, 4096);
-        QMX_HIP(hipMalloc(&p, want));
-        cap = want;
-        return QMX_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 }  // namespace qmx
 
 using namespace qmx;
@@ -61,6 +42,8 @@ inline uint64_t next_segment_uid() {
 }
 struct SparseSeg;     // QMX_DTYPE_SPARSE: rows, posting layout, dimension directory (api_sparse.hip)
 struct SparseQuery;   // ... a batch of sparse queries and their posting plan
+void sparse_delete(SparseSeg *sp);
+void sparse_delete(SparseQuery *sq);
 struct qmx_segment {
     const uint64_t uid = next_segment_uid();      // never reused: what a cache keyed by a segment compares (a freed segment's address may come back)
     int device = 0;
@@ -117,6 +100,21 @@ struct qmx_segment {
     uint32_t auto_i8_fallback = 0;
     SparseSeg *sparse = nullptr;      // QMX_DTYPE_SPARSE only
 
+    qmx_segment() = default;
+    qmx_segment(const qmx_segment &) = delete;
+    qmx_segment &operator=(const qmx_segment &) = delete;
+    // every device pointer above is the segment's own, d_rows where owns_rows says so (the current device is the segment's: qmx_segment_destroy)
+    ~qmx_segment() {
+        if (owns_rows) dev_free(d_rows);
+        dev_free(d_point_deleted); dev_free(d_vec_deleted);
+        dev_free(d_bq_mean); dev_free(d_bq_stddev);
+        dev_free(d_centroids); dev_free(d_pq_pair); dev_free(d_pq_rot);
+        dev_free(d_row_offsets); dev_free(d_sq_bi);
+        dev_free(d_tq_sf); dev_free(d_tq_l2); dev_free(d_tq_xm); dev_free(d_tq_shift); dev_free(d_tq_scale); dev_free(d_tq_weights);
+        dev_free(d_tq_tables); dev_free(d_tq_l1); dev_free(d_tq_norms);
+        dev_free(d_rows_split); dev_free(d_i8_scale); dev_free(d_i8_stats);
+        sparse_delete(sparse);
+    }
     bool fast_layout() const {
         if (dtype == QMX_DTYPE_BQ || dtype == QMX_DTYPE_TQ) return row_stride % 16 == 0 && ((uintptr_t)d_rows % 16) == 0;
         if (dtype <= QMX_DTYPE_U8) {
@@ -200,6 +198,23 @@ struct qmx_query {
     bool timing = false;
     const void *last_kernel = nullptr;   // host handle of the last top-k scan / graph walk kernel launched for this batch
     SparseQuery *sparse = nullptr;       // a batch over a QMX_DTYPE_SPARSE segment (qmx_sparse_query_create / qmx_query_create_internal)
+
+    qmx_query() = default;
+    qmx_query(const qmx_query &) = delete;
+    qmx_query &operator=(const qmx_query &) = delete;
+    // the stream is idle (qmx_query_destroy synchronised it); the DevBuf members free themselves behind this body
+    ~qmx_query() {
+        dev_free(d_queries);
+        dev_free(d_err);
+        if (sh_done) (void)hipEventDestroy(sh_done);
+        if (sh_merged) (void)hipEventDestroy(sh_merged);
+        for (auto &p : evs) {
+            if (p.a) (void)hipEventDestroy(p.a);
+            if (p.b) (void)hipEventDestroy(p.b);
+        }
+        sparse_delete(sparse);
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+    }
 };
 
 // QMX_DTYPE_SPARSE is served by the entry points include/qdrant_amd.h lists; every other one refuses it
@@ -389,6 +404,14 @@ struct qmx_hnsw {
     // host copy of the plain arrays (graphs built by qmx_hnsw_build; empty otherwise) for qmx_hnsw_export_plain
     std::vector<uint32_t> h_reindex, h_neighbors, h_ep_ids, h_ep_levels, h_xp_ids, h_xp_levels;
     std::vector<uint64_t> h_level_offsets, h_offsets;
+
+    qmx_hnsw() = default;
+    qmx_hnsw(const qmx_hnsw &) = delete;
+    qmx_hnsw &operator=(const qmx_hnsw &) = delete;
+    ~qmx_hnsw() {
+        dev_free(d_reindex); dev_free(d_neighbors); dev_free(d_ep_ids); dev_free(d_ep_levels); dev_free(d_xp_ids); dev_free(d_xp_levels);
+        dev_free(d_level_offsets); dev_free(d_offsets); dev_free(d_l0); dev_free(d_l0x);
+    }
 };
 
 constexpr uint32_t HNSW_SLOT_CAP = 4096;
@@ -462,8 +485,6 @@ TqRotationHost tq_rotation(const qmx_segment *s);
 TqRotationHost tq_rotation_inverse(const qmx_segment *s);
 }
 // sparse vectors (api_sparse.hip)
-void sparse_segment_free(qmx_segment *s);
-void sparse_query_free(qmx_query *q);
 int32_t sparse_query_create_internal(const qmx_segment *seg, const uint32_t *point_ids, uint32_t nq, qmx_query **out);
 int32_t sparse_score_matrix(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride);
 int32_t sparse_score_pairs(qmx_query *q, const PairSel &sel, const uint32_t *d_ids, uint64_t n_items, float *d_scores);

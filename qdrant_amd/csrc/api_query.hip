@@ -123,6 +123,30 @@ int32_t qmx_query_update(qmx_query *q, const float *queries) {
     return query_encode(q, queries);
 }
 
+// the stored rows `point_ids` as the batch's queries
+static int32_t internal_encode(qmx_query *q, const uint32_t *point_ids) {
+    const qmx_segment *seg = q->seg;
+    const uint32_t nq = q->nq;
+    const void *d_ids = nullptr;
+    QMX_TRY(stage_in(q, q->ids, point_ids, (size_t)nq * 4, &d_ids));
+    if (seg->dtype == QMX_DTYPE_SQ_U8) {   // encode_internal_vector (encoded_vectors_u8.rs:715-728)
+        float shift = (seg->distance == QMX_DISTANCE_DOT || seg->distance == QMX_DISTANCE_COSINE)
+                          ? (float)seg->sq.actual_dim * seg->sq.offset * seg->sq.offset : 0.0f;
+        if (seg->sq.invert) shift = -shift;
+        QMX_TRY(launch_sq_internal_query(q->stream, seg->d_rows, seg->d_row_offsets, seg->sq.actual_dim, (const uint32_t *)d_ids, nq, seg->n, shift,
+                                         q->d_queries, q->q_stride, q->aux_off, q->d_err));
+        return check_err_flag(q);
+    }
+    // the stored row IS the query (already preprocessed at insert): FilteredScorer::new_internal
+    QMX_TRY(q->misc.reserve((size_t)nq * seg->row_bytes));
+    QMX_TRY(launch_gather_rows(q->stream, seg->d_rows, seg->row_stride, seg->row_bytes, (const uint32_t *)d_ids, nq, seg->n, q->misc.p, q->d_err));
+    // BQ: EncodedVectorsBin::encode_internal_vector (encoded_vectors_binary.rs:923-934) = the stored bits, packed as bytes
+    const bool bq = seg->dtype == QMX_DTYPE_BQ;
+    QMX_TRY(launch_pack_queries(q->stream, bq ? (int)QMX_DTYPE_U8 : (int)seg->dtype, bq ? (int)QMX_DISTANCE_DOT : (int)seg->distance, q->misc.p, 1,
+                                (uint32_t)seg->row_bytes, nq, bq ? (uint32_t)seg->row_bytes : seg->dim, q->d_queries, q->q_stride, q->aux_off));
+    return check_err_flag(q);
+}
+
 int32_t qmx_query_create_internal(const qmx_segment *seg, const uint32_t *point_ids, uint32_t nq, qmx_query **out) {
     QMX_REQUIRE(seg && out && (nq == 0 || point_ids), QMX_ERR_BAD_ARG, "NULL argument");
     *out = nullptr;
@@ -133,31 +157,7 @@ int32_t qmx_query_create_internal(const qmx_segment *seg, const uint32_t *point_
                 seg->dtype);
     qmx_query *q = nullptr;
     QMX_TRY(query_alloc(seg, nq, &q, true));
-    int32_t rc = QMX_OK;
-    do {
-        if (nq == 0) break;
-        const void *d_ids = nullptr;
-        if ((rc = stage_in(q, q->ids, point_ids, (size_t)nq * 4, &d_ids)) != QMX_OK) break;
-        if (seg->dtype == QMX_DTYPE_SQ_U8) {   // encode_internal_vector (encoded_vectors_u8.rs:715-728)
-            float shift = (seg->distance == QMX_DISTANCE_DOT || seg->distance == QMX_DISTANCE_COSINE)
-                              ? (float)seg->sq.actual_dim * seg->sq.offset * seg->sq.offset : 0.0f;
-            if (seg->sq.invert) shift = -shift;
-            if ((rc = launch_sq_internal_query(q->stream, seg->d_rows, seg->d_row_offsets, seg->sq.actual_dim, (const uint32_t *)d_ids,
-                                               nq, seg->n, shift, q->d_queries, q->q_stride, q->aux_off, q->d_err)) != QMX_OK) break;
-            if ((rc = check_err_flag(q)) != QMX_OK) break;
-            break;
-        }
-        // the stored row IS the query (already preprocessed at insert): FilteredScorer::new_internal
-        if ((rc = q->misc.reserve((size_t)nq * seg->row_bytes)) != QMX_OK) break;
-        if ((rc = launch_gather_rows(q->stream, seg->d_rows, seg->row_stride, seg->row_bytes, (const uint32_t *)d_ids, nq,
-                                     seg->n, q->misc.p, q->d_err)) != QMX_OK) break;
-        // BQ: EncodedVectorsBin::encode_internal_vector (encoded_vectors_binary.rs:923-934) = the stored bits, packed as bytes
-        const bool bq = seg->dtype == QMX_DTYPE_BQ;
-        if ((rc = launch_pack_queries(q->stream, bq ? (int)QMX_DTYPE_U8 : (int)seg->dtype, bq ? (int)QMX_DISTANCE_DOT : (int)seg->distance,
-                                      q->misc.p, 1, (uint32_t)seg->row_bytes, nq, bq ? (uint32_t)seg->row_bytes : seg->dim, q->d_queries,
-                                      q->q_stride, q->aux_off)) != QMX_OK) break;
-        if ((rc = check_err_flag(q)) != QMX_OK) break;
-    } while (0);
+    const int32_t rc = nq ? internal_encode(q, point_ids) : QMX_OK;
     if (rc != QMX_OK) {
         qmx_query_destroy(q);
         return rc;
@@ -170,49 +170,6 @@ int32_t qmx_query_destroy(qmx_query *q) {
     if (!q) return QMX_OK;
     (void)hipSetDevice(q->device);
     if (q->stream) (void)hipStreamSynchronize(q->stream);
-    if (q->d_queries) (void)hipFree(q->d_queries);
-    if (q->d_err) (void)hipFree(q->d_err);
-    q->partial.release();
-    q->out.release();
-    q->counts.release();
-    q->ids.release();
-    q->scores.release();
-    q->misc.release();
-    q->enc.release();
-    q->bounds.release();
-    q->gthr.release();
-    q->cq_coefs.release();
-    q->filter.release();
-    q->cq_sims.release();
-    q->mv_qfirst.release();
-    q->mv_offsets.release();
-    q->mv_deleted.release();
-    q->cq_scores.release();
-    q->cq_desc.release();
-    q->cq_multi.release();
-    q->sp_bq.release(); q->sp_f32.release(); q->sp_cand.release(); q->sp_cnt.release(); q->sp_ver.release(); q->sp_vscores.release(); q->sp_sample.release(); q->sp_wl.release(); q->xcnt.release(); q->tq_rot.release(); q->sp_plan.release(); q->sp_fq.release(); q->sp_probe.release(); q->sp_pscores.release(); q->pq_table.release(); q->sh_lists.release(); q->sh_out.release();
-    if (q->sh_done) (void)hipEventDestroy(q->sh_done);
-    if (q->sh_merged) (void)hipEventDestroy(q->sh_merged);
-    q->cand.release();
-    q->cand_cnt.release();
-    q->cand_ids.release();
-    q->mmr_ids.release();
-    q->mmr_rel.release();
-    q->mmr_spill.release();
-    q->grp_state.release(); q->grp_pages.release(); q->grp_scores.release(); q->grp_queries.release(); q->grp_partial.release(); q->grp_out.release();
-    q->hnsw_vis.release();
-    q->hnsw_log.release();
-    q->hnsw_scored.release();
-    q->hnsw_pq8.release();
-    q->hnsw_lutx.release();
-    q->hnsw_next.release();
-    q->hnsw_refc.release();
-    for (auto &p : q->evs) {
-        if (p.a) (void)hipEventDestroy(p.a);
-        if (p.b) (void)hipEventDestroy(p.b);
-    }
-    sparse_query_free(q);
-    if (q->own_stream) (void)hipStreamDestroy(q->own_stream);
     delete q;
     return QMX_OK;
 }
@@ -585,84 +542,107 @@ int32_t qmx_rescore(qmx_query *q, const uint32_t *ids, const uint32_t *counts, u
     return check_err_flag(q);
 }
 
+// centroid <-> centroid (encoded_vectors_pq.rs:574-618 | TurboQuantizer::score_symmetric); no query involved
+static int32_t quantized_score_internal(const qmx_segment *seg, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t n, float *out) {
+    QMX_HIP(hipSetDevice(seg->device));
+    Staging st;
+    DevBuf be;
+    const uint32_t *d_a = nullptr, *d_b = nullptr;
+    float *d_out = nullptr;
+    QMX_TRY(st.in(a_ids, (size_t)n * 4, &d_a));
+    QMX_TRY(st.in(b_ids, (size_t)n * 4, &d_b));
+    QMX_TRY(st.out(out, (size_t)n * 4, &d_out));
+    QMX_TRY(be.reserve(4));
+    int *d_err = (int *)be.p;
+    QMX_HIP(hipMemset(d_err, 0, 4));
+    if (tq_l1(seg)) {    // score_symmetric's L1 arm (quantization.rs:429-440): both rows dequantised, ONE inverse rotation of the difference, sum |x| over padded_dim
+        DevBuf da, db;
+        const uint32_t pd = seg->tq_padded_dim;
+        const uint64_t B = 32768;
+        QMX_TRY(da.reserve((size_t)std::min<uint64_t>(n, B) * pd * 8));
+        QMX_TRY(db.reserve((size_t)std::min<uint64_t>(n, B) * pd * 8));
+        for (uint64_t r0 = 0; r0 < n; r0 += B) {
+            const uint32_t cnt = (uint32_t)std::min<uint64_t>(B, n - r0);
+            QMX_TRY(launch_tq_l1_dequant(nullptr, seg->d_rows, seg->row_stride, seg->d_tq_sf, d_a + r0, 0, cnt, seg->n, pd, seg->tq_value_bits, seg->d_tq_shift,
+                                         seg->d_tq_scale, (double *)da.p, d_err, nullptr));
+            QMX_TRY(launch_tq_l1_dequant(nullptr, seg->d_rows, seg->row_stride, seg->d_tq_sf, d_b + r0, 0, cnt, seg->n, pd, seg->tq_value_bits, seg->d_tq_shift,
+                                         seg->d_tq_scale, (double *)db.p, d_err, nullptr));
+            QMX_TRY(launch_tq_l1_diff(nullptr, (double *)da.p, (const double *)db.p, (uint64_t)cnt * pd));
+            QMX_TRY(launch_tq_rotate_f64(nullptr, (double *)da.p, cnt, tq_rotation_inverse(seg)));
+            QMX_TRY(launch_tq_l1_scores(nullptr, (const double *)da.p, cnt, pd, pd, nullptr, pd, 0, 1, d_out, 0, r0, seg->tq_invert ? 1 : 0, nullptr, 0));
+        }
+        QMX_HIP(hipDeviceSynchronize());
+    } else if (seg->dtype == QMX_DTYPE_TQ) {
+        TqEc ec{seg->d_tq_weights, seg->d_tq_xm, seg->tq_weight_scale, seg->tq_mm_const};
+        QMX_TRY(launch_tq_internal(nullptr, seg->d_rows, (uint32_t)seg->row_stride, seg->d_tq_sf, seg->d_tq_l2, seg->tq_code_bytes, seg->tq_value_bits,
+                                   seg->tq_invert ? 1 : 0, seg->n, d_a, d_b, n, d_out, d_err, seg->d_tq_weights ? &ec : nullptr));
+    } else {
+        QMX_TRY(launch_pq_internal(nullptr, seg->distance, seg->dim, seg->pq, seg->d_centroids, seg->d_pq_pair, seg->d_rows, seg->row_stride, seg->n, d_a, d_b, n,
+                                   d_out, d_err));
+    }
+    int flag = 0;
+    QMX_HIP(hipMemcpy(&flag, d_err, 4, hipMemcpyDeviceToHost));
+    QMX_TRY(st.back());
+    QMX_REQUIRE(!flag, QMX_ERR_OUT_OF_BOUNDS, "point offset out of range for this segment");
+    return QMX_OK;
+}
+
+// the diagonal pairs (i, b[i]) of a batch whose query i is the stored point a[i]
+static int32_t internal_pairs(qmx_query *q, const uint32_t *b_ids, uint32_t n, float *out) {
+    const void *d_ids = nullptr;
+    QMX_TRY(stage_in(q, q->ids, b_ids, (size_t)n * 4, &d_ids));
+    const bool out_dev = is_device_ptr(out);
+    float *d_scores = out;
+    if (!out_dev) {
+        QMX_TRY(q->scores.reserve((size_t)n * 4));
+        d_scores = (float *)q->scores.p;
+    }
+    PairSel sel{nullptr, 0, nullptr};
+    QMX_TRY(score_pairs_device(q, sel, (const uint32_t *)d_ids, n, d_scores, false));
+    if (!out_dev) QMX_HIP(hipMemcpyAsync(out, d_scores, (size_t)n * 4, hipMemcpyDeviceToHost, q->stream));
+    return check_err_flag(q);
+}
+
 int32_t qmx_score_internal(const qmx_segment *seg, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t n, float *out) {
     QMX_REQUIRE(seg && (n == 0 || (a_ids && b_ids && out)), QMX_ERR_BAD_ARG, "NULL argument");
     if (n == 0) return QMX_OK;
     if (is_sparse(seg)) return sparse_score_internal(seg, a_ids, b_ids, n, out);
-    if (seg->dtype == QMX_DTYPE_PQ || seg->dtype == QMX_DTYPE_TQ) {   // centroid <-> centroid (encoded_vectors_pq.rs:574-618 | TurboQuantizer::score_symmetric); no query involved
-        QMX_HIP(hipSetDevice(seg->device));
-        DevBuf ba, bb, bo, be;
-        int32_t rc = QMX_OK;
-        do {
-            if ((rc = ba.reserve((size_t)n * 4)) != QMX_OK || (rc = bb.reserve((size_t)n * 4)) != QMX_OK ||
-                (rc = bo.reserve((size_t)n * 4)) != QMX_OK || (rc = be.reserve(4)) != QMX_OK) break;
-            hipError_t e = hipMemcpy(ba.p, a_ids, (size_t)n * 4, hipMemcpyDefault);
-            if (e == hipSuccess) e = hipMemcpy(bb.p, b_ids, (size_t)n * 4, hipMemcpyDefault);
-            if (e == hipSuccess) e = hipMemset(be.p, 0, 4);
-            if (e != hipSuccess) { rc = hip_status(e, "stage ids", __FILE__, __LINE__); break; }
-            if (tq_l1(seg)) {    // score_symmetric's L1 arm (quantization.rs:429-440): both rows dequantised, ONE inverse rotation of the difference, sum |x| over padded_dim
-                DevBuf da, db;
-                const uint32_t pd = seg->tq_padded_dim;
-                const uint64_t B = 32768;
-                if ((rc = da.reserve((size_t)std::min<uint64_t>(n, B) * pd * 8)) == QMX_OK) rc = db.reserve((size_t)std::min<uint64_t>(n, B) * pd * 8);
-                for (uint64_t r0 = 0; r0 < n && rc == QMX_OK; r0 += B) {
-                    const uint32_t cnt = (uint32_t)std::min<uint64_t>(B, n - r0);
-                    rc = launch_tq_l1_dequant(nullptr, seg->d_rows, seg->row_stride, seg->d_tq_sf, (const uint32_t *)ba.p + r0, 0, cnt, seg->n, pd, seg->tq_value_bits,
-                                              seg->d_tq_shift, seg->d_tq_scale, (double *)da.p, (int *)be.p, nullptr);
-                    if (rc == QMX_OK)
-                        rc = launch_tq_l1_dequant(nullptr, seg->d_rows, seg->row_stride, seg->d_tq_sf, (const uint32_t *)bb.p + r0, 0, cnt, seg->n, pd, seg->tq_value_bits,
-                                                  seg->d_tq_shift, seg->d_tq_scale, (double *)db.p, (int *)be.p, nullptr);
-                    if (rc == QMX_OK) rc = launch_tq_l1_diff(nullptr, (double *)da.p, (const double *)db.p, (uint64_t)cnt * pd);
-                    if (rc == QMX_OK) rc = launch_tq_rotate_f64(nullptr, (double *)da.p, cnt, tq_rotation_inverse(seg));
-                    if (rc == QMX_OK)
-                        rc = launch_tq_l1_scores(nullptr, (const double *)da.p, cnt, pd, pd, nullptr, pd, 0, 1, (float *)bo.p, 0, r0, seg->tq_invert ? 1 : 0, nullptr, 0);
-                }
-                if (rc == QMX_OK && hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-                da.release(); db.release();
-            }
-            else if (seg->dtype == QMX_DTYPE_TQ)
-            {
-                TqEc ec{seg->d_tq_weights, seg->d_tq_xm, seg->tq_weight_scale, seg->tq_mm_const};
-                rc = launch_tq_internal(nullptr, seg->d_rows, (uint32_t)seg->row_stride, seg->d_tq_sf, seg->d_tq_l2, seg->tq_code_bytes, seg->tq_value_bits,
-                                        seg->tq_invert ? 1 : 0, seg->n, (const uint32_t *)ba.p, (const uint32_t *)bb.p, n, (float *)bo.p, (int *)be.p,
-                                        seg->d_tq_weights ? &ec : nullptr);
-            }
-            else
-                rc = launch_pq_internal(nullptr, seg->distance, seg->dim, seg->pq, seg->d_centroids, seg->d_pq_pair, seg->d_rows, seg->row_stride, seg->n,
-                                        (const uint32_t *)ba.p, (const uint32_t *)bb.p, n, (float *)bo.p, (int *)be.p);
-            if (rc != QMX_OK) break;
-            int flag = 0;
-            e = hipMemcpy(&flag, be.p, 4, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * 4, hipMemcpyDefault);
-            if (e != hipSuccess) { rc = hip_status(e, "copy scores", __FILE__, __LINE__); break; }
-            if (flag) { set_error("point offset out of range for this segment"); rc = QMX_ERR_OUT_OF_BOUNDS; }
-        } while (0);
-        ba.release(); bb.release(); bo.release(); be.release();
-        return rc;
-    }
-    // query i = stored point a[i] (FilteredScorer::new_internal), then the diagonal pairs (i, b[i])
+    if (seg->dtype == QMX_DTYPE_PQ || seg->dtype == QMX_DTYPE_TQ) return quantized_score_internal(seg, a_ids, b_ids, n, out);
+    // query i = stored point a[i] (FilteredScorer::new_internal)
     qmx_query *q = nullptr;
     QMX_TRY(qmx_query_create_internal(seg, a_ids, n, &q));
-    int32_t rc = QMX_OK;
-    do {
-        const void *d_ids = nullptr;
-        if ((rc = stage_in(q, q->ids, b_ids, (size_t)n * 4, &d_ids)) != QMX_OK) break;
-        const bool out_dev = is_device_ptr(out);
-        float *d_scores = out;
-        if (!out_dev) {
-            if ((rc = q->scores.reserve((size_t)n * 4)) != QMX_OK) break;
-            d_scores = (float *)q->scores.p;
-        }
-        PairSel sel{nullptr, 0, nullptr};
-        if ((rc = score_pairs_device(q, sel, (const uint32_t *)d_ids, n, d_scores, false)) != QMX_OK) break;
-        if (!out_dev) {
-            hipError_t e = hipMemcpyAsync(out, d_scores, (size_t)n * 4, hipMemcpyDeviceToHost, q->stream);
-            if (e != hipSuccess) { rc = hip_status(e, "copy scores", __FILE__, __LINE__); break; }
-        }
-        rc = check_err_flag(q);
-    } while (0);
+    const int32_t rc = internal_pairs(q, b_ids, n, out);
     qmx_query_destroy(q);
     return rc;
+}
+
+// every query of the batch against the `n` rows of the transient block `blk` (the layout of the batch's own segment)
+static int32_t score_block(qmx_query *q, const qmx_segment *blk, uint32_t n, float *scores) {
+    const size_t sbytes = (size_t)q->nq * n * sizeof(float);
+    const bool out_dev = is_device_ptr(scores);
+    float *d_scores = scores;
+    if (!out_dev) {
+        QMX_TRY(q->scores.reserve(sbytes));
+        d_scores = (float *)q->scores.p;
+    }
+    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += MAX_QT) {
+        const uint32_t nq_tile = std::min<uint32_t>(MAX_QT, q->nq - tile0);
+        ScanArgs a;
+        fill_args(q, tile0, nq_tile, a);
+        a.rows = blk->d_rows;
+        a.n_rows = n;
+        a.row_stride = blk->row_stride;
+        a.row_offsets = blk->d_row_offsets;
+        a.del = blk->deleted_view();
+        a.n_cand = n;
+        a.top = 1;
+        a.scores = d_scores + (size_t)tile0 * n;
+        a.scores_stride = n;
+        uint32_t grid = 0;
+        QMX_TRY(launch_scan(q, (int)pow2_ceil(nq_tile), SCAN_SCORES, a, &grid));
+    }
+    if (!out_dev) QMX_HIP(hipMemcpyAsync(scores, d_scores, sbytes, hipMemcpyDeviceToHost, q->stream));
+    return check_err_flag(q);
 }
 
 int32_t qmx_score_bytes(qmx_query *q, const void *rows, uint32_t n, uint64_t stride_bytes, float *scores) {
@@ -690,38 +670,7 @@ int32_t qmx_score_bytes(qmx_query *q, const void *rows, uint32_t n, uint64_t str
     d.bq = &bq;
     qmx_segment *tmp = nullptr;
     QMX_TRY(qmx_segment_create(&d, &tmp));
-    int32_t rc = QMX_OK;
-    do {
-        const size_t sbytes = (size_t)q->nq * n * sizeof(float);
-        const bool out_dev = is_device_ptr(scores);
-        float *d_scores = scores;
-        if (!out_dev) {
-            if ((rc = q->scores.reserve(sbytes)) != QMX_OK) break;
-            d_scores = (float *)q->scores.p;
-        }
-        for (uint32_t tile0 = 0; tile0 < q->nq && rc == QMX_OK; tile0 += MAX_QT) {
-            const uint32_t nq_tile = std::min<uint32_t>(MAX_QT, q->nq - tile0);
-            ScanArgs a;
-            fill_args(q, tile0, nq_tile, a);
-            a.rows = tmp->d_rows;
-            a.n_rows = n;
-            a.row_stride = tmp->row_stride;
-            a.row_offsets = tmp->d_row_offsets;
-            a.del = tmp->deleted_view();
-            a.n_cand = n;
-            a.top = 1;
-            a.scores = d_scores + (size_t)tile0 * n;
-            a.scores_stride = n;
-            uint32_t grid = 0;
-            rc = launch_scan(q, (int)pow2_ceil(nq_tile), SCAN_SCORES, a, &grid);
-        }
-        if (rc != QMX_OK) break;
-        if (!out_dev) {
-            hipError_t e = hipMemcpyAsync(scores, d_scores, sbytes, hipMemcpyDeviceToHost, q->stream);
-            if (e != hipSuccess) { rc = hip_status(e, "copy scores", __FILE__, __LINE__); break; }
-        }
-        rc = check_err_flag(q);
-    } while (0);
+    const int32_t rc = score_block(q, tmp, n, scores);
     (void)hipStreamSynchronize(q->stream);
     qmx_segment_destroy(tmp);
     return rc;

@@ -12,7 +12,8 @@ static int32_t split_stage(qmx_query *q, const char *what) {
     hipError_t e = hipStreamSynchronize(q->stream);
     fprintf(stderr, "[qmx] split stage %-28s %s\n", what, e == hipSuccess ? "ok" : hipGetErrorString(e));
     fflush(stderr);
-    return e == hipSuccess ? QMX_OK : QMX_ERR_OTHER;
+    QMX_HIP(e);
+    return QMX_OK;
 }
 
 // the verification pool of a search (kernels.hpp VerifyPool): SPLIT_VCAP entries per query of the batch, shared - behind qmx_query::sp_ver as
@@ -758,33 +759,19 @@ int32_t qmx_merge_topk(int32_t device_id, const qmx_scored_point *lists, const u
     const size_t lbytes = (size_t)n_lists * nq * k * sizeof(qmx_scored_point);
     const size_t cbytes = (size_t)n_lists * nq * sizeof(uint32_t);
     const size_t obytes = (size_t)nq * k * sizeof(qmx_scored_point);
-    DevBuf bl, bc, bo, boc;
-    const qmx_scored_point *d_lists = lists;
-    const uint32_t *d_lc = list_counts;
-    qmx_scored_point *d_out = out;
-    uint32_t *d_oc = out_counts;
-    int32_t rc = QMX_OK;
-    do {
-        if (!is_device_ptr(lists)) {
-            if ((rc = bl.reserve(lbytes)) != QMX_OK) break;
-            if (hipMemcpy(bl.p, lists, lbytes, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_lists = (const qmx_scored_point *)bl.p;
-        }
-        if (list_counts && !is_device_ptr(list_counts)) {
-            if ((rc = bc.reserve(cbytes)) != QMX_OK) break;
-            if (hipMemcpy(bc.p, list_counts, cbytes, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_lc = (const uint32_t *)bc.p;
-        }
-        const bool od = is_device_ptr(out), ocd = is_device_ptr(out_counts);
-        if (!od) { if ((rc = bo.reserve(obytes)) != QMX_OK) break; d_out = (qmx_scored_point *)bo.p; }
-        if (!ocd) { if ((rc = boc.reserve((size_t)nq * 4)) != QMX_OK) break; d_oc = (uint32_t *)boc.p; }
-        if ((rc = launch_merge_points(nullptr, d_lists, d_lc, nullptr, n_lists, nq, k, d_out, d_oc)) != QMX_OK) break;
-        if (!od && hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        if (!ocd && hipMemcpy(out_counts, d_oc, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        if (hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-    } while (0);
-    bl.release(); bc.release(); bo.release(); boc.release();
-    return rc;
+    Staging st;
+    const qmx_scored_point *d_lists = nullptr;
+    const uint32_t *d_lc = nullptr;
+    qmx_scored_point *d_out = nullptr;
+    uint32_t *d_oc = nullptr;
+    QMX_TRY(st.in(lists, lbytes, &d_lists));
+    QMX_TRY(st.in(list_counts, cbytes, &d_lc));
+    QMX_TRY(st.out(out, obytes, &d_out));
+    QMX_TRY(st.out(out_counts, (size_t)nq * 4, &d_oc));
+    QMX_TRY(launch_merge_points(nullptr, d_lists, d_lc, nullptr, n_lists, nq, k, d_out, d_oc));
+    QMX_TRY(st.back());
+    QMX_HIP(hipDeviceSynchronize());
+    return QMX_OK;
 }
 
 int32_t qmx_merge_topk_async(int32_t device_id, void *hip_stream, const qmx_scored_point *lists_dev,

@@ -7,33 +7,6 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 // segment
 // ---------------------------------------------------------------------------------------------
-static void segment_free(qmx_segment *seg) {
-    if (seg->owns_rows && seg->d_rows) (void)hipFree(seg->d_rows);
-    if (seg->d_point_deleted) (void)hipFree(seg->d_point_deleted);
-    if (seg->d_vec_deleted) (void)hipFree(seg->d_vec_deleted);
-    if (seg->d_centroids) (void)hipFree(seg->d_centroids);
-    if (seg->d_pq_pair) (void)hipFree(seg->d_pq_pair);
-    if (seg->d_pq_rot) (void)hipFree(seg->d_pq_rot);
-    if (seg->d_rows_split) (void)hipFree(seg->d_rows_split);
-    if (seg->d_i8_scale) (void)hipFree(seg->d_i8_scale);
-    if (seg->d_i8_stats) (void)hipFree(seg->d_i8_stats);
-    if (seg->d_row_offsets) (void)hipFree(seg->d_row_offsets);
-    if (seg->d_bq_mean) (void)hipFree(seg->d_bq_mean);
-    if (seg->d_bq_stddev) (void)hipFree(seg->d_bq_stddev);
-    if (seg->d_sq_bi) (void)hipFree(seg->d_sq_bi);
-    if (seg->d_tq_sf) (void)hipFree(seg->d_tq_sf);
-    if (seg->d_tq_l2) (void)hipFree(seg->d_tq_l2);
-    if (seg->d_tq_xm) (void)hipFree(seg->d_tq_xm);
-    if (seg->d_tq_shift) (void)hipFree(seg->d_tq_shift);
-    if (seg->d_tq_scale) (void)hipFree(seg->d_tq_scale);
-    if (seg->d_tq_weights) (void)hipFree(seg->d_tq_weights);
-    if (seg->d_tq_tables) (void)hipFree(seg->d_tq_tables);
-    if (seg->d_tq_l1) (void)hipFree(seg->d_tq_l1);
-    if (seg->d_tq_norms) (void)hipFree(seg->d_tq_norms);
-    sparse_segment_free(seg);
-    delete seg;
-}
-
 static int32_t segment_upload(qmx_segment *s, const qmx_segment_desc *desc) {
     const uint64_t src_stride = desc->row_stride_bytes ? desc->row_stride_bytes : s->row_bytes;
     QMX_REQUIRE(src_stride >= s->row_bytes, QMX_ERR_BAD_ARG, "row_stride_bytes %llu < row size %llu",
@@ -51,14 +24,12 @@ static int32_t segment_upload(qmx_segment *s, const qmx_segment_desc *desc) {
         DevBuf tmp;
         if (!on_device && !is_device_ptr(desc->data)) {
             QMX_TRY(tmp.reserve((size_t)s->n * src_stride));
-            hipError_t e = hipMemcpy(tmp.p, desc->data, (size_t)(s->n - 1) * src_stride + s->row_bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { tmp.release(); return hip_status(e, "hipMemcpy(SQ rows)", __FILE__, __LINE__); }
+            QMX_HIP(hipMemcpy(tmp.p, desc->data, (size_t)(s->n - 1) * src_stride + s->row_bytes, hipMemcpyHostToDevice));
             d_src = tmp.p;
         }
-        int32_t rc = launch_sq_split(nullptr, d_src, src_stride, s->n, ad, s->d_rows, s->d_row_offsets);
-        if (rc == QMX_OK && hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-        tmp.release();
-        return rc;
+        QMX_TRY(launch_sq_split(nullptr, d_src, src_stride, s->n, ad, s->d_rows, s->d_row_offsets));
+        QMX_HIP(hipDeviceSynchronize());
+        return QMX_OK;
     }
     if (s->dtype == QMX_DTYPE_TQ) {
         // split [codes][scaling_factor][l2_length] rows into a 16-byte aligned, zero padded code block + the extras columns
@@ -74,15 +45,13 @@ static int32_t segment_upload(qmx_segment *s, const qmx_segment_desc *desc) {
         DevBuf tmp;
         if (!on_device && !is_device_ptr(desc->data)) {
             QMX_TRY(tmp.reserve((size_t)s->n * src_stride));
-            hipError_t e = hipMemcpy(tmp.p, desc->data, (size_t)(s->n - 1) * src_stride + s->row_bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { tmp.release(); return hip_status(e, "hipMemcpy(TQ rows)", __FILE__, __LINE__); }
+            QMX_HIP(hipMemcpy(tmp.p, desc->data, (size_t)(s->n - 1) * src_stride + s->row_bytes, hipMemcpyHostToDevice));
             d_src = tmp.p;
         }
-        int32_t rc = launch_tq_split(nullptr, d_src, src_stride, s->n, s->tq_code_bytes, (uint32_t)s->row_stride, has_l2 ? 1 : 0, s->d_rows, s->d_tq_sf,
-                                     s->d_tq_l2, s->d_tq_xm);
-        if (rc == QMX_OK && hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-        tmp.release();
-        return rc;
+        QMX_TRY(launch_tq_split(nullptr, d_src, src_stride, s->n, s->tq_code_bytes, (uint32_t)s->row_stride, has_l2 ? 1 : 0, s->d_rows, s->d_tq_sf,
+                                s->d_tq_l2, s->d_tq_xm));
+        QMX_HIP(hipDeviceSynchronize());
+        return QMX_OK;
     }
     if (on_device) {
         s->d_rows = const_cast<void *>(desc->data);
@@ -119,8 +88,7 @@ static int32_t segment_pq_rot(qmx_segment *s) {
     if (launch_pq_rotate(nullptr, s->d_rows, s->row_stride, s->n, s->pq_m, s->d_pq_rot) != QMX_OK || hipDeviceSynchronize() != hipSuccess) {
         (void)hipGetLastError();
         ::qmx::clear_stale_error();
-        (void)hipFree(s->d_pq_rot);
-        s->d_pq_rot = nullptr;
+        dev_free(s->d_pq_rot);
     }
     return QMX_OK;
 }
@@ -129,12 +97,9 @@ static int32_t segment_pq_rot(qmx_segment *s) {
 // the verification band (4.5 ms per 30 GB; nothing for other storages)
 // ---- derived copies of an f32 dot / cosine block (scan_split.hip): what the prefilters stream instead of the f32 rows ----
 static void segment_drop_copy(qmx_segment *s) {
-    if (s->d_rows_split) (void)hipFree(s->d_rows_split);
-    if (s->d_i8_scale) (void)hipFree(s->d_i8_scale);
-    if (s->d_i8_stats) (void)hipFree(s->d_i8_stats);
-    s->d_rows_split = nullptr;
-    s->d_i8_scale = nullptr;
-    s->d_i8_stats = nullptr;
+    dev_free(s->d_rows_split);
+    dev_free(s->d_i8_scale);
+    dev_free(s->d_i8_stats);
     s->split_i8 = false;
     s->split_half = false;
     s->copy_bytes = 0;
@@ -144,13 +109,14 @@ static bool segment_i8_eligible(const qmx_segment *s) { return s->split_stats &&
 static bool segment_f16_eligible(const qmx_segment *s) { return s->split_stats && s->dim % 128 == 0 && split_fallback_qt(s->dim) != 0; }
 // the int8 copy: column maxima / sums of squares (one pass), the scales (host: split_i8_choose_scales), the worst row's code norms under them (a second
 // pass), the codes (a third).  false: out of memory, or an element that is not finite - no copy is left behind
-static bool segment_build_i8(qmx_segment *s) {
-    uint32_t *d_colmax = nullptr;
-    float *d_colsq = nullptr;
+static bool i8_copy_passes(qmx_segment *s) {
     uint32_t h[4] = {0, 0, 1, 0};
     std::vector<float> colmax(s->dim), colsq(s->dim), scale(s->dim);
-    bool ok = hipMalloc((void **)&d_colmax, (size_t)s->dim * 4) == hipSuccess && hipMalloc((void **)&d_colsq, (size_t)s->dim * 4) == hipSuccess &&
+    DevBuf bcolmax, bcolsq;      // (filled by bare hipMalloc: a failure here is no error and leaves no error text)
+    bool ok = hipMalloc(&bcolmax.p, (size_t)s->dim * 4) == hipSuccess && hipMalloc(&bcolsq.p, (size_t)s->dim * 4) == hipSuccess &&
               hipMalloc((void **)&s->d_i8_scale, (size_t)s->dim * 4) == hipSuccess && hipMalloc((void **)&s->d_i8_stats, 16) == hipSuccess;
+    uint32_t *d_colmax = (uint32_t *)bcolmax.p;
+    float *d_colsq = (float *)bcolsq.p;
     if (ok) ok = launch_split_i8_colstats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, d_colmax, d_colsq) == QMX_OK &&
                  hipMemcpy(colmax.data(), d_colmax, (size_t)s->dim * 4, hipMemcpyDeviceToHost) == hipSuccess &&
                  hipMemcpy(colsq.data(), d_colsq, (size_t)s->dim * 4, hipMemcpyDeviceToHost) == hipSuccess;
@@ -163,8 +129,10 @@ static bool segment_build_i8(qmx_segment *s) {
     if (ok) ok = hipMalloc(&s->d_rows_split, split_i8_copy_bytes(s->n, s->dim)) == hipSuccess;
     if (ok) ok = launch_split_i8_copy(nullptr, s->d_rows, s->row_stride, s->n, s->dim, s->d_i8_scale, s->d_rows_split) == QMX_OK &&
                  hipDeviceSynchronize() == hipSuccess;
-    if (d_colmax) (void)hipFree(d_colmax);
-    if (d_colsq) (void)hipFree(d_colsq);
+    return ok;
+}
+static bool segment_build_i8(qmx_segment *s) {
+    const bool ok = i8_copy_passes(s);
     (void)hipGetLastError();
     if (!ok) {
         segment_drop_copy(s);
@@ -204,10 +172,15 @@ static int32_t auto_trial(qmx_segment *s, const float *d_trial_queries, float *m
     float best = 3.0e38f;
     for (int rep = 0; rep < 3 && rc == QMX_OK; ++rep) {            // (the first run pays the scratch allocations: the best of three is the step)
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = QMX_ERR_OTHER;
-        if (rc == QMX_OK && hipEventRecord(e0, q->stream) != hipSuccess) rc = QMX_ERR_OTHER;
+        auto hip = [&](hipError_t e, const char *what) {
+            if (e != hipSuccess && rc == QMX_OK) rc = hip_status(e, what, __FILE__, __LINE__);
+        };
+        hip(hipEventCreate(&e0), "hipEventCreate");
+        hip(hipEventCreate(&e1), "hipEventCreate");
+        if (rc == QMX_OK) hip(hipEventRecord(e0, q->stream), "hipEventRecord");
         if (rc == QMX_OK) rc = qmx_search_topk(q, AUTO_TRIAL_TOP, nullptr, 0, out.data(), counts.data(), nullptr, c_out);
-        if (rc == QMX_OK && (hipEventRecord(e1, q->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) rc = QMX_ERR_OTHER;
+        if (rc == QMX_OK) hip(hipEventRecord(e1, q->stream), "hipEventRecord");
+        if (rc == QMX_OK) hip(hipEventSynchronize(e1), "hipEventSynchronize");
         float ms = 0.0f;
         if (rc == QMX_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms < best) best = ms;
         if (e0) (void)hipEventDestroy(e0);
@@ -218,18 +191,8 @@ static int32_t auto_trial(qmx_segment *s, const float *d_trial_queries, float *m
     *ms_out = (rc == QMX_OK && best < 3.0e38f) ? best : 0.0f;          // (a trial that failed measured nothing: 0 in qmx_segment_get_info, not a sentinel)
     return rc;
 }
-static int32_t segment_auto_copy(qmx_segment *s) {
-    s->auto_choice = true;
-    if (!segment_i8_eligible(s) || !segment_build_i8(s)) {
-        if (segment_f16_eligible(s)) QMX_TRY(segment_build_f16(s, true));
-        return QMX_OK;
-    }
-    // the trial batch: rows n / 256, 3 n / 256, ... (stored rows are preprocessed: the query path normalises them again - a no-op up to round-off)
-    float *d_tq = nullptr;
-    if (hipMalloc((void **)&d_tq, (size_t)AUTO_TRIAL_QUERIES * s->dim * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return QMX_OK;                                                  // (no room for a trial: the int8 copy stays, its fallback is exact whatever happens)
-    }
+// the int8 copy is built: try it on the trial batch `d_tq` (room for AUTO_TRIAL_QUERIES rows) and, where it is not plainly good, against the half copy
+static int32_t auto_choose(qmx_segment *s, float *d_tq) {
     const uint64_t step = s->n / AUTO_TRIAL_QUERIES;
     bool ok = true;
     for (uint32_t i = 0; i < AUTO_TRIAL_QUERIES && ok; ++i)
@@ -237,8 +200,8 @@ static int32_t segment_auto_copy(qmx_segment *s) {
                             hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
     ok = ok && hipDeviceSynchronize() == hipSuccess;
     qmx_counters c_i8{}, c_half{};
-    int32_t rc = ok ? auto_trial(s, d_tq, &s->auto_i8_ms, &c_i8) : QMX_ERR_OTHER;
-    if (rc == QMX_OK) {
+    int32_t rc = QMX_OK;
+    if (ok && auto_trial(s, d_tq, &s->auto_i8_ms, &c_i8) == QMX_OK) {
         s->auto_i8_verified = (float)c_i8.verified_rows / (float)AUTO_TRIAL_QUERIES;
         s->auto_i8_fallback = c_i8.fallback_queries;
         const bool easy = c_i8.fallback_queries == 0 && c_i8.verified_rows <= (uint64_t)AUTO_EASY_VERIFIED * AUTO_TRIAL_QUERIES;
@@ -264,10 +227,26 @@ static int32_t segment_auto_copy(qmx_segment *s) {
             }
         }
     } else {
-        rc = QMX_OK;                                                    // (a trial that could not run decides nothing: the int8 copy stays)
-        ::qmx::clear_stale_error();
+        ::qmx::clear_stale_error();                                     // (a trial that could not run decides nothing: the int8 copy stays)
     }
-    (void)hipFree(d_tq);
+    return rc;
+}
+static int32_t segment_auto_copy(qmx_segment *s) {
+    s->auto_choice = true;
+    if (!segment_i8_eligible(s) || !segment_build_i8(s)) {
+        if (segment_f16_eligible(s)) QMX_TRY(segment_build_f16(s, true));
+        return QMX_OK;
+    }
+    // the trial batch: rows n / 256, 3 n / 256, ... (stored rows are preprocessed: the query path normalises them again - a no-op up to round-off)
+    int32_t rc;
+    {
+        DevBuf tq;
+        if (hipMalloc(&tq.p, (size_t)AUTO_TRIAL_QUERIES * s->dim * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return QMX_OK;                                              // (no room for a trial: the int8 copy stays, its fallback is exact whatever happens)
+        }
+        rc = auto_choose(s, (float *)tq.p);
+    }
     (void)hipGetLastError();
     return rc;
 }
@@ -276,15 +255,14 @@ static int32_t segment_split_stats(qmx_segment *s) {
     if (s->dtype != QMX_DTYPE_F32 || (s->distance != QMX_DISTANCE_DOT && s->distance != QMX_DISTANCE_COSINE) || s->dim % 32 != 0 ||
         s->n < (1u << 18) || !s->fast_layout())
         return QMX_OK;
-    uint32_t *d_stats = nullptr;
-    QMX_HIP(hipMalloc((void **)&d_stats, 8));
-    int32_t rc = QMX_OK;
     uint32_t h[2] = {0, 0};
-    if (hipMemset(d_stats, 0, 8) != hipSuccess) rc = QMX_ERR_OTHER;
-    if (rc == QMX_OK) rc = launch_split_row_stats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, d_stats);
-    if (rc == QMX_OK && hipMemcpy(h, d_stats, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = QMX_ERR_OTHER;
-    (void)hipFree(d_stats);
-    if (rc != QMX_OK) return rc;
+    {
+        DevBuf stats;
+        QMX_TRY(stats.reserve(8));
+        QMX_HIP(hipMemset(stats.p, 0, 8));
+        QMX_TRY(launch_split_row_stats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, (uint32_t *)stats.p));
+        QMX_HIP(hipMemcpy(h, stats.p, 8, hipMemcpyDeviceToHost));
+    }
     memcpy(&s->row_maxabs, &h[0], 4);
     float mss;
     memcpy(&mss, &h[1], 4);
@@ -308,15 +286,12 @@ static int32_t segment_sq_stats(qmx_segment *s) {
         s->d_sq_bi = nullptr;
         return QMX_OK;
     }
-    uint32_t *d_stats = nullptr;
-    QMX_HIP(hipMalloc((void **)&d_stats, 8));
-    int32_t rc = QMX_OK;
+    DevBuf stats;
     uint32_t h[2] = {0u, 0u};
-    if (hipMemset(d_stats, 0, 8) != hipSuccess) rc = QMX_ERR_OTHER;
-    if (rc == QMX_OK) rc = launch_sqw_stats(nullptr, s->d_row_offsets, s->n, s->sq.multiplier, s->d_sq_bi, d_stats);
-    if (rc == QMX_OK && hipMemcpy(h, d_stats, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = QMX_ERR_OTHER;
-    (void)hipFree(d_stats);
-    if (rc != QMX_OK) return rc;
+    QMX_TRY(stats.reserve(8));
+    QMX_HIP(hipMemset(stats.p, 0, 8));
+    QMX_TRY(launch_sqw_stats(nullptr, s->d_row_offsets, s->n, s->sq.multiplier, s->d_sq_bi, (uint32_t *)stats.p));
+    QMX_HIP(hipMemcpy(h, stats.p, 8, hipMemcpyDeviceToHost));
     memcpy(&s->sq_off_absmax, &h[0], 4);
     s->sq_wide = h[1] == 0 && s->sq_off_absmax < 3.0e38f;
     return QMX_OK;
@@ -325,15 +300,12 @@ static int32_t segment_sq_stats(qmx_segment *s) {
 // 4-bit TurboQuant blocks large enough for the 128-query pass (scan_tq4w.hip): the ranges of the extras columns its integer reject bound rests on
 static int32_t segment_tq_stats(qmx_segment *s) {
     if (s->dtype != QMX_DTYPE_TQ || s->tq_value_bits != 4 || s->n < (1u << 18) || s->d_tq_l1 || !s->d_tq_sf) return QMX_OK;
-    uint32_t *d_stats = nullptr;
-    QMX_HIP(hipMalloc((void **)&d_stats, 32));
-    int32_t rc = QMX_OK;
+    DevBuf stats;
     uint32_t h[8] = {0x7F800000u, 0u, 0x7F800000u, 0u, 0u, 0u, 0u, 0u};
-    if (hipMemcpy(d_stats, h, 32, hipMemcpyHostToDevice) != hipSuccess) rc = QMX_ERR_OTHER;
-    if (rc == QMX_OK) rc = launch_tq4w_stats(nullptr, s->d_tq_sf, s->d_tq_l2, s->d_rows, s->row_stride, (uint32_t)s->row_stride, s->n, d_stats);
-    if (rc == QMX_OK && hipMemcpy(h, d_stats, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = QMX_ERR_OTHER;
-    (void)hipFree(d_stats);
-    if (rc != QMX_OK) return rc;
+    QMX_TRY(stats.reserve(32));
+    QMX_HIP(hipMemcpy(stats.p, h, 32, hipMemcpyHostToDevice));
+    QMX_TRY(launch_tq4w_stats(nullptr, s->d_tq_sf, s->d_tq_l2, s->d_rows, s->row_stride, (uint32_t)s->row_stride, s->n, (uint32_t *)stats.p));
+    QMX_HIP(hipMemcpy(h, stats.p, 32, hipMemcpyDeviceToHost));
     memcpy(&s->tq_sf_min, &h[0], 4);
     memcpy(&s->tq_sf_max, &h[1], 4);
     memcpy(&s->tq_l2_min, &h[2], 4);
@@ -483,42 +455,26 @@ int32_t qmx_tq_fit_plus(int32_t device_id, uint32_t distance, uint32_t dim, cons
     memset(&d, 0, sizeof(d));
     d.dtype = QMX_DTYPE_TQ; d.distance = distance; d.dim = dim; d.tq = &pre; d.device_id = device_id;
     tmp.device = device_id; tmp.dtype = QMX_DTYPE_TQ; tmp.distance = distance; tmp.dim = dim;
-    int32_t rc = tq_segment_setup(&tmp, &d);
-    DevBuf bin, brot, bsh, bsc;
-    do {
-        if (rc != QMX_OK) break;
-        const uint32_t pd = tmp.tq_padded_dim, n = (uint32_t)n_sample;
-        // the outermost centroid and the two quantiles Phi(-+c_outer) (:172-184, quantile.rs:155-156)
-        const float c_outer = tmp.tq_value_bits == 4 ? 2.733f : tmp.tq_value_bits == 2 ? 1.510f : 0.7978846f;
-        const double p_outer = tq_std_normal_cdf((double)c_outer);
-        float qp = (float)(2.0 * p_outer - 1.0);
-        qp = qp < 0.0f ? 0.0f : qp > 0.99999f ? 0.99999f : qp;
-        const double min_q = (1.0 - (double)qp) / 2.0, max_q = 1.0 - min_q;
-        if ((rc = brot.reserve((size_t)std::max<uint32_t>(n, 1) * pd * 8)) != QMX_OK) break;
-        if ((rc = bsh.reserve((size_t)pd * 4)) != QMX_OK || (rc = bsc.reserve((size_t)pd * 4)) != QMX_OK) break;
-        const float *d_in = sample;
-        if (n && !is_device_ptr(sample)) {
-            if ((rc = bin.reserve((size_t)n * dim * 4)) != QMX_OK) break;
-            if (hipMemcpy(bin.p, sample, (size_t)n * dim * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_in = (const float *)bin.p;
-        }
-        if (n && (rc = launch_tq_rotate(nullptr, d_in, n, tq_rotation(&tmp), (double *)brot.p)) != QMX_OK) break;
-        if ((rc = launch_tq_plus_fit(nullptr, (double *)brot.p, n, pd, distance, min_q, max_q, c_outer, (float *)bsh.p, (float *)bsc.p)) != QMX_OK) break;
-        if (hipDeviceSynchronize() != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        if (hipMemcpy(shift_out, bsh.p, (size_t)pd * 4, hipMemcpyDefault) != hipSuccess || hipMemcpy(scale_out, bsc.p, (size_t)pd * 4, hipMemcpyDefault) != hipSuccess) {
-            rc = QMX_ERR_OTHER;
-            break;
-        }
-    } while (0);
-    bin.release(); brot.release(); bsh.release(); bsc.release();
-    if (tmp.d_tq_tables) (void)hipFree(tmp.d_tq_tables);
-    if (tmp.d_tq_l1) (void)hipFree(tmp.d_tq_l1);
-    if (tmp.d_tq_norms) (void)hipFree(tmp.d_tq_norms);
-    if (tmp.d_tq_shift) (void)hipFree(tmp.d_tq_shift);
-    if (tmp.d_tq_scale) (void)hipFree(tmp.d_tq_scale);
-    if (tmp.d_tq_weights) (void)hipFree(tmp.d_tq_weights);
-    if (rc == QMX_ERR_OTHER) set_error("qmx_tq_fit_plus: HIP error");
-    return rc;
+    QMX_TRY(tq_segment_setup(&tmp, &d));
+    const uint32_t pd = tmp.tq_padded_dim, n = (uint32_t)n_sample;
+    // the outermost centroid and the two quantiles Phi(-+c_outer) (:172-184, quantile.rs:155-156)
+    const float c_outer = tmp.tq_value_bits == 4 ? 2.733f : tmp.tq_value_bits == 2 ? 1.510f : 0.7978846f;
+    const double p_outer = tq_std_normal_cdf((double)c_outer);
+    float qp = (float)(2.0 * p_outer - 1.0);
+    qp = qp < 0.0f ? 0.0f : qp > 0.99999f ? 0.99999f : qp;
+    const double min_q = (1.0 - (double)qp) / 2.0, max_q = 1.0 - min_q;
+    DevBuf brot;
+    Staging st;
+    const float *d_in = nullptr;
+    float *d_shift = nullptr, *d_scale = nullptr;
+    QMX_TRY(brot.reserve((size_t)std::max<uint32_t>(n, 1) * pd * 8));
+    QMX_TRY(st.out(shift_out, (size_t)pd * 4, &d_shift));
+    QMX_TRY(st.out(scale_out, (size_t)pd * 4, &d_scale));
+    QMX_TRY(st.in(sample, (size_t)n * dim * 4, &d_in));
+    if (n) QMX_TRY(launch_tq_rotate(nullptr, d_in, n, tq_rotation(&tmp), (double *)brot.p));
+    QMX_TRY(launch_tq_plus_fit(nullptr, (double *)brot.p, n, pd, distance, min_q, max_q, c_outer, d_shift, d_scale));
+    QMX_HIP(hipDeviceSynchronize());
+    return st.back();
 }
 
 int32_t qmx_tq_encode(int32_t device_id, uint32_t distance, uint32_t dim, const qmx_tq_params *params, const float *vectors, uint64_t n, void *out_rows) {
@@ -531,39 +487,29 @@ int32_t qmx_tq_encode(int32_t device_id, uint32_t distance, uint32_t dim, const 
     memset(&d, 0, sizeof(d));
     d.dtype = QMX_DTYPE_TQ; d.distance = distance; d.dim = dim; d.tq = params; d.device_id = device_id;
     tmp.device = device_id; tmp.dtype = QMX_DTYPE_TQ; tmp.distance = distance; tmp.dim = dim;
-    int32_t rc = tq_segment_setup(&tmp, &d);
-    DevBuf bin, brot, bout;
-    do {
-        if (rc != QMX_OK) break;
-        const uint32_t row_bytes = (uint32_t)tmp.row_bytes;
-        const uint64_t CH = 65536;         // vectors per pass (the f64 scratch is padded_dim * 8 bytes per vector)
-        const bool in_dev = is_device_ptr(vectors), out_dev = is_device_ptr(out_rows);
-        if ((rc = brot.reserve((size_t)std::min<uint64_t>(n, CH) * tmp.tq_padded_dim * 8)) != QMX_OK) break;
-        if (!in_dev && (rc = bin.reserve((size_t)std::min<uint64_t>(n, CH) * dim * 4)) != QMX_OK) break;
-        if (!out_dev && (rc = bout.reserve((size_t)std::min<uint64_t>(n, CH) * row_bytes)) != QMX_OK) break;
-        for (uint64_t r0 = 0; r0 < n && rc == QMX_OK; r0 += CH) {
-            const uint32_t cnt = (uint32_t)std::min<uint64_t>(CH, n - r0);
-            const float *d_in = vectors + r0 * dim;
-            if (!in_dev) {
-                if (hipMemcpy(bin.p, vectors + r0 * dim, (size_t)cnt * dim * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-                d_in = (const float *)bin.p;
-            }
-            void *d_out = out_dev ? (void *)((char *)out_rows + r0 * row_bytes) : bout.p;
-            if ((rc = launch_tq_rotate(nullptr, d_in, cnt, tq_rotation(&tmp), (double *)brot.p)) != QMX_OK) break;
-            if ((rc = launch_tq_quantize(nullptr, (double *)brot.p, cnt, tmp.tq_padded_dim, tmp.tq_value_bits, distance, d_out, row_bytes, tmp.d_tq_shift,
-                                         tmp.d_tq_scale)) != QMX_OK) break;
-            if (hipDeviceSynchronize() != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            if (!out_dev && hipMemcpy((char *)out_rows + r0 * row_bytes, bout.p, (size_t)cnt * row_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
+    QMX_TRY(tq_segment_setup(&tmp, &d));
+    const uint32_t row_bytes = (uint32_t)tmp.row_bytes;
+    const uint64_t CH = 65536;         // vectors per pass (the f64 scratch is padded_dim * 8 bytes per vector)
+    const bool in_dev = is_device_ptr(vectors), out_dev = is_device_ptr(out_rows);
+    DevBuf bin, brot, bout;            // (one pass's worth each, reused by every pass: not a Staging)
+    QMX_TRY(brot.reserve((size_t)std::min<uint64_t>(n, CH) * tmp.tq_padded_dim * 8));
+    if (!in_dev) QMX_TRY(bin.reserve((size_t)std::min<uint64_t>(n, CH) * dim * 4));
+    if (!out_dev) QMX_TRY(bout.reserve((size_t)std::min<uint64_t>(n, CH) * row_bytes));
+    for (uint64_t r0 = 0; r0 < n; r0 += CH) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(CH, n - r0);
+        const float *d_in = vectors + r0 * dim;
+        if (!in_dev) {
+            QMX_HIP(hipMemcpy(bin.p, vectors + r0 * dim, (size_t)cnt * dim * 4, hipMemcpyHostToDevice));
+            d_in = (const float *)bin.p;
         }
-    } while (0);
-    bin.release(); brot.release(); bout.release();
-    if (tmp.d_tq_tables) (void)hipFree(tmp.d_tq_tables);
-    if (tmp.d_tq_l1) (void)hipFree(tmp.d_tq_l1);
-    if (tmp.d_tq_norms) (void)hipFree(tmp.d_tq_norms);
-    if (tmp.d_tq_shift) (void)hipFree(tmp.d_tq_shift);
-    if (tmp.d_tq_scale) (void)hipFree(tmp.d_tq_scale);
-    if (tmp.d_tq_weights) (void)hipFree(tmp.d_tq_weights);
-    return rc;
+        void *d_out = out_dev ? (void *)((char *)out_rows + r0 * row_bytes) : bout.p;
+        QMX_TRY(launch_tq_rotate(nullptr, d_in, cnt, tq_rotation(&tmp), (double *)brot.p));
+        QMX_TRY(launch_tq_quantize(nullptr, (double *)brot.p, cnt, tmp.tq_padded_dim, tmp.tq_value_bits, distance, d_out, row_bytes, tmp.d_tq_shift,
+                                   tmp.d_tq_scale));
+        QMX_HIP(hipDeviceSynchronize());
+        if (!out_dev) QMX_HIP(hipMemcpy((char *)out_rows + r0 * row_bytes, bout.p, (size_t)cnt * row_bytes, hipMemcpyDeviceToHost));
+    }
+    return QMX_OK;
 }
 
 int32_t qmx_segment_create(const qmx_segment_desc *desc, qmx_segment **out) {
@@ -625,7 +571,7 @@ int32_t qmx_segment_create(const qmx_segment_desc *desc, qmx_segment **out) {
                 e = hipMalloc((void **)&s->d_pq_pair, pbytes);
                 if (e != hipSuccess) { rc = hip_status(e, "PQ pair table", __FILE__, __LINE__); break; }
                 rc = launch_pq_pair_table(nullptr, desc->distance, desc->dim, s->pq, s->d_centroids, s->d_pq_pair);
-                if (rc == QMX_OK && hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
+                if (rc == QMX_OK && (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_status(e, "PQ pair table", __FILE__, __LINE__);
             }
             break;
         }
@@ -660,7 +606,7 @@ int32_t qmx_segment_create(const qmx_segment_desc *desc, qmx_segment **out) {
     if (rc == QMX_OK) rc = segment_tq_stats(s);
     if (rc == QMX_OK) rc = segment_sq_stats(s);
     if (rc != QMX_OK) {
-        segment_free(s);
+        delete s;
         return rc;
     }
     *out = s;
@@ -706,7 +652,8 @@ int32_t qmx_segment_create_from_files(const qmx_segment_desc *desc, const char *
     FILE *f = fopen(vectors_path, "rb");
     QMX_REQUIRE(f, QMX_ERR_BAD_ARG, "cannot open %s", vectors_path);
     int32_t rc = QMX_OK;
-    void *d_tmp = nullptr, *h_pin = nullptr;
+    DevBuf tmp;
+    void *h_pin = nullptr;
     do {
         if (fseek(f, 0, SEEK_END) != 0) { set_error("cannot seek %s", vectors_path); rc = QMX_ERR_OTHER; break; }
         const uint64_t len = (uint64_t)ftell(f);
@@ -723,25 +670,25 @@ int32_t qmx_segment_create_from_files(const qmx_segment_desc *desc, const char *
         const uint64_t n = desc->n ? desc->n : in_file;
         if (n > in_file) { set_error("%s holds %llu rows, %llu asked for", vectors_path, (unsigned long long)in_file, (unsigned long long)n); rc = QMX_ERR_BAD_ARG; break; }
         const size_t total = (size_t)n * row_bytes;
-        if (hipMalloc(&d_tmp, std::max<size_t>(total, 16)) != hipSuccess) { set_error("device allocation of %zu bytes failed", total); rc = QMX_ERR_OUT_OF_MEMORY; break; }
+        if (hipMalloc(&tmp.p, std::max<size_t>(total, 16)) != hipSuccess) { set_error("device allocation of %zu bytes failed", total); rc = QMX_ERR_OUT_OF_MEMORY; break; }
         const size_t chunk = 64u << 20;
         if (hipHostMalloc(&h_pin, chunk, hipHostMallocDefault) != hipSuccess) { set_error("pinned staging allocation failed"); rc = QMX_ERR_OUT_OF_MEMORY; break; }
         for (size_t off = 0; off < total && rc == QMX_OK; off += chunk) {
             const size_t want = std::min(chunk, total - off);
             if (fread(h_pin, 1, want, f) != want) { set_error("short read from %s", vectors_path); rc = QMX_ERR_OTHER; break; }
-            if (hipMemcpy((char *)d_tmp + off, h_pin, want, hipMemcpyHostToDevice) != hipSuccess) { set_error("upload failed"); rc = QMX_ERR_OTHER; break; }
+            const hipError_t e = hipMemcpy((char *)tmp.p + off, h_pin, want, hipMemcpyHostToDevice);
+            if (e != hipSuccess) rc = hip_status(e, "upload of the vectors file", __FILE__, __LINE__);
         }
         if (rc != QMX_OK) break;
         qmx_segment_desc d = *desc;
         d.n = n;
-        d.data = d_tmp;
+        d.data = tmp.p;
         d.row_stride_bytes = 0;
         d.flags = desc->flags & ~QMX_SEG_DATA_ON_DEVICE;          // copied (and re-packed to the 16-byte row pitch) into the segment's own block
         rc = qmx_segment_create(&d, out);
     } while (0);
     fclose(f);
     if (h_pin) (void)hipHostFree(h_pin);
-    if (d_tmp) (void)hipFree(d_tmp);
     if (rc != QMX_OK || !deleted_path) return rc;
     // the "drop" file: header, padding to align_of::<usize>() = 8, then the bit words
     FILE *g = fopen(deleted_path, "rb");
@@ -783,25 +730,25 @@ int32_t qmx_segment_create_chunked(const qmx_segment_desc *desc, const void *con
         QMX_TRY(file_row_bytes(desc, &row_bytes, &header));
         const uint64_t src_stride = desc->row_stride_bytes ? desc->row_stride_bytes : row_bytes;
         QMX_REQUIRE(src_stride >= row_bytes, QMX_ERR_BAD_ARG, "row_stride_bytes %llu < row size %llu", (unsigned long long)src_stride, (unsigned long long)row_bytes);
-        void *d_tmp = nullptr;
-        QMX_HIP(hipMalloc(&d_tmp, (size_t)std::max<uint64_t>(1, desc->n) * row_bytes));
+        DevBuf tmp;
+        QMX_HIP(hipMalloc(&tmp.p, (size_t)std::max<uint64_t>(1, desc->n) * row_bytes));
+        void *const d_tmp = tmp.p;
         hipError_t e = hipSuccess;
         for (uint32_t c = 0; e == hipSuccess && c < n_chunks && (uint64_t)c * rows_per_chunk < desc->n; ++c) {
             const uint64_t row0 = (uint64_t)c * rows_per_chunk, cnt = std::min<uint64_t>(rows_per_chunk, desc->n - row0);
             if (!chunks[c]) { e = hipErrorInvalidValue; break; }
             e = hipMemcpy2D((char *)d_tmp + row0 * row_bytes, row_bytes, chunks[c], src_stride, row_bytes, cnt, hipMemcpyDefault);
         }
-        if (e != hipSuccess) {
-            (void)hipFree(d_tmp);
-            return hip_status(e, "chunk upload", __FILE__, __LINE__);
-        }
+        if (e != hipSuccess) return hip_status(e, "chunk upload", __FILE__, __LINE__);
         qmx_segment_desc d2 = *desc;
         d2.data = d_tmp;
         d2.row_stride_bytes = row_bytes;
         d2.flags |= QMX_SEG_DATA_ON_DEVICE;
         const int32_t rc = qmx_segment_create(&d2, out);
-        if (rc != QMX_OK || !*out || (*out)->d_rows != d_tmp) (void)hipFree(d_tmp);     // (split into the segment's own blocks, or refused)
-        else (*out)->owns_rows = true;                                                   // PQ / BQ: the gathered block IS the segment's block
+        if (rc == QMX_OK && *out && (*out)->d_rows == d_tmp) {      // PQ / BQ: the gathered block IS the segment's block
+            (void)tmp.detach();
+            (*out)->owns_rows = true;
+        }                                                           // (else: split into the segment's own blocks, or refused)
         if (rc == QMX_OK && *out) (*out)->flags &= ~QMX_SEG_DATA_ON_DEVICE;
         return rc;
     }
@@ -825,7 +772,7 @@ int32_t qmx_segment_create_chunked(const qmx_segment_desc *desc, const void *con
     }
     if (e != hipSuccess) {
         const int32_t rc = hip_status(e, "chunk upload", __FILE__, __LINE__);
-        segment_free(s);
+        delete s;
         return rc;
     }
     *out = s;
@@ -835,7 +782,7 @@ int32_t qmx_segment_create_chunked(const qmx_segment_desc *desc, const void *con
 int32_t qmx_segment_destroy(qmx_segment *seg) {
     if (!seg) return QMX_OK;
     (void)hipSetDevice(seg->device);
-    segment_free(seg);
+    delete seg;
     return QMX_OK;
 }
 
@@ -844,13 +791,10 @@ int32_t qmx_segment_set_deleted(qmx_segment *seg, const uint64_t *point_deleted,
     QMX_REQUIRE(seg, QMX_ERR_BAD_ARG, "NULL segment");
     QMX_HIP(hipSetDevice(seg->device));
     auto upload = [&](const uint64_t *src, uint64_t nbits, uint64_t **dst, uint64_t *dst_bits) -> int32_t {
-        if (*dst) (void)hipFree(*dst);
-        *dst = nullptr;
+        dev_free(*dst);
         *dst_bits = 0;
         if (!src) return QMX_OK;
-        const size_t words = (size_t)((nbits + 63) / 64);
-        QMX_HIP(hipMalloc((void **)dst, std::max<size_t>(words, 1) * 8));
-        if (words) QMX_HIP(hipMemcpy(*dst, src, words * 8, hipMemcpyDefault));
+        QMX_TRY(dev_upload(dst, src, (size_t)((nbits + 63) / 64)));
         *dst_bits = nbits;
         return QMX_OK;
     };
@@ -922,26 +866,16 @@ int32_t qmx_preprocess_f32(int32_t device_id, uint32_t distance, const float *in
     QMX_TRY(check_device(device_id, nullptr));
     const size_t bytes = (size_t)n * dim * sizeof(float);
     if (bytes == 0) return QMX_OK;
-    const bool in_dev = is_device_ptr(in), out_dev = is_device_ptr(out);
-    float *d_in = const_cast<float *>(in), *d_out = out;
-    DevBuf bin, bout;
-    if (!in_dev) {
-        QMX_TRY(bin.reserve(bytes));
-        QMX_HIP(hipMemcpy(bin.p, in, bytes, hipMemcpyHostToDevice));
-        d_in = (float *)bin.p;
-    }
-    if (!out_dev) {
-        QMX_TRY(bout.reserve(bytes));
-        d_out = (float *)bout.p;
-    }
-    int32_t rc = QMX_OK;
-    if (distance == QMX_DISTANCE_COSINE) rc = launch_cosine_preprocess_f32(nullptr, d_in, d_out, n, dim);
-    else if (d_out != d_in) rc = hipMemcpy(d_out, d_in, bytes, hipMemcpyDeviceToDevice) == hipSuccess ? QMX_OK : QMX_ERR_OTHER;
-    if (rc == QMX_OK && !out_dev) rc = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) == hipSuccess ? QMX_OK : QMX_ERR_OTHER;
-    if (rc == QMX_OK && hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-    bin.release();
-    bout.release();
-    return rc;
+    Staging st;
+    const float *d_in = nullptr;
+    float *d_out = nullptr;
+    QMX_TRY(st.in(in, bytes, &d_in));
+    QMX_TRY(st.out(out, bytes, &d_out));
+    if (distance == QMX_DISTANCE_COSINE) QMX_TRY(launch_cosine_preprocess_f32(nullptr, d_in, d_out, n, dim));
+    else if (d_out != d_in) QMX_HIP(hipMemcpy(d_out, d_in, bytes, hipMemcpyDeviceToDevice));
+    QMX_TRY(st.back());
+    QMX_HIP(hipDeviceSynchronize());
+    return QMX_OK;
 }
 
 int32_t qmx_cast_f32(int32_t device_id, uint32_t dst_dtype, const float *in, uint64_t count, void *out) {
@@ -949,26 +883,15 @@ int32_t qmx_cast_f32(int32_t device_id, uint32_t dst_dtype, const float *in, uin
     QMX_REQUIRE(dst_dtype <= QMX_DTYPE_U8, QMX_ERR_BAD_ARG, "bad dtype");
     QMX_TRY(check_device(device_id, nullptr));
     if (count == 0) return QMX_OK;
-    const size_t in_bytes = (size_t)count * 4, out_bytes = (size_t)count * elem_bytes(dst_dtype);
-    const bool in_dev = is_device_ptr(in), out_dev = is_device_ptr(out);
-    DevBuf bin, bout;
-    const float *d_in = in;
-    void *d_out = out;
-    if (!in_dev) {
-        QMX_TRY(bin.reserve(in_bytes));
-        QMX_HIP(hipMemcpy(bin.p, in, in_bytes, hipMemcpyHostToDevice));
-        d_in = (const float *)bin.p;
-    }
-    if (!out_dev) {
-        QMX_TRY(bout.reserve(out_bytes));
-        d_out = bout.p;
-    }
-    int32_t rc = launch_cast_f32(nullptr, (int)dst_dtype, d_in, d_out, count);
-    if (rc == QMX_OK && !out_dev) rc = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost) == hipSuccess ? QMX_OK : QMX_ERR_OTHER;
-    if (rc == QMX_OK && hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-    bin.release();
-    bout.release();
-    return rc;
+    Staging st;
+    const float *d_in = nullptr;
+    void *d_out = nullptr;
+    QMX_TRY(st.in(in, (size_t)count * 4, &d_in));
+    QMX_TRY(st.out(out, (size_t)count * elem_bytes(dst_dtype), &d_out));
+    QMX_TRY(launch_cast_f32(nullptr, (int)dst_dtype, d_in, d_out, count));
+    QMX_TRY(st.back());
+    QMX_HIP(hipDeviceSynchronize());
+    return QMX_OK;
 }
 
 int32_t qmx_sq_encode(int32_t device_id, uint32_t distance, const qmx_sq_params *params, const float *in, uint64_t n,
@@ -979,29 +902,15 @@ int32_t qmx_sq_encode(int32_t device_id, uint32_t distance, const qmx_sq_params 
     QMX_REQUIRE(params->alpha != 0.0f, QMX_ERR_BAD_ARG, "alpha must be non-zero");
     QMX_TRY(check_device(device_id, nullptr));
     if (n == 0) return QMX_OK;
-    const size_t in_bytes = (size_t)n * dim * 4, out_bytes = (size_t)n * (4 + (size_t)params->actual_dim);
-    DevBuf bin, bout;
-    const float *d_in = in;
-    void *d_out = out_rows;
-    int32_t rc = QMX_OK;
-    do {
-        if (!is_device_ptr(in)) {
-            if ((rc = bin.reserve(in_bytes)) != QMX_OK) break;
-            if (hipMemcpy(bin.p, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_in = (const float *)bin.p;
-        }
-        const bool out_dev = is_device_ptr(out_rows);
-        if (!out_dev) {
-            if ((rc = bout.reserve(out_bytes)) != QMX_OK) break;
-            d_out = bout.p;
-        }
-        if ((rc = launch_sq_encode(nullptr, (int)distance, *params, dim, d_in, n, nullptr, 0, nullptr, (uint8_t *)d_out, 0, 0)) != QMX_OK) break;
-        if (!out_dev && hipMemcpy(out_rows, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        if (hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-    } while (0);
-    bin.release();
-    bout.release();
-    return rc;
+    Staging st;
+    const float *d_in = nullptr;
+    uint8_t *d_out = nullptr;
+    QMX_TRY(st.in(in, (size_t)n * dim * 4, &d_in));
+    QMX_TRY(st.out((uint8_t *)out_rows, (size_t)n * (4 + (size_t)params->actual_dim), &d_out));
+    QMX_TRY(launch_sq_encode(nullptr, (int)distance, *params, dim, d_in, n, nullptr, 0, nullptr, d_out, 0, 0));
+    QMX_TRY(st.back());
+    QMX_HIP(hipDeviceSynchronize());
+    return QMX_OK;
 }
 
 uint64_t qmx_bq_row_bytes(uint32_t dim, uint32_t encoding) { return bq_row_bytes(dim, encoding); }
@@ -1013,64 +922,37 @@ int32_t qmx_bq_encode_ex(int32_t device_id, const qmx_bq_params *params, const f
     QMX_TRY(check_device(device_id, nullptr));
     if (n == 0) return QMX_OK;
     const size_t row_bytes = (size_t)bq_row_bytes(dim, encoding);
-    const size_t in_bytes = (size_t)n * dim * 4, out_bytes = (size_t)n * row_bytes;
     const bool stats = params && params->mean && params->stddev && encoding != QMX_BQ_ONE_BIT;
-    DevBuf bin, bout, bm, bs;
-    const float *d_in = in, *d_mean = nullptr, *d_sd = nullptr;
-    void *d_out = out_rows;
-    int32_t rc = QMX_OK;
-    do {
-        if (!is_device_ptr(in)) {
-            if ((rc = bin.reserve(in_bytes)) != QMX_OK) break;
-            if (hipMemcpy(bin.p, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_in = (const float *)bin.p;
-        }
-        if (stats) {
-            if ((rc = bm.reserve((size_t)dim * 4)) != QMX_OK || (rc = bs.reserve((size_t)dim * 4)) != QMX_OK) break;
-            if (hipMemcpy(bm.p, params->mean, (size_t)dim * 4, hipMemcpyDefault) != hipSuccess ||
-                hipMemcpy(bs.p, params->stddev, (size_t)dim * 4, hipMemcpyDefault) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_mean = (const float *)bm.p;
-            d_sd = (const float *)bs.p;
-        }
-        const bool out_dev = is_device_ptr(out_rows);
-        if (!out_dev) {
-            if ((rc = bout.reserve(out_bytes)) != QMX_OK) break;
-            d_out = bout.p;
-        }
-        if ((rc = launch_bq_encode(nullptr, d_in, n, dim, encoding, d_mean, d_sd, (uint8_t *)d_out, row_bytes)) != QMX_OK) break;
-        if (!out_dev && hipMemcpy(out_rows, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        if (hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-    } while (0);
-    bin.release();
-    bout.release();
-    bm.release();
-    bs.release();
-    return rc;
+    Staging st;
+    const float *d_in = nullptr, *d_mean = nullptr, *d_sd = nullptr;
+    uint8_t *d_out = nullptr;
+    QMX_TRY(st.in(in, (size_t)n * dim * 4, &d_in));
+    if (stats) {
+        QMX_TRY(st.in(params->mean, (size_t)dim * 4, &d_mean));
+        QMX_TRY(st.in(params->stddev, (size_t)dim * 4, &d_sd));
+    }
+    QMX_TRY(st.out((uint8_t *)out_rows, (size_t)n * row_bytes, &d_out));
+    QMX_TRY(launch_bq_encode(nullptr, d_in, n, dim, encoding, d_mean, d_sd, d_out, row_bytes));
+    QMX_TRY(st.back());
+    QMX_HIP(hipDeviceSynchronize());
+    return QMX_OK;
 }
 
 int32_t qmx_vector_stats(int32_t device_id, const float *vectors, uint64_t n, uint32_t dim, float *min_out, float *max_out, float *mean_out, float *stddev_out) {
     QMX_REQUIRE((n == 0 || vectors) && dim > 0 && mean_out && stddev_out, QMX_ERR_BAD_ARG, "bad argument");
     QMX_TRY(check_device(device_id, nullptr));
-    DevBuf bin, bout;
-    int32_t rc = QMX_OK;
-    do {
-        const float *d_in = vectors;
-        if (n && !is_device_ptr(vectors)) {
-            if ((rc = bin.reserve((size_t)n * dim * 4)) != QMX_OK) break;
-            if (hipMemcpy(bin.p, vectors, (size_t)n * dim * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_in = (const float *)bin.p;
-        }
-        if ((rc = bout.reserve((size_t)dim * 16)) != QMX_OK) break;
-        float *o = (float *)bout.p;
-        if ((rc = launch_vector_stats(nullptr, d_in, (uint64_t)dim * 4, n, dim, o, o + dim, o + 2 * (size_t)dim, o + 3 * (size_t)dim)) != QMX_OK) break;
-        if (hipDeviceSynchronize() != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        float *dst[4] = {min_out, max_out, mean_out, stddev_out};
-        for (int k = 0; k < 4 && rc == QMX_OK; ++k)
-            if (dst[k] && hipMemcpy(dst[k], o + (size_t)k * dim, (size_t)dim * 4, hipMemcpyDefault) != hipSuccess) rc = QMX_ERR_OTHER;
-    } while (0);
-    bin.release(); bout.release();
-    if (rc == QMX_ERR_OTHER) set_error("qmx_vector_stats: HIP error");
-    return rc;
+    Staging st;
+    DevBuf bout;      // the four columns in one block: min_out / max_out are optional for the caller, not for the kernel
+    const float *d_in = nullptr;
+    QMX_TRY(st.in(vectors, (size_t)n * dim * 4, &d_in));
+    QMX_TRY(bout.reserve((size_t)dim * 16));
+    float *o = (float *)bout.p;
+    QMX_TRY(launch_vector_stats(nullptr, d_in, (uint64_t)dim * 4, n, dim, o, o + dim, o + 2 * (size_t)dim, o + 3 * (size_t)dim));
+    QMX_HIP(hipDeviceSynchronize());
+    float *dst[4] = {min_out, max_out, mean_out, stddev_out};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k]) QMX_HIP(hipMemcpy(dst[k], o + (size_t)k * dim, (size_t)dim * 4, hipMemcpyDefault));
+    return QMX_OK;
 }
 
 int32_t qmx_bq_encode(int32_t device_id, const float *in, uint64_t n, uint32_t dim, void *out_rows) {
@@ -1091,55 +973,13 @@ int32_t qmx_pq_train(int32_t device_id, const float *sample, uint64_t n, uint32_
         if (out_iterations) for (uint32_t c = 0; c < m; ++c) out_iterations[c] = 0;
         return QMX_OK;
     }
-    DevBuf bin, bcen;
-    const float *d_in = sample;
-    float *d_cen = out_centroids;
-    int32_t rc = QMX_OK;
-    do {
-        if (!is_device_ptr(sample)) {
-            if ((rc = bin.reserve((size_t)n * dim * 4)) != QMX_OK) break;
-            if (hipMemcpy(bin.p, sample, (size_t)n * dim * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_in = (const float *)bin.p;
-        }
-        const bool out_dev = is_device_ptr(out_centroids);
-        if (!out_dev) {
-            if ((rc = bcen.reserve(cbytes)) != QMX_OK) break;
-            d_cen = (float *)bcen.p;
-        }
-        if ((rc = launch_pq_train(nullptr, dim, chunk_size, n_centroids, d_in, n, max_iterations, accuracy, threads, d_cen, out_iterations)) != QMX_OK) break;
-        if (!out_dev && hipMemcpy(out_centroids, d_cen, cbytes, hipMemcpyDeviceToHost) != hipSuccess) rc = QMX_ERR_OTHER;
-    } while (0);
-    bin.release();
-    bcen.release();
-    return rc;
-}
-
-int32_t qmx_sq_fit_min_max(int32_t device_id, uint32_t distance, const float *in, uint64_t n, uint32_t dim, qmx_sq_params *out) {
-    QMX_REQUIRE(out && (n == 0 || in) && dim > 0, QMX_ERR_BAD_ARG, "bad argument");
-    QMX_REQUIRE(distance <= QMX_DISTANCE_MANHATTAN, QMX_ERR_BAD_ARG, "bad distance");
-    QMX_TRY(check_device(device_id, nullptr));
-    DevBuf bin;
-    const float *d_in = in;
-    if (n && !is_device_ptr(in)) {
-        QMX_TRY(bin.reserve((size_t)n * dim * 4));
-        if (hipMemcpy(bin.p, in, (size_t)n * dim * 4, hipMemcpyHostToDevice) != hipSuccess) { bin.release(); return QMX_ERR_OTHER; }
-        d_in = (const float *)bin.p;
-    }
-    float mn = 0.f, mx = 0.f;
-    const int32_t rc = launch_minmax_f32(nullptr, d_in, n * dim, &mn, &mx);
-    bin.release();
-    QMX_TRY(rc);
-    memset(out, 0, sizeof(*out));
-    out->actual_dim = ((dim + 15) / 16) * 16;                 // get_actual_dim (:622-624)
-    out->alpha = (mx - mn) / 127.0f;                          // alpha_offset_from_min_max (:523-527)
-    out->offset = mn;
-    out->invert = (distance == QMX_DISTANCE_EUCLID || distance == QMX_DISTANCE_MANHATTAN) ? 1 : 0;   // quantized_vectors.rs:232
-    float m;
-    if (distance == QMX_DISTANCE_DOT || distance == QMX_DISTANCE_COSINE) m = out->alpha * out->alpha;      // :210-221
-    else if (distance == QMX_DISTANCE_MANHATTAN) m = out->alpha;
-    else m = -2.0f * out->alpha * out->alpha;
-    out->multiplier = out->invert ? -m : m;
-    return QMX_OK;
+    Staging st;
+    const float *d_in = nullptr;
+    float *d_cen = nullptr;
+    QMX_TRY(st.in(sample, (size_t)n * dim * 4, &d_in));
+    QMX_TRY(st.out(out_centroids, cbytes, &d_cen));
+    QMX_TRY(launch_pq_train(nullptr, dim, chunk_size, n_centroids, d_in, n, max_iterations, accuracy, threads, d_cen, out_iterations));
+    return st.back();
 }
 
 static void sq_params_from_min_max(uint32_t distance, uint32_t dim, float mn, float mx, qmx_sq_params *out) {
@@ -1155,6 +995,19 @@ static void sq_params_from_min_max(uint32_t distance, uint32_t dim, float mn, fl
     out->multiplier = out->invert ? -m : m;
 }
 
+int32_t qmx_sq_fit_min_max(int32_t device_id, uint32_t distance, const float *in, uint64_t n, uint32_t dim, qmx_sq_params *out) {
+    QMX_REQUIRE(out && (n == 0 || in) && dim > 0, QMX_ERR_BAD_ARG, "bad argument");
+    QMX_REQUIRE(distance <= QMX_DISTANCE_MANHATTAN, QMX_ERR_BAD_ARG, "bad distance");
+    QMX_TRY(check_device(device_id, nullptr));
+    Staging st;
+    const float *d_in = nullptr;
+    QMX_TRY(st.in(in, (size_t)n * dim * 4, &d_in));
+    float mn = 0.f, mx = 0.f;
+    QMX_TRY(launch_minmax_f32(nullptr, d_in, n * dim, &mn, &mx));
+    sq_params_from_min_max(distance, dim, mn, mx, out);
+    return QMX_OK;
+}
+
 int32_t qmx_sq_fit_quantile(int32_t device_id, uint32_t distance, const float *sample, uint64_t n_sample, uint32_t dim, uint64_t count,
                             float quantile, qmx_sq_params *out, int32_t *found) {
     QMX_REQUIRE(out && found && (n_sample == 0 || sample) && dim > 0, QMX_ERR_BAD_ARG, "bad argument");
@@ -1167,22 +1020,13 @@ int32_t qmx_sq_fit_quantile(int32_t device_id, uint32_t distance, const float *s
     uint64_t cut = std::min<uint64_t>((len - 1) / 2, (uint64_t)((float)n_sample * (1.0f - quantile) / 2.0f));   // :58-62 (f32 arithmetic, truncating cast)
     cut = std::max<uint64_t>(cut, 1);
     if (len - 2 * cut - 1 < 2) return QMX_OK;                                                              // :70-72
-    DevBuf bin, btmp;
-    const float *d_in = sample;
-    int32_t rc = QMX_OK;
+    Staging st;
+    DevBuf btmp;
+    const float *d_in = nullptr;
     float mm[2] = {0.f, 0.f};
-    do {
-        if (!is_device_ptr(sample)) {
-            if ((rc = bin.reserve((size_t)len * 4)) != QMX_OK) break;
-            if (hipMemcpy(bin.p, sample, (size_t)len * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_in = (const float *)bin.p;
-        }
-        if ((rc = btmp.reserve((size_t)len * 4)) != QMX_OK) break;
-        rc = launch_order_statistics_f32(nullptr, d_in, (float *)btmp.p, len, cut + 1, len - cut - 1, mm);
-    } while (0);
-    bin.release();
-    btmp.release();
-    QMX_TRY(rc);
+    QMX_TRY(st.in(sample, (size_t)len * 4, &d_in));
+    QMX_TRY(btmp.reserve((size_t)len * 4));
+    QMX_TRY(launch_order_statistics_f32(nullptr, d_in, (float *)btmp.p, len, cut + 1, len - cut - 1, mm));
     sq_params_from_min_max(distance, dim, mm[0], mm[1], out);
     *found = 1;
     return QMX_OK;
@@ -1195,34 +1039,16 @@ int32_t qmx_pq_encode(int32_t device_id, const qmx_pq_params *params, const floa
     QMX_TRY(check_device(device_id, nullptr));
     if (n == 0) return QMX_OK;
     const uint32_t m = (dim + params->chunk_size - 1) / params->chunk_size;
-    const size_t in_bytes = (size_t)n * dim * 4, out_bytes = (size_t)n * m, cbytes = (size_t)params->n_centroids * dim * 4;
-    DevBuf bin, bout, bc;
-    const float *d_in = in, *d_c = params->centroids;
-    uint8_t *d_out = out_codes;
-    int32_t rc = QMX_OK;
-    do {
-        if (!is_device_ptr(in)) {
-            if ((rc = bin.reserve(in_bytes)) != QMX_OK) break;
-            if (hipMemcpy(bin.p, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_in = (const float *)bin.p;
-        }
-        if (!is_device_ptr(params->centroids)) {
-            if ((rc = bc.reserve(cbytes)) != QMX_OK) break;
-            if (hipMemcpy(bc.p, params->centroids, cbytes, hipMemcpyHostToDevice) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            d_c = (const float *)bc.p;
-        }
-        const bool out_dev = is_device_ptr(out_codes);
-        if (!out_dev) {
-            if ((rc = bout.reserve(out_bytes)) != QMX_OK) break;
-            d_out = (uint8_t *)bout.p;
-        }
-        if ((rc = launch_pq_encode(nullptr, dim, *params, d_c, d_in, n, d_out)) != QMX_OK) break;
-        if (!out_dev && hipMemcpy(out_codes, d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        if (hipDeviceSynchronize() != hipSuccess) rc = QMX_ERR_OTHER;
-    } while (0);
-    bin.release(); bout.release(); bc.release();
-    return rc;
+    Staging st;
+    const float *d_in = nullptr, *d_c = nullptr;
+    uint8_t *d_out = nullptr;
+    QMX_TRY(st.in(in, (size_t)n * dim * 4, &d_in));
+    QMX_TRY(st.in(params->centroids, (size_t)params->n_centroids * dim * 4, &d_c));
+    QMX_TRY(st.out(out_codes, (size_t)n * m, &d_out));
+    QMX_TRY(launch_pq_encode(nullptr, dim, *params, d_c, d_in, n, d_out));
+    QMX_TRY(st.back());
+    QMX_HIP(hipDeviceSynchronize());
+    return QMX_OK;
 }
-
 
 }  // extern "C"

@@ -27,6 +27,10 @@ struct SparseSeg {
     // pair scores of qmx_sparse_mmr_select (sparse_mmr.hip); null under no map or a monotone one
     uint32_t *d_inv_vals = nullptr, *d_inv_keys = nullptr;
     uint32_t n_inv = 0;
+    ~SparseSeg() {
+        dev_free(d_off); dev_free(d_idx); dev_free(d_val); dev_free(d_post); dev_free(d_post_id); dev_free(d_post_w);
+        dev_free(d_inv_vals); dev_free(d_inv_keys);
+    }
 };
 
 // a query batch: CSR lists sorted by (remapped) index, and the posting plan of every query (its dimensions that have postings, ascending)
@@ -49,6 +53,12 @@ struct SparseQuery {
     bool internal = false;                   // made by qmx_query_create_internal: stored rows, whose original order is not known
     std::vector<uint64_t> h_entries;         // [nq]: posting entries of each query
     uint64_t longest = 0;                    // entries of the longest list
+    ~SparseQuery() {
+        dev_free(d_off); dev_free(d_idx); dev_free(d_val); dev_free(d_poff); dev_free(d_pstart); dev_free(d_pend); dev_free(d_pw);
+        dev_free(d_pmn); dev_free(d_pd256);
+        if (!own_original) return;
+        dev_free(d_oidx); dev_free(d_oval); dev_free(d_opstart); dev_free(d_opend); dev_free(d_opw);
+    }
 };
 
 static SparseRows rows_of(const qmx_segment *s) {
@@ -60,40 +70,9 @@ static SparseQueries queries_of(const qmx_query *q) {
     return SparseQueries{sq->d_off, sq->d_idx, sq->d_val};
 }
 
-void sparse_segment_free(qmx_segment *s) {
-    SparseSeg *sp = s->sparse;
-    if (!sp) return;
-    if (sp->d_off) (void)hipFree(sp->d_off);
-    if (sp->d_idx) (void)hipFree(sp->d_idx);
-    if (sp->d_val) (void)hipFree(sp->d_val);
-    if (sp->d_post) (void)hipFree(sp->d_post);
-    if (sp->d_post_id) (void)hipFree(sp->d_post_id);
-    if (sp->d_post_w) (void)hipFree(sp->d_post_w);
-    if (sp->d_inv_vals) (void)hipFree(sp->d_inv_vals);
-    if (sp->d_inv_keys) (void)hipFree(sp->d_inv_keys);
-    delete sp;
-    s->sparse = nullptr;
-}
-
-void sparse_query_free(qmx_query *q) {
-    SparseQuery *sq = q->sparse;
-    if (!sq) return;
-    for (void *p : {(void *)sq->d_off, (void *)sq->d_idx, (void *)sq->d_val, (void *)sq->d_poff, (void *)sq->d_pstart, (void *)sq->d_pend, (void *)sq->d_pw,
-                    (void *)sq->d_pmn, (void *)sq->d_pd256})
-        if (p) (void)hipFree(p);
-    if (sq->own_original)
-        for (void *p : {(void *)sq->d_oidx, (void *)sq->d_oval, (void *)sq->d_opstart, (void *)sq->d_opend, (void *)sq->d_opw})
-            if (p) (void)hipFree(p);
-    delete sq;
-    q->sparse = nullptr;
-}
-
-template <typename T>
-static int32_t upload(T **dst, const T *src, size_t count) {
-    QMX_HIP(hipMalloc((void **)dst, std::max<size_t>(count, 1) * sizeof(T)));
-    if (count) QMX_HIP(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyDefault));
-    return QMX_OK;
-}
+// what the destructors of qmx_segment / qmx_query call: the structs above are complete in this file only
+void sparse_delete(SparseSeg *sp) { delete sp; }
+void sparse_delete(SparseQuery *sq) { delete sq; }
 
 // (index, value) pairs of one vector sorted by index; false on a duplicate index (validate_sparse_vector_impl, sparse_vector.rs:302-323)
 static bool sort_pairs(std::vector<std::pair<uint32_t, float>> &v) {
@@ -141,16 +120,16 @@ static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, cons
     posting_plan(sp, q->nq, off, idx, val, poff, pstart, pend, pw, &sq->h_entries, u8 ? &pmn : nullptr, u8 ? &pd256 : nullptr);
     for (uint64_t e : sq->h_entries) sq->posting_entries += e;
     for (uint32_t qi = 0; qi < q->nq; ++qi) sq->longest = std::max(sq->longest, off[qi + 1] - off[qi]);
-    QMX_TRY(upload(&sq->d_off, off.data(), off.size()));
-    QMX_TRY(upload(&sq->d_idx, idx.data(), idx.size()));
-    QMX_TRY(upload(&sq->d_val, val.data(), val.size()));
-    QMX_TRY(upload(&sq->d_poff, poff.data(), poff.size()));
-    QMX_TRY(upload(&sq->d_pstart, pstart.data(), pstart.size()));
-    QMX_TRY(upload(&sq->d_pend, pend.data(), pend.size()));
-    QMX_TRY(upload(&sq->d_pw, pw.data(), pw.size()));
+    QMX_TRY(dev_upload(&sq->d_off, off.data(), off.size()));
+    QMX_TRY(dev_upload(&sq->d_idx, idx.data(), idx.size()));
+    QMX_TRY(dev_upload(&sq->d_val, val.data(), val.size()));
+    QMX_TRY(dev_upload(&sq->d_poff, poff.data(), poff.size()));
+    QMX_TRY(dev_upload(&sq->d_pstart, pstart.data(), pstart.size()));
+    QMX_TRY(dev_upload(&sq->d_pend, pend.data(), pend.size()));
+    QMX_TRY(dev_upload(&sq->d_pw, pw.data(), pw.size()));
     if (u8) {
-        QMX_TRY(upload(&sq->d_pmn, pmn.data(), pmn.size()));
-        QMX_TRY(upload(&sq->d_pd256, pd256.data(), pd256.size()));
+        QMX_TRY(dev_upload(&sq->d_pmn, pmn.data(), pmn.size()));
+        QMX_TRY(dev_upload(&sq->d_pd256, pd256.data(), pd256.size()));
     }
     if (!oidx) {
         sq->d_oidx = sq->d_idx;
@@ -166,11 +145,11 @@ static int32_t query_finish(qmx_query *q, const std::vector<uint64_t> &off, cons
     std::vector<float> opw;
     posting_plan(sp, q->nq, off, *oidx, *oval, opoff, opstart, opend, opw, nullptr);
     sq->own_original = true;
-    QMX_TRY(upload(&sq->d_oidx, oidx->data(), oidx->size()));
-    QMX_TRY(upload(&sq->d_oval, oval->data(), oval->size()));
-    QMX_TRY(upload(&sq->d_opstart, opstart.data(), opstart.size()));
-    QMX_TRY(upload(&sq->d_opend, opend.data(), opend.size()));
-    QMX_TRY(upload(&sq->d_opw, opw.data(), opw.size()));
+    QMX_TRY(dev_upload(&sq->d_oidx, oidx->data(), oidx->size()));
+    QMX_TRY(dev_upload(&sq->d_oval, oval->data(), oval->size()));
+    QMX_TRY(dev_upload(&sq->d_opstart, opstart.data(), opstart.size()));
+    QMX_TRY(dev_upload(&sq->d_opend, opend.data(), opend.size()));
+    QMX_TRY(dev_upload(&sq->d_opw, opw.data(), opw.size()));
     return QMX_OK;
 }
 
@@ -246,25 +225,21 @@ int32_t sparse_score_pairs(qmx_query *q, const PairSel &sel, const uint32_t *d_i
 
 int32_t sparse_score_internal(const qmx_segment *seg, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t n, float *out) {
     QMX_HIP(hipSetDevice(seg->device));
-    DevBuf ba, bb, bo, be;
-    int32_t rc = QMX_OK;
-    do {
-        if ((rc = ba.reserve((size_t)n * 4)) != QMX_OK || (rc = bb.reserve((size_t)n * 4)) != QMX_OK || (rc = bo.reserve((size_t)n * 4)) != QMX_OK ||
-            (rc = be.reserve(4)) != QMX_OK)
-            break;
-        hipError_t e = hipMemcpy(ba.p, a_ids, (size_t)n * 4, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemcpy(bb.p, b_ids, (size_t)n * 4, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemset(be.p, 0, 4);
-        if (e != hipSuccess) { rc = hip_status(e, "stage ids", __FILE__, __LINE__); break; }
-        if ((rc = launch_sparse_score_internal(nullptr, rows_of(seg), (const uint32_t *)ba.p, (const uint32_t *)bb.p, n, (float *)bo.p, (int *)be.p)) != QMX_OK) break;
-        int flag = 0;
-        e = hipMemcpy(&flag, be.p, 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out, bo.p, (size_t)n * 4, hipMemcpyDefault);
-        if (e != hipSuccess) { rc = hip_status(e, "copy scores", __FILE__, __LINE__); break; }
-        if (flag) { set_error("point offset out of range for this segment"); rc = QMX_ERR_OUT_OF_BOUNDS; }
-    } while (0);
-    ba.release(); bb.release(); bo.release(); be.release();
-    return rc;
+    Staging st;
+    DevBuf be;
+    const uint32_t *d_a = nullptr, *d_b = nullptr;
+    float *d_out = nullptr;
+    QMX_TRY(st.in(a_ids, (size_t)n * 4, &d_a));
+    QMX_TRY(st.in(b_ids, (size_t)n * 4, &d_b));
+    QMX_TRY(st.out(out, (size_t)n * 4, &d_out));
+    QMX_TRY(be.reserve(4));
+    QMX_HIP(hipMemset(be.p, 0, 4));
+    QMX_TRY(launch_sparse_score_internal(nullptr, rows_of(seg), d_a, d_b, n, d_out, (int *)be.p));
+    int flag = 0;
+    QMX_HIP(hipMemcpy(&flag, be.p, 4, hipMemcpyDeviceToHost));
+    QMX_TRY(st.back());
+    QMX_REQUIRE(!flag, QMX_ERR_OUT_OF_BOUNDS, "point offset out of range for this segment");
+    return QMX_OK;
 }
 
 // Nearest: the posting top-k over every point (sparse_topk_postings_kernel), or plain_search over an id list (sparse_topk_ids_kernel); over f16 / u8
@@ -344,6 +319,121 @@ int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids,
 
 extern "C" {
 
+// the device arrays of a new sparse segment `s` from its descriptor: rows (remapped and sorted), the posting layout and its directory
+static int32_t sparse_segment_build(qmx_segment *s, const qmx_sparse_segment_desc *d, std::vector<uint64_t> &&h_off) {
+    SparseSeg *sp = s->sparse;
+    QMX_REQUIRE(sp, QMX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    const uint64_t nnz = h_off[d->n];
+    sp->nnz = nnz;
+    sp->h_off = std::move(h_off);
+    for (uint64_t r = 0; r < d->n; ++r) {
+        sp->n_nonempty += sp->h_off[r + 1] > sp->h_off[r];
+        sp->longest_row = std::max(sp->longest_row, sp->h_off[r + 1] - sp->h_off[r]);
+    }
+    QMX_TRY(dev_upload(&sp->d_off, sp->h_off.data(), sp->h_off.size()));
+    QMX_TRY(dev_upload(&sp->d_idx, d->indices, nnz));
+    QMX_TRY(dev_upload(&sp->d_val, d->values, nnz));
+    DevBuf flag, keys, vals, dims, counts_dev, dir, mn, d256;
+    QMX_TRY(flag.reserve(4));
+    uint32_t *d_flag = (uint32_t *)flag.p;
+    QMX_HIP(hipMemset(d_flag, 0, 4));
+    if (d->map_keys) {      // IndicesTracker: every stored index is remapped, then every row re-sorted
+        std::vector<std::pair<uint32_t, uint32_t>> m(d->n_map);
+        std::vector<uint32_t> k(d->n_map), v(d->n_map);
+        if (d->n_map) {
+            QMX_HIP(hipMemcpy(k.data(), d->map_keys, d->n_map * 4, hipMemcpyDefault));
+            QMX_HIP(hipMemcpy(v.data(), d->map_values, d->n_map * 4, hipMemcpyDefault));
+        }
+        for (uint64_t i = 0; i < d->n_map; ++i) m[i] = {k[i], v[i]};
+        std::sort(m.begin(), m.end());
+        bool dup = false;
+        for (uint64_t i = 1; i < d->n_map; ++i) dup = dup || m[i - 1].first == m[i].first;
+        QMX_REQUIRE(!dup, QMX_ERR_BAD_ARG, "the dimension map holds a key twice");
+        sp->has_map = true;
+        for (auto &p : m) {
+            sp->map_keys.push_back(p.first);
+            sp->map_vals.push_back(p.second);
+        }
+        QMX_TRY(dev_upload(keys, sp->map_keys.data(), sp->map_keys.size()));
+        QMX_TRY(dev_upload(vals, sp->map_vals.data(), sp->map_vals.size()));
+        QMX_TRY(launch_sparse_remap(nullptr, sp->d_idx, nnz, (const uint32_t *)keys.p, (const uint32_t *)vals.p, d->n_map, d_flag));
+        uint32_t missing = 0;
+        QMX_HIP(hipMemcpy(&missing, d_flag, 4, hipMemcpyDeviceToHost));
+        QMX_REQUIRE(!missing, QMX_ERR_BAD_ARG, "a stored index is not in the dimension map");
+        // the map by remapped id, kept where it changes the order (the first original index of a remapped id two of them share)
+        bool monotone = true;
+        for (size_t i = 1; i < sp->map_vals.size(); ++i) monotone = monotone && sp->map_vals[i - 1] < sp->map_vals[i];
+        if (!monotone) {
+            std::vector<std::pair<uint32_t, uint32_t>> inv;
+            for (size_t i = 0; i < sp->map_keys.size(); ++i) inv.push_back({sp->map_vals[i], sp->map_keys[i]});
+            std::sort(inv.begin(), inv.end());
+            std::vector<uint32_t> iv, ik;
+            for (size_t i = 0; i < inv.size(); ++i)
+                if (i == 0 || inv[i].first != inv[i - 1].first) {
+                    iv.push_back(inv[i].first);
+                    ik.push_back(inv[i].second);
+                }
+            sp->n_inv = (uint32_t)iv.size();
+            QMX_TRY(dev_upload(&sp->d_inv_vals, iv.data(), iv.size()));
+            QMX_TRY(dev_upload(&sp->d_inv_keys, ik.data(), ik.size()));
+        }
+    }
+    // sorted by index on the way in; duplicates refused
+    QMX_TRY(launch_sparse_check_rows(nullptr, sp->d_off, sp->d_idx, s->n, d_flag));
+    uint32_t flags = 0;
+    QMX_HIP(hipMemcpy(&flags, d_flag, 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) {
+        QMX_TRY(launch_sparse_sort_rows(nullptr, sp->d_off, sp->d_idx, sp->d_val, s->n));
+        QMX_HIP(hipMemset(d_flag, 0, 4));
+        QMX_TRY(launch_sparse_check_rows(nullptr, sp->d_off, sp->d_idx, s->n, d_flag));
+        QMX_HIP(hipMemcpy(&flags, d_flag, 4, hipMemcpyDeviceToHost));
+    }
+    QMX_REQUIRE(!(flags & 2u), QMX_ERR_BAD_ARG, "a sparse vector holds an index twice");
+    // the posting layout and its directory
+    QMX_HIP(hipMalloc((void **)&sp->d_post, std::max<uint64_t>(nnz, 1) * 8));
+    QMX_TRY(dims.reserve(std::max<uint64_t>(nnz, 1) * 4));
+    QMX_TRY(counts_dev.reserve(std::max<uint64_t>(nnz, 1) * 4));
+    QMX_TRY(sparse_build_postings(nullptr, sp->d_off, sp->d_idx, sp->d_val, s->n, nnz, sp->d_post, (uint32_t *)dims.p, (uint32_t *)counts_dev.p, d_flag));
+    uint32_t n_dims = 0;
+    QMX_HIP(hipMemcpy(&n_dims, d_flag, 4, hipMemcpyDeviceToHost));
+    sp->dir_dims.resize(n_dims);
+    std::vector<uint32_t> counts(n_dims);
+    if (n_dims) {
+        QMX_HIP(hipMemcpy(sp->dir_dims.data(), dims.p, (size_t)n_dims * 4, hipMemcpyDeviceToHost));
+        QMX_HIP(hipMemcpy(counts.data(), counts_dev.p, (size_t)n_dims * 4, hipMemcpyDeviceToHost));
+    }
+    sp->dir_start.assign(n_dims + 1, 0);
+    for (uint32_t i = 0; i < n_dims; ++i) sp->dir_start[i + 1] = sp->dir_start[i] + counts[i];
+    sp->wtype = d->flags & QMX_SPARSE_WEIGHT_MASK;
+    if (sp->wtype == QMX_SPARSE_WEIGHT_F32) return QMX_OK;
+    // f16 / u8 index weights: the packed layout is encoded into (post_id, post_w) and freed - 8 B per entry become 6 B / 5 B.  The u8
+    // parameters of every posting list stay on the host beside the directory.
+    const bool u8 = sp->wtype == QMX_SPARSE_WEIGHT_U8;
+    QMX_TRY(dev_upload(dir, sp->dir_start.data(), sp->dir_start.size()));
+    QMX_HIP(hipMalloc((void **)&sp->d_post_id, std::max<uint64_t>(nnz, 1) * 4));
+    QMX_HIP(hipMalloc(&sp->d_post_w, std::max<uint64_t>(nnz, 1) * (u8 ? 1 : 2)));
+    float *d_mn = nullptr, *d_d256 = nullptr;
+    if (u8) {
+        QMX_TRY(mn.reserve(std::max<size_t>(n_dims, 1) * 4));
+        QMX_TRY(d256.reserve(std::max<size_t>(n_dims, 1) * 4));
+        d_mn = (float *)mn.p;
+        d_d256 = (float *)d256.p;
+        QMX_TRY(launch_sparse_post_params(nullptr, sp->d_post, (const uint64_t *)dir.p, n_dims, d_mn, d_d256));
+    }
+    QMX_TRY(launch_sparse_post_encode(nullptr, sp->d_post, (const uint64_t *)dir.p, n_dims, d_mn, d_d256, sp->wtype, sp->d_post_id, sp->d_post_w));
+    if (u8) {
+        sp->dir_min.resize(n_dims);
+        sp->dir_d256.resize(n_dims);
+        if (n_dims) {
+            QMX_HIP(hipMemcpy(sp->dir_min.data(), d_mn, (size_t)n_dims * 4, hipMemcpyDeviceToHost));
+            QMX_HIP(hipMemcpy(sp->dir_d256.data(), d_d256, (size_t)n_dims * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    QMX_HIP(hipDeviceSynchronize());
+    dev_free(sp->d_post);
+    return QMX_OK;
+}
+
 int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment **out) {
     QMX_REQUIRE(d && out, QMX_ERR_BAD_ARG, "NULL argument");
     *out = nullptr;
@@ -371,119 +461,7 @@ int32_t qmx_sparse_segment_create(const qmx_sparse_segment_desc *d, qmx_segment 
     s->distance = QMX_DISTANCE_DOT;
     s->n = d->n;
     s->sparse = new (std::nothrow) SparseSeg();
-    SparseSeg *sp = s->sparse;
-    uint32_t *d_flag = nullptr, *d_keys = nullptr, *d_vals = nullptr, *d_dims = nullptr, *d_counts = nullptr;
-    uint64_t *d_dir = nullptr;
-    float *d_mn = nullptr, *d_d256 = nullptr;
-    int32_t rc = QMX_OK;
-    auto hip = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == QMX_OK) rc = hip_status(e, what, __FILE__, __LINE__);
-        return rc == QMX_OK;
-    };
-    do {
-        if (!sp) { set_error("host allocation failed"); rc = QMX_ERR_OUT_OF_MEMORY; break; }
-        sp->nnz = nnz;
-        sp->h_off = std::move(h_off);
-        for (uint64_t r = 0; r < d->n; ++r) {
-            sp->n_nonempty += sp->h_off[r + 1] > sp->h_off[r];
-            sp->longest_row = std::max(sp->longest_row, sp->h_off[r + 1] - sp->h_off[r]);
-        }
-        if ((rc = upload(&sp->d_off, sp->h_off.data(), sp->h_off.size())) != QMX_OK) break;
-        if ((rc = upload(&sp->d_idx, d->indices, nnz)) != QMX_OK) break;
-        if ((rc = upload(&sp->d_val, d->values, nnz)) != QMX_OK) break;
-        if (!hip(hipMalloc((void **)&d_flag, 4), "hipMalloc(flag)") || !hip(hipMemset(d_flag, 0, 4), "hipMemset(flag)")) break;
-        if (d->map_keys) {      // IndicesTracker: every stored index is remapped, then every row re-sorted
-            std::vector<std::pair<uint32_t, uint32_t>> m(d->n_map);
-            std::vector<uint32_t> k(d->n_map), v(d->n_map);
-            if (d->n_map && (!hip(hipMemcpy(k.data(), d->map_keys, d->n_map * 4, hipMemcpyDefault), "map keys") ||
-                             !hip(hipMemcpy(v.data(), d->map_values, d->n_map * 4, hipMemcpyDefault), "map values")))
-                break;
-            for (uint64_t i = 0; i < d->n_map; ++i) m[i] = {k[i], v[i]};
-            std::sort(m.begin(), m.end());
-            bool dup = false;
-            for (uint64_t i = 1; i < d->n_map; ++i) dup = dup || m[i - 1].first == m[i].first;
-            if (dup) { set_error("the dimension map holds a key twice"); rc = QMX_ERR_BAD_ARG; break; }
-            sp->has_map = true;
-            for (auto &p : m) {
-                sp->map_keys.push_back(p.first);
-                sp->map_vals.push_back(p.second);
-            }
-            if ((rc = upload(&d_keys, sp->map_keys.data(), sp->map_keys.size())) != QMX_OK) break;
-            if ((rc = upload(&d_vals, sp->map_vals.data(), sp->map_vals.size())) != QMX_OK) break;
-            if ((rc = launch_sparse_remap(nullptr, sp->d_idx, nnz, d_keys, d_vals, d->n_map, d_flag)) != QMX_OK) break;
-            uint32_t missing = 0;
-            if (!hip(hipMemcpy(&missing, d_flag, 4, hipMemcpyDeviceToHost), "remap flag")) break;
-            if (missing) { set_error("a stored index is not in the dimension map"); rc = QMX_ERR_BAD_ARG; break; }
-            // the map by remapped id, kept where it changes the order (the first original index of a remapped id two of them share)
-            bool monotone = true;
-            for (size_t i = 1; i < sp->map_vals.size(); ++i) monotone = monotone && sp->map_vals[i - 1] < sp->map_vals[i];
-            if (!monotone) {
-                std::vector<std::pair<uint32_t, uint32_t>> inv;
-                for (size_t i = 0; i < sp->map_keys.size(); ++i) inv.push_back({sp->map_vals[i], sp->map_keys[i]});
-                std::sort(inv.begin(), inv.end());
-                std::vector<uint32_t> iv, ik;
-                for (size_t i = 0; i < inv.size(); ++i)
-                    if (i == 0 || inv[i].first != inv[i - 1].first) {
-                        iv.push_back(inv[i].first);
-                        ik.push_back(inv[i].second);
-                    }
-                sp->n_inv = (uint32_t)iv.size();
-                if ((rc = upload(&sp->d_inv_vals, iv.data(), iv.size())) != QMX_OK) break;
-                if ((rc = upload(&sp->d_inv_keys, ik.data(), ik.size())) != QMX_OK) break;
-            }
-        }
-        // sorted by index on the way in; duplicates refused
-        if ((rc = launch_sparse_check_rows(nullptr, sp->d_off, sp->d_idx, s->n, d_flag)) != QMX_OK) break;
-        uint32_t flags = 0;
-        if (!hip(hipMemcpy(&flags, d_flag, 4, hipMemcpyDeviceToHost), "row check")) break;
-        if (flags & 1u) {
-            if ((rc = launch_sparse_sort_rows(nullptr, sp->d_off, sp->d_idx, sp->d_val, s->n)) != QMX_OK) break;
-            if (!hip(hipMemset(d_flag, 0, 4), "hipMemset(flag)")) break;
-            if ((rc = launch_sparse_check_rows(nullptr, sp->d_off, sp->d_idx, s->n, d_flag)) != QMX_OK) break;
-            if (!hip(hipMemcpy(&flags, d_flag, 4, hipMemcpyDeviceToHost), "row check")) break;
-        }
-        if (flags & 2u) { set_error("a sparse vector holds an index twice"); rc = QMX_ERR_BAD_ARG; break; }
-        // the posting layout and its directory
-        if (!hip(hipMalloc((void **)&sp->d_post, std::max<uint64_t>(nnz, 1) * 8), "hipMalloc(postings)")) break;
-        if (!hip(hipMalloc((void **)&d_dims, std::max<uint64_t>(nnz, 1) * 4), "hipMalloc(dims)")) break;
-        if (!hip(hipMalloc((void **)&d_counts, std::max<uint64_t>(nnz, 1) * 4), "hipMalloc(counts)")) break;
-        if ((rc = sparse_build_postings(nullptr, sp->d_off, sp->d_idx, sp->d_val, s->n, nnz, sp->d_post, d_dims, d_counts, d_flag)) != QMX_OK) break;
-        uint32_t n_dims = 0;
-        if (!hip(hipMemcpy(&n_dims, d_flag, 4, hipMemcpyDeviceToHost), "directory size")) break;
-        sp->dir_dims.resize(n_dims);
-        std::vector<uint32_t> counts(n_dims);
-        if (n_dims && (!hip(hipMemcpy(sp->dir_dims.data(), d_dims, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "directory") ||
-                       !hip(hipMemcpy(counts.data(), d_counts, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "directory")))
-            break;
-        sp->dir_start.assign(n_dims + 1, 0);
-        for (uint32_t i = 0; i < n_dims; ++i) sp->dir_start[i + 1] = sp->dir_start[i] + counts[i];
-        sp->wtype = d->flags & QMX_SPARSE_WEIGHT_MASK;
-        if (sp->wtype == QMX_SPARSE_WEIGHT_F32) break;
-        // f16 / u8 index weights: the packed layout is encoded into (post_id, post_w) and freed - 8 B per entry become 6 B / 5 B.  The u8
-        // parameters of every posting list stay on the host beside the directory.
-        const bool u8 = sp->wtype == QMX_SPARSE_WEIGHT_U8;
-        if ((rc = upload(&d_dir, sp->dir_start.data(), sp->dir_start.size())) != QMX_OK) break;
-        if (!hip(hipMalloc((void **)&sp->d_post_id, std::max<uint64_t>(nnz, 1) * 4), "hipMalloc(posting ids)")) break;
-        if (!hip(hipMalloc(&sp->d_post_w, std::max<uint64_t>(nnz, 1) * (u8 ? 1 : 2)), "hipMalloc(posting weights)")) break;
-        if (u8) {
-            if (!hip(hipMalloc((void **)&d_mn, std::max<size_t>(n_dims, 1) * 4), "hipMalloc(min)")) break;
-            if (!hip(hipMalloc((void **)&d_d256, std::max<size_t>(n_dims, 1) * 4), "hipMalloc(diff256)")) break;
-            if ((rc = launch_sparse_post_params(nullptr, sp->d_post, d_dir, n_dims, d_mn, d_d256)) != QMX_OK) break;
-        }
-        if ((rc = launch_sparse_post_encode(nullptr, sp->d_post, d_dir, n_dims, d_mn, d_d256, sp->wtype, sp->d_post_id, sp->d_post_w)) != QMX_OK) break;
-        if (u8) {
-            sp->dir_min.resize(n_dims);
-            sp->dir_d256.resize(n_dims);
-            if (n_dims && (!hip(hipMemcpy(sp->dir_min.data(), d_mn, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "posting parameters") ||
-                           !hip(hipMemcpy(sp->dir_d256.data(), d_d256, (size_t)n_dims * 4, hipMemcpyDeviceToHost), "posting parameters")))
-                break;
-        }
-        if (!hip(hipDeviceSynchronize(), "posting encode")) break;
-        (void)hipFree(sp->d_post);
-        sp->d_post = nullptr;
-    } while (0);
-    for (void *p : {(void *)d_flag, (void *)d_keys, (void *)d_vals, (void *)d_dims, (void *)d_counts, (void *)d_dir, (void *)d_mn, (void *)d_d256})
-        if (p) (void)hipFree(p);
+    const int32_t rc = sparse_segment_build(s, d, std::move(h_off));
     if (rc != QMX_OK) {
         qmx_segment_destroy(s);
         return rc;
@@ -581,31 +559,24 @@ int32_t qmx_sparse_idf_statistics(const qmx_segment *seg, const uint32_t *dims, 
     }
     const uint64_t n_words = (n_corpus_bits + 63) / 64;
     DevBuf mask, ranges, cnt;
-    int32_t rc = QMX_OK;
-    do {
-        if ((rc = mask.reserve(std::max<size_t>(n_words, 1) * 8)) != QMX_OK || (rc = ranges.reserve(std::max<size_t>(n, 1) * 16)) != QMX_OK ||
-            (rc = cnt.reserve(((size_t)n + 1) * 8)) != QMX_OK)
-            break;
-        uint64_t *d_start = (uint64_t *)ranges.p, *d_end = d_start + n;
-        unsigned long long *d_cnt = (unsigned long long *)cnt.p;
-        hipError_t e = n_words ? hipMemcpy(mask.p, corpus_words, n_words * 8, hipMemcpyDefault) : hipSuccess;
-        if (e == hipSuccess && n) e = hipMemcpy(d_start, start.data(), (size_t)n * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && n) e = hipMemcpy(d_end, end.data(), (size_t)n * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(d_cnt, 0, ((size_t)n + 1) * 8);
-        if (e != hipSuccess) { rc = hip_status(e, "stage corpus statistics", __FILE__, __LINE__); break; }
-        DeletedView del = seg->deleted_view();
-        del.allowed = (const uint64_t *)mask.p;
-        del.n_allowed_bits = n_corpus_bits;
-        if ((rc = launch_sparse_idf_corpus(nullptr, sp->d_post, sp->d_post_id, d_start, d_end, n, longest, del, seg->scan_rows(), d_cnt, d_cnt + n)) != QMX_OK)
-            break;
-        std::vector<unsigned long long> h_cnt((size_t)n + 1);
-        e = hipMemcpy(h_cnt.data(), d_cnt, h_cnt.size() * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = hip_status(e, "corpus statistics", __FILE__, __LINE__); break; }
-        for (uint32_t i = 0; i < n; ++i) df_out[i] = h_cnt[i];
-        *n_docs_out = h_cnt[n];
-    } while (0);
-    mask.release(); ranges.release(); cnt.release();
-    return rc;
+    QMX_TRY(mask.reserve(std::max<size_t>(n_words, 1) * 8));
+    QMX_TRY(ranges.reserve(std::max<size_t>(n, 1) * 16));
+    QMX_TRY(cnt.reserve(((size_t)n + 1) * 8));
+    uint64_t *d_start = (uint64_t *)ranges.p, *d_end = d_start + n;
+    unsigned long long *d_cnt = (unsigned long long *)cnt.p;
+    if (n_words) QMX_HIP(hipMemcpy(mask.p, corpus_words, n_words * 8, hipMemcpyDefault));
+    if (n) QMX_HIP(hipMemcpy(d_start, start.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    if (n) QMX_HIP(hipMemcpy(d_end, end.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    QMX_HIP(hipMemset(d_cnt, 0, ((size_t)n + 1) * 8));
+    DeletedView del = seg->deleted_view();
+    del.allowed = (const uint64_t *)mask.p;
+    del.n_allowed_bits = n_corpus_bits;
+    QMX_TRY(launch_sparse_idf_corpus(nullptr, sp->d_post, sp->d_post_id, d_start, d_end, n, longest, del, seg->scan_rows(), d_cnt, d_cnt + n));
+    std::vector<unsigned long long> h_cnt((size_t)n + 1);
+    QMX_HIP(hipMemcpy(h_cnt.data(), d_cnt, h_cnt.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; ++i) df_out[i] = h_cnt[i];
+    *n_docs_out = h_cnt[n];
+    return QMX_OK;
 }
 
 // VectorQueryContext::fancy_idf: f32 throughout, f32::ln = libm logf (computed here on the host: the device's logf rounds differently)

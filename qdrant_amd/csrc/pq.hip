@@ -14,6 +14,7 @@
 // chain, so <= 1e-5 relative to the reference's mul+add chain; the exact-order VALU kernel is the
 // bit-parity variant).
 #include "hnsw_build.hpp"
+#include "dev_mem.hpp"
 
 namespace qmx {
 
@@ -1017,43 +1018,36 @@ int32_t launch_pq_train(hipStream_t st, uint32_t dim, uint32_t chunk_size, uint3
     if (threads == 0) threads = 1;
     // first-k init (kmeans.rs:27): centroid j = sample row j, every chunk
     QMX_HIP(hipMemcpyAsync(d_centroids, d_data, (size_t)n_centroids * dim * sizeof(float), hipMemcpyDeviceToDevice, st));
-    uint8_t *d_codes = nullptr, *d_done = nullptr;
-    float *d_abs = nullptr;
-    uint32_t *d_iters = nullptr;
+    DevBuf b_codes, b_done, b_abs, b_iters;
     const size_t n_thr = (size_t)g.m * n_centroids * chunk_size;
-    int32_t rc = QMX_OK;
-    do {
-        if (hipMalloc((void **)&d_codes, (size_t)n * g.m) != hipSuccess || hipMalloc((void **)&d_done, g.m) != hipSuccess ||
-            hipMalloc((void **)&d_abs, n_thr * sizeof(float)) != hipSuccess || hipMalloc((void **)&d_iters, (size_t)g.m * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("out of device memory for k-means scratch");
-            rc = QMX_ERR_OUT_OF_MEMORY;
-            break;
+    QMX_TRY(b_codes.reserve((size_t)n * g.m));
+    QMX_TRY(b_done.reserve(g.m));
+    QMX_TRY(b_abs.reserve(n_thr * sizeof(float)));
+    QMX_TRY(b_iters.reserve((size_t)g.m * 4));
+    uint8_t *d_codes = (uint8_t *)b_codes.p, *d_done = (uint8_t *)b_done.p;
+    float *d_abs = (float *)b_abs.p;
+    uint32_t *d_iters = (uint32_t *)b_iters.p;
+    QMX_HIP(hipMemsetAsync(d_done, 0, g.m, st));
+    QMX_HIP(hipMemsetAsync(d_iters, 0, (size_t)g.m * 4, st));
+    std::vector<uint8_t> done(g.m);
+    for (uint32_t it = 0; it < max_iters; ++it) {
+        QMX_TRY(launch_pq_encode(st, dim, pq, d_centroids, d_data, n, d_codes));     // update_indexes
+        ::qmx::clear_stale_error();
+        hipLaunchKernelGGL(pq_train_update_kernel, dim3((uint32_t)((n_thr + 255) / 256)), dim3(256), 0, st, g, d_data, n, d_codes, threads,
+                           d_done, d_centroids, d_abs);
+        hipLaunchKernelGGL(pq_train_diff_kernel, dim3((g.m + 63) / 64), dim3(64), 0, st, g, d_abs, accuracy, d_done, d_iters);
+        QMX_HIP(hipGetLastError());
+        if ((it & 3) == 3 || it + 1 == max_iters) {           // all chunks converged?  (poll every 4 iterations)
+            QMX_HIP(hipMemcpyAsync(done.data(), d_done, g.m, hipMemcpyDeviceToHost, st));
+            QMX_HIP(hipStreamSynchronize(st));
+            bool all = true;
+            for (uint8_t d : done) all = all && d;
+            if (all) break;
         }
-        if (hipMemsetAsync(d_done, 0, g.m, st) != hipSuccess || hipMemsetAsync(d_iters, 0, (size_t)g.m * 4, st) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-        std::vector<uint8_t> done(g.m);
-        for (uint32_t it = 0; it < max_iters && rc == QMX_OK; ++it) {
-            if ((rc = launch_pq_encode(st, dim, pq, d_centroids, d_data, n, d_codes)) != QMX_OK) break;     // update_indexes
-            ::qmx::clear_stale_error();
-            hipLaunchKernelGGL(pq_train_update_kernel, dim3((uint32_t)((n_thr + 255) / 256)), dim3(256), 0, st, g, d_data, n, d_codes, threads,
-                               d_done, d_centroids, d_abs);
-            hipLaunchKernelGGL(pq_train_diff_kernel, dim3((g.m + 63) / 64), dim3(64), 0, st, g, d_abs, accuracy, d_done, d_iters);
-            if (hipGetLastError() != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-            if ((it & 3) == 3 || it + 1 == max_iters) {           // all chunks converged?  (poll every 4 iterations)
-                if (hipMemcpyAsync(done.data(), d_done, g.m, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = QMX_ERR_OTHER; break; }
-                bool all = true;
-                for (uint8_t d : done) all = all && d;
-                if (all) break;
-            }
-        }
-        if (rc == QMX_OK && iters_host && hipMemcpyAsync(iters_host, d_iters, (size_t)g.m * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = QMX_ERR_OTHER;
-        if (rc == QMX_OK && hipStreamSynchronize(st) != hipSuccess) rc = QMX_ERR_OTHER;
-    } while (0);
-    if (d_codes) (void)hipFree(d_codes);
-    if (d_done) (void)hipFree(d_done);
-    if (d_abs) (void)hipFree(d_abs);
-    if (d_iters) (void)hipFree(d_iters);
-    return rc;
+    }
+    if (iters_host) QMX_HIP(hipMemcpyAsync(iters_host, d_iters, (size_t)g.m * 4, hipMemcpyDeviceToHost, st));
+    QMX_HIP(hipStreamSynchronize(st));
+    return QMX_OK;
 }
 
 }  // namespace qmx

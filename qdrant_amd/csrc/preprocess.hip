@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "dev_mem.hpp"
 
 namespace qmx {
 
@@ -258,21 +259,20 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float *in, uint64_t c
     }
 }
 int32_t launch_minmax_f32(hipStream_t st, const float *in, uint64_t count, float *min_out, float *max_out) {
-    uint32_t *d = nullptr;
-    QMX_HIP(hipMalloc((void **)&d, 8));
+    DevBuf acc;
+    QMX_TRY(acc.reserve(8));
+    uint32_t *d = (uint32_t *)acc.p;
     // host-side images of score_to_ord(f32::MAX) and score_to_ord(f32::MIN)
     const uint32_t init[2] = {0x7F7FFFFFu | 0x80000000u, ~0xFF7FFFFFu};
-    hipError_t e = hipMemcpyAsync(d, init, 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && count) {
+    QMX_HIP(hipMemcpyAsync(d, init, 8, hipMemcpyHostToDevice, st));
+    if (count) {
         ::qmx::clear_stale_error();
         hipLaunchKernelGGL(minmax_kernel, dim3(2048), dim3(256), 0, st, in, count, d);
-        e = hipGetLastError();
+        QMX_HIP(hipGetLastError());
     }
     uint32_t res[2] = {init[0], init[1]};
-    if (e == hipSuccess) e = hipMemcpyAsync(res, d, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d);
-    QMX_HIP(e);
+    QMX_HIP(hipMemcpyAsync(res, d, 8, hipMemcpyDeviceToHost, st));
+    QMX_HIP(hipStreamSynchronize(st));
     auto unord = [](uint32_t o) {
         union { uint32_t u; float f; } cv;
         cv.u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;

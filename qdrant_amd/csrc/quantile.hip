@@ -9,6 +9,7 @@
 // (`take_random_vectors`, Permutor): the sample is an input here, as the k-means sample of PQ is.  Given the sample the result
 // is a pure order statistic: exact on any implementation (a full radix sort of <= 5 000 x dim floats here).
 #include "kernels.hpp"
+#include "dev_mem.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -19,14 +20,12 @@ int32_t launch_order_statistics_f32(hipStream_t st, const float *d_in, float *d_
     size_t tmp_bytes = 0;
     ::qmx::clear_stale_error();
     QMX_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_in, d_tmp, (size_t)n, 0, 32, st));
-    void *d_work = nullptr;
-    QMX_HIP(hipMalloc(&d_work, tmp_bytes ? tmp_bytes : 16));
-    hipError_t e = rocprim::radix_sort_keys(d_work, tmp_bytes, d_in, d_tmp, (size_t)n, 0, 32, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_out[0], d_tmp + lo_pos, sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_out[1], d_tmp + hi_pos, sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_work);
-    QMX_HIP(e);
+    DevBuf work;
+    QMX_TRY(work.reserve(tmp_bytes));
+    QMX_HIP(rocprim::radix_sort_keys(work.p, tmp_bytes, d_in, d_tmp, (size_t)n, 0, 32, st));
+    QMX_HIP(hipMemcpyAsync(&h_out[0], d_tmp + lo_pos, sizeof(float), hipMemcpyDeviceToHost, st));
+    QMX_HIP(hipMemcpyAsync(&h_out[1], d_tmp + hi_pos, sizeof(float), hipMemcpyDeviceToHost, st));
+    QMX_HIP(hipStreamSynchronize(st));
     return QMX_OK;
 }
 

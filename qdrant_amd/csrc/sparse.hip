@@ -7,6 +7,7 @@
 // order from 0.0, each add rounded (`__fadd_rn`).  No fused multiply-add, no atomics on scores.
 #include "custom_combine.hpp"
 #include "kernels.hpp"
+#include "dev_mem.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_run_length_encode.hpp>
@@ -139,37 +140,22 @@ int32_t sparse_build_postings(hipStream_t st, const uint64_t *offsets, const uin
         return QMX_OK;
     }
     QMX_REQUIRE(nnz <= 0xFFFFFFFFull, QMX_ERR_NOT_SUPPORTED, "a sparse segment holds at most 2^32 - 1 non-zeros (got %llu)", (unsigned long long)nnz);
-    uint64_t *payload = nullptr;
-    uint32_t *keys_sorted = nullptr;
-    void *tmp = nullptr;
-    int32_t rc = QMX_OK;
-    auto fail = [&](hipError_t e, const char *what) { rc = hip_status(e, what, __FILE__, __LINE__); };
-    do {
-        hipError_t e = hipMalloc(&payload, nnz * 8);
-        if (e != hipSuccess) { fail(e, "hipMalloc(payload)"); break; }
-        e = hipMalloc(&keys_sorted, nnz * 4);
-        if (e != hipSuccess) { fail(e, "hipMalloc(keys)"); break; }
-        ::qmx::clear_stale_error();
-        hipLaunchKernelGGL(sparse_post_payload_kernel, dim3(blocks_of(n)), dim3(SP_BLOCK), 0, st, offsets, val, n, payload);
-        if ((e = hipGetLastError()) != hipSuccess) { fail(e, "sparse_post_payload_kernel"); break; }
-        size_t sort_bytes = 0, rle_bytes = 0;
-        e = rocprim::radix_sort_pairs(nullptr, sort_bytes, idx, keys_sorted, payload, post, (size_t)nnz, 0, 32, st);
-        if (e == hipSuccess) e = rocprim::run_length_encode(nullptr, rle_bytes, keys_sorted, (unsigned int)nnz, dims, counts, n_dims_dev, st);
-        if (e != hipSuccess) { fail(e, "rocprim temporary storage"); break; }
-        size_t tmp_bytes = std::max(sort_bytes, rle_bytes);
-        e = hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 16));
-        if (e != hipSuccess) { fail(e, "hipMalloc(sort scratch)"); break; }
-        e = rocprim::radix_sort_pairs(tmp, sort_bytes, idx, keys_sorted, payload, post, (size_t)nnz, 0, 32, st);
-        if (e != hipSuccess) { fail(e, "rocprim::radix_sort_pairs"); break; }
-        e = rocprim::run_length_encode(tmp, rle_bytes, keys_sorted, (unsigned int)nnz, dims, counts, n_dims_dev, st);
-        if (e != hipSuccess) { fail(e, "rocprim::run_length_encode"); break; }
-        e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { fail(e, "posting build"); break; }
-    } while (0);
-    if (payload) (void)hipFree(payload);
-    if (keys_sorted) (void)hipFree(keys_sorted);
-    if (tmp) (void)hipFree(tmp);
-    return rc;
+    DevBuf b_payload, b_keys, tmp;
+    QMX_TRY(b_payload.reserve(nnz * 8));
+    QMX_TRY(b_keys.reserve(nnz * 4));
+    uint64_t *payload = (uint64_t *)b_payload.p;
+    uint32_t *keys_sorted = (uint32_t *)b_keys.p;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sparse_post_payload_kernel, dim3(blocks_of(n)), dim3(SP_BLOCK), 0, st, offsets, val, n, payload);
+    QMX_HIP(hipGetLastError());
+    size_t sort_bytes = 0, rle_bytes = 0;
+    QMX_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, idx, keys_sorted, payload, post, (size_t)nnz, 0, 32, st));
+    QMX_HIP(rocprim::run_length_encode(nullptr, rle_bytes, keys_sorted, (unsigned int)nnz, dims, counts, n_dims_dev, st));
+    QMX_TRY(tmp.reserve(std::max(sort_bytes, rle_bytes)));
+    QMX_HIP(rocprim::radix_sort_pairs(tmp.p, sort_bytes, idx, keys_sorted, payload, post, (size_t)nnz, 0, 32, st));
+    QMX_HIP(rocprim::run_length_encode(tmp.p, rle_bytes, keys_sorted, (unsigned int)nnz, dims, counts, n_dims_dev, st));
+    QMX_HIP(hipStreamSynchronize(st));
+    return QMX_OK;
 }
 
 // ---- gather scoring (RawScorer) ----
