@@ -103,10 +103,7 @@ int32_t qmx_custom_hnsw_search(const qmx_hnsw *g, qmx_query *ex, const qmx_custo
     QMX_HIP(hipSetDevice(ex->device));
     if (counters) memset(counters, 0, sizeof(*counters));
     if (n_queries == 0) return QMX_OK;
-    if (is_stopped && *is_stopped) {
-        set_error("search cancelled");
-        return QMX_ERR_CANCELLED;
-    }
+    QMX_CHECK_CANCELLED(is_stopped);
     uint32_t max_examples = 0;
     QMX_TRY(custom_validate(ex, queries, n_queries, ex->nq, &max_examples));
     const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);

@@ -1001,10 +1001,7 @@ int32_t hnsw_search_sync(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t
     QMX_HIP(hipSetDevice(q->device));
     if (counters) memset(counters, 0, sizeof(*counters));
     if (q->nq == 0) return QMX_OK;
-    if (is_stopped && *is_stopped) {
-        set_error("search cancelled");
-        return QMX_ERR_CANCELLED;
-    }
+    QMX_CHECK_CANCELLED(is_stopped);
     if (g->n_points == 0) {   // get_entry_point() -> None -> empty result (graph_layers.rs:539-542)
         if (is_device_ptr(out_counts)) QMX_HIP(hipMemset(out_counts, 0, (size_t)q->nq * 4));
         else memset(out_counts, 0, (size_t)q->nq * 4);
@@ -1108,10 +1105,7 @@ int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_qu
     if (counters) memset(counters, 0, sizeof(*counters));
     const uint32_t nq = links->nq;
     if (nq == 0) return QMX_OK;
-    if (is_stopped && *is_stopped) {
-        set_error("search cancelled");
-        return QMX_ERR_CANCELLED;
-    }
+    QMX_CHECK_CANCELLED(is_stopped);
     if (g->n_points == 0) {
         if (is_device_ptr(out_counts)) QMX_HIP(hipMemset(out_counts, 0, (size_t)nq * 4));
         else memset(out_counts, 0, (size_t)nq * 4);
@@ -1149,10 +1143,7 @@ int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_qu
         // (the walk is deterministic: the second run pops the same candidates, now all listed; a count above n_points + 1 cannot be)
         QMX_REQUIRE(xcap < g->n_points + 1u, QMX_ERR_OTHER, "a search popped %u candidates of a graph of %u points", worst, g->n_points);
         xcap = (uint32_t)std::min<uint64_t>((uint64_t)g->n_points + 1, worst);
-        if (is_stopped && *is_stopped) {
-            set_error("search cancelled");
-            return QMX_ERR_CANCELLED;
-        }
+        QMX_CHECK_CANCELLED(is_stopped);
     }
     // base_search_context: FixedLengthPriorityQueue(ef) over the base scores of the popped candidates, into_iter_sorted().take(top)
     QMX_TRY(qmx_rescore(base, (const uint32_t *)links->cand_ids.p, (const uint32_t *)links->xcnt.p, xcap, top, out, out_counts));

@@ -228,6 +228,14 @@ static inline int32_t refuse_sparse(const char *fn) {
     do {                                                     \
         if (is_sparse(x)) return refuse_sparse(__func__);    \
     } while (0)
+// the caller's cancellation flag, read between the launches of a search
+#define QMX_CHECK_CANCELLED(is_stopped)                      \
+    do {                                                     \
+        if ((is_stopped) && *(is_stopped)) {                 \
+            set_error("search cancelled");                   \
+            return QMX_ERR_CANCELLED;                        \
+        }                                                    \
+    } while (0)
 
 
 // f32 dot / cosine rows of >= 32 elements scan 8..32 queries per pass on the f32 matrix cores (scan_mfma.hip)
@@ -369,6 +377,7 @@ constexpr uint32_t SPLIT_FQT = 64;          // queries per conditional exact pas
 // device block behind qmx_query::sp_plan: what the prefilter of one search did and which of its queries take the exact scan after all
 struct SplitPlanLayout {
     size_t count, run16, run64, tile_ovf, ovf_q, zero_bytes, list, gthr_packed, bytes;   // byte offsets (SplitStats sits at 0)
+    static constexpr size_t pool_used = 24;      // ... the fill level of the verification pool (VerifyPool::used), behind SplitStats
     uint32_t n_run64, list_cap;
     explicit SplitPlanLayout(uint32_t nq, uint32_t fqt = SPLIT_FQT) {      // fqt: queries per conditional exact pass (64; 32 for rows the 64-query shape does not take)
         n_run64 = (nq + fqt - 1) / fqt;
@@ -380,6 +389,27 @@ struct SplitPlanLayout {
         list = (zero_bytes + 7) / 8 * 8;
         gthr_packed = (list + (size_t)list_cap * 4 + 7) / 8 * 8;
         bytes = gthr_packed + (size_t)list_cap * 8;
+    }
+};
+
+// qmx_query::sp_f32 of a prefilter search: arrays of SPLIT_QT_MAX floats, one entry per query of the tile.  The pack, scan, refine and select kernels of a
+// route hand them to each other and index them themselves; which array sits where is fixed here.
+struct SplitF32 {
+    static constexpr size_t floats = 5 * SPLIT_QT_MAX, floats_wide = 4 * SPLIT_QT_MAX;      // f32 split / int8 copy; SQ / TQ wide and PQ
+    float *qnorm, *thr, *band, *scales, *qmax;      // f32 split: |q|, the reject thresholds, the error bands, the accumulator scales, max |q_i|
+    float *i8_texact, *i8_qscale;                   // int8 copy: the exact k-th best so far (in qnorm's place), the queries' scales (in qmax's); thr and band as above
+    float *wide_qinfo, *wide_high;                  // SQ / TQ wide: per-query terms [2 * SPLIT_QT_MAX] (the high-digit bounds of TurboQuant from entry 3 * SPLIT_QT on); band as above
+    int32_t *wide_thr;                              // ... the integer bounds on the whole sum, then on the high sum alone
+    float *pq_band;                                 // PQ prefilter: the bands in units of the integer score
+    explicit SplitF32(void *p) {
+        float *f = (float *)p;
+        qnorm = i8_texact = wide_qinfo = pq_band = f;
+        thr = f + SPLIT_QT_MAX;
+        band = f + 2 * SPLIT_QT_MAX;
+        scales = f + 3 * SPLIT_QT_MAX;
+        wide_thr = (int32_t *)scales;
+        qmax = i8_qscale = f + 4 * SPLIT_QT_MAX;
+        wide_high = f + 3 * SPLIT_QT;
     }
 };
 

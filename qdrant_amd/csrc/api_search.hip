@@ -1,11 +1,116 @@
 // api_search.hip — the C-ABI of include/qdrant_amd.h, brute-force top-k: the exact scans, the prefilters, the merge, the oversampled quantized search.
 // (One of the api_*.hip translation units; what they share: api_internal.hpp.)
+// search_enqueue: search_plan decides the route once, then one function per route runs - tq_l1_search, pq_prefilter_search, wide_exact_search (SQ / TQ), and per
+// tile of the f32 / exact driver split_tile (f16_split_scan | i8_copy_scan) or exact_tile.  The prefilter routes share one skeleton, each step written once:
+// prefilter_begin (plan block, verification pool, sample), bound_enqueue, the route's approximate pass, verify_and_sort, overflow_passes, close_counters.
 #include "api_internal.hpp"
 
 extern "C" {
 
+// what one search_enqueue carries to its route: the caller's arguments, and the launches counted so far (qmx_counters::kernel_launches)
+struct SearchCall {
+    qmx_query *q;
+    uint32_t top;
+    const uint32_t *d_ids;
+    uint64_t n_cand;      // rows of the id list, or of the block
+    qmx_scored_point *d_out;
+    uint32_t *d_counts;
+    const volatile uint8_t *is_stopped;
+    qmx_counters *counters;
+    bool timed;
+    uint32_t launches;
+};
 
+// the arguments of a scan of the whole candidate set for queries tile0 .. tile0 + nq_tile
+static ScanArgs tile_args(const qmx_query *q, uint32_t top, uint64_t n_cand, uint32_t tile0, uint32_t nq_tile) {
+    ScanArgs a;
+    fill_args(q, tile0, nq_tile, a);
+    a.n_cand = n_cand;
+    a.top = top;
+    return a;
+}
+static ScanArgs tile_args(const SearchCall &c, uint32_t tile0, uint32_t nq_tile) { return tile_args(c.q, c.top, c.n_cand, tile0, nq_tile); }
 
+// a scoring launch between the events of timing mode; the kernel it noted is what qmx_query_last_kernel reports
+#define QMX_TIMED_SCAN(c, launch)                                  \
+    do {                                                           \
+        size_t slot__ = 0;                                         \
+        if ((c).timed) QMX_TRY(timing_begin((c).q, &slot__));      \
+        QMX_TRY(launch);                                           \
+        (c).q->last_kernel = last_noted_kernel();                  \
+        if ((c).timed) QMX_TRY(timing_end((c).q, slot__));         \
+    } while (0)
+
+// ---- the route of a search, decided once ----
+constexpr uint32_t PQF_TILE = 256;          // PQ prefilter: queries per pass (64 four-query groups; the regroup kernel's histogram)
+constexpr uint32_t PQF_WCAP = 512;          // ... candidates one wave may list per pass (expected: tens)
+constexpr uint32_t TQW_FQT = 32;            // SQ / TQ wide: queries per conditional exact pass
+
+enum SearchRoute {
+    ROUTE_TQ_L1,          // Manhattan TurboQuant: the score matrix, one block per query selects
+    ROUTE_PQ_PREFILTER,   // pq_prefilter.hip
+    ROUTE_TQ_WIDE,        // scan_tq4w.hip
+    ROUTE_SQ_WIDE,        // scan_sqw.hip
+    ROUTE_SPLIT_ROWS,     // scan_split.hip over the f32 rows themselves (more than 64 queries)
+    ROUTE_SPLIT_F16,      // ... over an f16 copy (QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY)
+    ROUTE_I8_COPY,        // ... over the int8 copy (QMX_SEG_I8_COPY)
+    ROUTE_EXACT,          // tiles of the exact scans
+};
+struct SearchPlan {
+    SearchRoute route;
+    uint32_t tile_q;           // queries per tile of the route's loop
+    uint32_t split_qt;         // the split shape: SPLIT_QT, or SPLIT_QT_MAX over a half copy
+    uint32_t split_fqt;        // queries per conditional exact pass behind the f32 prefilters
+    uint32_t n_pass;           // exact tiles: passes of MAX_TOP_FAST entries
+    uint32_t split_min_tile;   // a tile of at least this many queries takes the split route, a smaller (remainder) tile the exact one
+    bool split() const { return route == ROUTE_SPLIT_ROWS || route == ROUTE_SPLIT_F16 || route == ROUTE_I8_COPY; }
+    bool tile_splits(uint32_t nq_tile) const { return split() && nq_tile >= split_min_tile; }
+};
+
+// (host arithmetic over the handles and the options: no HIP call, no allocation)
+static SearchPlan search_plan(const qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64_t n_cand) {
+    const qmx_segment *s = q->seg;
+    SearchPlan p{ROUTE_EXACT, 0, SPLIT_QT, SPLIT_FQT, (top + MAX_TOP_FAST - 1) / MAX_TOP_FAST, 0};
+    auto whole = [&p](SearchRoute route, uint32_t tile_q) {      // a route that serves the whole batch in tiles of its own
+        p.route = route;
+        p.tile_q = tile_q;
+        return p;
+    };
+    // (tiles of queries: at most 256 MiB of scores at a time)
+    if (tq_l1(s)) return whole(ROUTE_TQ_L1, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(q->nq, (1ull << 26) / std::max<uint64_t>(n_cand, 1))));
+    if (s->dtype == QMX_DTYPE_PQ && s->d_pq_rot && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && !option(OPT_NO_PQ_PREFILTER) &&
+        q->nq >= (uint32_t)std::max<int64_t>(1, option(OPT_PQ_PREFILTER_MIN_QUERIES)))
+        return whole(ROUTE_PQ_PREFILTER, PQF_TILE);
+    if (s->dtype == QMX_DTYPE_TQ && s->tq_wide && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && mfma_scan_ok(s) && option(OPT_TQ_WIDE_MIN_QUERIES) > 0 &&
+        q->nq >= (uint32_t)option(OPT_TQ_WIDE_MIN_QUERIES) && (size_t)MAX_QT_MFMA * q->q_stride <= 150 * 1024 && tq4w_shape_ok(tile_args(q, top, n_cand, 0, std::min<uint32_t>(q->nq, SPLIT_QT))))
+        return whole(ROUTE_TQ_WIDE, SPLIT_QT);
+    if (s->dtype == QMX_DTYPE_SQ_U8 && s->sq_wide && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && mfma_scan_ok(s) && option(OPT_SQ_WIDE_MIN_QUERIES) > 0 &&
+        q->nq >= (uint32_t)option(OPT_SQ_WIDE_MIN_QUERIES) && sqw_shape_ok(tile_args(q, top, n_cand, 0, std::min<uint32_t>(q->nq, SPLIT_QT))))
+        return whole(ROUTE_SQ_WIDE, SPLIT_QT);
+    // f32 dot / cosine rows of 256, 512 or 768 floats, whole block: 64 queries per pass (scan_mfma16.hip); everything else 32 / 16
+    const bool q64 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && q->nq > MAX_QT_MFMA && mfma16_dim_ok(64, s->dim) && !option(OPT_NO_MFMA16);
+    // ... and rows of 1024 .. 1536 floats 32 per pass: that kernel keeps the queries in registers, not in an LDS tile (tile_qt's limit)
+    const bool q32 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && q->nq > MAX_QT && s->dim > 768 && mfma16_dim_ok(32, s->dim) && !option(OPT_NO_MFMA16);
+    // more than 64 queries over a large f32 dot / cosine block: 128 per pass through the f16-split matrix-core prefilter, the survivors
+    // re-scored exactly (scan_split.hip); the result is the exact scan's, bit for bit
+    // ... and with a derived copy of the block (QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY) that path serves EVERY batch size: it streams 2 (4) bytes
+    // per element instead of 4 and is HBM-bound whatever the number of queries (10 M x 768: 3.0 ms per pass against 4.4 ms for the f32 stream)
+    // (rows of up to 768 floats: conditional exact passes of 64 queries; up to 2 048 floats - 1 024, 1 536: the 32-query shape - only over a derived copy)
+    const uint32_t split_fqt = split_fallback_qt(s->dim);
+    const bool split_dims = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && (mfma16_dim_ok(64, s->dim) || (s->d_rows_split && split_fqt != 0)) && !option(OPT_NO_MFMA16);
+    const bool split = split_dims && (q64 || (s->d_rows_split && q->nq >= (uint32_t)std::max<int64_t>(1, option(OPT_SPLIT_MIN_QUERIES)))) && s->split_stats &&
+                       !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && s->dim % 128 == 0 && s->row_stride % 16 == 0 && !option(OPT_NO_SPLIT_SCAN);
+    // the 256-query shape halves the bytes streamed per query; a batch that does not fill it is served by the 128-query shape (less matrix work)
+    if (split && s->d_rows_split && s->split_half && q->nq > SPLIT_QT && !option(OPT_NO_SPLIT256)) p.split_qt = SPLIT_QT_MAX;
+    if (split_fqt) p.split_fqt = split_fqt;
+    if (split) p.route = s->split_i8 ? ROUTE_I8_COPY : s->d_rows_split ? ROUTE_SPLIT_F16 : ROUTE_SPLIT_ROWS;
+    // (without a copy the prefilter pays from 65 queries on: a remainder tile of at most 64 takes the exact scan)
+    p.split_min_tile = s->d_rows_split ? 1 : MAX_QT_TOPK + 1;
+    p.tile_q = split ? p.split_qt : q64 ? MAX_QT_TOPK : q32 ? MAX_QT_MFMA : tile_qt(s, q);
+    return p;
+}
+
+// ---- the steps the routes share ----
 // triage aid (qmx_set_option("debug", 2)): synchronise after every stage of the split path and name it on stderr
 static int32_t split_stage(qmx_query *q, const char *what) {
     if (option(OPT_DEBUG) < 2) return QMX_OK;
@@ -17,22 +122,301 @@ static int32_t split_stage(qmx_query *q, const char *what) {
 }
 
 // the verification pool of a search (kernels.hpp VerifyPool): SPLIT_VCAP entries per query of the batch, shared - behind qmx_query::sp_ver as
-// [ids: cap][qsel: cap][off: nq][cnt: nq], exact scores in sp_vscores, the fill level in the plan block (byte 24: zeroed with it at the start of a search)
+// [ids: cap][qsel: cap][off: nq][cnt: nq], exact scores in sp_vscores, the fill level in the plan block (zeroed with it at the start of a search)
 static int32_t verify_pool(qmx_query *q, unsigned char *plan, VerifyPool *vp) {
     const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((uint64_t)q->nq * SPLIT_VCAP, 262144), 1u << 26);
     QMX_TRY(q->sp_ver.reserve(((size_t)cap * 2 + (size_t)q->nq * 2) * 4));
     QMX_TRY(q->sp_vscores.reserve((size_t)cap * 4));
     uint32_t *b = (uint32_t *)q->sp_ver.p;
-    vp->ids = b;
-    vp->qsel = b + cap;
-    vp->off = b + (size_t)2 * cap;
-    vp->cnt = vp->off + q->nq;
-    vp->used = (uint32_t *)(plan + 24);
-    vp->cap = cap;
     const int64_t mx = option(OPT_VERIFY_MAX_PER_QUERY);
-    vp->max_per_query = mx > 0 ? (uint32_t)std::min<int64_t>(mx, cap) : cap;
+    *vp = VerifyPool{b, b + cap, b + (size_t)2 * cap, b + (size_t)2 * cap + q->nq, (uint32_t *)(plan + SplitPlanLayout::pool_used), cap,
+                     mx > 0 ? (uint32_t)std::min<int64_t>(mx, cap) : cap};
     return QMX_OK;
 }
+
+// ids of a strided sample of the candidates (rows 0, step, 2 step, ...): a sample that sees the whole block, whatever its order
+__global__ void sample_ids_kernel(uint32_t *ids, uint32_t n, uint64_t step) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ids[i] = (uint32_t)((uint64_t)i * step);
+}
+
+// what a prefilter search starts with: the plan block and the verification pool behind it, then the sample - every 2^(prescan_shift + shift)-th row,
+// at least 8 192 rows, its id list kept across searches of the same block size - and the zeros of the plan block.  Returns the sample's size.
+static int32_t prefilter_begin(qmx_query *q, const SplitPlanLayout &pl, uint64_t n_cand, int shift, VerifyPool *vp, uint64_t *S_out) {
+    QMX_TRY(q->sp_plan.reserve(pl.bytes));
+    QMX_TRY(verify_pool(q, (unsigned char *)q->sp_plan.p, vp));
+    const int sshift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT) + shift, 1), 20);
+    const uint64_t S = std::min<uint64_t>(n_cand, std::max<uint64_t>(n_cand >> sshift, 8192));
+    if (q->sp_sample_n != S || q->sp_sample_of != n_cand) {
+        QMX_TRY(q->sp_sample.reserve((size_t)S * 4));
+        ::qmx::clear_stale_error();
+        hipLaunchKernelGGL(sample_ids_kernel, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, q->stream, (uint32_t *)q->sp_sample.p, (uint32_t)S, n_cand / S);
+        QMX_HIP(hipGetLastError());
+        q->sp_sample_n = S;
+        q->sp_sample_of = n_cand;
+    }
+    QMX_HIP(hipMemsetAsync(q->sp_plan.p, 0, pl.zero_bytes, q->stream));
+    *S_out = S;
+    return QMX_OK;
+}
+
+// exact scores of `n` candidates (the score-mode kernels, <= tile_qt queries per launch) -> one block per query selects its k best live ones; the k-th
+// becomes the tile's bound in gthr, a lower bound of the final k-th best: of a prefilter's sample, of the prefix an exact tile scans first
+static int32_t bound_enqueue(const SearchCall &c, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, uint32_t ktop, const DeletedView &del,
+                             uint32_t *launches) {
+    qmx_query *q = c.q;
+    QMX_TRY(q->scores.reserve((size_t)nq_tile * n * sizeof(float)));
+    QMX_TRY(score_matrix_enqueue(q, tile0, nq_tile, d_ids, n, (float *)q->scores.p, n, launches));
+    // (the bound at the tile's own offset: the bounds of earlier split tiles are read again by the plan of their exact passes)
+    return launch_custom_topk(q->stream, (const float *)q->scores.p, n, d_ids, del, nq_tile, ktop, c.d_out + (size_t)tile0 * c.top, c.d_counts + tile0,
+                              (uint64_t *)q->gthr.p + tile0);
+}
+
+// exact scores of the pool's rows (the pair kernels: the reference's bits), sorted by (score, lower id first) into the lists of queries 0 .. nq
+static int32_t verify_and_sort(const SearchCall &c, const VerifyPool &vp, uint32_t nq) {
+    qmx_query *q = c.q;
+    const void *scan_kernel = q->last_kernel;      // (the pair kernel is not what the search reports)
+    PairSel sel{vp.qsel, 0, nullptr, vp.used};
+    QMX_TRY(score_pairs_device(q, sel, vp.ids, vp.cap, (float *)q->sp_vscores.p, false));
+    q->last_kernel = scan_kernel;
+    QMX_TRY(split_stage(q, "verify gather"));
+    QMX_TRY(launch_sort_scored(q->stream, (const float *)q->sp_vscores.p, vp.ids, vp.cnt, 0, nq, c.top, c.d_out, c.d_counts, vp.off));
+    return split_stage(q, "verify sort");
+}
+
+// the exact top-k scan of `fqt` packed queries: what overflow_passes launches
+typedef int32_t (*OverflowScan)(hipStream_t st, int fqt, const ScanArgs &a, int num_cus, uint32_t *grid);
+static int32_t overflow_scan_f32(hipStream_t st, int fqt, const ScanArgs &a, int num_cus, uint32_t *grid) {
+    QMX_REQUIRE(mfma16_scan_ok(fqt, SCAN_TOPK, a), QMX_ERR_OTHER, "split fallback shape");
+    return launch_scan_f32_mfma16(st, fqt, a, num_cus, grid);
+}
+static int32_t overflow_scan_sq(hipStream_t st, int fqt, const ScanArgs &a, int num_cus, uint32_t *grid) { return launch_scan_sq_mfma(st, fqt, SCAN_TOPK, a, num_cus, grid); }
+static int32_t overflow_scan_tq(hipStream_t st, int fqt, const ScanArgs &a, int num_cus, uint32_t *grid) { return launch_scan_tq_mfma(st, fqt, SCAN_TOPK, a, num_cus, grid); }
+
+// the exact scan of the queries (of 0 .. nq) whose lists overflowed - masses of near-equal scores, a sample that is all deleted -, and of those only:
+// packed, one 16-query pass when 1..16 of them, passes of FQT otherwise.  The kernels start, read their flag and return when it is clear.
+static int32_t overflow_passes(const SearchCall &c, const SplitPlanLayout &pl, uint32_t nq, uint32_t FQT, OverflowScan scan, uint32_t *launches) {
+    qmx_query *q = c.q;
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
+    uint64_t *gthr_packed = (uint64_t *)(plan + pl.gthr_packed);
+    const uint32_t n_run = (nq + FQT - 1) / FQT;
+    QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), nq, (const uint64_t *)q->gthr.p, ovf_list, gthr_packed, n_run * FQT,
+                              (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), n_run, (SplitStats *)plan, q->d_queries,
+                              q->q_stride, q->sp_fq.p));
+    for (uint32_t pass = 0; pass <= n_run; ++pass) {      // pass 0: the 16-query shape; pass p >= 1: packed queries FQT (p - 1) ..
+        if (pass && nq <= 16) break;
+        const uint32_t p0 = pass ? (pass - 1) * FQT : 0;
+        const uint32_t nq_sub = pass ? std::min<uint32_t>(FQT, nq - p0) : std::min<uint32_t>(16, nq);
+        const int *run_if = pass ? (const int *)(plan + pl.run64) + (pass - 1) : (const int *)(plan + pl.run16);
+        ScanArgs a = tile_args(c, 0, nq_sub);
+        a.queries = (const char *)q->sp_fq.p + (size_t)p0 * q->q_stride;
+        a.partial = (uint64_t *)q->partial.p;
+        a.gthr = gthr_packed + p0;
+        a.run_if = run_if;
+        const int fqt = (int)std::max<uint32_t>(16, pow2_ceil(nq_sub));
+        a.partial_qt = (uint32_t)fqt;
+        uint32_t grid = (uint32_t)q->seg->num_cus * 8;
+        QMX_TRY(scan(q->stream, fqt, a, q->seg->num_cus, &grid));
+        QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, (uint32_t)fqt, nq_sub, c.top, c.d_out, c.d_counts, c.top, 0, nullptr, run_if,
+                                  ovf_list + p0));
+        if (launches) *launches += 2;
+    }
+    return split_stage(q, "fallback (conditional)");
+}
+
+// the PQ form of the same: the exact PQ kernel takes the overflowed queries through q_map, one launch over slabs of the block
+static int32_t pq_overflow_pass(const SearchCall &c, const SplitPlanLayout &pl) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
+    QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), q->nq, (const uint64_t *)q->gthr.p, ovf_list, (uint64_t *)(plan + pl.gthr_packed),
+                              pl.list_cap, (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), pl.n_run64, (SplitStats *)plan, nullptr, 0,
+                              nullptr));
+    ScanArgs a = tile_args(c, 0, q->nq);
+    a.q_map = ovf_list;
+    a.run_if = (const int *)(plan + pl.count);
+    const uint64_t want = (c.n_cand + 1023) / 1024, cap = std::max<uint64_t>(1, ((uint64_t)s->num_cus * 2 + q->nq - 1) / q->nq);
+    uint32_t slabs = (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
+    QMX_TRY(q->partial.reserve((size_t)slabs * q->nq * c.top * sizeof(uint64_t)));
+    a.partial = (uint64_t *)q->partial.p;
+    a.partial_qt = q->nq;
+    QMX_TRY(launch_scan_pq(q->stream, SCAN_TOPK, a, s->num_cus, &slabs));
+    return launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, slabs, q->nq, q->nq, c.top, c.d_out, c.d_counts, c.top, 0, nullptr, a.run_if, ovf_list,
+                             slabs * q->nq);
+}
+
+// what the host knows of a search at enqueue -> qmx_query::last_counters and the caller's; the prefilter's own share (candidates, verified rows, exact
+// passes of overflowed queries) is on the device until the stream is synchronised: fold_split_counters
+static void close_counters(const SearchCall &c, uint64_t vectors_scored, uint64_t bytes_read, uint64_t launches, uint32_t prefilter_queries) {
+    qmx_query *q = c.q;
+    qmx_counters &lc = q->last_counters;
+    lc.vectors_scored = vectors_scored;
+    lc.bytes_read = bytes_read;
+    lc.kernel_launches = launches;
+    lc.prefilter_queries = prefilter_queries;
+    q->last_row_bytes = q->seg->row_bytes;
+    q->last_n_cand = c.n_cand;
+    if (c.counters) *c.counters = lc;
+}
+
+// ---- Manhattan TurboQuant: the score matrix of a tile of queries, then one block per query selects its k best live candidates ----
+static int32_t tq_l1_search(const SearchCall &c, const SearchPlan &plan) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    const uint32_t qtile = plan.tile_q;
+    ScanArgs a;
+    fill_args(q, 0, q->nq, a);
+    QMX_TRY(q->scores.reserve((size_t)qtile * std::max<uint64_t>(c.n_cand, 1) * sizeof(float)));
+    for (uint32_t q0 = 0; q0 < q->nq; q0 += qtile) {
+        QMX_CHECK_CANCELLED(c.is_stopped);
+        const uint32_t nq_tile = std::min<uint32_t>(qtile, q->nq - q0);
+        QMX_TRY(tq_l1_scores_device(q, q0, nq_tile, c.d_ids, c.n_cand, (float *)q->scores.p, c.n_cand, nullptr));
+        QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, c.n_cand, c.d_ids, a.del, nq_tile, c.top, c.d_out + (size_t)q0 * c.top, c.d_counts + q0));
+        if (c.counters) c.counters->kernel_launches += 1 + 3 * (uint32_t)((c.n_cand + 65535) / 65536);
+    }
+    if (c.counters) {      // (this route adds to the caller's counters and leaves last_counters at zero)
+        c.counters->vectors_scored += (uint64_t)q->nq * c.n_cand;
+        c.counters->bytes_read += (uint64_t)((q->nq + qtile - 1) / qtile) * c.n_cand * s->row_bytes;
+    }
+    return QMX_OK;
+}
+
+// ---- PQ top-k of 4 and more queries over a large block: the 6-bit prefilter + exact verification (pq_prefilter.hip).  Same contract as the f32
+// prefilter below: the lists are the exact scan's, a query whose lists overflow takes the exact scan alone. ----
+static int32_t pq_prefilter_search(SearchCall &c) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    const SplitPlanLayout pl(q->nq);
+    const uint32_t m = s->pq_m, m_pad = (m + 31) / 32 * 32;
+    const uint32_t tile_max = std::min<uint32_t>(PQF_TILE, q->nq);
+    const uint32_t grid_max = pq_prefilter_grid(s->num_cus, tile_max, nullptr);
+    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, PQF_TILE) * sizeof(uint64_t)));
+    QMX_TRY(q->pq_table.reserve(pq_prefilter_table_bytes(m, tile_max) + (size_t)(PQF_TILE + 4) * 4));
+    QMX_TRY(q->sp_f32.reserve(SplitF32::floats_wide * sizeof(float)));
+    QMX_TRY(q->sp_cand.reserve((size_t)tile_max * SPLIT_CAND_CAP * sizeof(uint64_t)));
+    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
+    {   // (the grid of a smaller last tile may be larger than the first tile's: size for the worst over tile sizes 1..tile_max)
+        uint32_t g = grid_max;
+        for (uint32_t t = 4; t <= tile_max; t += 4) g = std::max(g, pq_prefilter_grid(s->num_cus, t, nullptr));
+        QMX_TRY(q->sp_wl.reserve(pq_prefilter_wlists_bytes(g, PQF_WCAP)));
+    }
+    // the sample (as for the f32 prefilter): its k-th best exact score per query is a lower bound of the final k-th best
+    VerifyPool vp;
+    uint64_t S = 0;
+    QMX_TRY(prefilter_begin(q, pl, c.n_cand, -2, &vp, &S));
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    float *band = SplitF32(q->sp_f32.p).pq_band;       // [PQF_TILE] in units of the integer score
+    uint32_t n_tiles = 0;
+    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += PQF_TILE, ++n_tiles) {
+        const uint32_t nq_tile = std::min<uint32_t>(PQF_TILE, q->nq - tile0);
+        QMX_CHECK_CANCELLED(c.is_stopped);
+        const uint64_t *gthr = (const uint64_t *)q->gthr.p + tile0;
+        const ScanArgs a = tile_args(c, tile0, nq_tile);
+        // 1. exact scores of the sample (the exact kernel's score mode over an id list) -> k-th best per query
+        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches));
+        // 2. the 6-bit tables of the tile's query groups, thresholds and bands in units of the integer score
+        int32_t *thr = (int32_t *)((unsigned char *)q->pq_table.p + pq_prefilter_table_bytes(m, tile_max));
+        QMX_TRY(launch_pq_lut8(q->stream, a.queries, q->q_stride, nq_tile, m, s->pq.n_centroids, gthr, q->pq_table.p, thr, band));
+        QMX_HIP(hipMemsetAsync(q->sp_cnt.p, 0, (size_t)SPLIT_QT_MAX * 4, q->stream));
+        // 3. the approximate scan of the whole block over the rotated copy
+        uint32_t grid = 0;
+        QMX_TIMED_SCAN(c, launch_pq_prefilter(q->stream, a, s->d_pq_rot, q->pq_table.p, thr, nq_tile, s->num_cus, q->sp_wl.p, PQF_WCAP, &grid));
+        // 4. per-wave lists -> per-query lists (deleted rows dropped), then the rows worth an exact score
+        int *tile_ovf = (int *)(plan + pl.tile_ovf) + n_tiles;
+        QMX_TRY(launch_regroup_lists(q->stream, a.del, (const unsigned char *)q->sp_wl.p + pq_prefilter_wlists_counts_bytes(grid), (const uint32_t *)q->sp_wl.p, PQF_WCAP,
+                                     grid * 16, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf));
+        QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, band, nq_tile, c.top, vp, tile0,
+                                    tile_ovf, (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan));
+        c.launches += 6;
+    }
+    // 5. exact scores of the survivors (pq_pair_kernel: score_point_sse's order), sorted; 6. the exact scan of the queries whose lists overflowed
+    QMX_TRY(verify_and_sort(c, vp, q->nq));
+    QMX_TRY(pq_overflow_pass(c, pl));
+    c.launches += 5;
+    q->last_split = true;
+    q->last_pq = true;
+    // the rotated copy once per four-query group (all but the first find it in L2) + the sample's rows per query
+    close_counters(c, (uint64_t)q->nq * c.n_cand, (uint64_t)((q->nq + 3) / 4) * c.n_cand * m_pad + (uint64_t)q->nq * S * s->row_bytes, c.launches, q->nq);
+    return QMX_OK;
+}
+
+// ---- 4-bit TurboQuant / scalar-int8 top-k of 33 and more queries over a large block: 128 queries per pass of the codes (scan_tq4w.hip, scan_sqw.hip).  The pass's scores are exact;
+// what it shares with the prefilters is the plumbing: a sample's k-th best score admits the candidates, per-wave lists are regrouped per query, the k best
+// keys of a query (band 0: every tie of the k-th score with them) are re-scored by the pair kernel and sorted; a query whose lists overflowed (masses of
+// equal scores, a sample that is all deleted) takes the 32-query scan - conditional launches that read their flag and return. ----
+static int32_t wide_exact_search(SearchCall &c) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    const bool sq = s->dtype == QMX_DTYPE_SQ_U8;
+    // TurboQuant, option tq_wide_high_digit: the pass multiplies the queries' HIGH digits only; its scores are within band[q] of the exact ones, the selection
+    // keeps what an exact score >= T could hide behind (approximate >= max(T - band, A_k - 2 band)) and the pair kernel re-scores that
+    const bool tq_high = !sq && option(OPT_TQ_WIDE_HIGH_DIGIT) != 0;
+    const SplitPlanLayout pl(q->nq, TQW_FQT);
+    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT) * sizeof(uint64_t)));
+    QMX_TRY(q->sp_bq.reserve(sq ? sqw_query_bytes(s->scan_dim) : tq4w_query_bytes(s->scan_dim)));
+    QMX_TRY(q->sp_f32.reserve(SplitF32::floats_wide * sizeof(float)));
+    QMX_TRY(q->sp_cand.reserve((size_t)SPLIT_QT * SPLIT_CAND_CAP * sizeof(uint64_t)));
+    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
+    QMX_TRY(q->sp_wl.reserve(sq ? sqw_wlists_bytes(s->num_cus) : tq4w_wlists_bytes(s->num_cus)));
+    QMX_TRY(q->sp_fq.reserve((size_t)pl.list_cap * q->q_stride));
+    QMX_TRY(q->partial.reserve((size_t)s->num_cus * 8 * TQW_FQT * std::min<uint32_t>(c.top, MAX_TOP_FAST) * sizeof(uint64_t)));
+    // the sample: every 128-th row (prescan_shift - 3; at least 8 192 rows): its k-th best score leaves ~128 k candidates per query to the pass - the pass's
+    // epilogue pays per candidate (10 M x 768, 128 queries: 2.07 / 2.00 / 2.01 ms with every 256-th / 128-th / 64-th row, whose own scores cost more).
+    // SQ: every 256-th (its epilogue is one integer add and compare per pair; the sample's scores and their selection are 0.19 ms of the search at 1 / 128)
+    VerifyPool vp;
+    uint64_t S = 0;
+    QMX_TRY(prefilter_begin(q, pl, c.n_cand, sq ? -2 : -3, &vp, &S));
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    const SplitF32 f(q->sp_f32.p);      // band: zero - the pass's scores are the exact ones - or infinite: a query without a usable bound
+    uint32_t n_tiles = 0;
+    c.launches = 2;     // (this route counts its verification's two launches up front, and not the plan of the conditional passes)
+    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += SPLIT_QT, ++n_tiles) {
+        const uint32_t nq_tile = std::min<uint32_t>(SPLIT_QT, q->nq - tile0);
+        QMX_CHECK_CANCELLED(c.is_stopped);
+        const uint64_t *gthr = (const uint64_t *)q->gthr.p + tile0;
+        const ScanArgs a = tile_args(c, tile0, nq_tile);
+        // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best
+        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches));
+        // 2. the queries' codes / digits as operand images, the integer reject bounds
+        if (sq) QMX_TRY(launch_sqw_pack(q->stream, a, gthr, s->sq_off_absmax, q->sp_bq.p, f.wide_thr, f.wide_qinfo, f.band, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+        else QMX_TRY(launch_tq4w_pack(q->stream, a, gthr, s->tq_sf_min, s->tq_sf_max, s->tq_l2_min, s->tq_l2_max, s->tq_c1, tq_high ? 1 : 0, q->sp_bq.p, f.wide_thr,
+                                      f.wide_qinfo, f.band, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+        // 3. the pass
+        uint32_t grid = 0;
+        if (sq) QMX_TIMED_SCAN(c, launch_scan_sqw(q->stream, a, q->sp_bq.p, f.wide_thr, s->d_sq_bi, f.wide_qinfo, s->num_cus, q->sp_wl.p, &grid));
+        else QMX_TIMED_SCAN(c, launch_scan_tq4w(q->stream, a, q->sp_bq.p, f.wide_thr, f.wide_qinfo, tq_high ? f.band : nullptr, s->num_cus, q->sp_wl.p, &grid));
+        // 4. per-wave lists -> per-query lists (deleted rows dropped), then the k best keys of each query
+        int *tile_ovf = (int *)(plan + pl.tile_ovf) + n_tiles;
+        QMX_TRY(launch_regroup_lists(q->stream, a.del, (const unsigned char *)q->sp_wl.p + (sq ? sqw_wlists_counts_bytes(s->num_cus) : tq4w_wlists_counts_bytes(s->num_cus)),
+                                     (const uint32_t *)q->sp_wl.p, sq ? sqw_wcap() : tq4w_wcap(), grid * 8, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p,
+                                     SPLIT_CAND_CAP, tile_ovf));
+        QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, vp, tile0, tile_ovf,
+                                    (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan, tq_high ? f.wide_high : nullptr, tq_high));
+        c.launches += 6;
+    }
+    // 5. the selected rows through the pair kernel (the same bits), sorted; 6. the 32-query scan of the queries whose lists overflowed
+    QMX_TRY(verify_and_sort(c, vp, q->nq));
+    QMX_TRY(overflow_passes(c, pl, q->nq, TQW_FQT, sq ? overflow_scan_sq : overflow_scan_tq, &c.launches));
+    q->last_split = true;
+    q->last_pq = false;
+    q->last_fqt = TQW_FQT;
+    close_counters(c, (uint64_t)q->nq * c.n_cand,
+                   (uint64_t)n_tiles * c.n_cand * s->row_bytes + (uint64_t)((q->nq + MAX_QT_MFMA - 1) / MAX_QT_MFMA) * S * s->row_bytes, c.launches, q->nq);
+    return QMX_OK;
+}
+
+// ---- the f32 prefilters (scan_split.hip): tiles of 128 / 256 queries; their verification and, if ever needed, the exact passes run once for all of them
+// after the tile loop ----
+struct SplitTiles {
+    SplitPlanLayout pl;
+    VerifyPool vp{};
+    uint64_t S = 0;                                         // rows of the sample
+    std::vector<std::pair<uint32_t, uint32_t>> tiles;       // (tile0, nq_tile) of the tiles that took the prefilter
+    SplitTiles(uint32_t nq, uint32_t fqt) : pl(nq, fqt) {}
+};
+
 // |approximate - exact| <= band * |q| * max |row|, worst case, every term at its bound:
 //   one product of f16-rounded operands (HALF copy): each operand within 2^-11 of its value -> (2^-10 + 2^-22) sum |q_i r_i| <= ... |q| |r|
 //   three products of f16 pairs: x - (h + l) within 2^-22 |x|, the dropped l.l term 2^-22                    -> 3 * 2^-22
@@ -44,272 +428,168 @@ static inline float split_rel_band(bool half, uint32_t dim) {
     return (half ? 9.765625e-4f + 9.5367432e-7f : 1.9073486e-6f) + acc;  // 2^-10 + 2^-20 | 2^-19
 }
 
-// ids of a strided sample of the candidates (rows 0, step, 2 step, ...): a sample that sees the whole block, whatever its order
-__global__ void sample_ids_kernel(uint32_t *ids, uint32_t n, uint64_t step) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) ids[i] = (uint32_t)((uint64_t)i * step);
+static int32_t split_begin(const SearchCall &c, const SearchPlan &plan, SplitTiles &sp) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    QMX_TRY(q->sp_bq.reserve(split_query_bytes(s->dim)));
+    QMX_TRY(q->sp_f32.reserve(SplitF32::floats * sizeof(float)));
+    QMX_TRY(q->sp_cand.reserve((size_t)plan.split_qt * SPLIT_CAND_CAP * sizeof(uint64_t)));
+    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
+    if (s->d_rows_split) QMX_TRY(q->sp_wl.reserve(split_wlists_bytes(s->num_cus)));
+    QMX_TRY(q->sp_fq.reserve((size_t)sp.pl.list_cap * q->q_stride));
+    if (s->split_i8) {
+        QMX_TRY(q->sp_probe.reserve((size_t)q->nq * (split_i8_probe() + 1) * 4));
+        QMX_TRY(q->sp_pscores.reserve((size_t)q->nq * split_i8_probe() * 4));
+        // (no memset of the probe counts: the gather of a tile reads the counts of the tiles up to it - its own, written by the probe kernel in front
+        // of it, and the earlier ones', emptied by their bound kernels)
+    }
+    // the sample: every (n_cand / S)-th row, S = n_cand / 256 (at least 8192): its k-th best leaves ~256 k candidates per query to the
+    // main pass, at 1 / 256 of the pass's row traffic for the sample's exact scores (measured on C2: 1/128 .. 1/512 are equally good)
+    // ("prescan_shift" - 2: the option of the exact scans' prefix pre-scan, 10 by default, moves this sample with it)
+    // (with the derived copy: one more halving - 8 192 rows of a 10 M block are one tile per row stream of the sample scan, and the
+    // refine step after the first sixteenth of the block owns the threshold anyway: 26 us of the step, measured)
+    // (a 2 048-row sample lets the four query tiles of a 128-query batch run side by side - 22 us instead of 63 for the pre-scan - but its weaker threshold
+    // triples the candidates of the first launch: regroup, refine and select together give the 40 us back, measured; 8 192 stays)
+    return prefilter_begin(q, sp.pl, c.n_cand, s->d_rows_split ? 1 : -2, &sp.vp, &sp.S);
 }
 
-// ---- PQ top-k of 4 and more queries over a large block: the 6-bit prefilter + exact verification (pq_prefilter.hip).  Same contract as the f32
-// prefilter below: the lists are the exact scan's, a query whose lists overflow takes the exact scan alone. ----
-constexpr uint32_t PQF_TILE = 256;          // queries per pass (64 four-query groups; the regroup kernel's histogram)
-constexpr uint32_t PQF_WCAP = 512;          // candidates one wave may list per pass (expected: tens)
-static int32_t pq_prefilter_enqueue(qmx_query *q, uint32_t top, uint64_t n_cand, qmx_scored_point *d_out, uint32_t *d_counts,
-                                    const volatile uint8_t *is_stopped, qmx_counters *counters, bool timed) {
+// steps 2 - 4 of a tile over the f32 rows or an f16 copy
+static int32_t f16_split_scan(SearchCall &c, SplitTiles &sp, const ScanArgs &a, uint32_t tile0, uint32_t nq_tile, int *tile_ovf) {
+    qmx_query *q = c.q;
     const qmx_segment *s = q->seg;
-    const SplitPlanLayout pl(q->nq);
-    const uint32_t m = s->pq_m, m_pad = (m + 31) / 32 * 32;
-    const uint32_t tile_max = std::min<uint32_t>(PQF_TILE, q->nq);
-    const uint32_t grid_max = pq_prefilter_grid(s->num_cus, tile_max, nullptr);
-    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, PQF_TILE) * sizeof(uint64_t)));
-    QMX_TRY(q->pq_table.reserve(pq_prefilter_table_bytes(m, tile_max) + (size_t)(PQF_TILE + 4) * 4));
-    QMX_TRY(q->sp_f32.reserve(1024 * sizeof(float)));
-    QMX_TRY(q->sp_cand.reserve((size_t)tile_max * SPLIT_CAND_CAP * sizeof(uint64_t)));
-    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
-    {   // (the grid of a smaller last tile may be larger than the first tile's: size for the worst over tile sizes 1..tile_max)
-        uint32_t g = grid_max;
-        for (uint32_t t = 4; t <= tile_max; t += 4) g = std::max(g, pq_prefilter_grid(s->num_cus, t, nullptr));
-        QMX_TRY(q->sp_wl.reserve(pq_prefilter_wlists_bytes(g, PQF_WCAP)));
-    }
-    QMX_TRY(q->sp_plan.reserve(pl.bytes));
     unsigned char *plan = (unsigned char *)q->sp_plan.p;
-    VerifyPool vp;
-    QMX_TRY(verify_pool(q, plan, &vp));
-    float *band = (float *)q->sp_f32.p;                       // [PQF_TILE] in units of the integer score
-    q->last_counters = qmx_counters{};
-    q->last_split = false;
-    // the sample (as for the f32 prefilter): its k-th best exact score per query is a lower bound of the final k-th best
-    const int sshift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT) - 2, 1), 20);
-    const uint64_t S = std::min<uint64_t>(n_cand, std::max<uint64_t>(n_cand >> sshift, 8192));
-    if (q->sp_sample_n != S || q->sp_sample_of != n_cand) {
-        QMX_TRY(q->sp_sample.reserve((size_t)S * 4));
-        ::qmx::clear_stale_error();
-        hipLaunchKernelGGL(sample_ids_kernel, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, q->stream, (uint32_t *)q->sp_sample.p, (uint32_t)S, n_cand / S);
-        QMX_HIP(hipGetLastError());
-        q->sp_sample_n = S;
-        q->sp_sample_of = n_cand;
+    const SplitF32 f(q->sp_f32.p);
+    // 2. the batch's queries split into f16 pairs; thresholds and bands in accumulator / score units
+    const float row_scale = split_row_scale(s->row_maxabs);
+    const int half = s->split_half ? 1 : 0;
+    const uint32_t tqt = nq_tile > SPLIT_QT ? SPLIT_QT_MAX : SPLIT_QT;      // the shape of THIS tile (a remainder of <= 128 queries takes the 128 shape)
+    QMX_TRY(launch_split_pack_queries(q->stream, (const float *)q->enc.p + (size_t)tile0 * s->dim, nq_tile, s->dim, f.qmax, f.qnorm, q->sp_bq.p, half, tqt));
+    QMX_TRY(launch_split_thresholds(q->stream, (const uint64_t *)q->gthr.p + tile0, f.qnorm, f.qmax, nq_tile, split_rel_band(half, s->dim), s->row_norm_max, row_scale,
+                                    f.scales, f.thr, f.band, tqt, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+    QMX_TRY(split_stage(q, "pack + thresholds"));
+    // 3. the approximate scan of the whole block
+    // over a derived copy in two launches: the strided sixteenth of the tiles first, whose k-th best approximate score tightens the
+    // threshold of the other fifteen (sp_refine_kernel): ~16 k candidates per query instead of ~10 k x 16 from the sample's threshold alone
+    for (uint32_t phase = s->d_rows_split ? 1 : 0; phase <= (s->d_rows_split ? 2u : 0u); ++phase) {
+        QMX_TIMED_SCAN(c, launch_scan_f32_split(q->stream, a, q->sp_bq.p, row_scale, f.scales, f.thr, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP,
+                                                s->num_cus, s->d_rows_split, half, q->sp_wl.p, phase, tqt));
+        if (s->d_rows_split)
+            QMX_TRY(launch_split_regroup(q->stream, a, q->sp_wl.p, s->num_cus, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf, phase, tqt));
+        if (phase == 1)
+            QMX_TRY(launch_split_refine(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, f.scales, f.thr));
     }
-    const uint32_t *d_sample = (const uint32_t *)q->sp_sample.p;
-    QMX_HIP(hipMemsetAsync(plan, 0, pl.zero_bytes, q->stream));
-    uint32_t n_tiles = 0, launches = 0;
-    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += PQF_TILE, ++n_tiles) {
-        const uint32_t nq_tile = std::min<uint32_t>(PQF_TILE, q->nq - tile0);
-        if (is_stopped && *is_stopped) {
-            set_error("search cancelled");
-            return QMX_ERR_CANCELLED;
-        }
-        uint64_t *gthr = (uint64_t *)q->gthr.p + tile0;
-        ScanArgs a;
-        fill_args(q, tile0, nq_tile, a);
-        a.n_cand = n_cand;
-        a.top = top;
-        // 1. exact scores of the sample (the exact kernel's score mode over an id list) -> k-th best per query
-        QMX_TRY(q->scores.reserve((size_t)nq_tile * S * sizeof(float)));
-        const uint32_t SQT = tile_qt(s, q);
-        for (uint32_t st0 = 0; st0 < nq_tile; st0 += SQT) {
-            const uint32_t nq_sub = std::min<uint32_t>(SQT, nq_tile - st0);
-            ScanArgs pre;
-            fill_args(q, tile0 + st0, nq_sub, pre);
-            pre.ids = d_sample;
-            pre.n_cand = S;
-            pre.top = 1;
-            pre.scores = (float *)q->scores.p + (size_t)st0 * S;
-            pre.scores_stride = S;
-            uint32_t pgrid = 0;
-            QMX_TRY(launch_scan(q, (int)pow2_ceil(nq_sub), SCAN_SCORES, pre, &pgrid));
-            ++launches;
-        }
-        QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, S, d_sample, a.del, nq_tile, top, d_out + (size_t)tile0 * top, d_counts + tile0, gthr));
-        // 2. the 6-bit tables of the tile's query groups, thresholds and bands in units of the integer score
-        int32_t *thr = (int32_t *)((unsigned char *)q->pq_table.p + pq_prefilter_table_bytes(m, tile_max));
-        QMX_TRY(launch_pq_lut8(q->stream, a.queries, q->q_stride, nq_tile, m, s->pq.n_centroids, gthr, q->pq_table.p, thr, band));
-        QMX_HIP(hipMemsetAsync(q->sp_cnt.p, 0, (size_t)SPLIT_QT_MAX * 4, q->stream));
-        // 3. the approximate scan of the whole block over the rotated copy
-        uint32_t grid = 0;
-        size_t slot = 0;
-        if (timed) QMX_TRY(timing_begin(q, &slot));
-        QMX_TRY(launch_pq_prefilter(q->stream, a, s->d_pq_rot, q->pq_table.p, thr, nq_tile, s->num_cus, q->sp_wl.p, PQF_WCAP, &grid));
-        q->last_kernel = last_noted_kernel();
-        if (timed) QMX_TRY(timing_end(q, slot));
-        // 4. per-wave lists -> per-query lists (deleted rows dropped), then the rows worth an exact score
-        int *tile_ovf = (int *)(plan + pl.tile_ovf) + n_tiles;
-        QMX_TRY(launch_regroup_lists(q->stream, a.del, (const unsigned char *)q->sp_wl.p + pq_prefilter_wlists_counts_bytes(grid), (const uint32_t *)q->sp_wl.p, PQF_WCAP,
-                                     grid * 16, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf));
-        QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, band, nq_tile, top, vp, tile0,
-                                    tile_ovf, (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan));
-        launches += 6;
-    }
-    const void *pf_kernel = q->last_kernel;
-    // 5. exact scores of the survivors (pq_pair_kernel: score_point_sse's order), sorted by (score, lower id first)
-    PairSel sel{vp.qsel, 0, nullptr, vp.used};
-    QMX_TRY(score_pairs_device(q, sel, vp.ids, vp.cap, (float *)q->sp_vscores.p, false));
-    QMX_TRY(launch_sort_scored(q->stream, (const float *)q->sp_vscores.p, vp.ids, vp.cnt, 0, q->nq, top, d_out, d_counts, vp.off));
-    // 6. the exact scan of the queries whose lists overflowed, and of those only (the kernels start, read the count and return when it is zero)
-    uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
-    QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), q->nq, (const uint64_t *)q->gthr.p, ovf_list, (uint64_t *)(plan + pl.gthr_packed),
-                              pl.list_cap, (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), pl.n_run64, (SplitStats *)plan, nullptr, 0,
-                              nullptr));
-    {
-        ScanArgs a;
-        fill_args(q, 0, q->nq, a);
-        a.n_cand = n_cand;
-        a.top = top;
-        a.q_map = ovf_list;
-        a.run_if = (const int *)(plan + pl.count);
-        const uint64_t want = (n_cand + 1023) / 1024, cap = std::max<uint64_t>(1, ((uint64_t)s->num_cus * 2 + q->nq - 1) / q->nq);
-        uint32_t slabs = (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
-        QMX_TRY(q->partial.reserve((size_t)slabs * q->nq * top * sizeof(uint64_t)));
-        a.partial = (uint64_t *)q->partial.p;
-        a.partial_qt = q->nq;
-        QMX_TRY(launch_scan_pq(q->stream, SCAN_TOPK, a, s->num_cus, &slabs));
-        QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, slabs, q->nq, q->nq, top, d_out, d_counts, top, 0, nullptr, a.run_if, ovf_list,
-                                  slabs * q->nq));
-        launches += 5;
-    }
-    q->last_kernel = pf_kernel;
-    q->last_split = true;
-    q->last_pq = true;
-    {
-        qmx_counters &c = q->last_counters;
-        c.vectors_scored = (uint64_t)q->nq * n_cand;
-        // the rotated copy once per four-query group (all but the first find it in L2) + the sample's rows per query
-        c.bytes_read = (uint64_t)((q->nq + 3) / 4) * n_cand * m_pad + (uint64_t)q->nq * S * s->row_bytes;
-        c.kernel_launches = launches;
-        c.prefilter_queries = q->nq;
-        q->last_row_bytes = s->row_bytes;
-        q->last_n_cand = n_cand;
-        if (counters) *counters = c;
-    }
+    QMX_TRY(split_stage(q, "split kernel"));
+    // 4. the rows worth an exact score
+    QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, sp.vp, tile0, tile_ovf,
+                                (uint32_t *)(plan + sp.pl.ovf_q) + tile0, (SplitStats *)plan));
+    c.launches += 8;
     return QMX_OK;
 }
 
-// ---- 4-bit TurboQuant / scalar-int8 top-k of 33 and more queries over a large block: 128 queries per pass of the codes (scan_tq4w.hip, scan_sqw.hip).  The pass's scores are exact;
-// what it shares with the prefilters is the plumbing: a sample's k-th best score admits the candidates, per-wave lists are regrouped per query, the k best
-// keys of a query (band 0: every tie of the k-th score with them) are re-scored by the pair kernel and sorted; a query whose lists overflowed (masses of
-// equal scores, a sample that is all deleted) takes the 32-query scan - conditional launches that read their flag and return. ----
-constexpr uint32_t TQW_FQT = 32;
-static int32_t wide_exact_enqueue(qmx_query *q, uint32_t top, uint64_t n_cand, qmx_scored_point *d_out, uint32_t *d_counts, const volatile uint8_t *is_stopped,
-                                  qmx_counters *counters, bool timed) {
+// steps 2' - 4' of a tile over the int8 copy
+static int32_t i8_copy_scan(SearchCall &c, SplitTiles &sp, const ScanArgs &a, uint32_t tile0, uint32_t nq_tile, int *tile_ovf) {
+    qmx_query *q = c.q;
     const qmx_segment *s = q->seg;
-    const bool sq = s->dtype == QMX_DTYPE_SQ_U8;
-    // TurboQuant, option tq_wide_high_digit: the pass multiplies the queries' HIGH digits only; its scores are within band[q] of the exact ones, the selection
-    // keeps what an exact score >= T could hide behind (approximate >= max(T - band, A_k - 2 band)) and the pair kernel re-scores that
-    const bool tq_high = !sq && option(OPT_TQ_WIDE_HIGH_DIGIT) != 0;
-    const SplitPlanLayout pl(q->nq, TQW_FQT);
-    const uint32_t grid_cap = (uint32_t)s->num_cus * 8;
-    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT) * sizeof(uint64_t)));
-    QMX_TRY(q->sp_bq.reserve(sq ? sqw_query_bytes(s->scan_dim) : tq4w_query_bytes(s->scan_dim)));
-    QMX_TRY(q->sp_f32.reserve(1024 * sizeof(float)));
-    QMX_TRY(q->sp_cand.reserve((size_t)SPLIT_QT * SPLIT_CAND_CAP * sizeof(uint64_t)));
-    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
-    QMX_TRY(q->sp_wl.reserve(sq ? sqw_wlists_bytes(s->num_cus) : tq4w_wlists_bytes(s->num_cus)));
-    QMX_TRY(q->sp_plan.reserve(pl.bytes));
-    QMX_TRY(q->sp_fq.reserve((size_t)pl.list_cap * q->q_stride));
-    QMX_TRY(q->partial.reserve((size_t)grid_cap * TQW_FQT * std::min<uint32_t>(top, MAX_TOP_FAST) * sizeof(uint64_t)));
     unsigned char *plan = (unsigned char *)q->sp_plan.p;
-    VerifyPool vp;
-    QMX_TRY(verify_pool(q, plan, &vp));
-    float *qinfo = (float *)q->sp_f32.p, *band = qinfo + 512;      // band: zero - the pass's scores are the exact ones - or infinite: a query without a usable bound
-    int32_t *thr_i = (int32_t *)(qinfo + 768);      // [256]: the bounds on the whole sum, then on the high sum alone
-    q->last_counters = qmx_counters{};
-    q->last_split = false;
-    // the sample: every 128-th row (prescan_shift - 3; at least 8 192 rows): its k-th best score leaves ~128 k candidates per query to the pass - the pass's
-    // epilogue pays per candidate (10 M x 768, 128 queries: 2.07 / 2.00 / 2.01 ms with every 256-th / 128-th / 64-th row, whose own scores cost more).
-    // SQ: every 256-th (its epilogue is one integer add and compare per pair; the sample's scores and their selection are 0.19 ms of the search at 1 / 128)
-    const int sshift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT) - (sq ? 2 : 3), 1), 20);
-    const uint64_t S = std::min<uint64_t>(n_cand, std::max<uint64_t>(n_cand >> sshift, 8192));
-    if (q->sp_sample_n != S || q->sp_sample_of != n_cand) {
-        QMX_TRY(q->sp_sample.reserve((size_t)S * 4));
-        ::qmx::clear_stale_error();
-        hipLaunchKernelGGL(sample_ids_kernel, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, q->stream, (uint32_t *)q->sp_sample.p, (uint32_t)S, n_cand / S);
-        QMX_HIP(hipGetLastError());
-        q->sp_sample_n = S;
-        q->sp_sample_of = n_cand;
+    const SplitF32 f(q->sp_f32.p);
+    // 2'. the int8 copy: codes, scales, worst-case bands, thresholds from the sample's exact k-th best
+    QMX_TRY(launch_split_i8_pack(q->stream, (const float *)q->enc.p + (size_t)tile0 * s->dim, nq_tile, s->dim, s->d_i8_scale, (const uint64_t *)q->gthr.p + tile0,
+                                 s->d_i8_stats, s->row_norm_max, q->sp_bq.p, f.i8_qscale, f.band, f.thr, f.i8_texact, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+    QMX_TRY(split_stage(q, "int8 pack"));
+    // 3'. the strided sixteenth, then the rest; after each launch the exact scores of the k best candidates so far renew the bound
+    const uint32_t np = split_i8_probe();
+    uint32_t *probe_ids = (uint32_t *)q->sp_probe.p, *probe_cnt = probe_ids + (size_t)q->nq * np;
+    // (which tiles the first launch takes: every 16th.  Its candidates are admitted on the SAMPLE's bound - a hundred times those of the main launch
+    // per tile -, so the first launch is bound by its candidate lists, not by its stream; strides of 8 .. 64 measured the same step time,
+    // profiles/r5_i8_sample_stride.md)
+    const uint32_t sstride = 16;
+    for (uint32_t ph = 1; ph <= 2; ++ph) {
+        const uint32_t phase = ph | (sstride << 8);
+        QMX_TIMED_SCAN(c, launch_scan_i8copy(q->stream, a, q->sp_bq.p, f.i8_qscale, f.thr, s->num_cus, s->d_rows_split, q->sp_wl.p, phase));
+        QMX_TRY(launch_split_regroup(q->stream, a, q->sp_wl.p, s->num_cus, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf, phase, SPLIT_QT));
+        QMX_TRY(launch_split_i8_probe(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, tile_ovf,
+                                      probe_ids + (size_t)tile0 * np, probe_cnt + tile0));
+        const void *scan_kernel = q->last_kernel;
+        PairSel psel{nullptr, np, probe_cnt};
+        QMX_TRY(score_pairs_device(q, psel, probe_ids, (uint64_t)(tile0 + nq_tile) * np, (float *)q->sp_pscores.p, false));
+        q->last_kernel = scan_kernel;
+        QMX_TRY(launch_split_i8_bound(q->stream, (const float *)q->sp_pscores.p + (size_t)tile0 * np, probe_cnt + tile0, nq_tile, c.top, f.band, f.i8_qscale, f.thr,
+                                      f.i8_texact));
     }
-    const uint32_t *d_sample = (const uint32_t *)q->sp_sample.p;
-    QMX_HIP(hipMemsetAsync(plan, 0, pl.zero_bytes, q->stream));
-    uint32_t n_tiles = 0, launches = 2;
-    const void *wide_kernel = nullptr;
-    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += SPLIT_QT, ++n_tiles) {
-        const uint32_t nq_tile = std::min<uint32_t>(SPLIT_QT, q->nq - tile0);
-        if (is_stopped && *is_stopped) {
-            set_error("search cancelled");
-            return QMX_ERR_CANCELLED;
-        }
-        uint64_t *gthr = (uint64_t *)q->gthr.p + tile0;
-        ScanArgs a;
-        fill_args(q, tile0, nq_tile, a);
-        a.n_cand = n_cand;
-        a.top = top;
-        // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best
-        QMX_TRY(q->scores.reserve((size_t)nq_tile * S * sizeof(float)));
-        QMX_TRY(score_matrix_enqueue(q, tile0, nq_tile, d_sample, S, (float *)q->scores.p, S, &launches));
-        QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, S, d_sample, a.del, nq_tile, top, d_out + (size_t)tile0 * top, d_counts + tile0, gthr));
-        // 2. the queries' codes / digits as operand images, the integer reject bounds
-        if (sq) QMX_TRY(launch_sqw_pack(q->stream, a, gthr, s->sq_off_absmax, q->sp_bq.p, thr_i, qinfo, band, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
-        else QMX_TRY(launch_tq4w_pack(q->stream, a, gthr, s->tq_sf_min, s->tq_sf_max, s->tq_l2_min, s->tq_l2_max, s->tq_c1, tq_high ? 1 : 0, q->sp_bq.p, thr_i, qinfo, band,
-                                      (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
-        // 3. the pass
-        uint32_t grid = 0;
-        size_t slot = 0;
-        if (timed) QMX_TRY(timing_begin(q, &slot));
-        if (sq) QMX_TRY(launch_scan_sqw(q->stream, a, q->sp_bq.p, thr_i, s->d_sq_bi, qinfo, s->num_cus, q->sp_wl.p, &grid));
-        else QMX_TRY(launch_scan_tq4w(q->stream, a, q->sp_bq.p, thr_i, qinfo, tq_high ? band : nullptr, s->num_cus, q->sp_wl.p, &grid));
-        wide_kernel = last_noted_kernel();
-        if (timed) QMX_TRY(timing_end(q, slot));
-        // 4. per-wave lists -> per-query lists (deleted rows dropped), then the k best keys of each query
-        int *tile_ovf = (int *)(plan + pl.tile_ovf) + n_tiles;
-        QMX_TRY(launch_regroup_lists(q->stream, a.del, (const unsigned char *)q->sp_wl.p + (sq ? sqw_wlists_counts_bytes(s->num_cus) : tq4w_wlists_counts_bytes(s->num_cus)), (const uint32_t *)q->sp_wl.p,
-                                     sq ? sqw_wcap() : tq4w_wcap(),
-                                     grid * 8, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf));
-        QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, band, nq_tile, top, vp, tile0, tile_ovf,
-                                    (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan, tq_high ? qinfo + 3 * SPLIT_QT : nullptr, tq_high));
-        launches += 6;
-    }
-    // 5. the selected rows through the pair kernel (the same bits), sorted by (score, lower id first)
-    PairSel sel{vp.qsel, 0, nullptr, vp.used};
-    QMX_TRY(score_pairs_device(q, sel, vp.ids, vp.cap, (float *)q->sp_vscores.p, false));
-    QMX_TRY(launch_sort_scored(q->stream, (const float *)q->sp_vscores.p, vp.ids, vp.cnt, 0, q->nq, top, d_out, d_counts, vp.off));
-    // 6. the 32-query scan of the queries whose lists overflowed, packed: one 16-query pass when 1..16 of them, passes of 32 otherwise
-    uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
-    uint64_t *gthr_packed = (uint64_t *)(plan + pl.gthr_packed);
-    QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), q->nq, (const uint64_t *)q->gthr.p, ovf_list, gthr_packed, pl.list_cap,
-                              (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), pl.n_run64, (SplitStats *)plan, q->d_queries,
-                              q->q_stride, q->sp_fq.p));
-    for (uint32_t pass = 0; pass <= pl.n_run64; ++pass) {
-        if (pass && q->nq <= 16) break;
-        const uint32_t p0 = pass ? (pass - 1) * TQW_FQT : 0;
-        const uint32_t nq_sub = pass ? std::min<uint32_t>(TQW_FQT, q->nq - p0) : std::min<uint32_t>(16, q->nq);
-        const int *run_if = pass ? (const int *)(plan + pl.run64) + (pass - 1) : (const int *)(plan + pl.run16);
-        ScanArgs a;
-        fill_args(q, 0, nq_sub, a);
-        a.queries = (const char *)q->sp_fq.p + (size_t)p0 * q->q_stride;
-        a.n_cand = n_cand;
-        a.top = top;
-        a.partial = (uint64_t *)q->partial.p;
-        a.gthr = gthr_packed + p0;
-        a.run_if = run_if;
-        const int fqt = (int)std::max<uint32_t>(16, pow2_ceil(nq_sub));
-        a.partial_qt = (uint32_t)fqt;
-        uint32_t grid = grid_cap;
-        if (sq) QMX_TRY(launch_scan_sq_mfma(q->stream, fqt, SCAN_TOPK, a, s->num_cus, &grid));
-        else QMX_TRY(launch_scan_tq_mfma(q->stream, fqt, SCAN_TOPK, a, s->num_cus, &grid));
-        QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, (uint32_t)fqt, nq_sub, top, d_out, d_counts, top, 0, nullptr, run_if, ovf_list + p0));
-        launches += 2;
-    }
-    q->last_kernel = wide_kernel;
+    QMX_TRY(split_stage(q, "int8 scan"));
+    // 4'. the rows worth an exact score: approximate score >= T_exact - band
+    QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, sp.vp, tile0, tile_ovf,
+                                (uint32_t *)(plan + sp.pl.ovf_q) + tile0, (SplitStats *)plan, f.i8_texact));
+    c.launches += 13;
+    return QMX_OK;
+}
+
+static int32_t split_tile(SearchCall &c, const SearchPlan &plan, SplitTiles &sp, uint32_t tile0, uint32_t nq_tile) {
+    qmx_query *q = c.q;
+    QMX_CHECK_CANCELLED(c.is_stopped);
+    const ScanArgs a = tile_args(c, tile0, nq_tile);
+    // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best (launches: counted in the tile's 8 / 13)
+    QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, sp.S, c.top, a.del, nullptr));
+    QMX_TRY(split_stage(q, "prescan"));
+    int *tile_ovf = (int *)((unsigned char *)q->sp_plan.p + sp.pl.tile_ovf) + sp.tiles.size();
+    if (plan.route == ROUTE_I8_COPY) QMX_TRY(i8_copy_scan(c, sp, a, tile0, nq_tile, tile_ovf));
+    else QMX_TRY(f16_split_scan(c, sp, a, tile0, nq_tile, tile_ovf));
+    QMX_TRY(split_stage(q, "select"));
+    sp.tiles.push_back({tile0, nq_tile});
+    return QMX_OK;
+}
+
+// 5. and 6. for the tiles that took the prefilter
+static int32_t split_finish(const SearchCall &c, const SearchPlan &plan, const SplitTiles &sp) {
+    qmx_query *q = c.q;
+    const uint32_t first = sp.tiles.front().first, last = sp.tiles.back().first + sp.tiles.back().second;
+    // (split tiles are a prefix of the batch - the remainder tile, if any, comes last -: the sort walks queries 0 .. last)
+    QMX_REQUIRE(first == 0, QMX_ERR_OTHER, "split tiles must start at query 0");
+    QMX_TRY(verify_and_sort(c, sp.vp, last));
+    QMX_TRY(overflow_passes(c, sp.pl, last, plan.split_fqt, overflow_scan_f32, nullptr));      // (not counted: the tile's 8 / 13 are this route's launches)
     q->last_split = true;
     q->last_pq = false;
-    q->last_fqt = TQW_FQT;
-    {
-        qmx_counters &c = q->last_counters;
-        c.vectors_scored = (uint64_t)q->nq * n_cand;
-        c.bytes_read = (uint64_t)n_tiles * n_cand * s->row_bytes + (uint64_t)((q->nq + MAX_QT_MFMA - 1) / MAX_QT_MFMA) * S * s->row_bytes;
-        c.kernel_launches = launches;
-        c.prefilter_queries = q->nq;
-        q->last_row_bytes = s->row_bytes;
-        q->last_n_cand = n_cand;
-        if (counters) *counters = c;
+    q->last_fqt = plan.split_fqt;
+    return QMX_OK;
+}
+
+// ---- a tile of the exact scans: its pre-scan, then one pass per MAX_TOP_FAST entries of the lists ----
+static int32_t exact_tile(SearchCall &c, const SearchPlan &plan, uint32_t tile0, uint32_t nq_tile) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    const int qt = (int)pow2_ceil(nq_tile);
+    for (uint32_t pass = 0; pass < plan.n_pass; ++pass) {
+        QMX_CHECK_CANCELLED(c.is_stopped);
+        const uint32_t off = pass * MAX_TOP_FAST;
+        const uint32_t ptop = std::min<uint32_t>(MAX_TOP_FAST, c.top - off);
+        ScanArgs a = tile_args(c, tile0, nq_tile);
+        a.ids = c.d_ids;
+        a.top = ptop;
+        a.partial = (uint64_t *)q->partial.p;
+        a.partial_qt = (uint32_t)qt;
+        a.key_bound = pass ? (const uint64_t *)q->bounds.p : nullptr;
+        // The chain-major scan (scan_mfma16.hip) keeps one top list per wave and query: 512 lists per query on the chip, each of
+        // which would learn its reject threshold from its own 1 / 512 of the rows (~k ln(n / 512 k) insertions per list, each
+        // a wave-serial event the other waves of the block wait for at the next barrier).  A pre-scan of the first 1 / 1024 of the
+        // block gives every list the k-th best score of that prefix as a starting threshold: a lower bound of the final k-th
+        // best score, so nothing that belongs to the result is rejected (ties pass), and only ~1024 k rows per query beat it.
+        // (Running the pre-scan as a top-k pass of the chain-major kernel itself was insertion-bound: 0.2 ms instead of 0.06.)
+        const bool m16 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && mfma16_scan_ok(qt, SCAN_TOPK, a);
+        const bool sqm = (s->dtype == QMX_DTYPE_SQ_U8 || s->dtype == QMX_DTYPE_TQ ? qt >= 4 : s->dtype == QMX_DTYPE_F16 && qt >= 8) && mfma_scan_ok(s);   // scan_sq_mfma.hip starts from the bound too
+        const bool m4 = s->dtype == QMX_DTYPE_F32 && qt >= 8 && mfma_scan_ok(s);                                        // scan_mfma.hip (4x4x1) as well
+        const bool bqk = s->dtype == QMX_DTYPE_BQ && qt >= 4;   // bq_rows_kernel: integer scores, selection-bound without a starting threshold
+        if (pass == 0 && c.n_cand >= (1u << 18) && (m16 || sqm || m4 || bqk) && !option(OPT_NO_PRESCAN)) {
+            const int pre_shift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT), 1), 20);  // tuning: measured 5..10 on C2, the main pass does not care, the pre-scan itself gets cheaper
+            const uint64_t pre_n = std::max<uint64_t>(c.n_cand >> pre_shift, 1u << 13) & ~(uint64_t)15;
+            QMX_TRY(bound_enqueue(c, tile0, nq_tile, c.d_ids, pre_n, ptop, a.del, nullptr));
+            a.gthr = (const uint64_t *)q->gthr.p + tile0;
+            c.launches += 2;
+        }
+        uint32_t grid = (uint32_t)s->num_cus * 8;      // partial lists: one per block; bound the grid by what the buffer holds
+        QMX_TIMED_SCAN(c, launch_scan(q, qt, SCAN_TOPK, a, &grid));
+        QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, (uint32_t)qt, nq_tile, ptop, c.d_out + (size_t)tile0 * c.top, c.d_counts + tile0, c.top,
+                                  off, plan.n_pass > 1 ? (uint64_t *)q->bounds.p : nullptr));
+        c.launches += 2;
     }
     return QMX_OK;
 }
@@ -319,339 +599,37 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
                               qmx_counters *counters, bool timed) {
     const qmx_segment *s = q->seg;
     if (is_sparse(s)) return sparse_search_enqueue(q, top, d_ids, n_ids, d_out, d_counts, is_stopped, counters, timed);
-    const uint64_t n_cand = d_ids ? n_ids : s->scan_rows();
-    if (tq_l1(s)) {     // the score matrix (tiles of queries: at most 256 MiB of scores at a time), then one block per query selects its k best live candidates
-        q->last_counters = qmx_counters{};
-        q->last_split = false;
-        ScanArgs a;
-        fill_args(q, 0, q->nq, a);
-        const uint32_t qtile = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(q->nq, (1ull << 26) / std::max<uint64_t>(n_cand, 1)));
-        QMX_TRY(q->scores.reserve((size_t)qtile * std::max<uint64_t>(n_cand, 1) * sizeof(float)));
-        for (uint32_t q0 = 0; q0 < q->nq; q0 += qtile) {
-            if (is_stopped && *is_stopped) {
-                set_error("search cancelled");
-                return QMX_ERR_CANCELLED;
-            }
-            const uint32_t nq_tile = std::min<uint32_t>(qtile, q->nq - q0);
-            QMX_TRY(tq_l1_scores_device(q, q0, nq_tile, d_ids, n_cand, (float *)q->scores.p, n_cand, nullptr));
-            QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, n_cand, d_ids, a.del, nq_tile, top, d_out + (size_t)q0 * top, d_counts + q0));
-            if (counters) counters->kernel_launches += 1 + 3 * (uint32_t)((n_cand + 65535) / 65536);
-        }
-        if (counters) {
-            counters->vectors_scored += (uint64_t)q->nq * n_cand;
-            counters->bytes_read += (uint64_t)((q->nq + qtile - 1) / qtile) * n_cand * s->row_bytes;
-        }
-        return QMX_OK;
-    }
-    if (s->dtype == QMX_DTYPE_PQ && s->d_pq_rot && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && !option(OPT_NO_PQ_PREFILTER) &&
-        q->nq >= (uint32_t)std::max<int64_t>(1, option(OPT_PQ_PREFILTER_MIN_QUERIES)))
-        return pq_prefilter_enqueue(q, top, n_cand, d_out, d_counts, is_stopped, counters, timed);
-    if (s->dtype == QMX_DTYPE_TQ && s->tq_wide && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && mfma_scan_ok(s) && option(OPT_TQ_WIDE_MIN_QUERIES) > 0 &&
-        q->nq >= (uint32_t)option(OPT_TQ_WIDE_MIN_QUERIES) && (size_t)MAX_QT_MFMA * q->q_stride <= 150 * 1024) {
-        ScanArgs probe;
-        fill_args(q, 0, std::min<uint32_t>(q->nq, SPLIT_QT), probe);
-        probe.n_cand = n_cand;
-        probe.top = top;
-        if (tq4w_shape_ok(probe)) return wide_exact_enqueue(q, top, n_cand, d_out, d_counts, is_stopped, counters, timed);
-    }
-    if (s->dtype == QMX_DTYPE_SQ_U8 && s->sq_wide && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && mfma_scan_ok(s) && option(OPT_SQ_WIDE_MIN_QUERIES) > 0 &&
-        q->nq >= (uint32_t)option(OPT_SQ_WIDE_MIN_QUERIES)) {
-        ScanArgs probe;
-        fill_args(q, 0, std::min<uint32_t>(q->nq, SPLIT_QT), probe);
-        probe.n_cand = n_cand;
-        probe.top = top;
-        if (sqw_shape_ok(probe)) return wide_exact_enqueue(q, top, n_cand, d_out, d_counts, is_stopped, counters, timed);
-    }
-    // partial lists: one per block; bound the grid by what the buffer holds
-    const uint32_t grid_cap = (uint32_t)s->num_cus * 8;
-    // f32 dot / cosine rows of 256, 512 or 768 floats, whole block: 64 queries per pass (scan_mfma16.hip); everything else 32 / 16
-    const bool q64 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && q->nq > MAX_QT_MFMA && mfma16_dim_ok(64, s->dim) &&
-                     !option(OPT_NO_MFMA16);
-    // ... and rows of 1024 .. 1536 floats 32 per pass: that kernel keeps the queries in registers, not in an LDS tile (tile_qt's limit)
-    const bool q32 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && q->nq > MAX_QT && s->dim > 768 && mfma16_dim_ok(32, s->dim) &&
-                     !option(OPT_NO_MFMA16);
-    // more than 64 queries over a large f32 dot / cosine block: 128 per pass through the f16-split matrix-core prefilter, the survivors
-    // re-scored exactly (scan_split.hip); the result is the exact scan's, bit for bit
-    // ... and with a derived copy of the block (QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY) that path serves EVERY batch size: it streams 2 (4) bytes
-    // per element instead of 4 and is HBM-bound whatever the number of queries (10 M x 768: 3.0 ms per pass against 4.4 ms for the f32 stream)
-    // (rows of up to 768 floats: conditional exact passes of 64 queries; up to 2 048 floats - 1 024, 1 536: the 32-query shape - only over a derived copy)
-    const uint32_t split_fqt = split_fallback_qt(s->dim);
-    const bool split_dims = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && (mfma16_dim_ok(64, s->dim) || (s->d_rows_split && split_fqt != 0)) && !option(OPT_NO_MFMA16);
-    const bool split = split_dims && (q64 || (s->d_rows_split && q->nq >= (uint32_t)std::max<int64_t>(1, option(OPT_SPLIT_MIN_QUERIES)))) && s->split_stats &&
-                       !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && s->dim % 128 == 0 && s->row_stride % 16 == 0 && !option(OPT_NO_SPLIT_SCAN);
-    // the 256-query shape halves the bytes streamed per query; a batch that does not fill it is served by the 128-query shape (less matrix work)
-    const uint32_t split_qt = (split && s->d_rows_split && s->split_half && q->nq > SPLIT_QT && !option(OPT_NO_SPLIT256)) ? SPLIT_QT_MAX : SPLIT_QT;
-    const uint32_t TQ = split ? split_qt : q64 ? MAX_QT_TOPK : q32 ? MAX_QT_MFMA : tile_qt(s, q);
-    const uint32_t ptop_max = std::min<uint32_t>(top, MAX_TOP_FAST);
-    const uint32_t n_pass = (top + MAX_TOP_FAST - 1) / MAX_TOP_FAST;
-    QMX_TRY(q->partial.reserve((size_t)grid_cap * std::min<uint32_t>(TQ, MAX_QT_TOPK) * ptop_max * sizeof(uint64_t)));
-    if (n_pass > 1) QMX_TRY(q->bounds.reserve((size_t)TQ * sizeof(uint64_t)));
-    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT_MAX) * sizeof(uint64_t)));
-    // ---- split passes first (their verification and, if ever needed, the exact fallback run once for all of them afterwards) ----
-    std::vector<std::pair<uint32_t, uint32_t>> split_tiles;      // (tile0, nq_tile)
-    float *sp_qnorm = nullptr, *sp_thr = nullptr, *sp_band = nullptr, *sp_scales = nullptr, *sp_qmax = nullptr;
-    const SplitPlanLayout pl(q->nq, split_fqt ? split_fqt : SPLIT_FQT);
-    unsigned char *plan = nullptr;
-    VerifyPool vp{};
+    SearchCall c{q, top, d_ids, d_ids ? n_ids : s->scan_rows(), d_out, d_counts, is_stopped, counters, timed, 0};
+    const SearchPlan plan = search_plan(q, top, d_ids, c.n_cand);
     q->last_counters = qmx_counters{};
     q->last_split = false;
-    if (split) {
-        QMX_TRY(q->sp_bq.reserve(split_query_bytes(s->dim)));
-        QMX_TRY(q->sp_f32.reserve(1280 * sizeof(float)));
-        QMX_TRY(q->sp_cand.reserve((size_t)split_qt * SPLIT_CAND_CAP * sizeof(uint64_t)));
-        QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
-        if (s->d_rows_split) QMX_TRY(q->sp_wl.reserve(split_wlists_bytes(s->num_cus)));
-        QMX_TRY(q->sp_plan.reserve(pl.bytes));
-        QMX_TRY(verify_pool(q, (unsigned char *)q->sp_plan.p, &vp));
-        QMX_TRY(q->sp_fq.reserve((size_t)pl.list_cap * q->q_stride));
-        if (s->split_i8) {
-            QMX_TRY(q->sp_probe.reserve((size_t)q->nq * (split_i8_probe() + 1) * 4));
-            QMX_TRY(q->sp_pscores.reserve((size_t)q->nq * split_i8_probe() * 4));
-            // (no memset of the probe counts: the gather of a tile reads the counts of the tiles up to it - its own, written by the probe kernel in front
-            // of it, and the earlier ones', emptied by their bound kernels)
-        }
-        plan = (unsigned char *)q->sp_plan.p;
-        float *f = (float *)q->sp_f32.p;
-        sp_qnorm = f; sp_thr = f + 256; sp_band = f + 512; sp_scales = f + 768; sp_qmax = f + 1024;
-        // the sample: every (n_cand / S)-th row, S = n_cand / 256 (at least 8192): its k-th best leaves ~256 k candidates per query to the
-        // main pass, at 1 / 256 of the pass's row traffic for the sample's exact scores (measured on C2: 1/128 .. 1/512 are equally good)
-        // ("prescan_shift" - 2: the option of the exact scans' prefix pre-scan, 10 by default, moves this sample with it)
-        // (with the derived copy: one more halving - 8 192 rows of a 10 M block are one tile per row stream of the sample scan, and the
-        // refine step after the first sixteenth of the block owns the threshold anyway: 26 us of the step, measured)
-        const int sshift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT) + (s->d_rows_split ? 1 : -2), 1), 20);
-        // (a 2 048-row sample lets the four query tiles of a 128-query batch run side by side - 22 us instead of 63 for the pre-scan - but its weaker threshold
-        // triples the candidates of the first launch: regroup, refine and select together give the 40 us back, measured; 8 192 stays)
-        const uint64_t S = std::min<uint64_t>(n_cand, std::max<uint64_t>(n_cand >> sshift, 8192));
-        if (q->sp_sample_n != S || q->sp_sample_of != n_cand) {
-            QMX_TRY(q->sp_sample.reserve((size_t)S * 4));
-            ::qmx::clear_stale_error();
-            hipLaunchKernelGGL(sample_ids_kernel, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, q->stream, (uint32_t *)q->sp_sample.p, (uint32_t)S, n_cand / S);
-            QMX_HIP(hipGetLastError());
-            q->sp_sample_n = S;
-            q->sp_sample_of = n_cand;
-        }
-        QMX_HIP(hipMemsetAsync(plan, 0, pl.zero_bytes, q->stream));
-    }
+    if (plan.route == ROUTE_TQ_L1) return tq_l1_search(c, plan);
+    if (plan.route == ROUTE_PQ_PREFILTER) return pq_prefilter_search(c);
+    if (plan.route == ROUTE_TQ_WIDE || plan.route == ROUTE_SQ_WIDE) return wide_exact_search(c);
+    // tiles of plan.tile_q queries: the split tiles first, then - a remainder without a copy, or the whole batch - the exact ones
+    const uint32_t TQ = plan.tile_q;
+    QMX_TRY(q->partial.reserve((size_t)s->num_cus * 8 * std::min<uint32_t>(TQ, MAX_QT_TOPK) * std::min<uint32_t>(top, MAX_TOP_FAST) * sizeof(uint64_t)));
+    if (plan.n_pass > 1) QMX_TRY(q->bounds.reserve((size_t)TQ * sizeof(uint64_t)));
+    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT_MAX) * sizeof(uint64_t)));
+    SplitTiles sp(q->nq, plan.split_fqt);
+    if (plan.split()) QMX_TRY(split_begin(c, plan, sp));
     for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += TQ) {
         const uint32_t nq_tile = std::min<uint32_t>(TQ, q->nq - tile0);
-        if (split && (nq_tile > MAX_QT_TOPK || s->d_rows_split)) {
-            if (is_stopped && *is_stopped) {
-                set_error("search cancelled");
-                return QMX_ERR_CANCELLED;
-            }
-            const uint32_t S = (uint32_t)q->sp_sample_n;
-            const uint32_t *d_sample = (const uint32_t *)q->sp_sample.p;
-            uint64_t *gthr = (uint64_t *)q->gthr.p + tile0;
-            ScanArgs a;
-            fill_args(q, tile0, nq_tile, a);
-            a.n_cand = n_cand;
-            a.top = top;
-            // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best
-            QMX_TRY(q->scores.reserve((size_t)nq_tile * S * sizeof(float)));
-            QMX_TRY(score_matrix_enqueue(q, tile0, nq_tile, d_sample, S, (float *)q->scores.p, S, nullptr));
-            QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, S, d_sample, a.del, nq_tile, top, d_out + (size_t)tile0 * top, d_counts + tile0, gthr));
-            QMX_TRY(split_stage(q, "prescan"));
-            if (s->split_i8) {
-                // 2'. the int8 copy: codes, scales, worst-case bands, thresholds from the sample's exact k-th best (sp_f32: qnorm -> T_exact, qmax -> the scales)
-                float *sp_texact = sp_qnorm, *sp_qscale = sp_qmax;
-                QMX_TRY(launch_split_i8_pack(q->stream, (const float *)q->enc.p + (size_t)tile0 * s->dim, nq_tile, s->dim, s->d_i8_scale, gthr, s->d_i8_stats,
-                                             s->row_norm_max, q->sp_bq.p, sp_qscale, sp_band, sp_thr, sp_texact, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
-                QMX_TRY(split_stage(q, "int8 pack"));
-                // 3'. the strided sixteenth, then the rest; after each launch the exact scores of the k best candidates so far renew the bound
-                const uint32_t np = split_i8_probe();
-                uint32_t *probe_ids = (uint32_t *)q->sp_probe.p, *probe_cnt = probe_ids + (size_t)q->nq * np;
-                int *tile_ovf = (int *)(plan + pl.tile_ovf) + split_tiles.size();
-                // (which tiles the first launch takes: every 16th.  Its candidates are admitted on the SAMPLE's bound - a hundred times those of the main launch
-                // per tile -, so the first launch is bound by its candidate lists, not by its stream; strides of 8 .. 64 measured the same step time,
-                // profiles/r5_i8_sample_stride.md)
-                const uint32_t sstride = 16;
-                for (uint32_t ph = 1; ph <= 2; ++ph) {
-                    const uint32_t phase = ph | (sstride << 8);
-                    size_t slot = 0;
-                    if (timed) QMX_TRY(timing_begin(q, &slot));
-                    QMX_TRY(launch_scan_i8copy(q->stream, a, q->sp_bq.p, sp_qscale, sp_thr, s->num_cus, s->d_rows_split, q->sp_wl.p, phase));
-                    q->last_kernel = last_noted_kernel();
-                    if (timed) QMX_TRY(timing_end(q, slot));
-                    QMX_TRY(launch_split_regroup(q->stream, a, q->sp_wl.p, s->num_cus, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf,
-                                                 phase, SPLIT_QT));
-                    QMX_TRY(launch_split_i8_probe(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, sp_band, nq_tile, top, tile_ovf,
-                                                  probe_ids + (size_t)tile0 * np, probe_cnt + tile0));
-                    const void *scan_kernel = q->last_kernel;
-                    PairSel psel{nullptr, np, probe_cnt};
-                    QMX_TRY(score_pairs_device(q, psel, probe_ids, (uint64_t)(tile0 + nq_tile) * np, (float *)q->sp_pscores.p, false));
-                    q->last_kernel = scan_kernel;
-                    QMX_TRY(launch_split_i8_bound(q->stream, (const float *)q->sp_pscores.p + (size_t)tile0 * np, probe_cnt + tile0, nq_tile, top, sp_band, sp_qscale,
-                                                  sp_thr, sp_texact));
-                }
-                QMX_TRY(split_stage(q, "int8 scan"));
-                // 4'. the rows worth an exact score: approximate score >= T_exact - band
-                QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, sp_band, nq_tile, top, vp, tile0,
-                                            tile_ovf, (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan, sp_texact));
-                QMX_TRY(split_stage(q, "select"));
-                split_tiles.push_back({tile0, nq_tile});
-                if (counters) counters->kernel_launches += 13;
-                continue;
-            }
-            // 2. the batch's queries split into f16 pairs; thresholds and bands in accumulator / score units
-            const float row_scale = split_row_scale(s->row_maxabs);
-            const int half = s->split_half ? 1 : 0;
-            const uint32_t tqt = nq_tile > SPLIT_QT ? SPLIT_QT_MAX : SPLIT_QT;      // the shape of THIS tile (a remainder of <= 128 queries takes the 128 shape)
-            QMX_TRY(launch_split_pack_queries(q->stream, (const float *)q->enc.p + (size_t)tile0 * s->dim, nq_tile, s->dim, sp_qmax, sp_qnorm, q->sp_bq.p, half, tqt));
-            QMX_TRY(launch_split_thresholds(q->stream, gthr, sp_qnorm, sp_qmax, nq_tile, split_rel_band(half, s->dim), s->row_norm_max, row_scale, sp_scales, sp_thr,
-                                            sp_band, tqt, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
-            QMX_TRY(split_stage(q, "pack + thresholds"));
-            // 3. the approximate scan of the whole block
-            // over a derived copy in two launches: the strided sixteenth of the tiles first, whose k-th best approximate score tightens the
-            // threshold of the other fifteen (sp_refine_kernel): ~16 k candidates per query instead of ~10 k x 16 from the sample's threshold alone
-            for (uint32_t phase = s->d_rows_split ? 1 : 0; phase <= (s->d_rows_split ? 2u : 0u); ++phase) {
-                size_t slot = 0;
-                if (timed) QMX_TRY(timing_begin(q, &slot));
-                QMX_TRY(launch_scan_f32_split(q->stream, a, q->sp_bq.p, row_scale, sp_scales, sp_thr, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p,
-                                              SPLIT_CAND_CAP, s->num_cus, s->d_rows_split, half, q->sp_wl.p, phase, tqt));
-                q->last_kernel = last_noted_kernel();
-                if (timed) QMX_TRY(timing_end(q, slot));
-                if (s->d_rows_split)
-                    QMX_TRY(launch_split_regroup(q->stream, a, q->sp_wl.p, s->num_cus, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP,
-                                                 (int *)(plan + pl.tile_ovf) + split_tiles.size(), phase, tqt));
-                if (phase == 1)
-                    QMX_TRY(launch_split_refine(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, sp_band, nq_tile, top,
-                                                sp_scales, sp_thr));
-            }
-            QMX_TRY(split_stage(q, "split kernel"));
-            // 4. the rows worth an exact score
-            QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, sp_band, nq_tile, top, vp, tile0,
-                                        (const int *)(plan + pl.tile_ovf) + split_tiles.size(), (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan));
-            QMX_TRY(split_stage(q, "select"));
-            split_tiles.push_back({tile0, nq_tile});
-            if (counters) counters->kernel_launches += 8;
-            continue;
-        }
-        const int qt = (int)pow2_ceil(nq_tile);
-        for (uint32_t pass = 0; pass < n_pass; ++pass) {
-            if (is_stopped && *is_stopped) {
-                set_error("search cancelled");
-                return QMX_ERR_CANCELLED;
-            }
-            const uint32_t off = pass * MAX_TOP_FAST;
-            const uint32_t ptop = std::min<uint32_t>(MAX_TOP_FAST, top - off);
-            ScanArgs a;
-            fill_args(q, tile0, nq_tile, a);
-            a.ids = d_ids;
-            a.n_cand = n_cand;
-            a.top = ptop;
-            a.partial = (uint64_t *)q->partial.p;
-            a.partial_qt = (uint32_t)qt;
-            a.key_bound = pass ? (const uint64_t *)q->bounds.p : nullptr;
-            // The chain-major scan (scan_mfma16.hip) keeps one top list per wave and query: 512 lists per query on the chip, each of
-            // which would learn its reject threshold from its own 1 / 512 of the rows (~k ln(n / 512 k) insertions per list, each
-            // a wave-serial event the other waves of the block wait for at the next barrier).  A pre-scan of the first 1 / 1024 of the
-            // block gives every list the k-th best score of that prefix as a starting threshold: a lower bound of the final k-th
-            // best score, so nothing that belongs to the result is rejected (ties pass), and only ~1024 k rows per query beat it.
-            // (Running the pre-scan as a top-k pass of the chain-major kernel itself was insertion-bound: 0.2 ms instead of 0.06.)
-            const bool m16 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && mfma16_scan_ok(qt, SCAN_TOPK, a);
-            const bool sqm = (s->dtype == QMX_DTYPE_SQ_U8 || s->dtype == QMX_DTYPE_TQ ? qt >= 4 : s->dtype == QMX_DTYPE_F16 && qt >= 8) && mfma_scan_ok(s);   // scan_sq_mfma.hip starts from the bound too
-            const bool m4 = s->dtype == QMX_DTYPE_F32 && qt >= 8 && mfma_scan_ok(s);                                        // scan_mfma.hip (4x4x1) as well
-            const bool bqk = s->dtype == QMX_DTYPE_BQ && qt >= 4;   // bq_rows_kernel: integer scores, selection-bound without a starting threshold
-            if (pass == 0 && n_cand >= (1u << 18) && (m16 || sqm || m4 || bqk) && !option(OPT_NO_PRESCAN)) {
-                const int pre_shift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT), 1), 20);  // tuning: measured 5..10 on C2, the main pass does not care, the pre-scan itself gets cheaper
-                const uint64_t pre_n = std::max<uint64_t>(n_cand >> pre_shift, 1u << 13) & ~(uint64_t)15;
-                {
-                    // score matrix of the prefix (the score-mode kernels, <= tile_qt queries per launch), one block per query selects its
-                    // k best live candidates, the k-th becomes the bound
-                    QMX_TRY(q->scores.reserve((size_t)nq_tile * pre_n * sizeof(float)));
-                    QMX_TRY(score_matrix_enqueue(q, tile0, nq_tile, d_ids, pre_n, (float *)q->scores.p, pre_n, nullptr));
-// (the bound at the tile's own offset: the bounds of earlier split tiles are read again by the plan of their exact passes)
-                    QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, pre_n, d_ids, a.del, nq_tile, ptop, d_out + (size_t)tile0 * top,
-                                               d_counts + tile0, (uint64_t *)q->gthr.p + tile0));
-                }
-                a.gthr = (const uint64_t *)q->gthr.p + tile0;
-                if (counters) counters->kernel_launches += 2;
-            }
-            uint32_t grid = grid_cap;
-            size_t slot = 0;
-            if (timed) QMX_TRY(timing_begin(q, &slot));
-            QMX_TRY(launch_scan(q, qt, SCAN_TOPK, a, &grid));
-            q->last_kernel = last_noted_kernel();
-            if (timed) QMX_TRY(timing_end(q, slot));
-            QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, (uint32_t)qt, nq_tile, ptop,
-                                      d_out + (size_t)tile0 * top, d_counts + tile0, top, off,
-                                      n_pass > 1 ? (uint64_t *)q->bounds.p : nullptr));
-            if (counters) counters->kernel_launches += 2;
-        }
+        if (plan.tile_splits(nq_tile)) QMX_TRY(split_tile(c, plan, sp, tile0, nq_tile));
+        else QMX_TRY(exact_tile(c, plan, tile0, nq_tile));
     }
-    if (!split_tiles.empty()) {
-        // 5. exact scores of the survivors (the gather kernel of qmx_rescore: the reference's bits), sorted by (score, lower id first)
-        const void *split_kernel = q->last_kernel;
-        const uint32_t first = split_tiles.front().first, last = split_tiles.back().first + split_tiles.back().second;
-        // (split tiles are a prefix of the batch - the remainder tile, if any, comes last -: the sort walks queries 0 .. last)
-        QMX_REQUIRE(first == 0, QMX_ERR_OTHER, "split tiles must start at query 0");
-        PairSel sel{vp.qsel, 0, nullptr, vp.used};
-        QMX_TRY(score_pairs_device(q, sel, vp.ids, vp.cap, (float *)q->sp_vscores.p, false));
-        QMX_TRY(split_stage(q, "verify gather"));
-        QMX_TRY(launch_sort_scored(q->stream, (const float *)q->sp_vscores.p, vp.ids, vp.cnt, 0, last, top, d_out, d_counts, vp.off));
-        QMX_TRY(split_stage(q, "verify sort"));
-        // 6. the exact scan of the queries whose lists overflowed (masses of near-equal scores, a sample that is all deleted), and of those only:
-        // packed, one 16-query pass when 1..16 of them, passes of 64 otherwise.  The kernels start, read their flag and return when it is clear.
-        uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
-        uint64_t *gthr_packed = (uint64_t *)(plan + pl.gthr_packed);
-        const uint32_t FQT = split_fqt ? split_fqt : SPLIT_FQT;
-        const uint32_t n_run64 = (last + FQT - 1) / FQT, n_slots = n_run64 * FQT;
-        QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), last, (const uint64_t *)q->gthr.p, ovf_list, gthr_packed, n_slots,
-                                  (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), n_run64, (SplitStats *)plan, q->d_queries,
-                                  q->q_stride, q->sp_fq.p));
-        for (uint32_t pass = 0; pass <= n_run64; ++pass) {      // pass 0: the 16-query shape; pass p >= 1: packed queries 64 (p - 1) ..
-            if (pass && last <= 16) break;
-            const uint32_t p0 = pass ? (pass - 1) * FQT : 0;
-            const uint32_t nq_sub = pass ? std::min<uint32_t>(FQT, last - p0) : std::min<uint32_t>(16, last);
-            const int *run_if = pass ? (const int *)(plan + pl.run64) + (pass - 1) : (const int *)(plan + pl.run16);
-            ScanArgs a;
-            fill_args(q, 0, nq_sub, a);
-            a.queries = (const char *)q->sp_fq.p + (size_t)p0 * q->q_stride;
-            a.n_cand = n_cand;
-            a.top = top;
-            a.partial = (uint64_t *)q->partial.p;
-            a.gthr = gthr_packed + p0;
-            a.run_if = run_if;
-            const int fqt = (int)std::max<uint32_t>(16, pow2_ceil(nq_sub));
-            a.partial_qt = (uint32_t)fqt;
-            uint32_t grid = grid_cap;
-            QMX_REQUIRE(mfma16_scan_ok(fqt, SCAN_TOPK, a), QMX_ERR_OTHER, "split fallback shape");
-            QMX_TRY(launch_scan_f32_mfma16(q->stream, fqt, a, s->num_cus, &grid));
-            QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, (uint32_t)fqt, nq_sub, top, d_out, d_counts, top, 0, nullptr, run_if,
-                                      ovf_list + p0));
-        }
-        QMX_TRY(split_stage(q, "fallback (conditional)"));
-        q->last_kernel = split_kernel;      // (the fallback launches above are not what ran)
-        q->last_split = true;
-        q->last_pq = false;
-        q->last_fqt = FQT;
+    if (!sp.tiles.empty()) QMX_TRY(split_finish(c, plan, sp));
+    uint32_t split_q = 0;
+    uint64_t bytes = 0;
+    for (auto &t : sp.tiles) {
+        split_q += t.second;
+        // one pass over the derived copy (2 or 4 bytes per element; the f32 rows themselves when there is none) + the sample's exact scores
+        bytes += c.n_cand * (uint64_t)s->dim * (s->split_i8 ? 1 : s->d_rows_split && s->split_half ? 2 : 4);
+        bytes += (uint64_t)((t.second + tile_qt(s, q) - 1) / tile_qt(s, q)) * q->sp_sample_n * s->row_bytes;
     }
-    {
-        // what the host knows at enqueue; the prefilter's own share (candidates, verified rows, exact passes of overflowed queries) is on the device
-        // until the stream is synchronised: fold_split_counters
-        qmx_counters &c = q->last_counters;
-        uint32_t split_q = 0;
-        uint64_t bytes = 0;
-        for (auto &t : split_tiles) {
-            split_q += t.second;
-            // one pass over the derived copy (2 or 4 bytes per element; the f32 rows themselves when there is none) + the sample's exact scores
-            bytes += n_cand * (uint64_t)s->dim * (s->split_i8 ? 1 : s->d_rows_split && s->split_half ? 2 : 4);
-            bytes += (uint64_t)((t.second + tile_qt(s, q) - 1) / tile_qt(s, q)) * q->sp_sample_n * s->row_bytes;
-        }
-        const uint32_t rest = q->nq - split_q;
-        bytes += (uint64_t)((rest + TQ - 1) / TQ) * n_cand * s->row_bytes * n_pass;
-        c.vectors_scored = (uint64_t)q->nq * n_cand * n_pass;
-        c.bytes_read = bytes;
-        c.kernel_launches = counters ? counters->kernel_launches : 0;
-        c.prefilter_queries = split_q;
-        q->last_row_bytes = s->row_bytes;
-        q->last_n_cand = n_cand;
-        if (counters) {
-            const uint64_t launches = counters->kernel_launches;
-            *counters = c;
-            counters->kernel_launches = launches;
-        }
-    }
+    bytes += (uint64_t)((q->nq - split_q + TQ - 1) / TQ) * c.n_cand * s->row_bytes * plan.n_pass;
+    // (kernel_launches: this driver adds its launches to what the caller's counters held, and an enqueue without counters - the async call - records 0)
+    close_counters(c, (uint64_t)q->nq * c.n_cand * plan.n_pass, bytes, counters ? counters->kernel_launches + c.launches : 0, split_q);
     return QMX_OK;
 }
 
@@ -673,19 +651,50 @@ int32_t fold_split_counters(qmx_query *q, qmx_counters *c) {
     return QMX_OK;
 }
 
+// an empty result: zero the counts, wherever they live
+static int32_t zero_counts(qmx_query *q, uint32_t *out_counts) {
+    if (is_device_ptr(out_counts)) {
+        QMX_HIP(hipMemsetAsync(out_counts, 0, (size_t)q->nq * 4, q->stream));
+        QMX_HIP(hipStreamSynchronize(q->stream));
+    } else {
+        for (uint32_t i = 0; i < q->nq; ++i) out_counts[i] = 0;
+    }
+    return QMX_OK;
+}
+
+// the lists and counts of a call whose `out` / `out_counts` may be host memory: written on the device - in place, or in the batch's own out / counts
+// buffers -, end() enqueues the copies back to what is on the host
+struct StagedLists {
+    qmx_query *q;
+    qmx_scored_point *out, *d_out;
+    uint32_t *out_counts, *d_counts;
+    size_t out_bytes;
+    int32_t begin(qmx_query *q_, uint32_t top, qmx_scored_point *out_, uint32_t *out_counts_) {
+        *this = StagedLists{q_, out_, out_, out_counts_, out_counts_, (size_t)q_->nq * top * sizeof(qmx_scored_point)};
+        if (!is_device_ptr(out)) {
+            QMX_TRY(q->out.reserve(out_bytes));
+            d_out = (qmx_scored_point *)q->out.p;
+        }
+        if (!is_device_ptr(out_counts)) {
+            QMX_TRY(q->counts.reserve((size_t)q->nq * sizeof(uint32_t)));
+            d_counts = (uint32_t *)q->counts.p;
+        }
+        return QMX_OK;
+    }
+    int32_t end() {
+        if (d_out != out) QMX_TRY(copy_out(q->stream, out, d_out, out_bytes));
+        if (d_counts != out_counts) QMX_TRY(copy_out(q->stream, out_counts, d_counts, (size_t)q->nq * sizeof(uint32_t)));
+        return QMX_OK;
+    }
+};
+
 int32_t qmx_search_topk(qmx_query *q, uint32_t top, const uint32_t *ids, uint64_t n_ids, qmx_scored_point *out,
                         uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
     QMX_REQUIRE(q && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     if (top == 0 && is_sparse(q)) {     // the sparse search returns an empty list for top 0 (TopK, lib/common/common/src/top_k.rs)
         if (counters) memset(counters, 0, sizeof(*counters));
         QMX_HIP(hipSetDevice(q->device));
-        if (is_device_ptr(out_counts)) {
-            QMX_HIP(hipMemsetAsync(out_counts, 0, (size_t)q->nq * 4, q->stream));
-            QMX_HIP(hipStreamSynchronize(q->stream));
-        } else {
-            for (uint32_t i = 0; i < q->nq; ++i) out_counts[i] = 0;
-        }
-        return QMX_OK;
+        return zero_counts(q, out_counts);
     }
     QMX_REQUIRE(top >= 1, QMX_ERR_BAD_ARG, "top must be > 0 (FixedLengthPriorityQueue::new panics on 0)");
     QMX_REQUIRE(top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u > %u not supported yet", top, MAX_TOP);
@@ -694,33 +703,14 @@ int32_t qmx_search_topk(qmx_query *q, uint32_t top, const uint32_t *ids, uint64_
     if (q->nq == 0) return QMX_OK;
     const void *d_ids = nullptr;
     if (ids) {
-        if (n_ids == 0) {  // empty candidate list: every queue stays empty
-            if (is_device_ptr(out_counts)) {
-                QMX_HIP(hipMemsetAsync(out_counts, 0, (size_t)q->nq * 4, q->stream));
-                QMX_HIP(hipStreamSynchronize(q->stream));
-            } else {
-                for (uint32_t i = 0; i < q->nq; ++i) out_counts[i] = 0;
-            }
-            return QMX_OK;
-        }
+        if (n_ids == 0) return zero_counts(q, out_counts);  // empty candidate list: every queue stays empty
         QMX_TRY(stage_in(q, q->ids, ids, (size_t)n_ids * 4, &d_ids));
     }
-    const bool out_dev = is_device_ptr(out);
-    const bool cnt_dev = is_device_ptr(out_counts);
-    qmx_scored_point *d_out = out;
-    uint32_t *d_counts = out_counts;
-    if (!out_dev) {
-        QMX_TRY(q->out.reserve((size_t)q->nq * top * sizeof(qmx_scored_point)));
-        d_out = (qmx_scored_point *)q->out.p;
-    }
-    if (!cnt_dev) {
-        QMX_TRY(q->counts.reserve((size_t)q->nq * sizeof(uint32_t)));
-        d_counts = (uint32_t *)q->counts.p;
-    }
+    StagedLists st;
+    QMX_TRY(st.begin(q, top, out, out_counts));
     const bool timed = q->timing || (q->seg->flags & QMX_SEG_TIME_KERNELS) != 0;
-    QMX_TRY(search_enqueue(q, top, (const uint32_t *)d_ids, n_ids, d_out, d_counts, is_stopped, counters, timed));
-    if (!out_dev) QMX_TRY(copy_out(q->stream, out, d_out, (size_t)q->nq * top * sizeof(qmx_scored_point)));
-    if (!cnt_dev) QMX_TRY(copy_out(q->stream, out_counts, d_counts, (size_t)q->nq * sizeof(uint32_t)));
+    QMX_TRY(search_enqueue(q, top, (const uint32_t *)d_ids, n_ids, st.d_out, st.d_counts, is_stopped, counters, timed));
+    QMX_TRY(st.end());
     QMX_TRY(check_err_flag(q));  // synchronises the stream
     if (counters) QMX_TRY(fold_split_counters(q, counters));
     if (timed) {
@@ -840,15 +830,11 @@ int32_t qmx_search_quantized(const qmx_hnsw *g, qmx_query *quantized, qmx_query 
     } else {
         QMX_TRY(qmx_search_topk(quantized, otop, ids, n_ids, d_cand, d_cnt, is_stopped, counters));
     }
-    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
     if (!rescore) {   // search_result.truncate(top)
-        qmx_scored_point *d_out = out;
-        uint32_t *d_oc = out_counts;
-        if (!out_dev) { QMX_TRY(quantized->out.reserve((size_t)nq * p->top * sizeof(qmx_scored_point))); d_out = (qmx_scored_point *)quantized->out.p; }
-        if (!cnt_dev) { QMX_TRY(quantized->counts.reserve((size_t)nq * 4)); d_oc = (uint32_t *)quantized->counts.p; }
-        QMX_TRY(launch_split_candidates(quantized->stream, d_cand, d_cnt, otop, nq, nullptr, p->top, d_out, d_oc));
-        if (!out_dev) QMX_TRY(copy_out(quantized->stream, out, d_out, (size_t)nq * p->top * sizeof(qmx_scored_point)));
-        if (!cnt_dev) QMX_TRY(copy_out(quantized->stream, out_counts, d_oc, (size_t)nq * 4));
+        StagedLists st;
+        QMX_TRY(st.begin(quantized, p->top, out, out_counts));
+        QMX_TRY(launch_split_candidates(quantized->stream, d_cand, d_cnt, otop, nq, nullptr, p->top, st.d_out, st.d_counts));
+        QMX_TRY(st.end());
         QMX_HIP(hipStreamSynchronize(quantized->stream));
         return QMX_OK;
     }

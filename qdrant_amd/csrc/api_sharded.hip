@@ -41,10 +41,7 @@ static int32_t sharded_enqueue(qmx_query *const *queries, const qmx_hnsw *const 
     }
     for (uint32_t i = 0; i < n_segments; ++i) {
         qmx_query *q = queries[i];
-        if (is_stopped && *is_stopped) {
-            set_error("search cancelled");
-            return QMX_ERR_CANCELLED;
-        }
+        QMX_CHECK_CANCELLED(is_stopped);
         QMX_HIP(hipSetDevice(q->device));
         QMX_TRY(q->out.reserve(lbytes));
         QMX_TRY(q->counts.reserve(cbytes));

@@ -279,10 +279,7 @@ int32_t sparse_search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids,
     for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += QT) {
         const uint32_t nq_tile = std::min<uint32_t>(QT, q->nq - tile0);
         for (uint32_t pass = 0; pass < n_pass; ++pass) {
-            if (is_stopped && *is_stopped) {
-                set_error("search cancelled");
-                return QMX_ERR_CANCELLED;
-            }
+            QMX_CHECK_CANCELLED(is_stopped);
             const uint32_t off = pass * MAX_TOP_FAST;
             const uint32_t ptop = std::min<uint32_t>(MAX_TOP_FAST, top - off);
             const uint64_t *bound = pass ? (const uint64_t *)q->bounds.p : nullptr;
