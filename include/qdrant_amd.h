@@ -452,8 +452,28 @@ QMX_API int32_t qmx_query_update(qmx_query *q, const float *queries);
  * (`BitSlice<u64, Lsb0>`, bit id = point id passes; ids past n_bits are rejected).  Applies to the brute-force
  * stream (like `peek_top_iter` over filtered points), to qmx_hnsw_search (filtered walk: rejected points are neither
  * scored nor traversed, as in `FilteredScorer::score_points`) — not to the plain score_points entry points, which
- * score what they are given.  NULL clears the filter.  The bitmap is copied. */
+ * score what they are given.  NULL clears the filter (and per-request filters, below).  The bitmap is copied. */
 QMX_API int32_t qmx_query_set_filter(qmx_query *q, const uint64_t *allowed, uint64_t n_bits);
+/* One payload filter per REQUEST of the batch: requests that differ only in their filter - every request of a
+ * multi-tenant collection carries `must: tenant == X` - share one pass of the block, where the reference runs one
+ * `execute_batch_search` per distinct filter (segments_searcher.rs:653-730 batches equal `BatchSearchParams` only).
+ * `bitmaps` is [n_filters][ceil(n_bits / 64)] words (each a `BitSlice<u64, Lsb0>` as above), `filter_of_query` [nq]:
+ * query i may return point id only if filter_of_query[i] == QMX_FILTER_NONE, or id < n_bits and bit id of bitmap
+ * filter_of_query[i] is set - AND-ed with the deleted flags, as the one filter is.  128 requests of 8 tenants carry
+ * 8 bitmaps.  Both arrays host or device memory, copied before the call returns.  n_filters >= 1 (0, like a NULL
+ * array: QMX_ERR_BAD_ARG); an index that is
+ * neither < n_filters nor QMX_FILTER_NONE: QMX_ERR_OUT_OF_BOUNDS.  Replaces a filter set by qmx_query_set_filter, and
+ * is replaced by it; qmx_query_set_filter(q, NULL, 0) clears both.
+ * Served by qmx_search_topk / _async over dense and quantized segments (every route: the lists are those of each
+ * request searched alone under its own filter), by qmx_hnsw_search / _acorn / _async / _traced over single-vector
+ * storages and by both stages of qmx_search_quantized.  Every other call that would apply the batch's filter - custom
+ * and multi-vector searches and walks, sparse batches, qmx_group_search, qmx_hnsw_search_with_vectors - returns
+ * QMX_ERR_NOT_SUPPORTED while they are set; the scoring calls (score_points, rescore, MMR) ignore filters as before.
+ * A per-request `top` needs no call of its own: the order of a list (score descending, offset ascending) is total,
+ * so the list for a smaller top is a prefix - search with the largest top of the batch and cut. */
+#define QMX_FILTER_NONE 0xFFFFFFFFu
+QMX_API int32_t qmx_query_set_filters(qmx_query *q, const uint64_t *bitmaps, uint64_t n_bits, uint32_t n_filters,
+                                      const uint32_t *filter_of_query);
 QMX_API int32_t qmx_query_destroy(qmx_query *q);
 /* Run this query batch's kernels on a caller-owned hipStream_t (NULL = the query's own stream). */
 QMX_API int32_t qmx_query_set_stream(qmx_query *q, void *hip_stream);

@@ -29,6 +29,8 @@ SEG_I8_COPY = 0x40
 SEG_AUTO_COPY = 0x80
 SEG_PQ_PREFILTER_COPY = 0x100
 
+FILTER_NONE = 0xFFFFFFFF     # qmx_query_set_filters: a request without a filter
+
 
 class ScoredPoint(C.Structure):
     _fields_ = [("idx", C.c_uint32), ("score", C.c_float)]
@@ -219,6 +221,7 @@ SIGNATURES = {
     "qmx_query_create_internal": (C.c_int32, [_P, _P, C.c_uint32, C.POINTER(_P)]),
     "qmx_query_update": (C.c_int32, [_P, _P]),
     "qmx_query_set_filter": (C.c_int32, [_P, _P, C.c_uint64]),
+    "qmx_query_set_filters": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, _P]),
     "qmx_query_destroy": (C.c_int32, [_P]),
     "qmx_query_set_stream": (C.c_int32, [_P, _P]),
     "qmx_query_synchronize": (C.c_int32, [_P]),

@@ -66,6 +66,7 @@ int32_t qmx_custom_score_points(qmx_query *ex, const qmx_custom_query *queries, 
 int32_t qmx_custom_search_topk(qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t top, const uint32_t *ids, uint64_t n_ids,
                                qmx_scored_point *out, uint32_t *out_counts) {
     QMX_REFUSE_SPARSE(ex);
+    QMX_REFUSE_FILTERS(ex);
     QMX_REQUIRE(ex && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     QMX_HIP(hipSetDevice(ex->device));
@@ -98,6 +99,7 @@ int32_t qmx_custom_search_topk(qmx_query *ex, const qmx_custom_query *queries, u
 int32_t qmx_custom_hnsw_search(const qmx_hnsw *g, qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t top, uint32_t ef,
                                qmx_scored_point *out, uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
     QMX_REFUSE_SPARSE(ex);
+    QMX_REFUSE_FILTERS(ex);
     QMX_REQUIRE(g && ex && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_TRY(hnsw_check(g, ex, top, ef));
     QMX_HIP(hipSetDevice(ex->device));
@@ -185,6 +187,7 @@ int32_t qmx_multi_search_topk(qmx_query *inner, const uint32_t *query_first, uin
                               const uint64_t *point_deleted, uint64_t n_deleted_bits, uint32_t top, const uint32_t *ids, uint64_t n_ids,
                               qmx_scored_point *out, uint32_t *out_counts) {
     QMX_REFUSE_SPARSE(inner);
+    QMX_REFUSE_FILTERS(inner);
     QMX_REQUIRE(inner && query_first && point_offsets && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     QMX_HIP(hipSetDevice(inner->device));
@@ -252,6 +255,7 @@ int32_t qmx_multi_custom_search_topk(qmx_query *inner, const uint32_t *example_f
                                      const uint64_t *point_offsets, uint32_t n_points, const uint64_t *point_deleted, uint64_t n_deleted_bits, uint32_t top,
                                      const uint32_t *ids, uint64_t n_ids, qmx_scored_point *out, uint32_t *out_counts) {
     QMX_REFUSE_SPARSE(inner);
+    QMX_REFUSE_FILTERS(inner);
     QMX_REQUIRE(inner && example_first && point_offsets && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     QMX_HIP(hipSetDevice(inner->device));
@@ -292,6 +296,7 @@ int32_t qmx_multi_custom_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const 
                                      uint32_t n_queries, const uint64_t *point_offsets, uint32_t n_points, const uint64_t *point_deleted, uint64_t n_deleted_bits,
                                      uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts, qmx_counters *counters) {
     QMX_REFUSE_SPARSE(inner);
+    QMX_REFUSE_FILTERS(inner);
     QMX_REQUIRE(g && inner && example_first && point_offsets && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     const qmx_segment *s = inner->seg;
     QMX_REQUIRE(g->device == s->device, QMX_ERR_BAD_ARG, "graph lives on device %d, the segment on %d", g->device, s->device);

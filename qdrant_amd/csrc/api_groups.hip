@@ -116,6 +116,7 @@ int32_t qmx_group_search(qmx_query *q, const qmx_group_keys *keys, uint32_t limi
                          uint32_t *out_n_groups, qmx_group_counters *counters) {
     QMX_REQUIRE(q && keys && out_n_groups, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REFUSE_SPARSE(q);
+    QMX_REFUSE_FILTERS(q);
     if (counters) memset(counters, 0, sizeof(*counters));
     const qmx_segment *s = q->seg;
     QMX_REQUIRE(keys->device == s->device, QMX_ERR_BAD_ARG, "the group keys live on device %d, the segment on device %d", keys->device, s->device);

@@ -782,6 +782,9 @@ int32_t hnsw_enqueue(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef,
                             const ExpandedOut *xo, const CustomWalk *cw, const PopTrace *pt) {
     const qmx_segment *s = q->seg;
     QMX_REQUIRE(!tq_l1(s) || !mw, QMX_ERR_NOT_SUPPORTED, "multi-vector walks through a TurboQuant storage over Manhattan are not built");
+    // (per-request filters index the walk's searches as the batch's queries: custom and multi-vector walks, whose searches are not the batch's entries, and
+    // the expanded-candidates walk of search_with_vectors refuse at their entry points - this is the backstop)
+    QMX_REQUIRE(!q->has_filters || (!mw && !cw && !xo), QMX_ERR_NOT_SUPPORTED, "this walk does not serve per-request filters (qmx_query_set_filters)");
     ScanArgs a;
     fill_args(q, 0, q->nq, a);
     if (tq_l1(s)) {   // the walk scores against the query as given (tq_l1_policy.hpp): f32 entries of dim floats, 16-byte padded
@@ -1068,6 +1071,8 @@ int32_t qmx_hnsw_search_traced(const qmx_hnsw *g, qmx_query *q, uint32_t top, ui
     QMX_TRY(q->cand.reserve((size_t)q->nq * pop_cap * sizeof(qmx_scored_point)));
     QMX_TRY(q->xcnt.reserve((size_t)q->nq * 4));
     PopTrace pt{(qmx_scored_point *)q->cand.p, (uint32_t *)q->xcnt.p, pop_cap};
+    // (a search without a live entry point - every point deleted, or rejected by the search's own filter - returns before it counts its pops)
+    QMX_HIP(hipMemsetAsync(q->xcnt.p, 0, (size_t)q->nq * 4, q->stream));
     QMX_TRY(hnsw_enqueue(g, q, top, ef, (qmx_scored_point *)q->out.p, (uint32_t *)q->counts.p, nullptr, false, false, nullptr, nullptr, nullptr, &pt));
     QMX_TRY(copy_out(q->stream, out, q->out.p, (size_t)q->nq * top * sizeof(qmx_scored_point)));
     QMX_TRY(copy_out(q->stream, out_counts, q->counts.p, (size_t)q->nq * 4));
@@ -1095,6 +1100,8 @@ int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_qu
                                      uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
     QMX_REFUSE_SPARSE(links);
     QMX_REFUSE_SPARSE(base);
+    QMX_REFUSE_FILTERS(links);
+    QMX_REFUSE_FILTERS(base);
     QMX_REQUIRE(g && links && base && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_REQUIRE(base->nq == links->nq && base->device == links->device, QMX_ERR_BAD_ARG, "the two query batches must match");
     QMX_REQUIRE(base->seg->n >= g->n_points, QMX_ERR_OUT_OF_BOUNDS, "graph has %u points, the base-vector segment %llu rows", g->n_points,
@@ -1160,6 +1167,7 @@ int32_t qmx_multi_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const uint32_
                               uint32_t n_points, const uint64_t *point_deleted, uint64_t n_deleted_bits, uint32_t top, uint32_t ef,
                               qmx_scored_point *out, uint32_t *out_counts, qmx_counters *counters) {
     QMX_REFUSE_SPARSE(inner);
+    QMX_REFUSE_FILTERS(inner);
     QMX_REQUIRE(g && inner && query_first && point_offsets && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     const qmx_segment *s = inner->seg;
     QMX_REQUIRE(g->device == s->device, QMX_ERR_BAD_ARG, "graph lives on device %d, the segment on %d", g->device, s->device);

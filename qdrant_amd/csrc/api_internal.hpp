@@ -133,6 +133,8 @@ struct qmx_segment {
         v.n_rows = n;
         v.allowed = nullptr;
         v.n_allowed_bits = 0;
+        v.filter_of = nullptr;
+        v.filter_stride = 0;
         return v;
     }
     // rows the brute-force stream visits: iter_zeros(point_deleted) ends at the bitslice length
@@ -186,6 +188,12 @@ struct qmx_query {
     DevBuf filter;             // payload-filter allow bitmap of this query batch (qmx_query_set_filter)
     uint64_t n_filter_bits = 0;
     bool has_filter = false;
+    // per-request filters (qmx_query_set_filters): `filter` holds [n_filters][filter_stride] words, filter_of the bitmap of each query; has_filter stays
+    // false - a call that reads has_filter alone would ignore them, and refuses instead (QMX_REFUSE_FILTERS)
+    DevBuf filter_of, filter_of_packed;   // [nq]; the same for the overflowed queries of a prefilter search, packed as their exact passes take them
+    uint32_t n_filters = 0;
+    uint64_t filter_stride = 0;           // words
+    bool has_filters = false;
     DevBuf hnsw_lutx;          // exact-order LUTs made for the hop prefilter's image of a LUT-free walk whose batch LUTs came from the matrix cores
     DevBuf hnsw_pq8;           // the 8-bit LUT images of the batch for the PQ walk's hop prefilter (HnswArgs::pq8)
     DevBuf hnsw_next;          // the walk's work counter (HnswArgs::next_query)
@@ -227,6 +235,16 @@ static inline int32_t refuse_sparse(const char *fn) {
 #define QMX_REFUSE_SPARSE(x)                                 \
     do {                                                     \
         if (is_sparse(x)) return refuse_sparse(__func__);    \
+    } while (0)
+// per-request filters (qmx_query_set_filters) are served by the dense top-k searches and the plain / ACORN walks; every other call that would filter refuses
+// a batch that carries them rather than ignore them
+static inline int32_t refuse_filters(const char *fn) {
+    set_error("%s: not supported on a batch with per-request filters (qmx_query_set_filters); clear them with qmx_query_set_filter(q, NULL, 0)", fn);
+    return QMX_ERR_NOT_SUPPORTED;
+}
+#define QMX_REFUSE_FILTERS(q)                                           \
+    do {                                                                \
+        if ((q) && (q)->has_filters) return refuse_filters(__func__);   \
     } while (0)
 // the caller's cancellation flag, read between the launches of a search
 #define QMX_CHECK_CANCELLED(is_stopped)                      \

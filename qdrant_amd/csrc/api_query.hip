@@ -177,6 +177,7 @@ int32_t qmx_query_destroy(qmx_query *q) {
 int32_t qmx_query_set_filter(qmx_query *q, const uint64_t *allowed, uint64_t n_bits) {
     QMX_REQUIRE(q, QMX_ERR_BAD_ARG, "NULL query");
     QMX_HIP(hipSetDevice(q->device));
+    q->has_filters = false;      // (either call replaces the other's filter)
     if (!allowed) {
         q->has_filter = false;
         q->n_filter_bits = 0;
@@ -188,6 +189,33 @@ int32_t qmx_query_set_filter(qmx_query *q, const uint64_t *allowed, uint64_t n_b
     QMX_HIP(hipStreamSynchronize(q->stream));     // the caller's buffer may go away
     q->n_filter_bits = n_bits;
     q->has_filter = true;
+    return QMX_OK;
+}
+
+int32_t qmx_query_set_filters(qmx_query *q, const uint64_t *bitmaps, uint64_t n_bits, uint32_t n_filters, const uint32_t *filter_of_query) {
+    QMX_REQUIRE(q, QMX_ERR_BAD_ARG, "NULL query");
+    QMX_REQUIRE(bitmaps && (filter_of_query || q->nq == 0), QMX_ERR_BAD_ARG, "NULL argument");
+    QMX_REQUIRE(n_filters >= 1, QMX_ERR_BAD_ARG, "n_filters must be >= 1");
+    QMX_HIP(hipSetDevice(q->device));
+    // the indices are validated on the host, whichever side they live on: the kernels index the bitmaps with them unchecked
+    // (behind the batch's entries: QMX_FILTER_NONE for the padding queries of a last tile, whose index a kernel may form before it drops them)
+    std::vector<uint32_t> fof((size_t)q->nq + SPLIT_QT_MAX, QMX_FILTER_NONE);
+    if (q->nq) QMX_HIP(hipMemcpy(fof.data(), filter_of_query, (size_t)q->nq * 4, hipMemcpyDefault));
+    for (uint32_t i = 0; i < q->nq; ++i)
+        QMX_REQUIRE(fof[i] < n_filters || fof[i] == QMX_FILTER_NONE, QMX_ERR_OUT_OF_BOUNDS, "filter_of_query[%u] = %u: not below n_filters = %u and not QMX_FILTER_NONE", i,
+                    fof[i], n_filters);
+    const size_t words = (size_t)((n_bits + 63) / 64);
+    QMX_HIP(hipStreamSynchronize(q->stream));     // (a search still running reads the buffers rewritten below)
+    q->has_filter = q->has_filters = false;
+    QMX_TRY(q->filter.reserve(std::max<size_t>(words * n_filters, 1) * 8));
+    QMX_TRY(q->filter_of.reserve(fof.size() * 4));
+    if (words) QMX_HIP(hipMemcpyAsync(q->filter.p, bitmaps, words * n_filters * 8, hipMemcpyDefault, q->stream));
+    QMX_HIP(hipMemcpyAsync(q->filter_of.p, fof.data(), fof.size() * 4, hipMemcpyHostToDevice, q->stream));
+    QMX_HIP(hipStreamSynchronize(q->stream));     // the caller's buffers, and fof, may go away
+    q->n_filter_bits = n_bits;
+    q->n_filters = n_filters;
+    q->filter_stride = words;
+    q->has_filters = true;
     return QMX_OK;
 }
 
@@ -280,6 +308,12 @@ void fill_args(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, ScanArgs &a
     if (q->has_filter) {
         a.del.allowed = (const uint64_t *)q->filter.p;
         a.del.n_allowed_bits = q->n_filter_bits;
+    }
+    if (q->has_filters) {        // per-request: the tile's queries index filter_of as they index a.queries
+        a.del.allowed = (const uint64_t *)q->filter.p;
+        a.del.n_allowed_bits = q->n_filter_bits;
+        a.del.filter_of = (const uint32_t *)q->filter_of.p + tile0;
+        a.del.filter_stride = q->filter_stride;
     }
     a.err_flag = q->d_err;
     a.tq_l1 = s->d_tq_l1;

@@ -201,9 +201,12 @@ static int32_t overflow_passes(const SearchCall &c, const SplitPlanLayout &pl, u
     uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
     uint64_t *gthr_packed = (uint64_t *)(plan + pl.gthr_packed);
     const uint32_t n_run = (nq + FQT - 1) / FQT;
+    // (per-request filters: the packed queries' bitmap indices, packed with them)
+    if (q->has_filters) QMX_TRY(q->filter_of_packed.reserve((size_t)n_run * FQT * 4));
+    const uint32_t *fof_packed = q->has_filters ? (const uint32_t *)q->filter_of_packed.p : nullptr;
     QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), nq, (const uint64_t *)q->gthr.p, ovf_list, gthr_packed, n_run * FQT,
                               (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), n_run, (SplitStats *)plan, q->d_queries,
-                              q->q_stride, q->sp_fq.p));
+                              q->q_stride, q->sp_fq.p, q->has_filters ? (const uint32_t *)q->filter_of.p : nullptr, (uint32_t *)q->filter_of_packed.p));
     for (uint32_t pass = 0; pass <= n_run; ++pass) {      // pass 0: the 16-query shape; pass p >= 1: packed queries FQT (p - 1) ..
         if (pass && nq <= 16) break;
         const uint32_t p0 = pass ? (pass - 1) * FQT : 0;
@@ -211,6 +214,7 @@ static int32_t overflow_passes(const SearchCall &c, const SplitPlanLayout &pl, u
         const int *run_if = pass ? (const int *)(plan + pl.run64) + (pass - 1) : (const int *)(plan + pl.run16);
         ScanArgs a = tile_args(c, 0, nq_sub);
         a.queries = (const char *)q->sp_fq.p + (size_t)p0 * q->q_stride;
+        if (fof_packed) a.del.filter_of = fof_packed + p0;
         a.partial = (uint64_t *)q->partial.p;
         a.gthr = gthr_packed + p0;
         a.run_if = run_if;
@@ -273,7 +277,9 @@ static int32_t tq_l1_search(const SearchCall &c, const SearchPlan &plan) {
         QMX_CHECK_CANCELLED(c.is_stopped);
         const uint32_t nq_tile = std::min<uint32_t>(qtile, q->nq - q0);
         QMX_TRY(tq_l1_scores_device(q, q0, nq_tile, c.d_ids, c.n_cand, (float *)q->scores.p, c.n_cand, nullptr));
-        QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, c.n_cand, c.d_ids, a.del, nq_tile, c.top, c.d_out + (size_t)q0 * c.top, c.d_counts + q0));
+        DeletedView del = a.del;      // (block b of the selection is query q0 + b)
+        if (del.filter_of) del.filter_of += q0;
+        QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, c.n_cand, c.d_ids, del, nq_tile, c.top, c.d_out + (size_t)q0 * c.top, c.d_counts + q0));
         if (c.counters) c.counters->kernel_launches += 1 + 3 * (uint32_t)((c.n_cand + 65535) / 65536);
     }
     if (c.counters) {      // (this route adds to the caller's counters and leaves last_counters at zero)
@@ -598,6 +604,7 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
                               qmx_scored_point *d_out, uint32_t *d_counts, const volatile uint8_t *is_stopped,
                               qmx_counters *counters, bool timed) {
     const qmx_segment *s = q->seg;
+    if (is_sparse(s)) QMX_REFUSE_FILTERS(q);
     if (is_sparse(s)) return sparse_search_enqueue(q, top, d_ids, n_ids, d_out, d_counts, is_stopped, counters, timed);
     SearchCall c{q, top, d_ids, d_ids ? n_ids : s->scan_rows(), d_out, d_counts, is_stopped, counters, timed, 0};
     const SearchPlan plan = search_plan(q, top, d_ids, c.n_cand);

@@ -660,6 +660,7 @@ int32_t qmx_sparse_custom_search_topk(qmx_query *ex, const qmx_custom_query *que
                                       qmx_scored_point *out, uint32_t *out_counts, const volatile uint8_t *is_stopped, qmx_counters *counters) {
     QMX_REQUIRE(ex && (n_queries == 0 || queries) && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
     QMX_TRY(sparse_custom_check(ex, __func__));
+    QMX_REFUSE_FILTERS(ex);
     QMX_REQUIRE(top >= 1 && top <= MAX_TOP, QMX_ERR_NOT_SUPPORTED, "top %u not in 1..%u", top, MAX_TOP);
     QMX_HIP(hipSetDevice(ex->device));
     if (counters) memset(counters, 0, sizeof(*counters));

@@ -165,12 +165,33 @@ struct DeletedView {
     uint64_t n_rows;
     const uint64_t *allowed;     // nullptr = no payload filter; ids past n_allowed_bits are rejected
     uint64_t n_allowed_bits;
-    __device__ __forceinline__ bool live(uint32_t id) const {
+    // per-request filters (qmx_query_set_filters): query q of the view is held to bitmap filter_of[q] of `allowed` - now [n_filters][filter_stride] words,
+    // every bitmap n_allowed_bits long - or, QMX_FILTER_NONE, to no filter.  nullptr = the one filter above for every query.  The index q is the one the
+    // kernel's queries, bounds and lists carry: fill_args offsets filter_of with the tile, the packed exact passes get a packed copy.
+    const uint32_t *filter_of = nullptr;
+    uint64_t filter_stride = 0;  // words
+    // the bitmap that holds query q: with per-request filters one more (wave-uniform where q is) load and an address, nothing else changes
+    __device__ __forceinline__ const uint64_t *allowed_of(uint32_t q) const {
+        if (!filter_of) return allowed;
+        const uint32_t f = filter_of[q];
+        return f == QMX_FILTER_NONE ? nullptr : allowed + (uint64_t)f * filter_stride;
+    }
+    __device__ __forceinline__ bool live_under(uint32_t id, const uint64_t *filter) const {
         bool vdel = (vec_deleted && id < n_vec_bits) ? bit_get(vec_deleted, id) : false;
         bool pdel = point_deleted ? (id < n_point_bits ? bit_get(point_deleted, id) : true)
                                   : !(id < n_rows);
-        bool ok = allowed ? (id < n_allowed_bits && bit_get(allowed, id)) : true;
+        bool ok = filter ? (id < n_allowed_bits && bit_get(filter, id)) : true;
         return !vdel && !pdel && ok;
+    }
+    __device__ __forceinline__ bool live(uint32_t id) const { return live_under(id, allowed); }
+    // live for query q of the view
+    __device__ __forceinline__ bool live(uint32_t id, uint32_t q) const { return live_under(id, allowed_of(q)); }
+    // the view of query q alone: its bitmap as the plain `allowed` (what a kernel whose block serves one query resolves once)
+    __device__ __forceinline__ DeletedView of_query(uint32_t q) const {
+        DeletedView v = *this;
+        v.allowed = allowed_of(q);
+        v.filter_of = nullptr;
+        return v;
     }
 };
 

@@ -110,11 +110,12 @@ __device__ __forceinline__ void live_masks(const DeletedView &d, const uint32_t 
 
 constexpr int CT_BLOCK = 1024;
 constexpr int CT_NW = CT_BLOCK / WAVE;
-__global__ __launch_bounds__(CT_BLOCK) void custom_topk_kernel(const float *scores, uint64_t n, const uint32_t *ids, DeletedView del, uint32_t top,
+__global__ __launch_bounds__(CT_BLOCK) void custom_topk_kernel(const float *scores, uint64_t n, const uint32_t *ids, DeletedView del_all, uint32_t top,
                                                                qmx_scored_point *out, uint32_t *out_counts, uint64_t *bound_out) {
     __shared__ uint64_t sh[CT_NW][WAVE];
     __shared__ uint64_t sh_bound;
     const uint32_t q = blockIdx.x;
+    const DeletedView del = del_all.of_query(q);      // (per-request filters: the block's query has one bitmap)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float *row = scores + (uint64_t)q * n;
     uint64_t bound = ~0ull;
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(CT_BLOCK) void custom_topk_kernel(const float *scor
 // (rank = number of larger keys: keys are distinct) - rank r goes to slot r.  Same lists, same tie order (the key carries the id) as the kernel above.
 constexpr int CTS_E = 16;
 constexpr uint64_t CTS_MAX_N = (uint64_t)CT_BLOCK * CTS_E;
-__global__ __launch_bounds__(CT_BLOCK) void custom_topk_small_kernel(const float *scores, uint32_t n, const uint32_t *ids, DeletedView del, uint32_t top,
+__global__ __launch_bounds__(CT_BLOCK) void custom_topk_small_kernel(const float *scores, uint32_t n, const uint32_t *ids, DeletedView del_all, uint32_t top,
                                                                      qmx_scored_point *out, uint32_t *out_counts, uint64_t *bound_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_cts[];
     uint64_t *surv = reinterpret_cast<uint64_t *>(smem_cts);          // [n]
@@ -210,6 +211,7 @@ __global__ __launch_bounds__(CT_BLOCK) void custom_topk_small_kernel(const float
     __shared__ uint64_t sh_bound;
     __shared__ uint32_t sh_cnt;
     const uint32_t q = blockIdx.x;
+    const DeletedView del = del_all.of_query(q);      // (per-request filters: the block's query has one bitmap)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float *row = scores + (uint64_t)q * n;
     uint64_t kreg[CTS_E];

@@ -227,6 +227,22 @@ template <class H, class = void>
 struct is_custom { static constexpr bool value = false; };
 template <class H>
 struct is_custom<H, decltype((void)H::CUSTOM)> { static constexpr bool value = H::CUSTOM; };
+
+// Per-request payload filters (qmx_query_set_filters) in the walk: the same hop policy under another name, instantiated beside the plain one and launched
+// only for a batch that carries such filters (launch_hnsw_hop).  The walks of every other batch are the instantiations they were: their liveness test does
+// not know of a second index.
+template <class H>
+struct HopPerQuery : H { static constexpr bool PER_QUERY_FILTER = true; };
+template <class H, class = void>
+struct per_query_filter { static constexpr bool value = false; };
+template <class H>
+struct per_query_filter<H, decltype((void)H::PER_QUERY_FILTER)> { static constexpr bool value = H::PER_QUERY_FILTER; };
+// filters().check_vector(id) of search qi
+template <class H>
+__device__ __forceinline__ bool walk_live(const DeletedView &d, uint32_t id, uint32_t qi) {
+    if constexpr (per_query_filter<H>::value) return d.live(id, qi);
+    else return d.live(id);
+}
 template <class HI>
 struct HopCustom {
     static constexpr int LPI = HI::LPI;
@@ -668,7 +684,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
     uint32_t ep_id = 0, ep_level = 0;
     for (uint32_t base = 0; base < h.n_ep && !have_ep; base += 64) {
         const uint32_t i = base + (uint32_t)lane;
-        const bool ok = i < h.n_ep && a.del.live(h.ep_ids[i < h.n_ep ? i : 0]);
+        const bool ok = i < h.n_ep && walk_live<H>(a.del, h.ep_ids[i < h.n_ep ? i : 0], qi);
         const uint64_t m = __ballot(ok);
         if (m) {
             const uint32_t first = base + (uint32_t)__builtin_ctzll(m);
@@ -680,7 +696,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
     if (!have_ep) {
         for (uint32_t i = 0; i < h.n_xp; ++i) {   // max_by_key(level): the last maximal element wins
             const uint32_t id = h.xp_ids[i], lv = h.xp_levels[i];
-            if (a.del.live(id) && (!have_ep || lv >= ep_level)) { ep_id = id; ep_level = lv; have_ep = true; }
+            if (walk_live<H>(a.del, id, qi) && (!have_ep || lv >= ep_level)) { ep_id = id; ep_level = lv; have_ep = true; }
         }
     }
     if (!have_ep) {
@@ -718,7 +734,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
                 const uint64_t i = base + (uint64_t)lane;
                 const bool on = i < o1;
                 const uint32_t id = on ? h.neighbors[i] : 0;
-                bool keep = on && id < h.n_points && a.del.live(id);
+                bool keep = on && id < h.n_points && walk_live<H>(a.del, id, qi);
                 const uint64_t mask = __ballot(keep);
                 const uint32_t rank = (uint32_t)__popcll(mask & lt_mask);
                 keep = keep && rank < remaining;
@@ -799,7 +815,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
                 const uint64_t i = base + (uint64_t)lane;
                 const bool on = i < o1;
                 const uint32_t id = h.l0 ? (on ? packed_id : 0) : (on ? h.neighbors[i] : 0);
-                const bool live = on && id < h.n_points && a.del.live(id);
+                const bool live = on && id < h.n_points && walk_live<H>(a.del, id, qi);
                 const uint32_t bit = 1u << (id & 31);
                 bool in_bm = true, was_visited = true;
                 if (lv.tab) {
@@ -951,7 +967,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
                     const bool valid = on && id < h.n_points;
                     const uint32_t bit = 1u << (id & 31);
                     const uint32_t old = valid ? atomicOr(&vis[id >> 5], bit) : bit;      // check_and_update_visited
-                    const bool lv = valid ? a.del.live(id) : false;                        // filters().check_vector(hop1), in flight with it
+                    const bool lv = valid ? walk_live<H>(a.del, id, qi) : false;           // filters().check_vector(hop1), in flight with it
                     const bool fresh = valid && !(old & bit);
                     const bool ok = fresh && lv;
                     const uint64_t okm = __ballot(ok), frm = __ballot(fresh);
@@ -1003,7 +1019,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
                     const uint32_t bit = 1u << (id & 31);
                     const uint32_t r1 = valid ? atomicOr(&vis[id >> 5], 0u) : bit;                        // hop1_visited_list.check(hop2)
                     const uint32_t old2 = valid ? atomicOr(&vis[half + (id >> 5)], bit) : bit;            // hop2_visited_list.check_and_update_visited(hop2)
-                    const bool lv = valid ? a.del.live(id) : false;                                       // filters().check_vector(hop2)
+                    const bool lv = valid ? walk_live<H>(a.del, id, qi) : false;                          // filters().check_vector(hop2)
                     const bool s1 = (r1 & bit) != 0;
                     const bool set2 = valid && !(old2 & bit);            // this lane set the hop-2 bit
                     if (s1 && set2) atomicAnd(&vis[half + (id >> 5)], ~bit);
@@ -1095,7 +1111,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
             const uint64_t i = base + (uint64_t)lane;
             const bool on = i < o1;
             const uint32_t id = h.l0 ? (on ? packed_id : 0) : (on ? h.neighbors[i] : 0);
-            const bool live = on && id < h.n_points && a.del.live(id);
+            const bool live = on && id < h.n_points && walk_live<H>(a.del, id, qi);
             const uint32_t bit = 1u << (id & 31);
             bool in_bm = true, was_visited = true;
             if (lv.tab) {
@@ -1398,6 +1414,11 @@ template <class H>
 int32_t launch_hnsw_hop(hipStream_t st, const ScanArgs &a, const HnswArgs &h, uint32_t grid, int *per_cu) {
     const uint32_t ef = h.ef > h.top ? h.ef : h.top;
     QMX_REQUIRE(ef >= 1 && ef <= HNSW_MAX_EF, QMX_ERR_NOT_SUPPORTED, "hnsw ef %u not in 1..%u", ef, HNSW_MAX_EF);
+    if constexpr (!per_query_filter<H>::value && !is_custom<H>::value && !is_maxsim<H>::value && !is_maxsim_q<H>::value && !is_maxsim_internal<H>::value) {
+        if (a.del.filter_of) return launch_hnsw_hop<HopPerQuery<H>>(st, a, h, grid, per_cu);      // (also for the occupancy query: the scratch is sized for the kernel that runs)
+    } else if constexpr (!per_query_filter<H>::value) {
+        QMX_REQUIRE(!a.del.filter_of, QMX_ERR_NOT_SUPPORTED, "this walk does not serve per-request filters (qmx_query_set_filters)");
+    }
     const bool qlds = h.lds_query_bytes > 0;
     if constexpr (is_maxsim<H>::value) QMX_REQUIRE(qlds, QMX_ERR_NOT_SUPPORTED, "the inner vectors of a multi-query must fit the LDS");
     if constexpr (is_custom<H>::value) QMX_REQUIRE(h.lds_query_bytes >= sizeof(CustomHeader), QMX_ERR_OTHER, "the custom walk keeps its header in LDS");

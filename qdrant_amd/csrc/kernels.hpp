@@ -420,7 +420,7 @@ int32_t launch_scan_sqw(hipStream_t st, const ScanArgs &a, const void *d_bq, con
 // the overflowed queries packed for the conditional exact passes: list, their pre-scan bounds, the passes' run flags
 int32_t launch_split_plan(hipStream_t st, const uint32_t *d_ovf_q, uint32_t nq, const uint64_t *d_gthr, uint32_t *d_list, uint64_t *d_gthr_packed, uint32_t list_cap,
                           uint32_t *d_count, int *d_run16, int *d_run64, uint32_t n_run64, SplitStats *d_stats, const void *d_queries, uint32_t q_stride,
-                          void *d_packed_queries);
+                          void *d_packed_queries, const uint32_t *d_filter_of = nullptr, uint32_t *d_filter_of_packed = nullptr);
 // order statistics of a float array (quantile.hip): the SQ quantile interval
 int32_t launch_order_statistics_f32(hipStream_t st, const float *d_in, float *d_tmp, uint64_t n, uint64_t lo_pos, uint64_t hi_pos, float *h_out);
 // BQ 1-bit (scan_bq.hip)

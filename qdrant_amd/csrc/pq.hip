@@ -211,6 +211,7 @@ __global__ __launch_bounds__(PQ_BLOCK) void pq_scan_kernel(const ScanArgs a, uin
     const uint32_t m = a.pq_m, ncent = a.pq_ncent;
     const uint32_t qsrc = a.q_map ? a.q_map[q] : q;          // (packed exact pass: list q belongs to query q_map[q] of the batch)
     if (qsrc == 0xFFFFFFFFu) return;
+    const DeletedView del = a.del.of_query(qsrc);            // (per-request filters: the block's query has one bitmap; the packed pass indexes through q_map)
     const float *glut = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(a.queries) + (uint64_t)qsrc * a.q_stride);
     if (LDS_LUT) {
         const uint4 *src = reinterpret_cast<const uint4 *>(glut);
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(PQ_BLOCK) void pq_scan_kernel(const ScanArgs a, uin
             const uint64_t key = make_key(score, id);
             bool c = valid && key > readlane_u64(list, top - 1);
             if (__ballot(c)) {
-                c = c && a.del.live(id) && (!a.key_bound || key < a.key_bound[q]);
+                c = c && del.live(id) && (!a.key_bound || key < a.key_bound[q]);
                 uint64_t mask = __ballot(c);
                 while (mask) {
                     const int src = __builtin_ctzll(mask);

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(BQR_BLOCK) void bq_rows_kernel(const ScanArgs a) {
                     const uint64_t thr = readlane_u64(list[q], top - 1);
                     bool cnd = valid && key > thr && key >= floor_key[q];
                     if (__ballot(cnd)) {
-                        cnd = cnd && a.del.live(id) && (!a.key_bound || key < a.key_bound[q]);
+                        cnd = cnd && a.del.live(id, (uint32_t)q) && (!a.key_bound || key < a.key_bound[q]);
                         uint64_t m = __ballot(cnd);
                         while (m) {
                             const int src = __builtin_ctzll(m);

@@ -103,7 +103,10 @@ __device__ __forceinline__ uint4 load_row_piece(const unsigned char *p) {
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
-template <class P, int QT, int R, int UNROLL, bool HAS_IDS, int MODE>
+// PERQ: the batch carries per-request filters (qmx_query_set_filters) - the liveness test picks the bitmap of the candidate's query
+// (the last template argument: the instantiation every batch without them runs is, but for that `false` in its name, the kernel it was; launch_scan_inst picks
+// the other one for a top-k scan by a.del.filter_of)
+template <class P, int QT, int R, int UNROLL, bool HAS_IDS, int MODE, bool PERQ = false>
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_kernel(const ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NW = SCAN_BLOCK / WAVE;
@@ -205,7 +208,9 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_kernel(const ScanArgs a) {
                         const uint64_t thr = readlane_u64(list[q], (int)a.top - 1);
                         bool c = valid[r] && (t == 0) && (key > thr);
                         if (__ballot(c)) {
-                            c = c && a.del.live(rid[r]) && (!a.key_bound || key < a.key_bound[q]);
+                            if constexpr (PERQ) c = c && a.del.live(rid[r], (uint32_t)q);
+                            else c = c && a.del.live(rid[r]);
+                            c = c && (!a.key_bound || key < a.key_bound[q]);
                             uint64_t m = __ballot(c);
                             while (m) {
                                 const int src = __builtin_ctzll(m);
@@ -259,10 +264,16 @@ int32_t launch_scan_inst(hipStream_t st, const ScanArgs &a, int num_cus, uint32_
     lds = (lds + 15) & ~(size_t)15;
     QMX_REQUIRE(lds <= 160 * 1024, QMX_ERR_NOT_SUPPORTED, "query tile needs %zu B of LDS (> 160 KiB)", lds);
     auto kfn = scan_kernel<P, QT, R, UNROLL, HAS_IDS, MODE>;
+    if constexpr (MODE == SCAN_TOPK) {
+        if (a.del.filter_of) kfn = scan_kernel<P, QT, R, UNROLL, HAS_IDS, MODE, true>;
+    }
     static thread_local DeviceOnce attr_once;
     if (attr_once.need()) {
-        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_kernel<P, QT, R, UNROLL, HAS_IDS, MODE>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if constexpr (MODE == SCAN_TOPK)
+            QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_kernel<P, QT, R, UNROLL, HAS_IDS, MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
         attr_once.mark();
     }
     int per_cu = 0;
@@ -371,7 +382,7 @@ __global__ __launch_bounds__(SMALL_BLOCK) void scan_small_kernel(const ScanArgs 
             const uint64_t key = make_key(score, id);
             bool cnd = valid && key > readlane_u64(list, top - 1);
             if (__ballot(cnd)) {
-                cnd = cnd && a.del.live(id) && (!a.key_bound || key < a.key_bound[q]);
+                cnd = cnd && a.del.live(id, q) && (!a.key_bound || key < a.key_bound[q]);
                 uint64_t m = __ballot(cnd);
                 while (m) {
                     const int src = __builtin_ctzll(m);

@@ -271,7 +271,7 @@ __device__ __forceinline__ void scan_f32_mfma_body(const ScanArgs &a, unsigned c
                 bool c = mine && !(score < thr_f[gp]);
                 if (__ballot(c)) {
                     const uint64_t key = make_key(score, res_row);
-                    c = c && key > thr[gp] && a.del.live(res_row) && (!a.key_bound || key < a.key_bound[q]);
+                    c = c && key > thr[gp] && a.del.live(res_row, q) && (!a.key_bound || key < a.key_bound[q]);
                     uint64_t mask = __ballot(c);
                     while (mask) {
                         const int src = __builtin_ctzll(mask);

@@ -73,10 +73,17 @@ __device__ __forceinline__ bool bit_get_uniform(const uint64_t *words, uint32_t 
     asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wv) : "s"(p) : "memory");
     return (wv >> (id & 63)) & 1;
 }
-__device__ __forceinline__ bool live_uniform(const DeletedView &d, uint32_t id) {   // DeletedView::live for a uniform id
+// DeletedView::live for a uniform id; `filter_of` / `stride`: the per-request filters of the view (DeletedView::filter_of, filter_stride) as the caller read them,
+// `q` the query the candidate belongs to - its bitmap index is one more scalar load, then its bitmap is the one filter (DeletedView::allowed_of)
+__device__ __forceinline__ bool live_uniform(const DeletedView &d, uint32_t id, const uint32_t *filter_of, uint64_t stride, uint32_t q) {
     const bool vdel = (d.vec_deleted && id < d.n_vec_bits) ? bit_get_uniform(d.vec_deleted, id) : false;
     const bool pdel = d.point_deleted ? (id < d.n_point_bits ? bit_get_uniform(d.point_deleted, id) : true) : !(id < d.n_rows);
-    const bool ok = d.allowed ? (id < d.n_allowed_bits && bit_get_uniform(d.allowed, id)) : true;
+    const uint64_t *allowed = d.allowed;
+    if (filter_of) {
+        const uint32_t f = sload_u32(filter_of + q);
+        allowed = f == QMX_FILTER_NONE ? nullptr : d.allowed + (uint64_t)f * stride;
+    }
+    const bool ok = allowed ? (id < d.n_allowed_bits && bit_get_uniform(allowed, id)) : true;
     return !vdel && !pdel && ok;
 }
 
@@ -98,7 +105,8 @@ struct M16Shape {
 
 template <int KSTEPS /* dim / 128: 512-byte K-steps per row */, int NW, int NT, int DBG = 0 /* tuning experiments (QMX_M16_DBG): 2 no row loads, 3 no fold / selection */,
           bool LAG = (NW == 8 && NT == 4 && KSTEPS == 6) /* half of the waves run one stage behind the others, see `lag` */,
-          bool IDS = false /* candidates = a.ids[0 .. n_cand) instead of rows 0 .. n_cand) (payload-filtered scans, peek_top_iter) */>
+          bool IDS = false /* candidates = a.ids[0 .. n_cand) instead of rows 0 .. n_cand) (payload-filtered scans, peek_top_iter) */,
+          bool PERQ = false /* the batch carries per-request filters (qmx_query_set_filters): the liveness test picks the candidate's query's bitmap */>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void scan_f32_mfma16_kernel(const ScanArgs a) {
     if (a.run_if && *a.run_if == 0) return;           // the exact pass behind the split prefilter was not needed (scan_split.hip)
     constexpr int KPS = KSTEPS % 2 == 0 ? 2 : 1;      // K-steps per ring stage
@@ -269,8 +277,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void scan_f32_mfma16_kern
                 mask &= mask - 1;
                 const uint64_t nk = readlane_u64(key, src);
                 const uint32_t id = (uint32_t)__builtin_amdgcn_readlane((int)res_row, src);
-                if (!live_uniform(a.del, id)) continue;
                 const int ql = src & 15;                                            // the source lane's query inside the tile
+                if constexpr (PERQ) {
+                    if (!live_uniform(a.del, id, a.del.filter_of, a.del.filter_stride, (uint32_t)(16 * tq + ql))) continue;
+                } else {
+                    if (!live_uniform(a.del, id, nullptr, 0, 0)) continue;
+                }
 #pragma unroll
                 for (int qq = 0; qq < 16; ++qq) {
                     if (ql == qq) {
@@ -444,6 +456,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void scan_f32_mfma16_kern
     }
 }
 
+// (PERQ is the last template argument: the instantiation every batch without per-request filters runs is, but for that `false` in its name, the kernel it
+// was - its liveness test does not know of a second index; launch_m16 picks the other one by a.del.filter_of)
 template <int KSTEPS, int NW, int NT, int DBG = 0, bool LAG = (NW == 8 && NT == 4 && KSTEPS == 6), bool IDS = false>
 static int32_t launch_m16(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out) {
     if constexpr (!IDS && DBG == 0 && LAG == (NW == 8 && NT == 4 && KSTEPS == 6)) {
@@ -454,10 +468,13 @@ static int32_t launch_m16(hipStream_t st, const ScanArgs &a, int num_cus, uint32
         }
     }
     typedef M16Shape<NW, NT, (KSTEPS % 2 == 0 ? 2 : 1)> S;
-    auto kfn = scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS>;
+    auto kfn = a.del.filter_of ? scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, true> : scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, false>;
     static thread_local DeviceOnce attr_once;
     if (attr_once.need()) {
-        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    160 * 1024));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    160 * 1024));
         attr_once.mark();
     }
     const uint64_t n_tiles = (a.n_cand + 15) / 16;

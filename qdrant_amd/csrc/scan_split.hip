@@ -381,7 +381,7 @@ __global__ __launch_bounds__(SP_THREADS, 1) void scan_f32_split_kernel(const Sca
                             if (__ballot(c)) {
                                 uint32_t q = wn * 64 + (uint32_t)nt * 16 + m_r;
                                 asm volatile("" : "+v"(q));                            // (keeps the buffer addresses out of the registers of the main loop)
-                                if (c && q < s.nq && a.del.live(row)) {
+                                if (c && q < s.nq && a.del.live(row, q)) {
                                     const uint32_t slot = atomicAdd(&s.cand_cnt[q], 1u);
                                     if (slot < s.cap) s.cand[(uint64_t)q * s.cap + slot] = make_key(v * inv_scale, row);
                                 }
@@ -846,7 +846,7 @@ __global__ __launch_bounds__(256) void sp_regroup_kernel(const uint4 *wlist, con
     };
     for (uint32_t i = threadIdx.x; i < total; i += 256) {
         const uint4 e = entry(i);
-        if (e.z < (uint32_t)SP_QT_MAX && del.live(e.x ^ 0xFFFFFFFFu)) atomicAdd(&hist[e.z], 1u);      // (e.z = 0xFFFFFFFF: an entry tq4w_finish_kernel withdrew)
+        if (e.z < (uint32_t)SP_QT_MAX && del.live(e.x ^ 0xFFFFFFFFu, e.z)) atomicAdd(&hist[e.z], 1u);      // (e.z = 0xFFFFFFFF: an entry tq4w_finish_kernel withdrew)
     }
     __syncthreads();
     if (threadIdx.x < SP_QT_MAX) {
@@ -857,7 +857,7 @@ __global__ __launch_bounds__(256) void sp_regroup_kernel(const uint4 *wlist, con
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < total; i += 256) {
         const uint4 e = entry(i);
-        if (e.z >= (uint32_t)SP_QT_MAX || !del.live(e.x ^ 0xFFFFFFFFu)) continue;
+        if (e.z >= (uint32_t)SP_QT_MAX || !del.live(e.x ^ 0xFFFFFFFFu, e.z)) continue;
         const uint32_t at = base[e.z] + atomicAdd(&hist[e.z], 1u);
         if (at < cap) cand[(uint64_t)e.z * cap + at] = ((uint64_t)e.y << 32) | e.x;
     }
@@ -1087,7 +1087,8 @@ __global__ __launch_bounds__(SEL_BLOCK) void sp_select_kernel(const uint64_t *ca
 // the conditional exact passes (api_*.hip: one 16-query pass when 1..16 queries overflowed, else passes of 64) ----
 __global__ __launch_bounds__(256) void sp_plan_kernel(const uint32_t *ovf_q, uint32_t nq, const uint64_t *gthr, uint32_t *list, uint64_t *gthr_packed,
                                                        uint32_t list_cap, uint32_t *count, int *run16, int *run64, uint32_t n_run64, SplitStats *stats,
-                                                       const uint4 *queries, uint32_t units_per_query, uint4 *packed_queries) {
+                                                       const uint4 *queries, uint32_t units_per_query, uint4 *packed_queries, const uint32_t *filter_of,
+                                                       uint32_t *filter_of_packed) {
     __shared__ uint32_t sh_cnt;
     const uint32_t lane = threadIdx.x & 63;
     if (threadIdx.x < 64) {
@@ -1123,6 +1124,9 @@ __global__ __launch_bounds__(256) void sp_plan_kernel(const uint32_t *ovf_q, uin
         const uint32_t src = list[j < cnt ? j : 0];
         packed_queries[gid] = queries[(uint64_t)src * units_per_query + u];
     }
+    // per-request filters follow their queries into the packed passes
+    if (filter_of)
+        for (uint32_t j = threadIdx.x; j < list_cap; j += 256) filter_of_packed[j] = filter_of[list[j < cnt ? j : 0]];
 }
 
 // ---- row statistics of an f32 block (once per segment): stats[0] = max |x|, stats[1] = max row sum of squares (uint bits) ----
@@ -1903,11 +1907,11 @@ int32_t launch_split_select(hipStream_t st, const uint64_t *d_cand, const uint32
 }
 int32_t launch_split_plan(hipStream_t st, const uint32_t *d_ovf_q, uint32_t nq, const uint64_t *d_gthr, uint32_t *d_list, uint64_t *d_gthr_packed, uint32_t list_cap,
                           uint32_t *d_count, int *d_run16, int *d_run64, uint32_t n_run64, SplitStats *d_stats, const void *d_queries, uint32_t q_stride,
-                          void *d_packed_queries) {
+                          void *d_packed_queries, const uint32_t *d_filter_of, uint32_t *d_filter_of_packed) {
     QMX_REQUIRE(q_stride % 16 == 0, QMX_ERR_OTHER, "query entries are whole 16-byte units");
     ::qmx::clear_stale_error();
     hipLaunchKernelGGL(sp_plan_kernel, dim3(1), dim3(256), 0, st, d_ovf_q, nq, d_gthr, d_list, d_gthr_packed, list_cap, d_count, d_run16, d_run64, n_run64, d_stats,
-                       (const uint4 *)d_queries, q_stride / 16, (uint4 *)d_packed_queries);
+                       (const uint4 *)d_queries, q_stride / 16, (uint4 *)d_packed_queries, d_filter_of, d_filter_of_packed);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(SQM_BLOCK) void scan_sq_mfma_kernel(const ScanArgs 
                     bool c = mine && !(score < thr_f[g]);
                     if (__ballot(c)) {
                         const uint64_t key = make_key(score, rid[r]);
-                        c = c && key > thr[g] && a.del.live(rid[r]) && (!a.key_bound || key < a.key_bound[q]);
+                        c = c && key > thr[g] && a.del.live(rid[r], q) && (!a.key_bound || key < a.key_bound[q]);
                         uint64_t mask = __ballot(c);
                         while (mask) {
                             const int src = __builtin_ctzll(mask);

@@ -51,6 +51,23 @@ def _bits_to_words(bits) -> Optional[np.ndarray]:
     return np.packbits(b.reshape(-1, 8), axis=1, bitorder="little").reshape(-1).view(np.uint64).copy()
 
 
+def pack_filters(masks, filter_of, nq: int):
+    """The arguments of `qmx_query_set_filters`, packed on the host: `masks` bool [F][n] -> u64 words [F][ceil(n / 64)] (each row a
+    `BitSlice<u64, Lsb0>`: bit i of a row is bit i % 64 of its word i // 64; the bits past n in a row's last word are zero), `filter_of` -> u32 [nq]
+    (`FILTER_NONE`, or None / a negative entry, for a request without a filter).  Returns (words, n_bits, n_filters, filter_of)."""
+    masks = np.asarray(masks, dtype=bool)
+    if masks.ndim != 2 or masks.shape[0] < 1:
+        raise ValueError("masks must be a bool array [F][n] with F >= 1")
+    fof = np.array([F.FILTER_NONE if f is None or int(f) < 0 else int(f) for f in filter_of], dtype=np.uint32)
+    if fof.shape != (nq,):
+        raise ValueError("filter_of must name one filter (or FILTER_NONE) per query: %d entries for %d queries" % (len(fof), nq))
+    n_filters, n_bits = masks.shape
+    pad = (-n_bits) % 64
+    b = np.concatenate([masks, np.zeros((n_filters, pad), dtype=bool)], axis=1) if pad else masks
+    words = np.packbits(b.reshape(n_filters, -1, 8), axis=2, bitorder="little").reshape(n_filters, -1).view(np.uint64)
+    return np.ascontiguousarray(words).reshape(n_filters, (n_bits + 63) // 64), n_bits, n_filters, fof
+
+
 class VectorStorage:
     """Device-resident dense vector storage (the read side of `DenseVectorStorageRead`,
     lib/segment/src/vector_storage/vector_storage_base.rs:265-316).
@@ -687,6 +704,12 @@ class RawScorer:
             return
         words = _bits_to_words(np.asarray(allowed, dtype=bool))
         F.check(F.lib().qmx_query_set_filter(self._h, F.ptr(words), len(allowed)))
+
+    def set_filters(self, masks, filter_of):
+        """One payload filter per request of the batch (`qmx_query_set_filters`): `masks` bool [F][n] over point ids, `filter_of` [nq] the mask of each
+        query (`FILTER_NONE` / None: no filter).  Replaces `set_filter`; `set_filter(None)` clears it."""
+        words, n_bits, n_filters, fof = pack_filters(masks, filter_of, self.nq)
+        F.check(F.lib().qmx_query_set_filters(self._h, F.ptr(words), n_bits, n_filters, F.ptr(fof)))
 
     def score_points(self, points: Sequence[int]) -> np.ndarray:
         """scores[qi, i] = similarity(query qi, stored point points[i])  (raw_scorer.rs:40)."""
