@@ -505,10 +505,12 @@ static int32_t i8_copy_scan(SearchCall &c, SplitTiles &sp, const ScanArgs &a, ui
     // 3'. the strided sixteenth, then the rest; after each launch the exact scores of the k best candidates so far renew the bound
     const uint32_t np = split_i8_probe();
     uint32_t *probe_ids = (uint32_t *)q->sp_probe.p, *probe_cnt = probe_ids + (size_t)q->nq * np;
-    // (which tiles the first launch takes: every 16th.  Its candidates are admitted on the SAMPLE's bound - a hundred times those of the main launch
-    // per tile -, so the first launch is bound by its candidate lists, not by its stream; strides of 8 .. 64 measured the same step time,
-    // profiles/r5_i8_sample_stride.md)
-    const uint32_t sstride = 16;
+    // (which tiles the first launch takes: every 16th, option i8_sample_stride.  Its candidates are admitted on the SAMPLE's bound - a hundred times
+    // those of the main launch per tile.  With the one epilogue for both launches that, not the stream, was what bounded the first launch, and strides
+    // of 8 .. 64 measured the same step time (profiles/r5_i8_sample_stride.md); with an epilogue made for dense candidates (option i8_dense_epilogue)
+    // 8 / 16 / 32 were measured again: profiles/r14_i8_dense_epilogue.md)
+    const int64_t sstride_opt = option(OPT_I8_SAMPLE_STRIDE);
+    const uint32_t sstride = sstride_opt >= 2 && sstride_opt <= 255 ? (uint32_t)sstride_opt : 16;
     for (uint32_t ph = 1; ph <= 2; ++ph) {
         const uint32_t phase = ph | (sstride << 8);
         QMX_TIMED_SCAN(c, launch_scan_i8copy(q->stream, a, q->sp_bq.p, f.i8_qscale, f.thr, s->num_cus, s->d_rows_split, q->sp_wl.p, phase));

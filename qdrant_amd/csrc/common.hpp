@@ -54,6 +54,10 @@ enum Option {
     OPT_I8_RESIDENT,          // 1 (default): the int8-copy prefilter over rows of up to 1 024 coordinates keeps the queries' whole operand image resident in LDS
                               // (scan_i8copy_kernel_res: no stage barrier, 97 KiB of LDS at 768 coordinates); 0 = the staged kernel of rounds 3 - 6 (scan_i8copy_kernel:
                               // 144 KiB), which longer rows take anyway
+    OPT_I8_DENSE_EPILOGUE,    // 1 (default): the FIRST launch of the resident int8 prefilter (the strided sample of the tiles, admitted on the sample's bound: tens of
+                              // candidates per wave and tile) lists them through a hit mask per lane and dense slots per wave (scan_i8copy_kernel_res_dense);
+                              // 0 = the one epilogue for both launches.  The same candidates per launch either way
+    OPT_I8_SAMPLE_STRIDE,     // the first launch of the int8 prefilter takes every n-th tile (default 16; 2 .. 255)
     OPT_GROUP_MATRIX_BYTES,   // qmx_group_search: byte budget of the fallback's score matrix, which tiles the unfinished queries (0 = 1 GiB)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT

@@ -415,7 +415,7 @@ __host__ __device__ inline uint64_t split_phase_tiles(uint64_t all_tiles, uint32
     const uint64_t first = (all_tiles + st - 1) / st;
     return ph == 0 ? all_tiles : ph == 1 ? first : all_tiles - first;
 }
-constexpr uint32_t SP_WCAP = 8192;                           // candidates one wave may list per pass (expected: ~200, heavy-tailed rows under the int8 band: thousands; more -> overflow -> the exact scan)
+constexpr uint32_t SP_WCAP = 8192;                           // candidates one wave may list per pass (expected: ~270 in the headline's first launch, heavy-tailed rows under the int8 band: thousands; more -> overflow -> the exact scan)
 constexpr int SP3_BM = SP_BM;                                // 256 rows per tile: a stage is 32 KiB of rows + 16 KiB of queries
 constexpr int SP3_A_UNITS = SP_A_UNITS;
 constexpr int SP3_ARING = 3;                                 // row stages in LDS: one being multiplied, two on their way
@@ -1546,11 +1546,31 @@ __device__ __forceinline__ void sp_static_for(F &&f) {
 // waves 0 - 3 on the block's even tiles, 4 - 7 on its odd ones: half the operand reads per matrix instruction, 250 registers - (equal), a block's tiles consecutive
 // instead of every gridDim-th (equal).  Ablation (wrong results, the same launches): without the matrix instructions and operand reads 0.628 ms per launch
 // instead of 0.68 - 0.69, with half of them 0.655: the stream alone - this kernel's loads and waits - is 0.76 of HBM, the matrix work costs 9 %.
-template <int AHEAD>
-__global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel_res(const ScanArgs a, const SplitArgs s) {
+//
+// DENSE: the epilogue of the FIRST launch (the strided sixteenth of the tiles, admitted on the sample's bound: ~1 % of a wave's 4 096 (row, query) pairs per
+// tile pass, ~28 candidates per wave and tile on the headline against 0.2 in the second launch).  The narrowing epilogue below visits a query tile's eight (row
+// tile, row) slots one ballot and one branch at a time - right where nearly every ballot is empty, as long as the tile's stream where a third of them are not
+// (~1 500 instructions per wave and tile; the dense one ~620, first launch 0.121 -> 0.098 ms: profiles/r14_i8_dense_epilogue.md).  The dense one
+// takes, per query tile, an 8-bit hit mask per lane (the same test on integers, sp_i8_int_threshold), and hands out the wave's slots one LEVEL at a time - every
+// lane's first hit, then every lane's second, ... - by one ballot per level: a level costs what one slot with a hit costs below, and there are as many levels as
+// the fullest lane has hits (one, rarely two; eight at most).  The same set of entries per launch, in another order inside a wave's list (regroup, probe and select
+// do not look at the order); `wcount` goes on past `wcap` as below, which is how sp_regroup_kernel sees an overflow.  One copy of the epilogue in the kernel
+// instead of three: the loop runs over stages and meets the tile's end in one place.
+// A pair is a candidate unless (float)acc < th.  |acc| <= 1 024 x 128 x 128 = 2^24 is exact in f32, so for a finite th that is acc >= ceil(th); !(x < NaN) holds
+// for every x; a query slot past nq admits nothing.  The integer stays within +-2^30, so that acc - threshold cannot wrap: its sign bit is the test.
+__device__ __forceinline__ int sp_i8_int_threshold(float th, bool live_query) {
+    constexpr int NOTHING = 1 << 30, EVERYTHING = -(1 << 30);
+    if (!live_query) return NOTHING;
+    if (!(th > -1.0e9f)) return EVERYTHING;               // NaN, -inf, anything below every accumulator
+    if (th > 1.0e9f) return NOTHING;
+    return (int)ceilf(th);
+}
+template <int AHEAD, bool DENSE>
+__device__ __forceinline__ void sp_i8copy_res_scan(const ScanArgs a, const SplitArgs s) {
     constexpr int SLOTS = AHEAD + 1, WAVES = SP3_THREADS / 64, THREADS = SP3_THREADS, MT = 2, NL = 2 * MT;
     static_assert(SP3_BM == WAVES * MT * 16, "a wave owns two row tiles of a 256-row tile");
     static_assert(NL * AHEAD <= 62, "vmcnt is six bits");
+    static_assert(SP8R_MAX_NCH * 128u * 128u * 128u <= (1u << 24), "the dense epilogue compares integers: every accumulator is exact in f32");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint4 *lds = reinterpret_cast<uint4 *>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1571,7 +1591,8 @@ __global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel_res(const S
 #pragma unroll 4
     for (uint32_t u = (uint32_t)tid; u < nch * SP_B_UNITS; u += THREADS) lds[u] = s.bq[u];
     for (int u = tid; u < SP_QT; u += THREADS) {
-        thr_lds[u] = s.thr[u];
+        if constexpr (DENSE) thr_lds[u] = __int_as_float(sp_i8_int_threshold(s.thr[u], (uint32_t)u < s.nq));
+        else thr_lds[u] = s.thr[u];
         qs_lds[u] = s.scales[u];
     }
     __syncthreads();
@@ -1636,6 +1657,50 @@ __global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel_res(const S
             }
         }
     };
+    // the dense epilogue (DENSE; thr_lds holds sp_i8_int_threshold's integers).  Bit 4 mt + j of a lane's mask is row row0 + 16 mt + j.
+    auto epilogue_dense = [&](uint64_t tile) __attribute__((always_inline)) {
+        static_assert(MT == 2, "a lane's hit mask is eight bits: two row tiles of four rows");
+        const uint32_t row0 = (uint32_t)(tile * SP3_BM) + ws * (MT * 16u) + 4 * kq_r;
+        uint32_t rows_there = 0xFFu;
+        if ((tile + 1) * SP3_BM > a.n_cand) {                        // (the block's last tile, when it is ragged)
+            rows_there = 0;
+#pragma unroll
+            for (int b = 0; b < 8; ++b) rows_there |= row0 + (uint32_t)(b >> 2) * 16 + (uint32_t)(b & 3) < n_rows32 ? 1u << b : 0u;
+        }
+        const int *const ith_lds = reinterpret_cast<const int *>(thr_lds);
+#pragma unroll
+        for (int nt = 0; nt < 8; ++nt) {
+            const uint32_t q = (uint32_t)nt * 16 + m_r;
+            const int ith = ith_lds[q];
+            // the misses' bits: the sign of acc - threshold, shifted in from the right, row 7 first (two instructions per accumulator, no condition code)
+            uint32_t miss = 0;
+#pragma unroll
+            for (int b = 7; b >= 0; --b) miss = __builtin_amdgcn_alignbit(miss, (uint32_t)(acc[b >> 2][nt][b & 3] - ith), 31);
+            uint32_t m = ~miss & rows_there;
+            uint64_t level = __ballot(m != 0);
+            if (!level) continue;                                    // nobody in the wave has a hit for these 16 queries
+            const float qs = qs_lds[q];
+            do {                                                     // every lane's lowest remaining hit
+                const uint32_t at = wcount + __builtin_amdgcn_mbcnt_hi((uint32_t)(level >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)level, 0u));
+                if (m != 0 && at < s.wcap) {
+                    // accumulator h of the lane's eight: a tree of seven bitwise selects under the three bits of h (as `?:` the compiler sees an
+                    // indexed vector element and spends fourteen conditional moves and seven compares on it)
+                    const uint32_t h = (uint32_t)__builtin_ctz(m);
+                    const int h0 = -(int)(h & 1u), h1 = -(int)((h >> 1) & 1u), h2 = -(int)(h >> 2);
+                    auto pick = [](int mask, int if_clear, int if_set) { return (if_set & mask) | (if_clear & ~mask); };
+                    const int x = pick(h1, pick(h0, acc[0][nt][0], acc[0][nt][1]), pick(h0, acc[0][nt][2], acc[0][nt][3]));
+                    const int y = pick(h1, pick(h0, acc[1][nt][0], acc[1][nt][1]), pick(h0, acc[1][nt][2], acc[1][nt][3]));
+                    const float v = (float)pick(h2, x, y);
+                    const uint32_t row = row0 + (h >> 2) * 16 + (h & 3u);
+                    const uint64_t key = make_key(v * qs, row);
+                    wl[at] = make_uint4((uint32_t)key, (uint32_t)(key >> 32), q, 0u);
+                }
+                m &= m - 1;
+                wcount += (uint32_t)__builtin_popcountll(level);
+                level = __ballot(m != 0);
+            } while (level);
+        }
+    };
     const uint64_t n_stages = my_tiles * nch;
     // the stage the loads are at, as (tile, kc), by running counters (tile_of divides: once per tile, not per stage); past the block's last stage they
     // repeat it (the waits count loads, not bytes)
@@ -1653,14 +1718,19 @@ __global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel_res(const S
     uint64_t it = 0, tile_c = my_tile(0), tile_done = 0;
     uint32_t kc = 0;
     // one stage; I = g mod SLOTS selects the register sets at compile time
+    auto clear_acc = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 8; ++nt) acc[mt][nt] = (i32x4s){0, 0, 0, 0};
+    };
     auto one_stage = [&](auto IC) __attribute__((always_inline)) {
         constexpr int I = decltype(IC)::value, IL = (I + AHEAD) % SLOTS;
-        if (kc == 0) {
-            if (it) epilogue(tile_done);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 8; ++nt) acc[mt][nt] = (i32x4s){0, 0, 0, 0};
+        if constexpr (!DENSE) {
+            if (kc == 0) {
+                if (it) epilogue(tile_done);
+                clear_acc();
+            }
         }
         load_stage(tile_r, kr, rc[IL]);                           // stage g + AHEAD -> the register set stage g - 1 ran on
         advance_r();
@@ -1681,21 +1751,54 @@ __global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel_res(const S
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (++kc == nch) {
-            kc = 0;
-            tile_done = tile_c;
-            if (++it < my_tiles) tile_c = my_tile(it);
+        if constexpr (!DENSE) {
+            if (++kc == nch) {
+                kc = 0;
+                tile_done = tile_c;
+                if (++it < my_tiles) tile_c = my_tile(it);
+            }
         }
     };
-    for (uint64_t g = 0; g < n_stages; g += SLOTS) {
-        sp_static_for<0, SLOTS>([&](auto IC) __attribute__((always_inline)) {
-            if (g + decltype(IC)::value < n_stages) one_stage(IC);
-        });
+    if constexpr (DENSE) {
+        // one stage per trip, on the register set g mod SLOTS; the tile's end - the one copy of the epilogue - where the stage that ran was the tile's last
+        // (the loads of the next AHEAD stages are on their way meanwhile, as they are when the other form meets its epilogue)
+        uint32_t set = 0;
+        clear_acc();
+        for (uint64_t g = 0; g < n_stages; ++g) {
+            sp_static_for<0, SLOTS>([&](auto IC) __attribute__((always_inline)) {
+                if (set == (uint32_t)decltype(IC)::value) one_stage(IC);
+            });
+            set = set + 1 == (uint32_t)SLOTS ? 0 : set + 1;
+            if (++kc == nch) {
+                kc = 0;
+                epilogue_dense(tile_c);
+                clear_acc();
+                if (++it < my_tiles) tile_c = my_tile(it);
+            }
+        }
+        // the loads past the last stage are still on their way into registers the compiler takes for free from here on (the count's store below among
+        // them: a list length of row bytes, an overflow out of nothing - seen at 10 M rows with few queries, where the last epilogue is short)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+        for (uint64_t g = 0; g < n_stages; g += SLOTS) {
+            sp_static_for<0, SLOTS>([&](auto IC) __attribute__((always_inline)) {
+                if (g + decltype(IC)::value < n_stages) one_stage(IC);
+            });
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        epilogue(tile_done);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    epilogue(tile_done);
     if (lane == 0) s.wcnt[blockIdx.x * WAVES + (uint32_t)w] = wcount;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+template <int AHEAD>
+__global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel_res(const ScanArgs a, const SplitArgs s) {
+    sp_i8copy_res_scan<AHEAD, false>(a, s);
+}
+// the first launch's instantiation (option i8_dense_epilogue): a kernel of its own name, so that what a search reports names the epilogue that ran
+template <int AHEAD>
+__global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel_res_dense(const ScanArgs a, const SplitArgs s) {
+    sp_i8copy_res_scan<AHEAD, true>(a, s);
 }
 
 // ---- after a launch: the k best candidates (by approximate score) of every query, for an exact look.  k of them are enough: approximate and exact
@@ -2019,12 +2122,15 @@ int32_t launch_scan_i8copy(hipStream_t st, const ScanArgs &a, const void *d_bq, 
     // rows of up to 1 024 coordinates: the queries' whole image resident in LDS (scan_i8copy_kernel_res; option i8_resident = 0: the staged kernel)
     const uint32_t nch_r = a.dim / 128;
     const bool resident = option(OPT_I8_RESIDENT) > 0 && nch_r <= SP8R_MAX_NCH;
-    void (*kfn)(const ScanArgs, const SplitArgs) = resident ? scan_i8copy_kernel_res<1> : scan_i8copy_kernel;
+    // ... and its first launch, dense in candidates, with the epilogue made for that (option i8_dense_epilogue = 0: the one kernel for both launches)
+    const bool dense = resident && (phase & 0xFFu) == 1 && option(OPT_I8_DENSE_EPILOGUE) > 0;
+    void (*kfn)(const ScanArgs, const SplitArgs) = dense ? scan_i8copy_kernel_res_dense<1> : resident ? scan_i8copy_kernel_res<1> : scan_i8copy_kernel;
     const size_t lds_bytes = resident ? sp8r_lds_bytes(nch_r) : (size_t)SP8_LDS;
     static thread_local DeviceOnce attr_once;
     if (attr_once.need()) {
         QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_i8copy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SP8_LDS));
         QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_i8copy_kernel_res<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp8r_lds_bytes(SP8R_MAX_NCH)));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_i8copy_kernel_res_dense<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp8r_lds_bytes(SP8R_MAX_NCH)));
         attr_once.mark();
     }
     QMX_REQUIRE(d_rows_i8 && d_wlists && split_i8_dim_ok(a.dim), QMX_ERR_BAD_ARG, "the int8 scan reads the int8 copy and writes per-wave candidate lists");
