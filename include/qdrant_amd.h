@@ -302,7 +302,9 @@ QMX_API uint32_t qmx_abi_version(void);
  * "pq_prefilter_min_queries", "hnsw_pq_per_cu", "tq_rotate_block", "no_topk_small", "verify_max_per_query", "hnsw_pq_direct_walk",
  * "hnsw_pq_table_build", "hnsw_no_pq_prefilter", "hnsw_no_lds_visited", "pq_lut_no_lds", "hnsw_per_cu", "tq_wide_min_queries", "tq_wide_high_digit", "sq_wide_min_queries", "i8_resident",
  * "i8_dense_epilogue" (default 1: the int8 prefilter's first launch lists its candidates through a hit mask per lane and dense slots per wave; 0: the one
- * epilogue for both launches), "i8_sample_stride" (the first launch takes every n-th tile; default 16), "group_matrix_bytes", "debug"
+ * epilogue for both launches), "i8_sample_stride" (the first launch takes every n-th tile; default 16), "prescan_beside_scan" (default 1: a prefilter's
+ * sample pre-scan and the top-k behind it run as 256-thread blocks that fit on a CU beside a block of the resident int8 scan - the pre-scan at 384 or 768 coordinates -; 0: the former 512- / 1024-
+ * thread shapes), "group_matrix_bytes", "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -
  * (qdrant_amd/csrc/common.hpp says what each selects; round 6 removed the experiments that had measured slower twice: their numbers stay under
  * profiles/).  Initial values come from the environment variables QMX_<NAME> read

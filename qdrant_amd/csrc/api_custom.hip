@@ -89,6 +89,7 @@ int32_t qmx_custom_search_topk(qmx_query *ex, const qmx_custom_query *queries, u
         DeletedView del = ex->seg->deleted_view();
         if (ex->has_filter) { del.allowed = (const uint64_t *)ex->filter.p; del.n_allowed_bits = ex->n_filter_bits; }
         QMX_TRY(launch_custom_topk(ex->stream, (const float *)ex->cq_scores.p, n, (const uint32_t *)d_ids, del, n_queries, top, d_out, d_oc));
+        ex->last_kernel = last_noted_kernel();     // (the selection kernel: what qmx_query_last_kernel reports after a custom search)
     }
     if (!out_dev) QMX_TRY(copy_out(ex->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
     if (!cnt_dev) QMX_TRY(copy_out(ex->stream, out_counts, d_oc, (size_t)n_queries * 4));

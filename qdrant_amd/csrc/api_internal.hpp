@@ -518,8 +518,11 @@ int32_t hnsw_search_sync(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t
 void fill_args(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, ScanArgs &a);
 int32_t launch_scan(const qmx_query *q, int qt, ScanMode mode, const ScanArgs &a, uint32_t *grid);
 int32_t tq_l1_scores_device(qmx_query *q, uint32_t q0, uint32_t nq, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride, const PairSel *sel);
+// (short_list: an id list of at most PRESCAN_BESIDE_MAX_N rows - a prefilter's sample, the ids of qmx_score_points - may take the shape that fits beside a
+//  resident int8 scan block, option prescan_beside_scan)
+constexpr uint64_t PRESCAN_BESIDE_MAX_N = 16384;
 int32_t score_matrix_enqueue(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride,
-                                    uint32_t *launches);
+                                    uint32_t *launches, bool short_list = false);
 int32_t score_ids_device(qmx_query *q, const uint32_t *d_ids, uint64_t n, float *d_scores, qmx_counters *counters);
 int32_t score_pairs_device(qmx_query *q, const PairSel &sel, const uint32_t *d_ids, uint64_t n_items, float *d_scores,
                                   bool timed);

@@ -397,7 +397,7 @@ int32_t tq_l1_scores_device(qmx_query *q, uint32_t q0, uint32_t nq, const uint32
 // The score matrix of queries [tile0, tile0 + nq_tile) of the batch against the candidates ids[0..n) (rows 0..n without ids): scores[(qi - tile0) * stride + i].
 // One launch per tile_qt queries; the f32 matrix-core kernel takes them all in one launch (scan_mfma.hip: score mode loops over its query tiles).
 int32_t score_matrix_enqueue(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride,
-                                    uint32_t *launches) {
+                                    uint32_t *launches, bool short_list) {
     const qmx_segment *s = q->seg;
     if (is_sparse(s)) {
         if (launches) ++*launches;
@@ -420,7 +420,13 @@ int32_t score_matrix_enqueue(const qmx_query *q, uint32_t tile0, uint32_t nq_til
         pre.scores = d_scores + (size_t)st0 * stride;
         pre.scores_stride = stride;
         uint32_t pgrid = 0;
-        QMX_TRY(launch_scan(q, (int)std::min<uint32_t>(pow2_ceil(nq_sub), std::max<uint32_t>(SQT, 8)), SCAN_SCORES, pre, &pgrid));
+        const int qt = (int)std::min<uint32_t>(pow2_ceil(nq_sub), std::max<uint32_t>(SQT, 8));
+        // a short id list against 16 or more queries: 16-query tiles on 4 waves, a block that starts beside one of the resident int8 scan instead of
+        // waiting for a CU without one (scan_mfma.hip launch_scan_f32_mfma_beside; the same score bits)
+        if (loops && short_list && d_ids && n <= PRESCAN_BESIDE_MAX_N && qt >= 16 && option(OPT_PRESCAN_BESIDE_SCAN) > 0)
+            QMX_TRY(launch_scan_f32_mfma_beside(q->stream, pre, s->num_cus, &pgrid));
+        else
+            QMX_TRY(launch_scan(q, qt, SCAN_SCORES, pre, &pgrid));
         if (launches) ++*launches;
     }
     return QMX_OK;
@@ -431,7 +437,7 @@ int32_t score_ids_device(qmx_query *q, const uint32_t *d_ids, uint64_t n, float 
     const qmx_segment *s = q->seg;
     const uint32_t TQ = tile_qt(s, q);
     uint32_t launches = 0;
-    QMX_TRY(score_matrix_enqueue(q, 0, q->nq, d_ids, n, d_scores, n, &launches));
+    QMX_TRY(score_matrix_enqueue(q, 0, q->nq, d_ids, n, d_scores, n, &launches, true));
     if (counters) {
         counters->kernel_launches += launches;
         counters->vectors_scored += (uint64_t)q->nq * n;
@@ -455,6 +461,7 @@ int32_t qmx_score_points(qmx_query *q, const uint32_t *ids, uint32_t n, float *s
         d_scores = (float *)q->scores.p;
     }
     QMX_TRY(score_ids_device(q, (const uint32_t *)d_ids, n, d_scores, counters));
+    if (q->seg->dtype <= QMX_DTYPE_U8) q->last_kernel = last_noted_kernel();      // (the dense score-mode launchers note theirs)
     if (!out_dev) QMX_HIP(hipMemcpyAsync(scores, d_scores, sbytes, hipMemcpyDeviceToHost, q->stream));
     return check_err_flag(q);
 }

@@ -161,15 +161,17 @@ static int32_t prefilter_begin(qmx_query *q, const SplitPlanLayout &pl, uint64_t
 }
 
 // exact scores of `n` candidates (the score-mode kernels, <= tile_qt queries per launch) -> one block per query selects its k best live ones; the k-th
-// becomes the tile's bound in gthr, a lower bound of the final k-th best: of a prefilter's sample, of the prefix an exact tile scans first
+// becomes the tile's bound in gthr, a lower bound of the final k-th best: of a prefilter's sample, of the prefix an exact tile scans first.
+// (sample: a prefilter's - its two kernels are the head of every batch's chain and, with four batches in flight, are dispatched while another batch's
+//  int8 scan holds every CU: they take the shapes that fit beside a scan block, option prescan_beside_scan.  An exact tile's prefix keeps the wide ones)
 static int32_t bound_enqueue(const SearchCall &c, uint32_t tile0, uint32_t nq_tile, const uint32_t *d_ids, uint64_t n, uint32_t ktop, const DeletedView &del,
-                             uint32_t *launches) {
+                             uint32_t *launches, bool sample) {
     qmx_query *q = c.q;
     QMX_TRY(q->scores.reserve((size_t)nq_tile * n * sizeof(float)));
-    QMX_TRY(score_matrix_enqueue(q, tile0, nq_tile, d_ids, n, (float *)q->scores.p, n, launches));
+    QMX_TRY(score_matrix_enqueue(q, tile0, nq_tile, d_ids, n, (float *)q->scores.p, n, launches, sample));
     // (the bound at the tile's own offset: the bounds of earlier split tiles are read again by the plan of their exact passes)
     return launch_custom_topk(q->stream, (const float *)q->scores.p, n, d_ids, del, nq_tile, ktop, c.d_out + (size_t)tile0 * c.top, c.d_counts + tile0,
-                              (uint64_t *)q->gthr.p + tile0);
+                              (uint64_t *)q->gthr.p + tile0, sample);
 }
 
 // exact scores of the pool's rows (the pair kernels: the reference's bits), sorted by (score, lower id first) into the lists of queries 0 .. nq
@@ -321,7 +323,7 @@ static int32_t pq_prefilter_search(SearchCall &c) {
         const uint64_t *gthr = (const uint64_t *)q->gthr.p + tile0;
         const ScanArgs a = tile_args(c, tile0, nq_tile);
         // 1. exact scores of the sample (the exact kernel's score mode over an id list) -> k-th best per query
-        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches));
+        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches, true));
         // 2. the 6-bit tables of the tile's query groups, thresholds and bands in units of the integer score
         int32_t *thr = (int32_t *)((unsigned char *)q->pq_table.p + pq_prefilter_table_bytes(m, tile_max));
         QMX_TRY(launch_pq_lut8(q->stream, a.queries, q->q_stride, nq_tile, m, s->pq.n_centroids, gthr, q->pq_table.p, thr, band));
@@ -384,7 +386,7 @@ static int32_t wide_exact_search(SearchCall &c) {
         const uint64_t *gthr = (const uint64_t *)q->gthr.p + tile0;
         const ScanArgs a = tile_args(c, tile0, nq_tile);
         // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best
-        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches));
+        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches, true));
         // 2. the queries' codes / digits as operand images, the integer reject bounds
         if (sq) QMX_TRY(launch_sqw_pack(q->stream, a, gthr, s->sq_off_absmax, q->sp_bq.p, f.wide_thr, f.wide_qinfo, f.band, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
         else QMX_TRY(launch_tq4w_pack(q->stream, a, gthr, s->tq_sf_min, s->tq_sf_max, s->tq_l2_min, s->tq_l2_max, s->tq_c1, tq_high ? 1 : 0, q->sp_bq.p, f.wide_thr,
@@ -537,7 +539,7 @@ static int32_t split_tile(SearchCall &c, const SearchPlan &plan, SplitTiles &sp,
     QMX_CHECK_CANCELLED(c.is_stopped);
     const ScanArgs a = tile_args(c, tile0, nq_tile);
     // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best (launches: counted in the tile's 8 / 13)
-    QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, sp.S, c.top, a.del, nullptr));
+    QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, sp.S, c.top, a.del, nullptr, true));
     QMX_TRY(split_stage(q, "prescan"));
     int *tile_ovf = (int *)((unsigned char *)q->sp_plan.p + sp.pl.tile_ovf) + sp.tiles.size();
     if (plan.route == ROUTE_I8_COPY) QMX_TRY(i8_copy_scan(c, sp, a, tile0, nq_tile, tile_ovf));
@@ -589,7 +591,7 @@ static int32_t exact_tile(SearchCall &c, const SearchPlan &plan, uint32_t tile0,
         if (pass == 0 && c.n_cand >= (1u << 18) && (m16 || sqm || m4 || bqk) && !option(OPT_NO_PRESCAN)) {
             const int pre_shift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT), 1), 20);  // tuning: measured 5..10 on C2, the main pass does not care, the pre-scan itself gets cheaper
             const uint64_t pre_n = std::max<uint64_t>(c.n_cand >> pre_shift, 1u << 13) & ~(uint64_t)15;
-            QMX_TRY(bound_enqueue(c, tile0, nq_tile, c.d_ids, pre_n, ptop, a.del, nullptr));
+            QMX_TRY(bound_enqueue(c, tile0, nq_tile, c.d_ids, pre_n, ptop, a.del, nullptr, false));
             a.gthr = (const uint64_t *)q->gthr.p + tile0;
             c.launches += 2;
         }

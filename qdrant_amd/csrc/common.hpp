@@ -58,6 +58,13 @@ enum Option {
                               // candidates per wave and tile) lists them through a hit mask per lane and dense slots per wave (scan_i8copy_kernel_res_dense);
                               // 0 = the one epilogue for both launches.  The same candidates per launch either way
     OPT_I8_SAMPLE_STRIDE,     // the first launch of the int8 prefilter takes every n-th tile (default 16; 2 .. 255)
+    OPT_PRESCAN_BESIDE_SCAN,  // 1 (default): the exact scores of a prefilter's sample (an id list of <= 16 384 rows, f32 matrix-core segments) are scored in 16-query
+                              // tiles by 4-wave blocks (scan_mfma.hip launch_scan_f32_mfma_beside) and their k best are selected by a 256-thread block
+                              // (custom_query.hip custom_topk_beside_kernel): both start on a CU that holds a block of the resident int8 scan.  0 = the 8-wave
+                              // 32-query tile and the 1024-thread top-k, which wait for a CU without one.  The pre-scan fits for rows of 384 or 768
+                              // coordinates only (tools/step_footprint.py: 192 registers, all there are): other lengths take 200 registers, 1 024 coordinates
+                              // also 68 KiB of LDS, and their blocks wait as before - with the same results.  Not in the header, a setting of the parity tests only: 2 = as 1,
+                              // and every top-k of a short score row (the custom queries') takes the 256-thread kernel, with scores of the test's choosing
     OPT_GROUP_MATRIX_BYTES,   // qmx_group_search: byte budget of the fallback's score matrix, which tiles the unfinished queries (0 = 1 GiB)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT

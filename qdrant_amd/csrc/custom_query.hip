@@ -293,20 +293,178 @@ __global__ __launch_bounds__(CT_BLOCK) void custom_topk_small_kernel(const float
     }
 }
 
+// The same selection once more, for the sample bound of the prefilters (n <= 16 384, top <= 64), in a block that starts on a CU whose other tenant is a
+// block of the resident int8 scan (2 waves and 320 registers per SIMD, 99 328 B of LDS: scan_split.hip sp8r_lds_bytes).  The kernel above cannot - 4 waves
+// per SIMD at 100 registers, a uint64 per score in LDS (65 680 B at 8 192 scores) - and waited for a CU without a scan block.  This one: 256 threads
+// (one wave per SIMD), no LDS per score.  A thread keeps the ORDER WORD (score_to_ord, 0 = dead / no such entry) of its <= 64 scores in registers.  The
+// largest word that at least `top` lanes of one wave reach with their maxima is a lower bound of the k-th best key's word; the entries that reach the
+// largest such bound over the 4 waves survive - a few times k of them - and get their full key (the id is read again for them alone) in a list of
+// CTB_CAP keys, which is ranked as above.  A row that leaves more survivors than the list holds (a mass of equal scores: the word cannot tell them
+// apart; a filter that leaves fewer than `top` lanes of every wave alive) takes the insertion walk of custom_topk_kernel instead, in the same launch.
+// Either way the keys that are compared are the full ones: the same lists, counts and bound as the kernels above.
+constexpr int CTB_BLOCK = 256;
+constexpr int CTB_NW = CTB_BLOCK / WAVE;
+constexpr uint32_t CTB_CAP = 2048;
+constexpr int CTB_U = 8;               // entries per thread whose loads are in flight together
+template <int E>
+__global__ __launch_bounds__(CTB_BLOCK) void custom_topk_beside_kernel(const float *scores, uint32_t n, const uint32_t *ids, DeletedView del_all, uint32_t top,
+                                                                       qmx_scored_point *out, uint32_t *out_counts, uint64_t *bound_out) {
+    static_assert(E % CTB_U == 0, "whole load batches");
+    __shared__ uint64_t surv[CTB_CAP];                  // (the insertion walk's 4 wave lists reuse its head)
+    __shared__ uint32_t sh_t[CTB_NW];
+    __shared__ uint64_t sh_bound;
+    __shared__ uint32_t sh_cnt;
+    const uint32_t q = blockIdx.x;
+    const DeletedView del = del_all.of_query(q);      // (per-request filters: the block's query has one bitmap)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float *row = scores + (uint64_t)q * n;
+    uint32_t ord[E];
+#pragma unroll
+    for (int e0 = 0; e0 < E; e0 += CTB_U) {
+        if ((uint32_t)e0 * CTB_BLOCK >= n) {                // (uniform: the row ends before this batch)
+#pragma unroll
+            for (int u = 0; u < CTB_U; ++u) ord[e0 + u] = 0u;
+            continue;
+        }
+        uint32_t id[CTB_U], o[CTB_U];
+        uint64_t keep[CTB_U];
+#pragma unroll
+        for (int u = 0; u < CTB_U; ++u) {
+            const uint32_t c = (uint32_t)(e0 + u) * CTB_BLOCK + threadIdx.x;
+            const uint32_t cc = c < n ? c : 0;
+            id[u] = ids ? ids[cc] : cc;
+            o[u] = c < n ? score_to_ord(row[cc]) : 0u;
+        }
+        live_masks<CTB_U>(del, id, keep);
+#pragma unroll
+        for (int u = 0; u < CTB_U; ++u) ord[e0 + u] = o[u] & (uint32_t)keep[u];      // (as a mask: see custom_topk_kernel)
+    }
+    if (threadIdx.x == 0) { sh_cnt = 0; sh_bound = 0; }
+    // the wave's bound: the largest lane maximum that at least `top` lane maxima reach (0: fewer than `top` lanes hold a live entry)
+    uint32_t m = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) m = ord[e] > m ? ord[e] : m;
+    uint32_t reach = 0;
+    for (int j = 0; j < WAVE; ++j) reach += (uint32_t)__builtin_amdgcn_readlane((int)m, j) >= m ? 1u : 0u;
+    const uint32_t mine = reach >= top ? m : 0u;
+    uint32_t tw = 0;
+    for (int j = 0; j < WAVE; ++j) {
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)mine, j);
+        tw = v > tw ? v : tw;
+    }
+    if (lane == 0) sh_t[wave] = tw;
+    __syncthreads();
+    uint32_t t = 0;
+#pragma unroll
+    for (int w = 0; w < CTB_NW; ++w) t = sh_t[w] > t ? sh_t[w] : t;
+    // the survivors, with their full keys: every live entry whose word is not below t
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (ord[e] != 0u && ord[e] >= t) {
+            const uint32_t slot = atomicAdd(&sh_cnt, 1u);
+            if (slot < CTB_CAP) {
+                const uint32_t c = (uint32_t)e * CTB_BLOCK + threadIdx.x;
+                surv[slot] = ((uint64_t)ord[e] << 32) | (uint32_t)(~(ids ? ids[c] : c));
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t cnt = sh_cnt;
+    uint32_t found;
+    if (cnt <= CTB_CAP) {
+        for (uint32_t i = threadIdx.x; i < cnt; i += CTB_BLOCK) {
+            const uint64_t my = surv[i];
+            uint32_t r = 0;
+            for (uint32_t j = 0; j < cnt; ++j) r += (surv[j] > my || (surv[j] == my && j < i)) ? 1u : 0u;    // (equal keys - a candidate listed twice - keep distinct slots)
+            if (r < top) {
+                qmx_scored_point p;
+                p.idx = key_idx(my);
+                p.score = key_score(my);
+                out[(uint64_t)q * top + r] = p;
+                if (r == top - 1) sh_bound = my;
+            }
+        }
+        found = cnt < top ? cnt : top;
+    } else {
+        // more survivors than the list holds: one bounded list per wave over the whole row, merged by wave 0 (custom_topk_kernel's pass)
+        const int ptop = (int)top;
+        uint64_t list = 0;
+        for (uint32_t base = (uint32_t)wave * WAVE; base < n; base += CTB_BLOCK * 4) {
+            uint64_t key[4], keep[4];
+            uint32_t id[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t c = base + (uint32_t)u * CTB_BLOCK + lane;
+                const uint32_t cc = c < n ? c : 0;
+                id[u] = ids ? ids[cc] : cc;
+                key[u] = c < n ? make_key(row[cc], id[u]) : 0ull;
+            }
+            live_masks<4>(del, id, keep);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                key[u] &= keep[u];
+                wave_offer(list, key[u], ptop, lane);
+            }
+        }
+        __syncthreads();                                    // (every thread has read cnt and is done with the survivors)
+        surv[wave * WAVE + lane] = list;
+        __syncthreads();
+        uint32_t got = 0;
+        if (wave == 0) {
+            uint64_t merged = surv[lane];
+            for (int w = 1; w < CTB_NW; ++w) wave_offer(merged, surv[w * WAVE + lane], ptop, lane);
+            const bool ok = lane < ptop && merged != 0;
+            if (ok) {
+                qmx_scored_point p;
+                p.idx = key_idx(merged);
+                p.score = key_score(merged);
+                out[(uint64_t)q * top + lane] = p;
+            }
+            got = (uint32_t)__popcll(__ballot(ok));
+            if (lane == 0) {
+                sh_bound = got == top ? readlane_u64(merged, ptop - 1) : 0ull;
+                sh_cnt = got;
+            }
+        }
+        __syncthreads();
+        found = sh_cnt;
+    }
+    for (uint32_t i = found + threadIdx.x; i < top; i += CTB_BLOCK) out[(uint64_t)q * top + i] = qmx_scored_point{0u, 0.0f};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out_counts[q] = found;
+        if (bound_out) bound_out[q] = found == top ? sh_bound : 0ull;
+    }
+}
+
 int32_t launch_custom_topk(hipStream_t st, const float *d_scores, uint64_t n, const uint32_t *d_ids, const DeletedView &del, uint32_t n_queries,
-                           uint32_t top, qmx_scored_point *d_out, uint32_t *d_counts, uint64_t *d_bound) {
+                           uint32_t top, qmx_scored_point *d_out, uint32_t *d_counts, uint64_t *d_bound, bool beside_scan) {
     if (n_queries == 0) return QMX_OK;
     ::qmx::clear_stale_error();
+    // a prefilter's sample bound (option prescan_beside_scan = 2: every short row) in the block that fits beside a resident scan block
+    const int64_t beside_opt = option(OPT_PRESCAN_BESIDE_SCAN);
+    if ((beside_scan ? beside_opt > 0 : beside_opt == 2) && n >= 1 && n <= (uint64_t)CTB_BLOCK * 64 && top >= 1 && top <= (uint32_t)WAVE &&
+        !option(OPT_NO_TOPK_SMALL)) {
+        QMX_NOTE_KERNEL(n <= (uint64_t)CTB_BLOCK * 32 ? custom_topk_beside_kernel<32> : custom_topk_beside_kernel<64>);
+        if (n <= (uint64_t)CTB_BLOCK * 32)
+            hipLaunchKernelGGL(custom_topk_beside_kernel<32>, dim3(n_queries), dim3(CTB_BLOCK), 0, st, d_scores, (uint32_t)n, d_ids, del, top, d_out, d_counts, d_bound);
+        else
+            hipLaunchKernelGGL(custom_topk_beside_kernel<64>, dim3(n_queries), dim3(CTB_BLOCK), 0, st, d_scores, (uint32_t)n, d_ids, del, top, d_out, d_counts, d_bound);
+        QMX_HIP(hipGetLastError());
+        return QMX_OK;
+    }
     if (n >= 1 && n <= CTS_MAX_N && !option(OPT_NO_TOPK_SMALL)) {
         static thread_local DeviceOnce attr_once;
         if (attr_once.need()) {
             QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(custom_topk_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CTS_MAX_N * 8)));
             attr_once.mark();
         }
+        QMX_NOTE_KERNEL(custom_topk_small_kernel);
         hipLaunchKernelGGL(custom_topk_small_kernel, dim3(n_queries), dim3(CT_BLOCK), (size_t)n * 8, st, d_scores, (uint32_t)n, d_ids, del, top, d_out, d_counts, d_bound);
         QMX_HIP(hipGetLastError());
         return QMX_OK;
     }
+    QMX_NOTE_KERNEL(custom_topk_kernel);
     hipLaunchKernelGGL(custom_topk_kernel, dim3(n_queries), dim3(CT_BLOCK), 0, st, d_scores, n, d_ids, del, top, d_out, d_counts, d_bound);
     QMX_HIP(hipGetLastError());
     return QMX_OK;

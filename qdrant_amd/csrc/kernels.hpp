@@ -284,6 +284,8 @@ int32_t launch_scan_dense(hipStream_t st, int dtype, int distance, int qt, ScanM
                           const ScanArgs &a, int num_cus, uint32_t *grid_out);
 // f32 dot / cosine, 8..32 queries per pass on v_mfma_f32_4x4x1 with the reference's bits (scan_mfma.hip)
 int32_t launch_scan_f32_mfma(hipStream_t st, int qt, ScanMode mode, const ScanArgs &a, int num_cus, uint32_t *grid_out);
+// ... the scores of a short candidate list, 16 queries per tile on 4 waves: a block that fits beside one of the resident int8 scan (option prescan_beside_scan)
+int32_t launch_scan_f32_mfma_beside(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out);
 // SQ int8 dot / cosine / euclid, 8..32 queries per pass on v_mfma_i32_16x16x64_i8 (scan_sq_mfma.hip)
 bool sq_mfma_ok(uint32_t distance, uint32_t actual_dim);
 int32_t launch_scan_sq_mfma(hipStream_t st, int qt, ScanMode mode, const ScanArgs &a, int num_cus, uint32_t *grid_out);
@@ -470,7 +472,8 @@ int32_t launch_custom_combine(hipStream_t st, const qmx_custom_query *d_queries,
 int32_t launch_maxsim(hipStream_t st, const float *d_sims, uint64_t n_rows, const uint32_t *d_qfirst, uint32_t n_queries, const uint64_t *d_offsets,
                       uint32_t n_points, const uint32_t *d_ids, uint64_t n, float *d_out, int *err_flag);
 int32_t launch_custom_topk(hipStream_t st, const float *d_scores, uint64_t n, const uint32_t *d_ids, const DeletedView &del, uint32_t n_queries,
-                           uint32_t top, qmx_scored_point *d_out, uint32_t *d_counts, uint64_t *d_bound = nullptr);   // d_bound[q] = the k-th best key of a full list, else 0
+                           uint32_t top, qmx_scored_point *d_out, uint32_t *d_counts, uint64_t *d_bound = nullptr,    // d_bound[q] = the k-th best key of a full list, else 0
+                           bool beside_scan = false);   // a prefilter's sample bound: the 256-thread kernel where it applies (option prescan_beside_scan)
 
 // Metric::preprocess + element casts (preprocess.hip)
 int32_t launch_cosine_preprocess_f32(hipStream_t st, const float *in, float *out, uint64_t n, uint32_t dim);

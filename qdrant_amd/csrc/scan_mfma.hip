@@ -350,7 +350,7 @@ __global__ __launch_bounds__(NWAVES * 64) void scan_f32_mfma_kernel(const ScanAr
 }
 
 template <int QW, int QSPLIT, int D, bool NT, int NWAVES, bool FAST, bool QH, bool HAS_IDS, int MODE>
-static int32_t launch_mfma_inst(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out) {
+static int32_t launch_mfma_inst(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out, uint32_t grid_cap = 0) {
     constexpr int QT = QW * QSPLIT;
     constexpr int MF_BLOCK = NWAVES * 64, MF_NW = NWAVES;
     constexpr int NSTREAM = MF_NW / QSPLIT;
@@ -374,6 +374,7 @@ static int32_t launch_mfma_inst(hipStream_t st, const ScanArgs &a, int num_cus, 
     const uint64_t want = (n_tiles + NSTREAM - 1) / NSTREAM;
     const uint64_t cap = (uint64_t)num_cus * per_cu;
     uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    if (grid_cap && grid > grid_cap) grid = grid_cap;
     if (grid < 1) grid = 1;
     if (grid_out) {
         if (*grid_out && MODE == SCAN_TOPK && grid > *grid_out) grid = *grid_out;
@@ -426,6 +427,26 @@ int32_t launch_scan_f32_mfma(hipStream_t st, int qt, ScanMode mode, const ScanAr
     if (qt == 64 && mfma16_scan_ok(64, mode, a)) return launch_scan_f32_mfma16(st, 64, a, num_cus, grid_out);   // api_*.hip only asks when it applies
     set_error("unsupported MFMA query tile %d", qt);
     return QMX_ERR_BAD_ARG;
+}
+
+// The score matrix of a SHORT candidate list (the prefilters' sample: <= 16 384 ids) in a shape that starts on a CU whose other tenant is a block of
+// the resident int8 scan (scan_split.hip sp8r_lds_bytes: 2 waves and 320 registers per SIMD, 99 328 B of LDS - what is left is 192 registers per SIMD
+// and 64 512 B).  The 32-query tile of launch_scan_f32_mfma (8 waves at 176 registers, 107 264 B at 768 coordinates) waits for a CU without a scan block;
+// this one - 16 queries, 4 waves = one per SIMD, 53 760 B at 768 coordinates - does not.  Per (row, query) the same instruction sequence as the 16-query
+// slice of that tile (QW = 16 either way: QSPLIT only says which waves share a row stream), so the same bits; the block walks twice the query tiles.
+// What it does beside a scan it takes from the scan, so it is built to take little (profiles/r15_prescan_beside_scan.md): a quarter of the blocks the
+// row count would give (a wave takes four 8-row tiles per query tile, not one).  A block's fill of its query tile, 52.5 KiB from L2 per 16 queries, is the
+// kernel's largest traffic, and it is per block.  (With that few blocks launch_mfma_inst finds room for every query tile's blocks at once: at 8 192 rows
+// and 128 queries 64 x 8 blocks of one query tile each.)  With one row tile per wave the scans beside it ran 5 % longer and the step was no faster than
+// without the overlap; an eighth and a sixteenth of the blocks measured slower again.
+// Registers (vector + the 64 accumulator registers): 188 for rows of a multiple of 384 floats, allocated as 192 - all a scan block leaves per SIMD, and
+// nothing but tools/step_footprint.py watches that; 194 -> 200 for other row lengths (the guarded main loop), which therefore still wait for a CU without
+// a scan block, with the same results (profiles/r15_step_footprint.md).
+int32_t launch_scan_f32_mfma_beside(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out) {
+    QMX_REQUIRE(a.ids != nullptr, QMX_ERR_BAD_ARG, "the short-list score matrix takes an id list");
+    const uint32_t grid_cap = (uint32_t)((a.n_cand + 127) / 128);
+    if (a.nseg % 12 == 0) return launch_mfma_inst<16, 1, 6, true, 4, true, false, true, SCAN_SCORES>(st, a, num_cus, grid_out, grid_cap);
+    return launch_mfma_inst<16, 1, 6, true, 4, false, false, true, SCAN_SCORES>(st, a, num_cus, grid_out, grid_cap);
 }
 
 }  // namespace qmx

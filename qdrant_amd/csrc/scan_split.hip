@@ -1525,8 +1525,11 @@ __global__ __launch_bounds__(SP3_THREADS, 1) void scan_i8copy_kernel(const ScanA
 // lane-constant offset inside each 1 KiB image), so a stage is four `global_load_dwordx4` of 1 KiB each, contiguous, INTO the matrix instruction's operand
 // registers, issued AHEAD stages in front of the matrix work and waited for by the kernel's own vmcnt (in-order); per stage and wave 32 matrix instructions
 // against all 128 queries and 16 operand reads.  Same integers, same thresholds, same candidates as scan_i8copy_kernel (which stays for longer rows and as option
-// i8_resident = 0); LDS per CU 97 KiB instead of 144: every small kernel of the other batches in flight - the sample's exact scores with their 50 KiB query tile
-// among them - fits beside a scan. ----
+// i8_resident = 0); LDS per CU 97 KiB instead of 144, 2 waves and 320 registers per SIMD: a block of another batch in flight starts beside a scan block when it
+// needs at most 64 512 B of LDS and 192 registers per SIMD.  The sample's exact scores did NOT, whatever this comment said until round 15: their 32-query tile
+// is 105 KiB at 768 coordinates (8 waves at 176 registers), and the 1024-thread top-k behind them holds 64 KiB of keys; both waited for a CU without a scan
+// block.  With option prescan_beside_scan (default 1) they run as a 16-query tile of 52.5 KiB on 4 waves at 192 registers (scan_mfma.hip launch_scan_f32_mfma_beside) and a
+// 256-thread top-k with 16 KiB (custom_query.hip custom_topk_beside_kernel), which do; profiles/r15_step_footprint.md lists every kernel of the step. ----
 constexpr uint32_t SP8R_MAX_NCH = 8;
 __host__ __device__ constexpr size_t sp8r_lds_bytes(uint32_t nch) { return (size_t)nch * SP_B_UNITS * 16 + 2 * SP_QT * 4; }
 // (non-temporal: every line of the copy is read once per pass, by one CU, whole - a load instruction covers 1 KiB of consecutive bytes; with plain loads the same
