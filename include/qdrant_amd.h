@@ -554,7 +554,10 @@ QMX_API int32_t qmx_query_last_counters(qmx_query *q, qmx_counters *out);
 
 /* `postprocess_search_result` rescoring (lib/segment/src/index/vector_index_search_common.rs:73-90):
  * query qi re-scores ids[qi * n_per_query .. +counts[qi]) with the ORIGINAL-vector scorer `q`,
- * sorts descending, truncates to `top`. */
+ * sorts descending, truncates to `top`; among equal scores the LOWER id first, the rule of qmx_search_topk.
+ * The live ids of one query must be DISTINCT (the lists of a walk or a scan are): the sort runs in passes of 64 keys, each bounded by the
+ * last key of the pass before, and of two entries with one id and one score both stay when they fall into one pass and one is lost when
+ * they straddle two.  Nothing is deduplicated here; lists of several segments go through qmx_merge_topk*. */
 QMX_API int32_t qmx_rescore(qmx_query *q, const uint32_t *ids, const uint32_t *counts,
                             uint32_t n_per_query, uint32_t top, qmx_scored_point *out,
                             uint32_t *out_counts);

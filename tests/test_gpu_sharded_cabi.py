@@ -149,6 +149,47 @@ def test_sharded_hnsw_search_merges_the_per_segment_walks(qa):
     s.close()
 
 
+@pytest.mark.parametrize("top", [10, 100])
+def test_a_point_that_lives_in_two_segments_is_returned_once(qa, top):
+    """Segments 0 and 2 hold the same rows under the same id base (a point mid-move between segments: what `SearchResultAggregator::push`'s
+    `seen` set is for, search_result_aggregator.rs:28-37): the lists are those of segments 0 and 1 alone, every id once."""
+    import torch
+    from qdrant_amd import sharded
+    n, dim, nq, ef = 900, 32, 5, 128
+    a, b = (O.preprocess(O.COSINE, O.synth(0x5EED0760 + 16 * r, 0, n, dim)) for r in range(2))
+    queries = O.synth(0x5EED0761, 0, nq, dim)
+    truth = O.DenseStorage(O.F32, O.COSINE, np.concatenate([a, b]))
+    want = truth.peek_top(queries, top)
+    sts = [qa.VectorStorage(r, qa.Distance.Cosine) for r in (a, b, a)]
+    bases = [0, n, 0]
+    two = sharded.SegmentsSearcher(sts[:2], nq, id_bases=bases[:2])
+    _same(two.search(queries, top), want)
+    s = sharded.SegmentsSearcher(sts, nq, id_bases=bases)
+    got = s.search(queries, top)
+    _same(got, want)
+    assert all(len(g) == top == len(set(g["idx"].tolist())) for g in got)
+    dev = torch.device("cuda", 0)
+    out = torch.full((nq, top, 2), 0x7F7F7F7F, dtype=torch.int32, device=dev)
+    cnt = torch.full((nq,), 0x7F7F7F7F, dtype=torch.int32, device=dev)
+    s.search_async(torch.from_numpy(queries).to(dev), top, out, cnt)
+    s.synchronize()
+    o, c = out.cpu().numpy(), cnt.cpu().numpy()
+    for i in range(nq):
+        assert c[i] == top and o[i, :, 0].view(np.uint32).tolist() == want[i]["idx"].tolist()
+        assert np.array_equal(o[i, :, 1].copy().view(np.uint32), want[i]["score"].view(np.uint32))
+    two.close()
+    s.close()
+    # the walks of three graphs (segment 2's built from another seed: it need not find the rows segment 0 found)
+    graphs = [qa.GraphLayers.build(st, m=8, ef_construct=48, seed=3 + i) for i, st in enumerate(sts)]
+    h = sharded.SegmentsSearcher(sts, nq, id_bases=bases, graphs=graphs)
+    for i, g in enumerate(h.search(queries, top, ef=ef)):
+        ids = g["idx"].tolist()
+        assert len(ids) == top == len(set(ids)) and max(ids) < 2 * n
+        exact = truth.score_points(queries[i:i + 1], g["idx"])[0]
+        assert np.array_equal(g["score"].view(np.uint32), exact.view(np.uint32)) and np.all(np.diff(g["score"]) <= 0)
+    h.close()
+
+
 def test_segments_on_two_devices(qa):
     """One segment per device, gathered by hipMemcpyPeerAsync: needs a multi-GPU node (skipped on the 1-GPU boxes)."""
     if qa.device_count() < 2:
@@ -176,3 +217,11 @@ def test_bad_arguments_are_refused(qa):
     hs = (C.c_void_p * 2)(a._h.value, a._h.value)
     assert F.lib().qmx_sharded_search_topk(hs, 2, 3, None, F.ptr(out), F.ptr(cnt), None, None) == F.ERR_BAD_ARG      # one batch twice
     assert F.lib().qmx_sharded_search_topk(hs, 0, 3, None, F.ptr(out), F.ptr(cnt), None, None) == F.ERR_BAD_ARG
+    # two segments x top 8193: one entry past the merge's 16384 per query, refused before anything is enqueued
+    c = qa.new_raw_scorer(O.synth(2, 0, 4, 32), st)
+    hs = (C.c_void_p * 2)(a._h.value, c._h.value)
+    big = np.full((4, 8193), 7, dtype=O.ScoredPointOffset)
+    assert F.lib().qmx_sharded_search_topk(hs, 2, 8193, None, F.ptr(big), F.ptr(cnt), None, None) == F.ERR_NOT_SUPPORTED
+    assert F.last_error() == "merge of 2 segments x top 8193 exceeds 16384 entries per query"
+    assert (big["idx"] == 7).all()
+    assert F.lib().qmx_sharded_search_topk(hs, 2, 8192, None, F.ptr(big), F.ptr(cnt), None, None) == F.OK and cnt.tolist() == [500] * 4
