@@ -302,7 +302,12 @@ QMX_API uint32_t qmx_abi_version(void);
  * "pq_prefilter_min_queries", "hnsw_pq_per_cu", "tq_rotate_block", "no_topk_small", "verify_max_per_query", "hnsw_pq_direct_walk",
  * "hnsw_pq_table_build", "hnsw_no_pq_prefilter", "hnsw_no_lds_visited", "pq_lut_no_lds", "hnsw_per_cu", "tq_wide_min_queries", "tq_wide_high_digit", "sq_wide_min_queries", "i8_resident",
  * "i8_dense_epilogue" (default 1: the int8 prefilter's first launch lists its candidates through a hit mask per lane and dense slots per wave; 0: the one
- * epilogue for both launches), "i8_sample_stride" (the first launch takes every n-th tile; default 16), "prescan_beside_scan" (default 1: a prefilter's
+ * epilogue for both launches), "i8_sample_stride" (the first launch takes every n-th tile; default 16),
+ * "i8_sample_scan" (default 1: the int8 prefilter takes its first bound from the int8 copy itself.  The sample is T = S / 16 whole 16-row tiles of the
+ * block, S = max(n >> (prescan_shift + 1), 8 192) rounded down to a multiple of 16: sample tile i (i < T) is rows 16 i step .. 16 i step + 15 with
+ * step = (n / 16) / T, integer divisions - complete row tiles only.  Their int8 scores pick each query's k best live sample rows, whose exact scores
+ * give the bound; 0: the exact f32 scores of rows 0, step', 2 step', ... with step' = n / S), "i8_sample_rows" (S of that sample; 0, the default: the rule
+ * above), "prescan_beside_scan" (default 1: a prefilter's
  * sample pre-scan and the top-k behind it run as 256-thread blocks that fit on a CU beside a block of the resident int8 scan - the pre-scan at 384 or 768 coordinates -; 0: the former 512- / 1024-
  * thread shapes), "group_matrix_bytes", "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -

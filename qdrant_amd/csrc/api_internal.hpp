@@ -185,6 +185,7 @@ struct qmx_query {
     uint32_t last_fqt = 64;          // queries per conditional exact pass of the last prefilter search (fold_split_counters)
     uint64_t last_row_bytes = 0, last_n_cand = 0;
     uint64_t sp_sample_n = 0, sp_sample_of = 0;
+    bool sp_sample_tiles = false;    // sp_sample lists whole 16-row tiles (the int8 route, option i8_sample_scan), not every n-th row
     DevBuf filter;             // payload-filter allow bitmap of this query batch (qmx_query_set_filter)
     uint64_t n_filter_bits = 0;
     bool has_filter = false;

@@ -140,20 +140,39 @@ __global__ void sample_ids_kernel(uint32_t *ids, uint32_t n, uint64_t step) {
     if (i < n) ids[i] = (uint32_t)((uint64_t)i * step);
 }
 
+// ids of a sample made of T whole 16-row tiles (the int8 copy's operand tiles, option i8_sample_scan): tile i of the sample is row tile i * step of the
+// block, step = (n / 16) / T - complete row tiles only, spread evenly.  Entry 16 i + r is row 16 i step + r (include/qdrant_amd.h states the rule)
+__global__ void sample_tile_ids_kernel(uint32_t *ids, uint32_t n, uint64_t step) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ids[i] = (uint32_t)((uint64_t)(i >> 4) * step * 16u + (i & 15u));
+}
+
 // what a prefilter search starts with: the plan block and the verification pool behind it, then the sample - every 2^(prescan_shift + shift)-th row,
 // at least 8 192 rows, its id list kept across searches of the same block size - and the zeros of the plan block.  Returns the sample's size.
-static int32_t prefilter_begin(qmx_query *q, const SplitPlanLayout &pl, uint64_t n_cand, int shift, VerifyPool *vp, uint64_t *S_out) {
+// (tiles: the int8 route's sample of whole 16-row tiles - the same size rounded down to a multiple of 16, or what option i8_sample_rows says)
+static int32_t prefilter_begin(qmx_query *q, const SplitPlanLayout &pl, uint64_t n_cand, int shift, VerifyPool *vp, uint64_t *S_out, bool tiles = false) {
     QMX_TRY(q->sp_plan.reserve(pl.bytes));
     QMX_TRY(verify_pool(q, (unsigned char *)q->sp_plan.p, vp));
     const int sshift = (int)std::min<int64_t>(std::max<int64_t>(option(OPT_PRESCAN_SHIFT) + shift, 1), 20);
-    const uint64_t S = std::min<uint64_t>(n_cand, std::max<uint64_t>(n_cand >> sshift, 8192));
-    if (q->sp_sample_n != S || q->sp_sample_of != n_cand) {
+    uint64_t S = std::min<uint64_t>(n_cand, std::max<uint64_t>(n_cand >> sshift, 8192));
+    if (tiles) {
+        const int64_t rows_opt = option(OPT_I8_SAMPLE_ROWS);
+        if (rows_opt > 0) S = std::min<uint64_t>(n_cand, std::max<int64_t>(rows_opt, 16));
+        S &= ~(uint64_t)15;
+        QMX_REQUIRE(S >= 16, QMX_ERR_OTHER, "a sample of row tiles needs a block of 16 rows");
+    }
+    if (q->sp_sample_n != S || q->sp_sample_of != n_cand || q->sp_sample_tiles != tiles) {
         QMX_TRY(q->sp_sample.reserve((size_t)S * 4));
         ::qmx::clear_stale_error();
-        hipLaunchKernelGGL(sample_ids_kernel, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, q->stream, (uint32_t *)q->sp_sample.p, (uint32_t)S, n_cand / S);
+        if (tiles)
+            hipLaunchKernelGGL(sample_tile_ids_kernel, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, q->stream, (uint32_t *)q->sp_sample.p, (uint32_t)S,
+                               (n_cand / 16) / (S / 16));
+        else
+            hipLaunchKernelGGL(sample_ids_kernel, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, q->stream, (uint32_t *)q->sp_sample.p, (uint32_t)S, n_cand / S);
         QMX_HIP(hipGetLastError());
         q->sp_sample_n = S;
         q->sp_sample_of = n_cand;
+        q->sp_sample_tiles = tiles;
     }
     QMX_HIP(hipMemsetAsync(q->sp_plan.p, 0, pl.zero_bytes, q->stream));
     *S_out = S;
@@ -421,6 +440,7 @@ struct SplitTiles {
     SplitPlanLayout pl;
     VerifyPool vp{};
     uint64_t S = 0;                                         // rows of the sample
+    bool i8_sample = false;                                 // the int8 route with option i8_sample_scan: the sample is tiles of the copy, scored there
     std::vector<std::pair<uint32_t, uint32_t>> tiles;       // (tile0, nq_tile) of the tiles that took the prefilter
     SplitTiles(uint32_t nq, uint32_t fqt) : pl(nq, fqt) {}
 };
@@ -458,7 +478,9 @@ static int32_t split_begin(const SearchCall &c, const SearchPlan &plan, SplitTil
     // refine step after the first sixteenth of the block owns the threshold anyway: 26 us of the step, measured)
     // (a 2 048-row sample lets the four query tiles of a 128-query batch run side by side - 22 us instead of 63 for the pre-scan - but its weaker threshold
     // triples the candidates of the first launch: regroup, refine and select together give the 40 us back, measured; 8 192 stays)
-    return prefilter_begin(q, sp.pl, c.n_cand, s->d_rows_split ? 1 : -2, &sp.vp, &sp.S);
+    // (the int8 copy, option i8_sample_scan: the same number of rows as whole 16-row tiles of the copy, scored by the int8 matrix instruction - i8_copy_scan)
+    sp.i8_sample = s->split_i8 && option(OPT_I8_SAMPLE_SCAN) > 0;
+    return prefilter_begin(q, sp.pl, c.n_cand, s->d_rows_split ? 1 : -2, &sp.vp, &sp.S, sp.i8_sample);
 }
 
 // steps 2 - 4 of a tile over the f32 rows or an f16 copy
@@ -494,19 +516,41 @@ static int32_t f16_split_scan(SearchCall &c, SplitTiles &sp, const ScanArgs &a, 
     return QMX_OK;
 }
 
-// steps 2' - 4' of a tile over the int8 copy
+// steps 2' - 4' of a tile over the int8 copy (option i8_sample_scan: step 1 as well)
 static int32_t i8_copy_scan(SearchCall &c, SplitTiles &sp, const ScanArgs &a, uint32_t tile0, uint32_t nq_tile, int *tile_ovf) {
     qmx_query *q = c.q;
     const qmx_segment *s = q->seg;
     unsigned char *plan = (unsigned char *)q->sp_plan.p;
     const SplitF32 f(q->sp_f32.p);
-    // 2'. the int8 copy: codes, scales, worst-case bands, thresholds from the sample's exact k-th best
-    QMX_TRY(launch_split_i8_pack(q->stream, (const float *)q->enc.p + (size_t)tile0 * s->dim, nq_tile, s->dim, s->d_i8_scale, (const uint64_t *)q->gthr.p + tile0,
-                                 s->d_i8_stats, s->row_norm_max, q->sp_bq.p, f.i8_qscale, f.band, f.thr, f.i8_texact, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+    // 2'. the int8 copy: codes, scales, worst-case bands, thresholds from the sample's exact k-th best - or, with the sample scored on the copy, no
+    // threshold yet (+inf: nothing is admitted; the band of a finite query is finite)
+    QMX_TRY(launch_split_i8_pack(q->stream, (const float *)q->enc.p + (size_t)tile0 * s->dim, nq_tile, s->dim, s->d_i8_scale,
+                                 sp.i8_sample ? nullptr : (const uint64_t *)q->gthr.p + tile0, s->d_i8_stats, s->row_norm_max, q->sp_bq.p, f.i8_qscale, f.band, f.thr,
+                                 f.i8_texact, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
     QMX_TRY(split_stage(q, "int8 pack"));
-    // 3'. the strided sixteenth, then the rest; after each launch the exact scores of the k best candidates so far renew the bound
     const uint32_t np = split_i8_probe();
     uint32_t *probe_ids = (uint32_t *)q->sp_probe.p, *probe_cnt = probe_ids + (size_t)q->nq * np;
+    if (sp.i8_sample) {
+        // 1'. "launch 0": the approximate scores of the sample's tiles, the k best live ones of each query (the top-k sees the deleted rows and the
+        // requests' filters), their exact scores by the pair kernel - any k distinct live rows bound the final k-th best from below -> thr, T_exact, gthr.
+        // What follows a scan launch below, with the top-k in the place of regroup and probe.
+        QMX_TRY(q->scores.reserve((size_t)nq_tile * sp.S * sizeof(float)));
+        QMX_TRY(launch_scan_i8copy_sample(q->stream, s->d_rows_split, q->sp_bq.p, s->dim, (const uint32_t *)q->sp_sample.p, (uint32_t)(sp.S / 16), nq_tile, f.i8_qscale,
+                                          (float *)q->scores.p));
+        QMX_TRY(launch_custom_topk(q->stream, (const float *)q->scores.p, sp.S, (const uint32_t *)q->sp_sample.p, a.del, nq_tile, c.top, c.d_out + (size_t)tile0 * c.top,
+                                   c.d_counts + tile0, nullptr, true));
+        QMX_TRY(launch_split_i8_picks(q->stream, c.d_out + (size_t)tile0 * c.top, c.d_counts + tile0, nq_tile, c.top, f.band, probe_ids + (size_t)tile0 * np,
+                                      probe_cnt + tile0));
+        const void *scan_kernel = q->last_kernel;
+        PairSel psel{nullptr, np, probe_cnt};
+        QMX_TRY(score_pairs_device(q, psel, probe_ids, (uint64_t)(tile0 + nq_tile) * np, (float *)q->sp_pscores.p, false));
+        q->last_kernel = scan_kernel;
+        QMX_TRY(launch_split_i8_sample_bound(q->stream, (const float *)q->sp_pscores.p + (size_t)tile0 * np, probe_ids + (size_t)tile0 * np, probe_cnt + tile0, nq_tile,
+                                             c.top, f.band, f.i8_qscale, f.thr, f.i8_texact, (uint64_t *)q->gthr.p + tile0));
+        QMX_TRY(split_stage(q, "int8 sample scan"));
+        c.launches += 3;      // (five launches in the place of the pre-scan's two)
+    }
+    // 3'. the strided sixteenth, then the rest; after each launch the exact scores of the k best candidates so far renew the bound
     // (which tiles the first launch takes: every 16th, option i8_sample_stride.  Its candidates are admitted on the SAMPLE's bound - a hundred times
     // those of the main launch per tile.  With the one epilogue for both launches that, not the stream, was what bounded the first launch, and strides
     // of 8 .. 64 measured the same step time (profiles/r5_i8_sample_stride.md); with an epilogue made for dense candidates (option i8_dense_epilogue)
@@ -539,7 +583,8 @@ static int32_t split_tile(SearchCall &c, const SearchPlan &plan, SplitTiles &sp,
     QMX_CHECK_CANCELLED(c.is_stopped);
     const ScanArgs a = tile_args(c, tile0, nq_tile);
     // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best (launches: counted in the tile's 8 / 13)
-    QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, sp.S, c.top, a.del, nullptr, true));
+    // (the int8 copy with option i8_sample_scan takes that bound from the copy itself, behind its pack: i8_copy_scan)
+    if (!sp.i8_sample) QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, sp.S, c.top, a.del, nullptr, true));
     QMX_TRY(split_stage(q, "prescan"));
     int *tile_ovf = (int *)((unsigned char *)q->sp_plan.p + sp.pl.tile_ovf) + sp.tiles.size();
     if (plan.route == ROUTE_I8_COPY) QMX_TRY(i8_copy_scan(c, sp, a, tile0, nq_tile, tile_ovf));
@@ -636,7 +681,12 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
         split_q += t.second;
         // one pass over the derived copy (2 or 4 bytes per element; the f32 rows themselves when there is none) + the sample's exact scores
         bytes += c.n_cand * (uint64_t)s->dim * (s->split_i8 ? 1 : s->d_rows_split && s->split_half ? 2 : 4);
-        bytes += (uint64_t)((t.second + tile_qt(s, q) - 1) / tile_qt(s, q)) * q->sp_sample_n * s->row_bytes;
+        // (the int8 route's sample of tiles: one byte per element, once per query group of the sample kernel; its exact rows are k per query)
+        if (sp.i8_sample) {
+            const uint32_t group = split_i8_sample_queries(s->dim, t.second);
+            bytes += (uint64_t)((t.second + group - 1) / group) * q->sp_sample_n * s->dim + (uint64_t)t.second * std::min<uint32_t>(top, MAX_TOP_FAST) * s->row_bytes;
+        } else
+            bytes += (uint64_t)((t.second + tile_qt(s, q) - 1) / tile_qt(s, q)) * q->sp_sample_n * s->row_bytes;
     }
     bytes += (uint64_t)((q->nq - split_q + TQ - 1) / TQ) * c.n_cand * s->row_bytes * plan.n_pass;
     // (kernel_launches: this driver adds its launches to what the caller's counters held, and an enqueue without counters - the async call - records 0)

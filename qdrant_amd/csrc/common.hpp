@@ -58,6 +58,11 @@ enum Option {
                               // candidates per wave and tile) lists them through a hit mask per lane and dense slots per wave (scan_i8copy_kernel_res_dense);
                               // 0 = the one epilogue for both launches.  The same candidates per launch either way
     OPT_I8_SAMPLE_STRIDE,     // the first launch of the int8 prefilter takes every n-th tile (default 16; 2 .. 255)
+    OPT_I8_SAMPLE_SCAN,       // 1 (default): the int8 prefilter takes its sample's bound from the int8 copy itself - the sample is S / 16 whole 16-row tiles of the
+                              // copy, scored against the packed queries by scan_i8copy_sample_kernel (a block that fits beside a resident scan block at every row
+                              // length the resident scan takes), the k best live ones of each query re-scored exactly by the pair kernel; 0 = the exact f32
+                              // scores of a strided row sample (the pre-scan of rounds 3 - 15).  The same lists either way; the candidate counters move
+    OPT_I8_SAMPLE_ROWS,       // rows of that sample (rounded down to whole 16-row tiles; 0, the default: max(n >> (prescan_shift + 1), 8 192))
     OPT_PRESCAN_BESIDE_SCAN,  // 1 (default): the exact scores of a prefilter's sample (an id list of <= 16 384 rows, f32 matrix-core segments) are scored in 16-query
                               // tiles by 4-wave blocks (scan_mfma.hip launch_scan_f32_mfma_beside) and their k best are selected by a 256-thread block
                               // (custom_query.hip custom_topk_beside_kernel): both start on a CU that holds a block of the resident int8 scan.  0 = the 8-wave

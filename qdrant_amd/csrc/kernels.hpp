@@ -396,6 +396,15 @@ int32_t launch_split_i8_probe(hipStream_t st, const uint64_t *d_cand, const uint
                               const int *d_tile_overflow, uint32_t *d_probe_ids, uint32_t *d_probe_cnt);
 int32_t launch_split_i8_bound(hipStream_t st, const float *d_scores, uint32_t *d_probe_cnt, uint32_t nq, uint32_t top, const float *d_band, const float *d_qscale,
                               float *d_thr, float *d_t_exact);
+// option i8_sample_scan: the sample's bound from tiles of the int8 copy (launch_split_i8_pack with d_gthr = nullptr runs first) - approximate scores of
+// the sample's 16-row tiles, launch_custom_topk over them, its picks into the probe slots, the pair kernel, the bound
+uint32_t split_i8_sample_queries(uint32_t dim, uint32_t nq);      // queries per block of the sample kernel
+int32_t launch_scan_i8copy_sample(hipStream_t st, const void *d_rows_i8, const void *d_bq, uint32_t dim, const uint32_t *d_sample, uint32_t n_tiles, uint32_t nq,
+                                  const float *d_qscale, float *d_scores);
+int32_t launch_split_i8_picks(hipStream_t st, const qmx_scored_point *d_lists, const uint32_t *d_counts, uint32_t nq, uint32_t top, const float *d_band,
+                              uint32_t *d_probe_ids, uint32_t *d_probe_cnt);
+int32_t launch_split_i8_sample_bound(hipStream_t st, const float *d_scores, const uint32_t *d_probe_ids, uint32_t *d_probe_cnt, uint32_t nq, uint32_t top,
+                                     float *d_band, const float *d_qscale, float *d_thr, float *d_t_exact, uint64_t *d_gthr);
 // TurboQuant 4 bits, 128 queries per pass: codes decoded once per tile into the matrix cores' operand images, exact scores, candidate lists (scan_tq4w.hip)
 bool tq4w_shape_ok(const ScanArgs &a);
 size_t tq4w_query_bytes(uint32_t code_bytes);

@@ -1163,7 +1163,8 @@ __global__ __launch_bounds__(256) void sp_row_stats_kernel(const unsigned char *
 // (+ the round-off of the f32 evaluation the exact scores carry).  On unit Gaussian rows that is ~0.7 standard deviations of the score - two
 // orders above the error that really occurs, the price of a bound nobody can break - so the pass works with EXACT lower bounds T_q of the
 // k-th best score instead of approximate ones: a row of the result has an approximate score >= T_q - band_q (one band, not two).  T_q comes from
-// the exact sample scores first, then - after each of the two launches - from the exact scores of the k best candidates so far
+// the sample first (the exact scores of its k best rows by int8 score - "launch 0", scan_i8copy_sample_kernel; option i8_sample_scan = 0: the exact scores
+// of a strided row sample), then - after each of the two launches - from the exact scores of the k best candidates so far
 // (sp_i8_probe_kernel, the gather kernel of qmx_rescore, sp_i8_bound_kernel): ~a few hundred rows per query are re-scored at the end.
 // Everything else (per-wave candidate lists, regroup, verification, per-query exact fallback) is the f16 path's.
 // =====================================================================================================================================
@@ -1327,12 +1328,15 @@ __global__ __launch_bounds__(256) void sp_i8_pack_kernel(const float *q, uint32_
     const float cf = __builtin_fminf(0.5f * c1, c2 * __builtin_sqrtf(sf2));
     // (1.001: the roundings of x / s, q s, q s / t and of this sum; the last term: the f32 evaluation of the exact score, dim 2^-23 |q| |row|, twice)
     const float b = t * (cf + 0.5f * sabs + 0.25f * (float)dim) * 1.001f + 2.0f * (float)dim * 1.1920929e-7f * row_norm_max * __builtin_sqrtf(ss);
-    const uint64_t k = gthr[qi];
-    const bool ok = bad == 0.0f && k != 0 && b < 3.0e38f;
+    // gthr == nullptr (option i8_sample_scan): the pack runs FIRST and the sample's bound comes after it, from the int8 copy itself
+    // (scan_i8copy_sample_kernel ... sp_i8_sample_bound_kernel): the band of a finite query is finite, nothing is admitted yet
+    const uint64_t k = gthr ? gthr[qi] : 0;
+    const bool finite = bad == 0.0f && b < 3.0e38f;
+    const bool ok = finite && k != 0;
     // no bound (the sample holds fewer than k live rows) or a query that is not finite: no candidates, and the infinite band sends the query - alone -
     // to the exact scan
     qscale[qi] = t;
-    band[qi] = ok ? b : __builtin_inff();
+    band[qi] = (gthr ? ok : finite) ? b : __builtin_inff();
     t_exact[qi] = ok ? key_score(k) : -__builtin_inff();
     thr[qi] = ok ? (key_score(k) - b) / t : __builtin_inff();
 }
@@ -1862,6 +1866,145 @@ __global__ __launch_bounds__(64) void sp_i8_bound_kernel(const float *scores, ui
     }
 }
 
+// ---- "Launch 0" (option i8_sample_scan): the sample's bound from the int8 copy itself.  The sample is T = S / 16 whole 16-row tiles of the copy
+// (api_search.hip sample_tile_ids_kernel states which), a 16-row tile is 2 KiB contiguous per 128-coordinate stage - two 1 KiB plane images at
+// (row tile mod 16) * 2048 inside the stage's 32 KiB - and loads by the resident scan's pattern (sp_gload16 into the operand registers, the next stage's
+// loads on their way behind the matrix work, the kernel's own vmcnt).
+// A block is 4 waves, a wave owns two sample tiles (two independent addresses), the block keeps the operand images of NQ queries of the tile in LDS
+// (nch x NQ / 16 x 2 KiB: 48 KiB for 64 queries at 768 coordinates) - at most 64 accumulator and 32 row registers per lane, so that the block starts beside
+// a block of the resident scan (tools/step_footprint.py).  It writes scores[q][16 i + r] = (float)acc * qscale[q] for row r of sample tile i: the matrix
+// launch_custom_topk reads, whose k best live columns the pair kernel then scores exactly (sp_i8_picks_kernel, sp_i8_sample_bound_kernel).
+// Grid: (ceil(T / 8), ceil(nq / NQ)).
+template <int NQ>
+__global__ __launch_bounds__(256) void scan_i8copy_sample_kernel(const uint4 *rows_i8, const uint4 *bq, uint32_t nch, const uint32_t *sample_ids, uint32_t n_tiles,
+                                                                 uint32_t nq, const float *qscale, float *scores) {
+    constexpr int NT = NQ / 16, MT = 2, NL = 2 * MT;
+    static_assert(NQ == 16 || NQ == 32 || NQ == 64, "whole query tiles, a divisor of the 128-query tile");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    uint4 *lds = reinterpret_cast<uint4 *>(smem_raw);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t q0 = blockIdx.y * NQ;
+    // the images of queries q0 .. q0 + NQ: NT x 128 units of each stage's SP_B_UNITS
+    for (uint32_t u = (uint32_t)tid; u < nch * (NT * 128u); u += 256) {
+        const uint32_t kc = u / (NT * 128u), r = u % (NT * 128u);
+        lds[u] = bq[(uint64_t)kc * SP_B_UNITS + (q0 / 16u) * 128u + r];
+    }
+    __syncthreads();
+    const uint32_t t0 = (blockIdx.x * 4u + w) * MT;              // the wave's first sample tile
+    if (t0 >= n_tiles) return;
+    const bool two = t0 + 1 < n_tiles;                           // (a last, odd tile: the wave loads it twice and stores it once)
+    const unsigned char *base[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const uint32_t rt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(sample_ids[(uint64_t)(two ? t0 + (uint32_t)mt : t0) * 16u] >> 4));   // row tile of the block
+        base[mt] = reinterpret_cast<const unsigned char *>(rows_i8) + ((uint64_t)(rt >> 4) * nch) * (SP3_A_UNITS * 16u) + (rt & 15u) * 2048u;
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // from here on the kernel counts its vector-memory traffic itself
+    const uint32_t kq_r = (uint32_t)lane >> 4, m_r = (uint32_t)lane & 15u;
+    const uint32_t lane_unit = kq_r * 16u + (m_r ^ (2u * kq_r));      // sp_unit(0, 0, kq_r, m_r)
+    const uint4 *const b_rd = lds + lane_unit;
+    const uint32_t lane_off = lane_unit * 16u;
+    // one stage's four loads: (sample tile mt, plane hl) of stage kc -> rc[mt * 2 + hl]; past the last stage the loads repeat it (the waits count loads)
+    auto load_stage = [&](uint32_t kc, i32x4s (&rc)[NL]) __attribute__((always_inline)) {
+        const uint64_t off = (uint64_t)(kc < nch ? kc : nch - 1) * (SP3_A_UNITS * 16u);
+        sp_gload16<0>(rc[0], base[0] + off, lane_off);
+        sp_gload16<1024>(rc[1], base[0] + off, lane_off);
+        sp_gload16<0>(rc[2], base[1] + off, lane_off);
+        sp_gload16<1024>(rc[3], base[1] + off, lane_off);
+    };
+    i32x4s acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (i32x4s){0, 0, 0, 0};
+    auto landed = [](i32x4s (&rc)[NL]) __attribute__((always_inline)) { asm volatile("" : "+v"(rc[0]), "+v"(rc[1]), "+v"(rc[2]), "+v"(rc[3]) : : "memory"); };
+    auto one_stage = [&](uint32_t kc, const i32x4s (&cur)[NL]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int hl = 0; hl < 2; ++hl) {
+            const uint4 *bb = b_rd + (size_t)kc * (NT * 128u) + hl * 64;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const i32x4s bv = *reinterpret_cast<const i32x4s *>(bb + nt * 128);
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(cur[mt * 2 + hl], bv, acc[mt][nt], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // Two stages per trip: the loads of both are issued together, stage kc + 1's are on their way while stage kc runs (`vmcnt(4)`: all but the last four
+    // have landed).  Every load is issued AND waited for inside the trip: no register with a load on its way lives across a branch or the loop's edge,
+    // where the compiler may copy it or hand it to somebody else (round 14's fault: a load that landed in a register with a new owner) - a row of an odd
+    // number of stages loads its last stage twice and multiplies it once.
+    i32x4s ra[NL], rb[NL];
+    for (uint32_t kc = 0; kc < nch; kc += 2) {
+        load_stage(kc, ra);
+        load_stage(kc + 1, rb);
+        asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NL) : "memory");
+        landed(ra);
+        one_stage(kc, ra);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        landed(rb);
+        if (kc + 1 < nch) one_stage(kc + 1, rb);
+    }
+    const uint64_t S = (uint64_t)n_tiles * 16u;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const uint32_t q = q0 + (uint32_t)nt * 16u + m_r;
+        if (q >= nq) continue;
+        const float qs = qscale[q];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            if (mt == 1 && !two) continue;
+            float4 v;
+            v.x = (float)acc[mt][nt][0] * qs;
+            v.y = (float)acc[mt][nt][1] * qs;
+            v.z = (float)acc[mt][nt][2] * qs;
+            v.w = (float)acc[mt][nt][3] * qs;
+            *reinterpret_cast<float4 *>(scores + (uint64_t)q * S + (uint64_t)(t0 + (uint32_t)mt) * 16u + 4u * kq_r) = v;      // rows 4 kq_r .. + 3 of the tile
+        }
+    }
+}
+// the k best live sample rows of every query, as the top-k behind the sample kernel left them in the tile's output lists -> the probe slots the pair
+// kernel reads.  One wave per query; a query that is not finite (infinite band since the pack) has nothing to learn here.
+__global__ __launch_bounds__(64) void sp_i8_picks_kernel(const qmx_scored_point *lists, const uint32_t *counts, uint32_t top, const float *band, uint32_t *probe_ids,
+                                                         uint32_t *probe_cnt) {
+    const uint32_t q = blockIdx.x, lane = threadIdx.x;
+    uint32_t n = counts[q] < top ? counts[q] : top;
+    n = n < SP_I8_PROBE ? n : SP_I8_PROBE;
+    if (!(band[q] < 3.0e38f)) n = 0;
+    if (lane < n) probe_ids[(uint64_t)q * SP_I8_PROBE + lane] = lists[(uint64_t)q * top + lane].idx;
+    if (lane == 0) probe_cnt[q] = n;
+}
+// ... and what their exact scores say, sp_i8_bound_kernel's form for the sample: any k distinct live rows bound the final k-th best from below, so the
+// smallest key (score, lower id first) of the k picks sets the first threshold, T_exact and gthr - the bound the conditional exact passes start from
+// (sp_plan_kernel).  Fewer than k live sample rows: no bound - the band becomes infinite, which sends the query alone to the exact scan.
+__global__ __launch_bounds__(64) void sp_i8_sample_bound_kernel(const float *scores, const uint32_t *probe_ids, uint32_t *probe_cnt, uint32_t top, float *band,
+                                                                const float *qscale, float *thr, float *t_exact, uint64_t *gthr) {
+    const uint32_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint32_t n = probe_cnt[q];
+    const float sc = (uint32_t)lane < n ? scores[(uint64_t)q * SP_I8_PROBE + lane] : 0.0f;
+    const uint64_t key = (uint32_t)lane < n && sc == sc ? make_key(sc, probe_ids[(uint64_t)q * SP_I8_PROBE + lane]) : 0ull;
+    uint32_t rank = 0;
+    for (int j = 0; j < 64; ++j) rank += (uint64_t)__shfl((unsigned long long)key, j, 64) > key ? 1u : 0u;      // (live keys are distinct: they carry the row)
+    if (lane == 0) probe_cnt[q] = 0;
+    const bool finite = band[q] < 3.0e38f;
+    const bool mine = finite && n >= top && key != 0 && rank == top - 1;
+    if (!__ballot(mine)) {
+        if (lane == 0) {
+            band[q] = __builtin_inff();
+            gthr[q] = 0;
+        }
+        return;
+    }
+    if (mine) {
+        t_exact[q] = sc;
+        thr[q] = (sc - band[q]) / qscale[q];
+        gthr[q] = key;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 bool split_scan_ok(const ScanArgs &a) {
     return a.dim % 128 == 0 && a.dim >= 128 && a.rem_pieces == 0 && a.tail_start == a.dim && a.row_stride % 16 == 0 && a.ids == nullptr && a.top <= 64 &&
@@ -2110,7 +2253,8 @@ int32_t launch_split_i8_copy(hipStream_t st, const void *rows, uint64_t row_stri
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }
-// one 128-query tile: codes, scales, bands, first thresholds (d_gthr: the sample's exact k-th best keys); zeroes the tile's candidate counters
+// one 128-query tile: codes, scales, bands, first thresholds (d_gthr: the sample's exact k-th best keys; nullptr: no threshold yet, +inf - the sample
+// is scored behind this launch, launch_scan_i8copy_sample); zeroes the tile's candidate counters
 int32_t launch_split_i8_pack(hipStream_t st, const float *d_q, uint32_t nq, uint32_t dim, const float *d_scale, const uint64_t *d_gthr, const uint32_t *d_row_stats,
                              float row_norm_max, void *d_bq, float *d_qscale, float *d_band, float *d_thr, float *d_t_exact, uint32_t *d_cand_cnt, uint32_t n_cnt) {
     QMX_REQUIRE(nq <= (uint32_t)SP_QT, QMX_ERR_BAD_ARG, "int8 tile of %u queries", nq);
@@ -2172,6 +2316,50 @@ int32_t launch_split_i8_bound(hipStream_t st, const float *d_scores, uint32_t *d
                               float *d_thr, float *d_t_exact) {
     ::qmx::clear_stale_error();
     hipLaunchKernelGGL(sp_i8_bound_kernel, dim3(nq), dim3(64), 0, st, d_scores, d_probe_cnt, top, d_band, d_qscale, d_thr, d_t_exact);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+// queries per block of the sample kernel: the largest of 64 / 32 / 16 whose operand image fits in the LDS a resident scan block leaves on its CU at this row
+// length - and no more than the tile holds.  Longer rows take the staged scan, beside which nothing fits: 16.
+uint32_t split_i8_sample_queries(uint32_t dim, uint32_t nq) {
+    const uint32_t nch = dim / 128;
+    if (nch > SP8R_MAX_NCH) return 16;
+    const size_t free_lds = (size_t)160 * 1024 - sp8r_lds_bytes(nch);
+    uint32_t pick = 16;
+    for (uint32_t c = 32; c <= 64; c *= 2)
+        if ((size_t)nch * (c / 16) * 2048 <= free_lds && c / 2 < nq) pick = c;
+    return pick;
+}
+// the approximate scores of the sample's tiles (d_sample: their 16 n_tiles row ids, tile after tile) for the nq queries packed in d_bq -> d_scores [nq][16 n_tiles]
+int32_t launch_scan_i8copy_sample(hipStream_t st, const void *d_rows_i8, const void *d_bq, uint32_t dim, const uint32_t *d_sample, uint32_t n_tiles, uint32_t nq,
+                                  const float *d_qscale, float *d_scores) {
+    QMX_REQUIRE(d_rows_i8 && split_i8_dim_ok(dim) && nq >= 1 && nq <= (uint32_t)SP_QT && n_tiles >= 1, QMX_ERR_BAD_ARG, "int8 sample scan of %u queries", nq);
+    const uint32_t nch = dim / 128, NQ = split_i8_sample_queries(dim, nq);
+    const size_t lds_bytes = (size_t)nch * (NQ / 16) * 2048;
+    QMX_REQUIRE(lds_bytes <= 65536, QMX_ERR_OTHER, "int8 sample scan: %zu B of query images", lds_bytes);
+    const dim3 grid((n_tiles + 7) / 8, (nq + NQ - 1) / NQ);
+    ::qmx::clear_stale_error();
+    if (NQ == 64)
+        hipLaunchKernelGGL(scan_i8copy_sample_kernel<64>, grid, dim3(256), lds_bytes, st, (const uint4 *)d_rows_i8, (const uint4 *)d_bq, nch, d_sample, n_tiles, nq, d_qscale, d_scores);
+    else if (NQ == 32)
+        hipLaunchKernelGGL(scan_i8copy_sample_kernel<32>, grid, dim3(256), lds_bytes, st, (const uint4 *)d_rows_i8, (const uint4 *)d_bq, nch, d_sample, n_tiles, nq, d_qscale, d_scores);
+    else
+        hipLaunchKernelGGL(scan_i8copy_sample_kernel<16>, grid, dim3(256), lds_bytes, st, (const uint4 *)d_rows_i8, (const uint4 *)d_bq, nch, d_sample, n_tiles, nq, d_qscale, d_scores);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+// the tile's lists (the top-k of the approximate sample scores) -> probe slots; then, behind the pair kernel, the sample's bound
+int32_t launch_split_i8_picks(hipStream_t st, const qmx_scored_point *d_lists, const uint32_t *d_counts, uint32_t nq, uint32_t top, const float *d_band,
+                              uint32_t *d_probe_ids, uint32_t *d_probe_cnt) {
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sp_i8_picks_kernel, dim3(nq), dim3(64), 0, st, d_lists, d_counts, top, d_band, d_probe_ids, d_probe_cnt);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+int32_t launch_split_i8_sample_bound(hipStream_t st, const float *d_scores, const uint32_t *d_probe_ids, uint32_t *d_probe_cnt, uint32_t nq, uint32_t top,
+                                     float *d_band, const float *d_qscale, float *d_thr, float *d_t_exact, uint64_t *d_gthr) {
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(sp_i8_sample_bound_kernel, dim3(nq), dim3(64), 0, st, d_scores, d_probe_ids, d_probe_cnt, top, d_band, d_qscale, d_thr, d_t_exact, d_gthr);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }

@@ -4,7 +4,7 @@
 
 Prints, over the middle half of the trace's second-launch scans (the timed region without its ends):
   * the time per step in which NO scan_i8copy_kernel_res* dispatch is open (the union of the scans' intervals taken out of the window);
-  * per sample pre-scan (scan_f32_mfma_kernel) and sample top-k (custom_topk_*) dispatch: whether its interval lies inside one scan's, overlaps one
+  * per sample pre-scan (scan_f32_mfma_kernel), sample scan over the int8 copy (scan_i8copy_sample_kernel, option i8_sample_scan) and sample top-k (custom_topk_*) dispatch: whether its interval lies inside one scan's, overlaps one
     partly, or meets none, and its mean duration (the trace has start and end times only: how long a dispatch waited for a CU is not in it);
   * the mean duration of the first and second scan launches.
 usage: tools/scan_overlap.py <kernel_trace.csv>"""
@@ -13,13 +13,15 @@ import sys
 
 
 def main():
-    scans, small = [], {"pre-scan": [], "top-k": []}
+    scans, small = [], {"pre-scan": [], "sample scan": [], "top-k": []}
     for r in csv.DictReader(open(sys.argv[1])):
         name, t0, t1 = r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])
         if "scan_i8copy_kernel" in name:
             scans.append((t0, t1, "res_dense" in name))
         elif "scan_f32_mfma_kernel" in name:
             small["pre-scan"].append((t0, t1, name))
+        elif "scan_i8copy_sample_kernel" in name:
+            small["sample scan"].append((t0, t1, name))
         elif "custom_topk_" in name:
             small["top-k"].append((t0, t1, name))
     # which launch: the first one has a kernel of its own (option i8_dense_epilogue); without it the strided sixteenth is the one under 0.3 ms

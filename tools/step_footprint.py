@@ -10,7 +10,10 @@ A resident scan block (scan_i8copy_kernel_res<1> / _res_dense<1>: 512 threads = 
 sp8r_lds_bytes(dim / 128)) leaves on its CU: 163 840 B - its LDS, and 512 - 2 x its allocation registers per SIMD.  A block of w waves per SIMD
 (threads / 256, rounded up) at r registers (rounded up to 8) fits when w * r and its LDS are within that - and it has no scratch to speak of.
 
-usage: tools/step_footprint.py [--prescan-beside-scan 0|1] [--rows N] [--dim D] [--queries Q] [--top K] [--keep DIR]      (prints markdown)"""
+With --i8-sample-scan 1 (the default, as the option) the sample's bound comes from the int8 copy: scan_i8copy_sample_kernel<NQ> with NQ as
+scan_split.hip split_i8_sample_queries picks it, the picks and the sample's bound kernel; 0 lists the f32 pre-scan.
+
+usage: tools/step_footprint.py [--prescan-beside-scan 0|1] [--i8-sample-scan 0|1] [--rows N] [--dim D] [--queries Q] [--top K] [--keep DIR]      (prints markdown)"""
 import argparse
 import os
 import re
@@ -77,7 +80,20 @@ def step_kernels(a):
         ("preprocess", "cosine_preprocess_lds_kernel", r"cosine_preprocess_lds_kernelE", 256, dim * 16, "preprocess.hip launch_cosine_preprocess_f32"),
         ("pack", "pack_queries_kernel", r"pack_queries_kernelE", 64, 0, "preprocess.hip launch_pack_queries"),
     ]
-    if a.prescan_beside_scan and S <= 16384 and nq >= 16:
+    res_lds = (dim // 128) * (128 * 2 * 4) * 16 + 2 * 128 * 4        # scan_split.hip sp8r_lds_bytes
+    if a.i8_sample_scan:
+        S = S // 16 * 16
+        nch = dim // 128                                               # scan_split.hip split_i8_sample_queries
+        group = 16
+        for c in (32, 64):
+            if nch <= 8 and nch * (c // 16) * 2048 <= LDS_PER_CU - res_lds and c // 2 < nq:
+                group = c
+        rows += [
+            ("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_split.hip launch_split_i8_pack"),
+            ("sample scan", "scan_i8copy_sample_kernel<%d>" % group, r"scan_i8copy_sample_kernel" + targs(group), 256, nch * (group // 16) * 2048,
+             "scan_split.hip launch_scan_i8copy_sample"),
+        ]
+    elif a.prescan_beside_scan and S <= 16384 and nq >= 16:
         d = 6
         rows.append(("pre-scan", "scan_f32_mfma_kernel<16,1,%d,nt,4 waves,%s,ids,scores>" % (d, "fast" if fast else "generic"),
                      r"scan_f32_mfma_kernel" + targs(16, 1, d, True, 4, fast, False, True, 1), 256, (16 * q_stride + 256 + 15) & ~15,
@@ -92,11 +108,16 @@ def step_kernels(a):
                      "custom_query.hip launch_custom_topk"))
     else:
         rows.append(("top-k", "custom_topk_small_kernel", r"custom_topk_small_kernelE", 1024, S * 8, "custom_query.hip launch_custom_topk"))
-    res_lds = (dim // 128) * (128 * 2 * 4) * 16 + 2 * 128 * 4        # scan_split.hip sp8r_lds_bytes
+    if a.i8_sample_scan:
+        rows += [
+            ("sample picks", "sp_i8_picks_kernel", r"sp_i8_picks_kernelE", 64, 0, "scan_split.hip launch_split_i8_picks"),
+            ("sample bound", "sp_i8_sample_bound_kernel", r"sp_i8_sample_bound_kernelE", 64, 0, "scan_split.hip launch_split_i8_sample_bound"),
+        ]
     m16 = lambda nw, nt: (4 if nw == 4 else 7) * 16 * 1040 + nw * nt * 4 * 64 * 4 + 16 * 16 * 4      # scan_mfma16.hip M16Shape::LDS (two K-steps per stage)
     ks = dim // 128
+    if not a.i8_sample_scan:
+        rows.append(("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_split.hip launch_split_i8_pack"))
     rows += [
-        ("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_split.hip launch_split_i8_pack"),
         ("first scan", "scan_i8copy_kernel_res_dense<1>", r"scan_i8copy_kernel_res_denseILi1EE", 512, res_lds, "scan_split.hip launch_scan_i8copy"),
         ("second scan", "scan_i8copy_kernel_res<1>", r"scan_i8copy_kernel_resILi1EE", 512, res_lds, "scan_split.hip launch_scan_i8copy"),
         ("regroup", "sp_regroup_kernel", r"sp_regroup_kernelE", 256, 0, "scan_split.hip launch_split_regroup"),
@@ -118,6 +139,7 @@ def step_kernels(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prescan-beside-scan", type=int, default=1)
+    ap.add_argument("--i8-sample-scan", type=int, default=1)
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--queries", type=int, default=128)
@@ -133,8 +155,10 @@ def main():
         kernels.update(parse(t))
     rows, S = step_kernels(a)
 
-    def find(pattern):
+    def find(pattern, optional=False):
         hits = [(k, v) for k, v in kernels.items() if re.search(r"^_ZN3qmx\d+(?:%s)" % pattern, k)]
+        if not hits and optional:      # (a conditional fallback scan whose shape is not instantiated at this row length)
+            return None
         if len(hits) != 1:
             sys.exit("kernel pattern %r matches %d symbols: %s" % (pattern, len(hits), [k for k, _ in hits][:6]))
         return hits[0][1]
@@ -144,7 +168,7 @@ def main():
     scan_lds = max(s["lds"] for s in scans) + [r[4] for r in rows if r[0] == "second scan"][0]
     scan_regs = 2 * max(up(s["vgprs"] + s["agprs"], REG_UNIT) for s in scans)
     free_lds, free_regs = LDS_PER_CU - scan_lds, REGS_PER_SIMD - scan_regs
-    print("# Footprint of the headline step's kernels (prescan_beside_scan = %d)\n" % a.prescan_beside_scan)
+    print("# Footprint of the headline step's kernels (prescan_beside_scan = %d, i8_sample_scan = %d)\n" % (a.prescan_beside_scan, a.i8_sample_scan))
     print("%d rows x %d f32, %d queries, top %d; sample of %d rows.  Compiler remarks of gfx950 code (`tools/step_footprint.py`), no GPU involved.\n"
           % (a.rows, a.dim, a.queries, a.top, S))
     print("A resident scan block takes %d B of LDS and %d registers per SIMD (2 waves): beside it a CU has **%d B of LDS and %d registers per SIMD** left.\n"
@@ -152,7 +176,10 @@ def main():
     print("| step | kernel | threads | VGPRs (+AGPRs) | static LDS | dynamic LDS | scratch | fits beside a resident scan |")
     print("|---|---|---:|---:|---:|---:|---:|---|")
     for what, label, pattern, threads, dyn, where in rows:
-        k = find(pattern)
+        k = find(pattern, optional="conditional" in what)
+        if k is None:
+            print("| %s | `%s` (%s) | %d | - | - | %d | - | (no such instantiation in the build) |" % (what, label, where, threads, dyn))
+            continue
         regs = k["vgprs"] + k["agprs"]
         need_regs = (threads + 255) // 256 * up(regs, REG_UNIT)
         why = []
