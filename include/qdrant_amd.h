@@ -309,7 +309,13 @@ QMX_API uint32_t qmx_abi_version(void);
  * give the bound; 0: the exact f32 scores of rows 0, step', 2 step', ... with step' = n / S), "i8_sample_rows" (S of that sample; 0, the default: the rule
  * above), "prescan_beside_scan" (default 1: a prefilter's
  * sample pre-scan and the top-k behind it run as 256-thread blocks that fit on a CU beside a block of the resident int8 scan - the pre-scan at 384 or 768 coordinates -; 0: the former 512- / 1024-
- * thread shapes), "group_matrix_bytes", "debug"
+ * thread shapes), "fallback_beside_scan" (default 1: the conditional exact pass at the end of an int8-copy prefilter search - the queries whose candidate
+ * lists overflowed - is one launch of 16-query block rows plus one merge, in a block that starts on a CU beside a block of the int8 scan where it fits
+ * there: rows of up to 768 coordinates, not 1 024; 0, and where it does not fit: a 16-query pass and passes of 64, three launch pairs per 128 queries,
+ * which wait for a CU without a scan block.  A batch with more than 16 overflowed queries then streams the block once per 16 of them instead of once
+ * per 64: 10 M x 768 Student-t rows through a forced int8 copy, where all 128 queries of every batch overflow, take 39.9 ms per batch against 22.0
+ * with the former passes - a block the library's own choice of copy keeps away from the int8 copy; the headline step, where nothing overflows, is
+ * 1.4 - 1.5 % faster), "group_matrix_bytes", "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -
  * (qdrant_amd/csrc/common.hpp says what each selects; round 6 removed the experiments that had measured slower twice: their numbers stay under
  * profiles/).  Initial values come from the environment variables QMX_<NAME> read

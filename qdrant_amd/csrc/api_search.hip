@@ -250,6 +250,58 @@ static int32_t overflow_passes(const SearchCall &c, const SplitPlanLayout &pl, u
     return split_stage(q, "fallback (conditional)");
 }
 
+// The int8 route's form of the same that starts beside a running int8 scan (option fallback_beside_scan): the plan, ONE launch of the 16-query shape whose
+// block row g serves packed queries 16 g .. 16 g + 15 (launch_scan_f32_mfma16_groups), one merge over all packed slots.  With four batches in flight
+// another batch's scan holds every CU while these are dispatched; blocks of the passes above cannot start there, and on a search without overflow
+// they start only to find that out.
+// Does a block of that launch fit on a CU beside a block of this segment's int8 scan?  The numbers the launches use: the scan's LDS at this row length
+// plus the pass's against the CU's 160 KiB, the scan's two waves per SIMD plus the pass's one against 512 registers (the kernels' attributes).
+static int32_t fallback_groups_fit(const qmx_query *q, uint32_t top, bool *fit) {
+    const qmx_segment *s = q->seg;
+    *fit = false;
+    if (option(OPT_FALLBACK_BESIDE_SCAN) <= 0 || !mfma16_dim_ok(16, s->dim) || top > 64 || s->row_stride % 16 != 0) return QMX_OK;
+    const uint32_t ks = s->dim / 128, perq = q->has_filters ? 1 : 0, res = option(OPT_I8_RESIDENT) > 0 ? 1 : 0;
+    static std::atomic<int> known[2][2][17];      // 0: not asked yet, 1: fits, 2: does not ([resident scan][per-request filters][K-steps]: what picks the kernels)
+    int k = known[res][perq][ks].load(std::memory_order_relaxed);
+    if (k == 0) {
+        size_t scan_lds = 0, pass_lds = 0;
+        int scan_regs = 0, pass_regs = 0;
+        QMX_TRY(split_i8_scan_footprint(s->dim, &scan_lds, &scan_regs));
+        QMX_TRY(mfma16_groups_footprint(s->dim, perq != 0, &pass_lds, &pass_regs));
+        k = scan_lds + pass_lds <= (size_t)160 * 1024 && scan_regs + pass_regs <= 512 ? 1 : 2;
+        known[res][perq][ks].store(k, std::memory_order_relaxed);
+    }
+    *fit = k == 1;
+    return QMX_OK;
+}
+// (partial lists: grid.x <= 2 blocks per CU, by ceil(nq / 16) groups, of 16 x top keys - search_enqueue reserves them)
+static size_t overflow_groups_partial_bytes(const qmx_query *q, uint32_t top) {
+    return (size_t)q->seg->num_cus * 2 * ((q->nq + 15) / 16) * 16 * top * sizeof(uint64_t);
+}
+static int32_t overflow_groups_pass(const SearchCall &c, const SplitPlanLayout &pl, uint32_t nq) {
+    qmx_query *q = c.q;
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
+    uint64_t *gthr_packed = (uint64_t *)(plan + pl.gthr_packed);
+    if (q->has_filters) QMX_TRY(q->filter_of_packed.reserve((size_t)pl.list_cap * 4));
+    QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), nq, (const uint64_t *)q->gthr.p, ovf_list, gthr_packed, pl.list_cap,
+                              (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), pl.n_run64, (SplitStats *)plan, q->d_queries,
+                              q->q_stride, q->sp_fq.p, q->has_filters ? (const uint32_t *)q->filter_of.p : nullptr, (uint32_t *)q->filter_of_packed.p));
+    ScanArgs a = tile_args(c, 0, nq);      // (nq: the packed slots; the kernel's block rows take 16 of them each and read how many are filled)
+    a.queries = q->sp_fq.p;
+    if (q->has_filters) a.del.filter_of = (const uint32_t *)q->filter_of_packed.p;
+    a.partial = (uint64_t *)q->partial.p;
+    a.partial_qt = 16;
+    a.gthr = gthr_packed;
+    a.run_if = (const int *)(plan + pl.count);
+    QMX_REQUIRE(mfma16_scan_ok(16, SCAN_TOPK, a), QMX_ERR_OTHER, "split fallback shape");
+    uint32_t grid = (uint32_t)q->seg->num_cus * 2;      // (the cap the reservation was made for)
+    QMX_REQUIRE(nq <= q->nq && overflow_groups_partial_bytes(q, c.top) <= q->partial.cap, QMX_ERR_OTHER, "split fallback: partial lists");
+    QMX_TRY(launch_scan_f32_mfma16_groups(q->stream, a, q->seg->num_cus, &grid));
+    QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, 16, nq, c.top, c.d_out, c.d_counts, c.top, 0, nullptr, a.run_if, ovf_list, 0, true));
+    return split_stage(q, "fallback (conditional, one launch)");
+}
+
 // the PQ form of the same: the exact PQ kernel takes the overflowed queries through q_map, one launch over slabs of the block
 static int32_t pq_overflow_pass(const SearchCall &c, const SplitPlanLayout &pl) {
     qmx_query *q = c.q;
@@ -441,6 +493,7 @@ struct SplitTiles {
     VerifyPool vp{};
     uint64_t S = 0;                                         // rows of the sample
     bool i8_sample = false;                                 // the int8 route with option i8_sample_scan: the sample is tiles of the copy, scored there
+    bool ovf_groups = false;                                // the int8 route with option fallback_beside_scan, where it fits: overflow_groups_pass
     std::vector<std::pair<uint32_t, uint32_t>> tiles;       // (tile0, nq_tile) of the tiles that took the prefilter
     SplitTiles(uint32_t nq, uint32_t fqt) : pl(nq, fqt) {}
 };
@@ -601,10 +654,12 @@ static int32_t split_finish(const SearchCall &c, const SearchPlan &plan, const S
     // (split tiles are a prefix of the batch - the remainder tile, if any, comes last -: the sort walks queries 0 .. last)
     QMX_REQUIRE(first == 0, QMX_ERR_OTHER, "split tiles must start at query 0");
     QMX_TRY(verify_and_sort(c, sp.vp, last));
-    QMX_TRY(overflow_passes(c, sp.pl, last, plan.split_fqt, overflow_scan_f32, nullptr));      // (not counted: the tile's 8 / 13 are this route's launches)
+    // (not counted: the tile's 8 / 13 are this route's launches)
+    if (sp.ovf_groups) QMX_TRY(overflow_groups_pass(c, sp.pl, last));
+    else QMX_TRY(overflow_passes(c, sp.pl, last, plan.split_fqt, overflow_scan_f32, nullptr));
     q->last_split = true;
     q->last_pq = false;
-    q->last_fqt = plan.split_fqt;
+    q->last_fqt = sp.ovf_groups ? 16 : plan.split_fqt;      // (fold_split_counters: f overflowed queries stream the block ceil(f / 16) times in the one-launch form)
     return QMX_OK;
 }
 
@@ -668,6 +723,10 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
     if (plan.n_pass > 1) QMX_TRY(q->bounds.reserve((size_t)TQ * sizeof(uint64_t)));
     QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT_MAX) * sizeof(uint64_t)));
     SplitTiles sp(q->nq, plan.split_fqt);
+    if (plan.route == ROUTE_I8_COPY) {
+        QMX_TRY(fallback_groups_fit(q, top, &sp.ovf_groups));
+        if (sp.ovf_groups) QMX_TRY(q->partial.reserve(overflow_groups_partial_bytes(q, top)));      // (before the first launch that uses the buffer)
+    }
     if (plan.split()) QMX_TRY(split_begin(c, plan, sp));
     for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += TQ) {
         const uint32_t nq_tile = std::min<uint32_t>(TQ, q->nq - tile0);

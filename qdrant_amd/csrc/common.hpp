@@ -70,6 +70,12 @@ enum Option {
                               // coordinates only (tools/step_footprint.py: 192 registers, all there are): other lengths take 200 registers, 1 024 coordinates
                               // also 68 KiB of LDS, and their blocks wait as before - with the same results.  Not in the header, a setting of the parity tests only: 2 = as 1,
                               // and every top-k of a short score row (the custom queries') takes the 256-thread kernel, with scores of the test's choosing
+    OPT_FALLBACK_BESIDE_SCAN, // 1 (default): the conditional exact pass at the end of an int8-copy prefilter search (the queries whose lists overflowed) is ONE launch of
+                              // the 16-query chain-major scan with a three-stage ring (scan_mfma16.hip launch_scan_f32_mfma16_groups: 55 040 B of LDS, one wave
+                              // per SIMD; block row g serves packed queries 16 g ..) and one merge, where a block of it fits on a CU beside a block of the
+                              // int8 scan (api_search.hip fallback_groups_fit: 768 coordinates yes, 1 024 no); 0, and where it does not fit: a 16-query pass and
+                              // passes of 64, three launch pairs per 128 queries, whose blocks wait for a CU without a scan block even to find that nothing
+                              // overflowed.  The same lists; a batch with more than 16 overflowed queries streams the block once per 16 of them, not per 64
     OPT_GROUP_MATRIX_BYTES,   // qmx_group_search: byte budget of the fallback's score matrix, which tiles the unfinished queries (0 = 1 GiB)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT

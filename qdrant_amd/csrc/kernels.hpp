@@ -329,6 +329,10 @@ int32_t launch_sq_internal_query(hipStream_t st, const void *codes, const float 
 bool mfma16_dim_ok(int qt, uint32_t dim);
 bool mfma16_scan_ok(int qt, ScanMode mode, const ScanArgs &a);   // qt = 16, 32 or 64
 int32_t launch_scan_f32_mfma16(hipStream_t st, int qt, const ScanArgs &a, int num_cus, uint32_t *grid_out);
+// ... the conditional exact pass behind the int8 prefilter in one launch of 16-query block rows, in a block that fits beside a resident int8 scan block
+// (option fallback_beside_scan), and what such a block needs of a CU
+int32_t launch_scan_f32_mfma16_groups(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out);
+int32_t mfma16_groups_footprint(uint32_t dim, bool perq, size_t *lds_bytes, int *regs_per_simd);
 // f32 dot / cosine, 65..128 queries per pass: f16-split matrix-core prefilter + exact verification (scan_split.hip)
 bool split_scan_ok(const ScanArgs &a);
 size_t split_query_bytes(uint32_t dim);
@@ -392,6 +396,7 @@ int32_t launch_split_i8_pack(hipStream_t st, const float *d_q, uint32_t nq, uint
                              float row_norm_max, void *d_bq, float *d_qscale, float *d_band, float *d_thr, float *d_t_exact, uint32_t *d_cand_cnt, uint32_t n_cnt);
 int32_t launch_scan_i8copy(hipStream_t st, const ScanArgs &a, const void *d_bq, const float *d_qscale, const float *d_thr, int num_cus, const void *d_rows_i8,
                            void *d_wlists, uint32_t phase);
+int32_t split_i8_scan_footprint(uint32_t dim, size_t *lds_bytes, int *regs_per_simd);      // what a block of that scan holds of its CU (registers: its two waves per SIMD)
 int32_t launch_split_i8_probe(hipStream_t st, const uint64_t *d_cand, const uint32_t *d_cand_cnt, uint32_t cap, const float *d_band, uint32_t nq, uint32_t top,
                               const int *d_tile_overflow, uint32_t *d_probe_ids, uint32_t *d_probe_cnt);
 int32_t launch_split_i8_bound(hipStream_t st, const float *d_scores, uint32_t *d_probe_cnt, uint32_t nq, uint32_t top, const float *d_band, const float *d_qscale,
@@ -466,7 +471,8 @@ int32_t launch_pack_queries(hipStream_t st, int dtype, int distance, const void 
 int32_t launch_merge_keys(hipStream_t st, const uint64_t *partial, uint32_t n_lists,
                           uint32_t qt_stride, uint32_t nq, uint32_t top, qmx_scored_point *out,
                           uint32_t *out_counts, uint32_t out_stride = 0, uint32_t out_offset = 0,
-                          uint64_t *next_bound = nullptr, const int *run_if = nullptr, const uint32_t *out_map = nullptr, uint32_t shared_grid = 0);
+                          uint64_t *next_bound = nullptr, const int *run_if = nullptr, const uint32_t *out_map = nullptr, uint32_t shared_grid = 0,
+                          bool grouped = false);   // grouped: the lists of launch_scan_f32_mfma16_groups - list q of *run_if is column q % 16 of group q / 16's n_lists lists
 int32_t launch_merge_points(hipStream_t st, const qmx_scored_point *lists, const uint32_t *list_counts,
                             const uint32_t *list_idx_base, uint32_t n_lists, uint32_t nq, uint32_t k, qmx_scored_point *out,
                             uint32_t *out_counts, uint64_t list_stride = 0, uint64_t count_stride = 0);   // strides in entries / words between lists (0 = contiguous arrays)

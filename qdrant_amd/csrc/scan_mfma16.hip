@@ -87,14 +87,16 @@ __device__ __forceinline__ bool live_uniform(const DeletedView &d, uint32_t id, 
     return !vdel && !pdel && ok;
 }
 
-template <int NW, int NT, int KPS /* 512-byte K-steps of a row per ring stage: 2, or 1 when the row has an odd number of them */>
+template <int NW, int NT, int KPS /* 512-byte K-steps of a row per ring stage: 2, or 1 when the row has an odd number of them */,
+          int RING = 0 /* ring depth in 16-row x 1 KiB stages; 0: 4 for 4 waves (two blocks share the CU's 160 KiB), 7 for 8 */>
 struct M16Shape {
     static constexpr int QT = 16 * NT;
     static constexpr int JW = 8 / NW;                  // SIMD lanes j per wave (2: j = w, w + 4;  1: j = w)
     static constexpr int CW = 4 * JW;                  // chains per wave: ci = r * JW + jj  ->  chain 8 r + w + 4 jj
     static constexpr int RPW = 16 / NW;                // rows of a stage fetched per wave
     static constexpr int STAGE = KPS == 2 ? M16_STAGE : M16_STAGE / 2;   // 16 rows x 1 KiB (pitch 1040) or 8 row pairs x (2 x 512 B) (pitch 1040)
-    static constexpr int NBUF = (NW == 4 ? 4 : 7) * (KPS == 2 ? 1 : 2);   // ring stages (4 waves: two blocks share the CU's 160 KiB)
+    static constexpr int NBUF = (RING ? RING : NW == 4 ? 4 : 7) * (KPS == 2 ? 1 : 2);   // ring stages (half stages with one K-step per stage)
+    static_assert(NBUF >= 3, "the stage loop keeps one stage in registers, one landing and at least one in flight");
     static constexpr int XCH = NW * NT * 4 * 64 * 4;   // fold exchange: [wave][query tile][reg][lane] f32
     static constexpr int IDR = 16 * 16 * 4;            // candidate ids of the last 16 tiles [tile iteration & 15][row] (id-list scans)
     static constexpr int LDS = NBUF * STAGE + XCH + IDR;
@@ -106,12 +108,28 @@ struct M16Shape {
 template <int KSTEPS /* dim / 128: 512-byte K-steps per row */, int NW, int NT, int DBG = 0 /* tuning experiments (QMX_M16_DBG): 2 no row loads, 3 no fold / selection */,
           bool LAG = (NW == 8 && NT == 4 && KSTEPS == 6) /* half of the waves run one stage behind the others, see `lag` */,
           bool IDS = false /* candidates = a.ids[0 .. n_cand) instead of rows 0 .. n_cand) (payload-filtered scans, peek_top_iter) */,
+          int RING = 0 /* M16Shape's ring depth (0: the shape's own) */,
+          bool GROUPS = false /* the conditional exact pass behind the int8 prefilter in ONE launch (option fallback_beside_scan): block row blockIdx.y serves
+                                 packed queries 16 y .. 16 y + 15 and returns at once when *a.run_if - the number of packed queries - is not above 16 y */,
           bool PERQ = false /* the batch carries per-request filters (qmx_query_set_filters): the liveness test picks the candidate's query's bitmap */>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void scan_f32_mfma16_kernel(const ScanArgs a) {
-    if (a.run_if && *a.run_if == 0) return;           // the exact pass behind the split prefilter was not needed (scan_split.hip)
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void scan_f32_mfma16_kernel(const ScanArgs a_launch) {
+    ScanArgs a = a_launch;
+    if constexpr (GROUPS) {
+        // (before any LDS access or row load: on the headline every block of this launch ends here)
+        static_assert(NT == 1, "a block row serves one 16-query tile");
+        const uint32_t q0 = 16u * blockIdx.y;
+        if (q0 >= (uint32_t)*a.run_if) return;
+        a.queries = reinterpret_cast<const char *>(a.queries) + (size_t)q0 * a.q_stride;
+        a.gthr += q0;
+        if constexpr (PERQ) a.del.filter_of += q0;
+        a.partial += (uint64_t)blockIdx.y * gridDim.x * 16u * a.top;
+        a.nq = a.nq - q0 < 16u ? a.nq - q0 : 16u;
+    } else {
+        if (a.run_if && *a.run_if == 0) return;       // the exact pass behind the split prefilter was not needed (scan_split.hip)
+    }
     constexpr int KPS = KSTEPS % 2 == 0 ? 2 : 1;      // K-steps per ring stage
     constexpr int KS = KSTEPS / KPS;                  // stages per 16-row tile
-    typedef M16Shape<NW, NT, KPS> S;
+    typedef M16Shape<NW, NT, KPS, RING> S;
     constexpr int QT = S::QT, JW = S::JW, CW = S::CW, RPW = S::RPW, NBUF = S::NBUF, PW = S::PW;
     constexpr int M16_STAGE_B = S::STAGE;
     static_assert(!LAG || KPS == 2, "the lagging-wave schedule is written for two-step stages");
@@ -468,13 +486,13 @@ static int32_t launch_m16(hipStream_t st, const ScanArgs &a, int num_cus, uint32
         }
     }
     typedef M16Shape<NW, NT, (KSTEPS % 2 == 0 ? 2 : 1)> S;
-    auto kfn = a.del.filter_of ? scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, true> : scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, false>;
+    auto kfn = a.del.filter_of ? scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, 0, false, true> : scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, 0, false, false>;
     static thread_local DeviceOnce attr_once;
     if (attr_once.need()) {
-        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
-        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, 0, false, false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_f32_mfma16_kernel<KSTEPS, NW, NT, DBG, LAG, IDS, 0, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_once.mark();
     }
     const uint64_t n_tiles = (a.n_cand + 15) / 16;
@@ -550,6 +568,62 @@ int32_t launch_scan_f32_mfma16(hipStream_t st, int qt, const ScanArgs &a, int nu
     }
     set_error("mfma16 scan: unsupported shape");
     return QMX_ERR_BAD_ARG;
+}
+
+// ---- The conditional exact pass behind the int8 prefilter as ONE launch that starts beside a resident int8 scan block (option fallback_beside_scan).
+// The 16-query shape with a ring of three stages: 3 x 16 640 + 4 096 + 1 024 = 55 040 B of LDS (six half stages for rows of an odd number of K-steps: the
+// same), 4 waves = one per SIMD.  grid.y = the 16-query groups of the batch; a block row whose group holds no overflowed query returns at the top of the
+// kernel, which on a search without overflow is every block.  Per (row, query) the instructions of the 16-query pass, so its bits; a batch in which
+// more than 16 queries overflow streams the block once per 16 of them, where the 64-query passes streamed it once per 64.
+constexpr int M16_GROUPS_RING = 3;
+typedef void (*M16Kernel)(const ScanArgs);
+template <int K0, int K1>
+static M16Kernel m16_groups_kernel(int ksteps, bool perq) {
+    if constexpr (K0 <= K1) {
+        if constexpr (!(K0 > 12 && K0 % 2 == 1)) {
+            if (ksteps == K0)
+                return perq ? scan_f32_mfma16_kernel<K0, 4, 1, 0, false, false, M16_GROUPS_RING, true, true>
+                            : scan_f32_mfma16_kernel<K0, 4, 1, 0, false, false, M16_GROUPS_RING, true, false>;
+        }
+        return m16_groups_kernel<K0 + 1, K1>(ksteps, perq);
+    } else {
+        return nullptr;
+    }
+}
+
+// what a block of that launch needs of a CU: LDS (static + dynamic) and registers per SIMD (one wave per SIMD; allocated in units of 8)
+int32_t mfma16_groups_footprint(uint32_t dim, bool perq, size_t *lds_bytes, int *regs_per_simd) {
+    const M16Kernel kfn = mfma16_dim_ok(16, dim) ? m16_groups_kernel<1, 16>((int)(dim / 128), perq) : nullptr;
+    QMX_REQUIRE(kfn != nullptr, QMX_ERR_BAD_ARG, "mfma16 scan: no 16-query shape for rows of %u coordinates", dim);
+    hipFuncAttributes fa;
+    QMX_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn)));
+    *lds_bytes = (size_t)M16Shape<4, 1, 2, M16_GROUPS_RING>::LDS + fa.sharedSizeBytes;
+    *regs_per_simd = (fa.numRegs + 7) / 8 * 8;
+    return QMX_OK;
+}
+
+// a.nq queries packed in a.queries (a.gthr, a.del.filter_of packed with them), *a.run_if = how many of them are to be scanned; a.partial: grid x n_groups
+// lists of 16 x top keys (group-major).  *grid_out: in: the cap on grid.x, out: grid.x.  The caller checked mfma16_scan_ok(16, SCAN_TOPK, a).
+int32_t launch_scan_f32_mfma16_groups(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out) {
+    typedef M16Shape<4, 1, 2, M16_GROUPS_RING> S;
+    static_assert(S::LDS == M16Shape<4, 1, 1, M16_GROUPS_RING>::LDS && S::LDS == 55040, "three stages or six half stages");
+    QMX_REQUIRE(a.run_if && a.gthr && a.partial && !a.ids && !a.key_bound && a.nq >= 1 && grid_out, QMX_ERR_BAD_ARG, "mfma16 groups: a packed conditional pass");
+    const bool perq = a.del.filter_of != nullptr;
+    const M16Kernel kfn = m16_groups_kernel<1, 16>((int)(a.nseg / 4), perq);
+    QMX_REQUIRE(kfn != nullptr, QMX_ERR_BAD_ARG, "mfma16 scan: unsupported row length");
+    const uint64_t n_tiles = (a.n_cand + 15) / 16;
+    int per_cu = 0;
+    QMX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, (size_t)S::LDS));
+    if (per_cu < 1) per_cu = 1;
+    const uint64_t cap = (uint64_t)num_cus * per_cu;
+    uint32_t grid = (uint32_t)(n_tiles < cap ? n_tiles : cap);
+    if (grid < 1) grid = 1;
+    if (*grid_out && grid > *grid_out) grid = *grid_out;
+    *grid_out = grid;
+    ::qmx::clear_stale_error();
+    hipLaunchKernelGGL(kfn, dim3(grid, (a.nq + 15) / 16), dim3(256), (size_t)S::LDS, st, a);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
 }
 
 }  // namespace qmx

@@ -2330,6 +2330,18 @@ uint32_t split_i8_sample_queries(uint32_t dim, uint32_t nq) {
         if ((size_t)nch * (c / 16) * 2048 <= free_lds && c / 2 < nq) pick = c;
     return pick;
 }
+// what a block of the int8 scan launch_scan_i8copy picks for this row length holds of its CU: LDS (static + dynamic) and registers per SIMD (512 threads: two
+// waves per SIMD, registers allocated in units of 8).  What another launch must fit into to start beside it: 160 KiB and 512 registers less these.
+int32_t split_i8_scan_footprint(uint32_t dim, size_t *lds_bytes, int *regs_per_simd) {
+    const uint32_t nch = dim / 128;
+    const bool resident = option(OPT_I8_RESIDENT) > 0 && nch <= SP8R_MAX_NCH;
+    void (*kfn)(const ScanArgs, const SplitArgs) = resident ? scan_i8copy_kernel_res<1> : scan_i8copy_kernel;
+    hipFuncAttributes fa;
+    QMX_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn)));
+    *lds_bytes = (resident ? sp8r_lds_bytes(nch) : (size_t)SP8_LDS) + fa.sharedSizeBytes;
+    *regs_per_simd = SP3_THREADS / 256 * ((fa.numRegs + 7) / 8 * 8);
+    return QMX_OK;
+}
 // the approximate scores of the sample's tiles (d_sample: their 16 n_tiles row ids, tile after tile) for the nq queries packed in d_bq -> d_scores [nq][16 n_tiles]
 int32_t launch_scan_i8copy_sample(hipStream_t st, const void *d_rows_i8, const void *d_bq, uint32_t dim, const uint32_t *d_sample, uint32_t n_tiles, uint32_t nq,
                                   const float *d_qscale, float *d_scores) {

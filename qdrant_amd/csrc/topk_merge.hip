@@ -50,9 +50,17 @@ __global__ __launch_bounds__(MERGE_BLOCK) void merge_keys_kernel(const uint64_t 
                                                                  uint32_t qt_stride, uint32_t top,
                                                                  qmx_scored_point *out, uint32_t *out_counts, uint32_t out_stride,
                                                                  uint32_t out_offset, uint64_t *next_bound, const int *run_if, const uint32_t *out_map,
-                                                                 uint32_t shared_grid) {
+                                                                 uint32_t shared_grid, uint32_t grouped) {
     if (run_if && *run_if == 0) return;      // the exact pass behind the split prefilter was not needed (scan_split.hip)
     const uint32_t q = blockIdx.x;
+    uint32_t col = q;                        // the query's place inside a list
+    if (grouped) {      // the one-launch conditional pass (scan_mfma16.hip launch_scan_f32_mfma16_groups): *run_if packed queries, the n_lists lists of
+                        // packed queries 16 g .. 16 g + 15 stand together, group after group
+        if (q >= (uint32_t)*run_if) return;
+        partial += (uint64_t)(q / 16) * n_lists * 16 * top;
+        col = q & 15;
+        qt_stride = 16;
+    }
     if (shared_grid) {      // pq_scan_kernel's packed pass: its `shared_grid` blocks were divided among the *run_if listed queries (pq.hip)
         const uint32_t cnt = (uint32_t)*run_if, nq_eff = cnt < gridDim.x ? cnt : gridDim.x;
         n_lists = shared_grid / nq_eff;
@@ -64,7 +72,7 @@ __global__ __launch_bounds__(MERGE_BLOCK) void merge_keys_kernel(const uint64_t 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint64_t list = 0;
     for (uint32_t l = wave; l < n_lists; l += MERGE_NW) {
-        const uint64_t key = lane < (int)top ? partial[((uint64_t)l * qt_stride + q) * top + lane] : 0;
+        const uint64_t key = lane < (int)top ? partial[((uint64_t)l * qt_stride + col) * top + lane] : 0;
         wave_offer(list, key, (int)top, lane);
     }
     const uint64_t nb = block_finish(list, (int)top, oq, out, out_stride, out_offset, out_counts);
@@ -151,12 +159,12 @@ __global__ __launch_bounds__(MERGE_BLOCK) void sort_scored_kernel(const float *s
 
 int32_t launch_merge_keys(hipStream_t st, const uint64_t *partial, uint32_t n_lists, uint32_t qt_stride,
                           uint32_t nq, uint32_t top, qmx_scored_point *out, uint32_t *out_counts, uint32_t out_stride,
-                          uint32_t out_offset, uint64_t *next_bound, const int *run_if, const uint32_t *out_map, uint32_t shared_grid) {
+                          uint32_t out_offset, uint64_t *next_bound, const int *run_if, const uint32_t *out_map, uint32_t shared_grid, bool grouped) {
     if (nq == 0) return QMX_OK;
     if (out_stride == 0) out_stride = top;
     ::qmx::clear_stale_error();
     hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(MERGE_BLOCK), 0, st, partial, n_lists, qt_stride, top, out, out_counts,
-                       out_stride, out_offset, next_bound, run_if, out_map, shared_grid);
+                       out_stride, out_offset, next_bound, run_if, out_map, shared_grid, grouped ? 1u : 0u);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }

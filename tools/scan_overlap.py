@@ -6,22 +6,96 @@ Prints, over the middle half of the trace's second-launch scans (the timed regio
   * the time per step in which NO scan_i8copy_kernel_res* dispatch is open (the union of the scans' intervals taken out of the window);
   * per sample pre-scan (scan_f32_mfma_kernel), sample scan over the int8 copy (scan_i8copy_sample_kernel, option i8_sample_scan) and sample top-k (custom_topk_*) dispatch: whether its interval lies inside one scan's, overlaps one
     partly, or meets none, and its mean duration (the trace has start and end times only: how long a dispatch waited for a CU is not in it);
-  * the mean duration of the first and second scan launches.
+  * the mean duration of the first and second scan launches;
+  * the conditional exact passes at the end of a search (scan_f32_mfma16_kernel, merge_keys_kernel; option fallback_beside_scan): per kernel the
+    interval from dispatch to end - a dispatch's interval opens when its packet is taken up, so a block that waits for room on a CU shows as a long
+    interval of a kernel that does nothing - and how many of those intervals end within END_SLACK_US after the end of a scan: a dispatch that
+    waited for a hand-over between two scans;
+  * per lane (the trace's stream, or queue where it has no stream column): the time between the end of the lane's second scan launch and the
+    dispatch of the first kernel of the lane's next step (the first dispatch behind the step's last tail kernel), and what share of it the
+    conditional passes' intervals cover.
 usage: tools/scan_overlap.py <kernel_trace.csv>"""
+import bisect
 import csv
 import sys
+
+END_SLACK_US = 5.0
+LONG_US = 100.0      # a conditional pass that does nothing ends within microseconds of getting a CU: a longer interval is a wait
+# what follows the second scan launch in a step's chain; the next step starts with the first dispatch of the lane that is none of these
+TAIL = ("sp_regroup_kernel", "sp_i8_probe_kernel", "pair_kernel", "sp_i8_bound_kernel", "sp_select_kernel", "sort_scored_kernel", "sp_plan_kernel",
+        "scan_f32_mfma16_kernel", "merge_keys_kernel")
+
+
+def lane_key(rows):
+    """the column that tells the batches in flight apart: the stream where the trace has one with several values, else the queue"""
+    for col in ("Stream_Id", "Queue_Id"):
+        if rows and col in rows[0] and len({r[col] for r in rows}) > 1:
+            return col
+    return None
+
+
+def stats_us(xs):
+    xs = sorted(xs)
+    if not xs:
+        return "none"
+    return "mean %.1f us, median %.1f, min %.1f, max %.1f" % (sum(xs) / len(xs) / 1e3, xs[len(xs) // 2] / 1e3, xs[0] / 1e3, xs[-1] / 1e3)
+
+
+def fallback_report(rows, scans, second, w0, w1, steps):
+    scan_ends = sorted(b for _, b in scans)
+    slack = int(END_SLACK_US * 1000)
+    for what in ("scan_f32_mfma16_kernel", "merge_keys_kernel"):
+        items = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if what in r["Kernel_Name"]]
+        items = [x for x in items if x[0] >= w0 and x[1] <= w1]
+        at_end = 0
+        for _, t1 in items:
+            i = bisect.bisect_right(scan_ends, t1) - 1          # the last scan end at or before this dispatch's end
+            if i >= 0 and t1 - scan_ends[i] <= slack:
+                at_end += 1
+        durs = [t1 - t0 for t0, t1 in items]
+        long_ones = sum(1 for d in durs if d > LONG_US * 1000)
+        print("%s: %d dispatches (%.1f per step), dispatch to end %s; %d longer than %.0f us (%.2f per step); %d (%.0f %%) end within %.0f us after a "
+              "scan's end; %.4f ms per step in all"
+              % (what, len(items), len(items) / steps, stats_us(durs), long_ones, LONG_US, long_ones / steps, at_end, 100.0 * at_end / max(len(items), 1),
+                 END_SLACK_US, sum(durs) / steps / 1e6))
+    col = lane_key(rows)
+    if col is None:
+        print("lane wait: the trace tells no lanes apart (one stream, one queue)")
+        return
+    lanes = {}
+    for r in rows:
+        lanes.setdefault(r[col], []).append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
+    second_set = set(second)
+    waits, cond_share = [], []
+    for items in lanes.values():
+        items.sort()
+        for i, (t0, t1, name) in enumerate(items):
+            if (t0, t1) not in second_set or "scan_i8copy_kernel" not in name or t0 < w0 or t1 > w1:
+                continue
+            cond = 0
+            for u0, u1, nm in items[i + 1:]:
+                if not any(k in nm for k in TAIL):
+                    waits.append(u0 - t1)
+                    cond_share.append(cond)
+                    break
+                if "scan_f32_mfma16_kernel" in nm or "merge_keys_kernel" in nm:
+                    cond += u1 - u0
+    print("lane wait (%s, %d lanes): from the end of a lane's second scan launch to the dispatch of its next step's first kernel: %d steps, %s; "
+          "of it inside the conditional passes' intervals: %s"
+          % (col, len(lanes), len(waits), stats_us(waits), stats_us(cond_share)))
 
 
 def main():
     scans, small = [], {"pre-scan": [], "sample scan": [], "top-k": []}
-    for r in csv.DictReader(open(sys.argv[1])):
+    rows = list(csv.DictReader(open(sys.argv[1])))
+    for r in rows:
         name, t0, t1 = r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])
-        if "scan_i8copy_kernel" in name:
+        if "scan_i8copy_sample_kernel" in name:
+            small["sample scan"].append((t0, t1, name))
+        elif "scan_i8copy_kernel" in name:
             scans.append((t0, t1, "res_dense" in name))
         elif "scan_f32_mfma_kernel" in name:
             small["pre-scan"].append((t0, t1, name))
-        elif "scan_i8copy_sample_kernel" in name:
-            small["sample scan"].append((t0, t1, name))
         elif "custom_topk_" in name:
             small["top-k"].append((t0, t1, name))
     # which launch: the first one has a kernel of its own (option i8_dense_epilogue); without it the strided sixteenth is the one under 0.3 ms
@@ -72,6 +146,7 @@ def main():
               "%.0f %% of their time beside a scan\n    %s"
               % (what, len(items), round(len(items) / steps), sum(durs) / max(len(durs), 1) / 1e3, min(durs, default=0) / 1e3, max(durs, default=0) / 1e3,
                  full, part, none, 100.0 * beside_ns / max(sum(durs), 1), "; ".join(names)))
+    fallback_report(rows, scans, second, w0, w1, steps)
     return 0
 
 

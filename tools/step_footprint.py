@@ -13,7 +13,11 @@ sp8r_lds_bytes(dim / 128)) leaves on its CU: 163 840 B - its LDS, and 512 - 2 x 
 With --i8-sample-scan 1 (the default, as the option) the sample's bound comes from the int8 copy: scan_i8copy_sample_kernel<NQ> with NQ as
 scan_split.hip split_i8_sample_queries picks it, the picks and the sample's bound kernel; 0 lists the f32 pre-scan.
 
-usage: tools/step_footprint.py [--prescan-beside-scan 0|1] [--i8-sample-scan 0|1] [--rows N] [--dim D] [--queries Q] [--top K] [--keep DIR]      (prints markdown)"""
+With --fallback-beside-scan 1 (the default, as the option) the conditional exact pass at the end of the step is the one-launch form of
+scan_mfma16.hip launch_scan_f32_mfma16_groups where its LDS fits beside the scan's (api_search.hip fallback_groups_fit); 0, and where it does not
+fit, lists the 16-query pass and the 64- (32-) query passes.  The closing line says whether every launch of a step without overflow fits.
+
+usage: tools/step_footprint.py [--prescan-beside-scan 0|1] [--i8-sample-scan 0|1] [--fallback-beside-scan 0|1] [--rows N] [--dim D] [--queries Q] [--top K] [--keep DIR]      (prints markdown)"""
 import argparse
 import os
 import re
@@ -113,8 +117,13 @@ def step_kernels(a):
             ("sample picks", "sp_i8_picks_kernel", r"sp_i8_picks_kernelE", 64, 0, "scan_split.hip launch_split_i8_picks"),
             ("sample bound", "sp_i8_sample_bound_kernel", r"sp_i8_sample_bound_kernelE", 64, 0, "scan_split.hip launch_split_i8_sample_bound"),
         ]
-    m16 = lambda nw, nt: (4 if nw == 4 else 7) * 16 * 1040 + nw * nt * 4 * 64 * 4 + 16 * 16 * 4      # scan_mfma16.hip M16Shape::LDS (two K-steps per stage)
+    # scan_mfma16.hip M16Shape::LDS (ring stages of 16 rows x 1 KiB at pitch 1040; the half stages of odd row lengths come to the same)
+    m16 = lambda nw, nt, ring=0: (ring or (4 if nw == 4 else 7)) * 16 * 1040 + nw * nt * 4 * 64 * 4 + 16 * 16 * 4
     ks = dim // 128
+    fqt = 64 if ks <= 6 else 32                                        # api_internal.hpp split_fallback_qt
+    # option fallback_beside_scan: the one-launch form where a block of it fits beside the scan (api_search.hip fallback_groups_fit decides from the
+    # kernels' attributes; here: the LDS, which is what rules it out at 1 024 coordinates - the table's last column shows the registers)
+    groups = a.fallback_beside_scan and m16(4, 1, 3) + res_lds <= LDS_PER_CU
     if not a.i8_sample_scan:
         rows.append(("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_split.hip launch_split_i8_pack"))
     rows += [
@@ -127,12 +136,22 @@ def step_kernels(a):
         ("select", "sp_select_kernel", r"sp_select_kernelE", 512, 0, "scan_split.hip launch_split_select"),
         ("sort", "sort_scored_kernel", r"sort_scored_kernelE", 256, 0, "topk_merge.hip launch_sort_scored"),
         ("plan", "sp_plan_kernel", r"sp_plan_kernelE", 256, 0, "scan_split.hip launch_split_plan"),
-        ("fallback scan, 16 queries (conditional)", "scan_f32_mfma16_kernel<%d,4 waves,1 tile>" % ks,
-         r"scan_f32_mfma16_kernel" + targs(ks, 4, 1, 0, False, False, False), 256, m16(4, 1), "scan_mfma16.hip launch_m16"),
-        ("fallback scans, 64 queries (conditional, two)", "scan_f32_mfma16_kernel<%d,8 waves,4 tiles>" % ks,
-         r"scan_f32_mfma16_kernel" + targs(ks, 8, 4, 0, ks == 6, False, False), 512, m16(8, 4), "scan_mfma16.hip launch_m16"),
-        ("fallback merges (conditional)", "merge_keys_kernel", r"merge_keys_kernelE", 256, 0, "topk_merge.hip launch_merge_keys"),
     ]
+    if groups:
+        rows += [
+            ("fallback scan, block rows of 16 queries (conditional)", "scan_f32_mfma16_kernel<%d,4 waves,1 tile,ring 3,groups>" % ks,
+             r"scan_f32_mfma16_kernel" + targs(ks, 4, 1, 0, False, False, 3, True, False), 256, m16(4, 1, 3), "scan_mfma16.hip launch_scan_f32_mfma16_groups"),
+            ("fallback merge (conditional)", "merge_keys_kernel", r"merge_keys_kernelE", 256, 0, "topk_merge.hip launch_merge_keys"),
+        ]
+    else:
+        nw, nt = (8, 4) if fqt == 64 else (8, 2)                       # scan_mfma16.hip launch_scan_f32_mfma16: 64 queries, or 32 at more than 6 K-steps
+        rows += [
+            ("fallback scan, 16 queries (conditional)", "scan_f32_mfma16_kernel<%d,4 waves,1 tile>" % ks,
+             r"scan_f32_mfma16_kernel" + targs(ks, 4, 1, 0, False, False, 0, False, False), 256, m16(4, 1), "scan_mfma16.hip launch_m16"),
+            ("fallback scans, %d queries (conditional, %d)" % (fqt, (nq + fqt - 1) // fqt), "scan_f32_mfma16_kernel<%d,%d waves,%d tiles>" % (ks, nw, nt),
+             r"scan_f32_mfma16_kernel" + targs(ks, nw, nt, 0, (nw, nt, ks) == (8, 4, 6), False, 0, False, False), 512, m16(nw, nt), "scan_mfma16.hip launch_m16"),
+            ("fallback merges (conditional)", "merge_keys_kernel", r"merge_keys_kernelE", 256, 0, "topk_merge.hip launch_merge_keys"),
+        ]
     return rows, S
 
 
@@ -140,6 +159,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prescan-beside-scan", type=int, default=1)
     ap.add_argument("--i8-sample-scan", type=int, default=1)
+    ap.add_argument("--fallback-beside-scan", type=int, default=1)
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--queries", type=int, default=128)
@@ -168,13 +188,15 @@ def main():
     scan_lds = max(s["lds"] for s in scans) + [r[4] for r in rows if r[0] == "second scan"][0]
     scan_regs = 2 * max(up(s["vgprs"] + s["agprs"], REG_UNIT) for s in scans)
     free_lds, free_regs = LDS_PER_CU - scan_lds, REGS_PER_SIMD - scan_regs
-    print("# Footprint of the headline step's kernels (prescan_beside_scan = %d, i8_sample_scan = %d)\n" % (a.prescan_beside_scan, a.i8_sample_scan))
+    print("# Footprint of the headline step's kernels (prescan_beside_scan = %d, i8_sample_scan = %d, fallback_beside_scan = %d)\n"
+          % (a.prescan_beside_scan, a.i8_sample_scan, a.fallback_beside_scan))
     print("%d rows x %d f32, %d queries, top %d; sample of %d rows.  Compiler remarks of gfx950 code (`tools/step_footprint.py`), no GPU involved.\n"
           % (a.rows, a.dim, a.queries, a.top, S))
     print("A resident scan block takes %d B of LDS and %d registers per SIMD (2 waves): beside it a CU has **%d B of LDS and %d registers per SIMD** left.\n"
           % (scan_lds, scan_regs, free_lds, free_regs))
     print("| step | kernel | threads | VGPRs (+AGPRs) | static LDS | dynamic LDS | scratch | fits beside a resident scan |")
     print("|---|---|---:|---:|---:|---:|---:|---|")
+    misfits = []
     for what, label, pattern, threads, dyn, where in rows:
         k = find(pattern, optional="conditional" in what)
         if k is None:
@@ -192,7 +214,15 @@ def main():
         fits = "yes" if not why else "no (%s)" % ", ".join(why)
         if what in ("first scan", "second scan"):
             fits = "(the scan)"
+        elif why:
+            misfits.append(what)
         print("| %s | `%s` (%s) | %d | %d | %d | %d | %d | %s |" % (what, label, where, threads, regs, k["lds"], dyn, k["scratch"], fits))
+    # (the conditional launches are part of every step: they are enqueued whether or not a query overflowed)
+    if misfits:
+        print("\n**%d coordinates: NOT every launch of a step without overflow fits beside a resident scan block** - these wait for a CU without one: %s."
+              % (a.dim, "; ".join(misfits)))
+    else:
+        print("\n**%d coordinates: every launch of a step without overflow fits beside a resident scan block.**" % a.dim)
 
 
 if __name__ == "__main__":
