@@ -281,7 +281,7 @@ static int32_t segment_sq_stats(qmx_segment *s) {
     if (s->dtype != QMX_DTYPE_SQ_U8 || s->n < (1u << 18) || !s->d_row_offsets || !sq_mfma_ok(s->distance, s->scan_dim) || !(s->sq.multiplier > 0.f) ||
         s->scan_dim % 64 != 0)
         return QMX_OK;
-    if (hipMalloc((void **)&s->d_sq_bi, (size_t)s->n * sizeof(int32_t)) != hipSuccess) {      // (no memory for the column: the 32-query kernel serves)
+    if (hipMalloc((void **)&s->d_sq_bi, (size_t)sqw_bi_entries(s->n) * sizeof(int32_t)) != hipSuccess) {      // (no memory for the column: the 32-query kernel serves)
         (void)hipGetLastError();
         s->d_sq_bi = nullptr;
         return QMX_OK;
@@ -293,7 +293,10 @@ static int32_t segment_sq_stats(qmx_segment *s) {
     QMX_TRY(launch_sqw_stats(nullptr, s->d_row_offsets, s->n, s->sq.multiplier, s->d_sq_bi, (uint32_t *)stats.p));
     QMX_HIP(hipMemcpy(h, stats.p, 8, hipMemcpyDeviceToHost));
     memcpy(&s->sq_off_absmax, &h[0], 4);
-    s->sq_wide = h[1] == 0 && s->sq_off_absmax < 3.0e38f;
+    // the pass's integer test adds a code dot (at most 127^2 dim) to a column entry (max |vector_offset| / multiplier at most, + 2): a block where that sum
+    // could reach 2^30 - un-centred dot / cosine data, vector_offset / multiplier ~ dim (offset / alpha)^2 - keeps the 32-query kernel
+    const bool in_range = (double)s->sq_off_absmax / (double)s->sq.multiplier + 16129.0 * (double)s->scan_dim < 1073741824.0;
+    s->sq_wide = h[1] == 0 && s->sq_off_absmax < 3.0e38f && in_range;
     return QMX_OK;
 }
 

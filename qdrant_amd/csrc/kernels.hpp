@@ -428,6 +428,7 @@ size_t sqw_query_bytes(uint32_t dim);
 size_t sqw_wlists_counts_bytes(int num_cus);
 size_t sqw_wlists_bytes(int num_cus);
 uint32_t sqw_wcap();
+uint64_t sqw_bi_entries(uint64_t n);      // entries of the column launch_sqw_stats fills: n rounded up to whole 256-row tiles
 int32_t launch_sqw_stats(hipStream_t st, const float *d_off, uint64_t n, float multiplier, int32_t *d_bi, uint32_t *d_stats);
 int32_t launch_sqw_pack(hipStream_t st, const ScanArgs &a, const uint64_t *d_gthr, float off_absmax, void *d_bq, int32_t *d_thr_i, float *d_qinfo, float *d_band,
                         uint32_t *d_cand_cnt, uint32_t n_cnt);

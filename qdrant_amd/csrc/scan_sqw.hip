@@ -42,18 +42,25 @@ struct SqWideArgs {
     uint32_t nch;             // stages per tile: codes of a row / 64
     uint32_t nq;              // live queries (<= 128)
     const int32_t *thr_i;     // [128] A[query]: a pair with dot + B[row] below this cannot reach the query's threshold
-    const int32_t *bi;        // [n] B[row] (sqw_stats_kernel)
+    const int32_t *bi;        // [sqw_bi_entries(n)] B[row] (sqw_stats_kernel)
     uint4 *wlist;             // [waves][wcap] (dot, row, query, 0); sqw_finish_kernel turns them into (key lo, key hi, query, 0)
     uint32_t *wcnt;           // [waves] entries each wave wanted to append (may run past wcap: overflow)
     uint32_t wcap;
 };
 
-// ---- once per segment: bi[row] = ceil(vector_offset / multiplier) + 1 (clamped to +-2^30), stats[0] = max |vector_offset| (uint bits of a non-negative
-// float), stats[1] != 0: an offset that is not finite ----
-__global__ __launch_bounds__(256) void sqw_stats_kernel(const float *off, uint64_t n, float multiplier, int32_t *bi, uint32_t *stats) {
+// ---- once per segment: bi[row] = ceil(vector_offset / multiplier) + 1, stats[0] = max |vector_offset| (uint bits of a non-negative float), stats[1] != 0:
+// an offset that is not finite.  The column is padded to whole 256-row tiles (sqw_bi_entries; the padding holds zeros: the scan loads the entries of a
+// lane's four rows as one 16-byte piece, those of rows past the block included, and drops such rows by their number).  The clamp to +-2^30 never acts on
+// a block the pass serves: segment_sq_stats (api_segment.hip) leaves a block whose max |vector_offset| / multiplier + 127^2 dim reaches 2^30 to the
+// 32-query scan, so dot + bi[row] is the exact integer and cannot wrap ----
+__global__ __launch_bounds__(256) void sqw_stats_kernel(const float *off, uint64_t n, uint64_t n_pad, float multiplier, int32_t *bi, uint32_t *stats) {
     float hi = 0.0f;
     bool bad = false;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_pad; i += (uint64_t)gridDim.x * 256) {
+        if (i >= n) {
+            bi[i] = 0;
+            continue;
+        }
         const float v = off[i];
         bad = bad || !(__builtin_fabsf(v) < __builtin_inff());
         hi = __builtin_fmaxf(hi, __builtin_fabsf(v));
@@ -99,7 +106,9 @@ __global__ __launch_bounds__(256) void sqw_pack_kernel(const unsigned char *quer
             const double sizes = m * 16129.0 * (double)dim + __builtin_fabs((double)q_off) + (double)off_absmax + __builtin_fabs((double)t);
             const double a_thr = ((double)t - (double)q_off) / m - (sizes * eps / m + 3.0);
             ti = a_thr <= -2147483647.0 ? (int32_t)0x80000000 : a_thr >= 2147483520.0 ? 0x7FFFFFFF : (int32_t)__builtin_floor(a_thr);
-            if (!(a_thr == a_thr)) { ti = 0x7FFFFFFF; tf = __builtin_inff(); bd = __builtin_inff(); }
+            // a bound that is not a number, or one above the int32 range (a bound there would pass nothing, true members included; segment_sq_stats'
+            // gate keeps the scores of a served block far below it): no candidates and the infinite band - the 32-query scan serves the query
+            if (!(a_thr < 2147483520.0)) { ti = 0x7FFFFFFF; tf = __builtin_inff(); bd = __builtin_inff(); }
         }
     }
     thr_i[qi] = ti;
@@ -202,16 +211,15 @@ __global__ __launch_bounds__(SW_THREADS, 1) void scan_sqw_kernel(const ScanArgs 
     uint4 *const wl = s.wlist + (uint64_t)(blockIdx.x * (WAVES) + (uint32_t)w) * s.wcap;
     uint32_t wcount = 0;
     const uint32_t n_rows32 = (uint32_t)a.n_cand;
-    // B of the lane's eight rows of the running tile (rows 4 kq_r .. + 3 of both 16-row tiles of the wave)
+    // B of the lane's eight rows of the running tile (rows 4 kq_r .. + 3 of both 16-row tiles of the wave): entry j is row r + j's, also in the block's
+    // last tile - the column is padded to whole tiles (sqw_bi_entries), so the 16 bytes stay inside it, and the epilogue drops rows past the block
     i32x4q bi8[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     auto load_bi = [&](uint64_t it) __attribute__((always_inline)) {
         const uint64_t row0 = (blockIdx.x + it * gridDim.x) * BM;
         const unsigned char *src = uniform_ptr((uint64_t)(uintptr_t)(s.bi + row0));
-        const uint64_t room = last_row - row0;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            uint32_t r = (uint32_t)w * 32u + (uint32_t)mt * 16u + 4 * kq_r;
-            if ((uint64_t)r + 3 > room) r = room >= 3 ? (uint32_t)room - 3u : 0u;      // (entries of rows past the block are never used; keep the 16 bytes inside the column)
+            const uint32_t r = (uint32_t)w * 32u + (uint32_t)mt * 16u + 4 * kq_r;
             sw_gload16(bi8[mt], src, r * 4u);
         }
     };
@@ -362,11 +370,14 @@ size_t sqw_query_bytes(uint32_t dim) { return (size_t)(dim / 64) * SW_B_UNITS * 
 size_t sqw_wlists_counts_bytes(int num_cus) { return ((size_t)num_cus * (SW_THREADS / 64) * 4 + 255) / 256 * 256; }
 size_t sqw_wlists_bytes(int num_cus) { return sqw_wlists_counts_bytes(num_cus) + (size_t)num_cus * (SW_THREADS / 64) * SW_WCAP * 16; }
 uint32_t sqw_wcap() { return SW_WCAP; }
+uint64_t sqw_bi_entries(uint64_t n) { return (n + SW_BM - 1) / SW_BM * SW_BM; }
 
+// d_bi: sqw_bi_entries(n) entries
 int32_t launch_sqw_stats(hipStream_t st, const float *d_off, uint64_t n, float multiplier, int32_t *d_bi, uint32_t *d_stats) {
     ::qmx::clear_stale_error();
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (n + 255) / 256);
-    hipLaunchKernelGGL(sqw_stats_kernel, dim3(grid ? grid : 1), dim3(256), 0, st, d_off, n, multiplier, d_bi, d_stats);
+    const uint64_t n_pad = sqw_bi_entries(n);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, n_pad / 256);
+    hipLaunchKernelGGL(sqw_stats_kernel, dim3(grid ? grid : 1), dim3(256), 0, st, d_off, n, n_pad, multiplier, d_bi, d_stats);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }

@@ -283,10 +283,14 @@ class SqOracle:
         """queries: already metric-preprocessed f32 [nq, dim]"""
         queries = f32(np.atleast_2d(queries))
         out = np.empty((queries.shape[0], len(ids)), dtype=np.float32)
+        rows = np.ascontiguousarray(self.rows)
+        base, stride = rows.ctypes.data, rows.strides[0]      # (a row's address by arithmetic: one row view per call is most of a block's time)
+        addresses = [base + i * stride for i in np.asarray(ids).tolist()]
+        sq, score, isa = C.byref(self.sq), _lib.qo_sq_score, self.isa
         for qi in range(queries.shape[0]):
             codes, off = self.encode_query(queries[qi])
-            for j, i in enumerate(ids):
-                out[qi, j] = _lib.qo_sq_score(C.byref(self.sq), _p(codes), off, _p(self.rows[i]), self.isa)
+            codes_p = _p(codes)
+            out[qi] = [score(sq, codes_p, off, a, isa) for a in addresses]
         return out
 
     def score_internal(self, a, b):
