@@ -504,10 +504,24 @@ struct SplitTiles {
 //   f32 accumulation of the matrix cores over dim terms: dim * 2^-23 * sum |terms| (a round-off of 2^-23 per addition covers
 //   truncating adders as well), f16 subnormal flush of tiny elements: < 2^-27 sqrt(dim)
 // both rounded up generously; the exact side carries no error (the survivors are re-scored by the reference-order kernel).
+// Those terms are RELATIVE to the operands, and hold while an operand's f16 parts are normal numbers.  The scales are one power of two per block and one
+// per batch (of its largest |q|; both exponents clamped at +-100), so what they leave a member far below the largest is an ABSOLUTE resolution: f16
+// subnormals are 2^-24 apart, an element x s of any size is h + l to within 2^-25 - in accumulator units of its side, whatever the element's own size.
+// Summed against the other side (Cauchy-Schwarz) and brought back to score units:
+//     sqrt(dim) * 2^-24 * (max |row| / query scale + |q| / row scale)          (split_abs_band; twice the worst case)
+// For the batch's largest query over an unclamped block that is below 2^-36 sqrt(dim) of |q| max |row| - nothing beside the relative terms; for a query
+// 2^-20 of the batch's largest it is the band; for one 2^-40 of it, or a zero query, it exceeds |q| max |row|, the range of the scores themselves.  Such
+// a band selects nothing, and only costs lists that overflow (a wave's list is shared by its 64 queries: the whole tile would follow), so
+// sp_thresholds_kernel makes it infinite: the query collects no candidates and takes the exact scan alone, as a query without a sample bound does.  The
+// alternative - every query below a fixed fraction of the batch's largest to the exact scan - needs no term, but says nothing about a block whose own
+// scale is clamped (2^-110: the rows reach f16 at 2^-8 and below) and gives up queries this band still serves.
+// The matrix cores of gfx950 read f16 subnormal operands as they are (measured: 32 products of 2^-24 and 2^10 accumulate to 2^-9); were they flushed, the
+// resolution would be 2^-14, and this term too small by 2^10 (tests/test_split_band_model.py runs both and pins where they part).
 static inline float split_rel_band(bool half, uint32_t dim) {
     const float acc = (float)dim * 1.1920929e-7f;                      // dim * 2^-23
     return (half ? 9.765625e-4f + 9.5367432e-7f : 1.9073486e-6f) + acc;  // 2^-10 + 2^-20 | 2^-19
 }
+static inline float split_abs_band(uint32_t dim) { return 5.9604645e-8f * sqrtf((float)dim); }      // 2^-24 sqrt(dim), accumulator units of one side
 
 static int32_t split_begin(const SearchCall &c, const SearchPlan &plan, SplitTiles &sp) {
     qmx_query *q = c.q;
@@ -547,8 +561,8 @@ static int32_t f16_split_scan(SearchCall &c, SplitTiles &sp, const ScanArgs &a, 
     const int half = s->split_half ? 1 : 0;
     const uint32_t tqt = nq_tile > SPLIT_QT ? SPLIT_QT_MAX : SPLIT_QT;      // the shape of THIS tile (a remainder of <= 128 queries takes the 128 shape)
     QMX_TRY(launch_split_pack_queries(q->stream, (const float *)q->enc.p + (size_t)tile0 * s->dim, nq_tile, s->dim, f.qmax, f.qnorm, q->sp_bq.p, half, tqt));
-    QMX_TRY(launch_split_thresholds(q->stream, (const uint64_t *)q->gthr.p + tile0, f.qnorm, f.qmax, nq_tile, split_rel_band(half, s->dim), s->row_norm_max, row_scale,
-                                    f.scales, f.thr, f.band, tqt, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+    QMX_TRY(launch_split_thresholds(q->stream, (const uint64_t *)q->gthr.p + tile0, f.qnorm, f.qmax, nq_tile, split_rel_band(half, s->dim), split_abs_band(s->dim),
+                                    s->row_norm_max, row_scale, f.scales, f.thr, f.band, tqt, (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
     QMX_TRY(split_stage(q, "pack + thresholds"));
     // 3. the approximate scan of the whole block
     // over a derived copy in two launches: the strided sixteenth of the tiles first, whose k-th best approximate score tightens the

@@ -255,18 +255,25 @@ static int32_t segment_split_stats(qmx_segment *s) {
     if (s->dtype != QMX_DTYPE_F32 || (s->distance != QMX_DISTANCE_DOT && s->distance != QMX_DISTANCE_COSINE) || s->dim % 32 != 0 ||
         s->n < (1u << 18) || !s->fast_layout())
         return QMX_OK;
+    // two passes: the largest |x| first, then the largest norm from the squares of the rows as the split scales them (a power of two, so the norm of an
+    // ordinary block keeps its bits): the squares of a block at 2^-110 would all be zero in f32, those of a block at 2^100 infinite
     uint32_t h[2] = {0, 0};
+    float row_scale = 1.0f;
     {
         DevBuf stats;
         QMX_TRY(stats.reserve(8));
-        QMX_HIP(hipMemset(stats.p, 0, 8));
-        QMX_TRY(launch_split_row_stats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, (uint32_t *)stats.p));
-        QMX_HIP(hipMemcpy(h, stats.p, 8, hipMemcpyDeviceToHost));
+        for (int pass = 0; pass < 2; ++pass) {
+            QMX_HIP(hipMemset(stats.p, 0, 8));
+            QMX_TRY(launch_split_row_stats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, row_scale, (uint32_t *)stats.p));
+            QMX_HIP(hipMemcpy(h, stats.p, 8, hipMemcpyDeviceToHost));
+            memcpy(&s->row_maxabs, &h[0], 4);
+            row_scale = split_row_scale(s->row_maxabs);
+            if (row_scale == 1.0f) break;      // (the first pass's squares were the scaled ones already; also a block without a finite, positive maximum)
+        }
     }
-    memcpy(&s->row_maxabs, &h[0], 4);
     float mss;
     memcpy(&mss, &h[1], 4);
-    s->row_norm_max = sqrtf(mss);
+    s->row_norm_max = sqrtf(mss) / row_scale;
     s->split_stats = s->row_maxabs > 0.f && s->row_maxabs < 3.0e38f && s->row_norm_max < 3.0e38f;   // (NaN / inf rows: the exact scan only)
     if (!s->split_stats) return QMX_OK;
     if (s->flags & QMX_SEG_AUTO_COPY) return segment_auto_copy(s);

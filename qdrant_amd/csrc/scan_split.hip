@@ -134,11 +134,13 @@ __global__ __launch_bounds__(256) void sp_pack_queries_kernel(const float *q, ui
     chunk[sp_unit(nt, 0, kq, n)] = *reinterpret_cast<const uint4 *>(&h);
     chunk[sp_unit(nt, 1, kq, n)] = *reinterpret_cast<const uint4 *>(&l);
 }
-// thr[q] in accumulator units: (exact k-th best of the sample - band) * scale.  band[q] = rel_band * row_norm_max * |q| (score units).
+// thr[q] in accumulator units: (exact k-th best of the sample - band) * scale.  band[q] = rel_band * row_norm_max * |q| + abs_band * (row_norm_max /
+// query scale + |q| / row scale) (score units; split_rel_band and split_abs_band in api_search.hip say what each term covers); a band that reaches
+// row_norm_max * |q| - the whole range of the query's scores - rejects nothing, and is infinite.
 // Also: the batch's scales (scales[0] = query scale, [1] = row scale x query scale = accumulator units per score unit, [2] = its inverse) and the
 // zeroed candidate counters of the pass.
 __global__ __launch_bounds__(256) void sp_thresholds_kernel(const uint64_t *gthr, const float *qnorm, const float *qmax, uint32_t nq, float rel_band,
-                                                            float row_norm_max, float row_scale, float *scales, float *thr, float *band, uint32_t *cand_cnt,
+                                                            float abs_band, float row_norm_max, float row_scale, float *scales, float *thr, float *band, uint32_t *cand_cnt,
                                                             uint32_t n_cnt) {
     __shared__ float sh_mx[4];
     const float qs = sp_batch_scale(qmax, nq, sh_mx);
@@ -150,11 +152,14 @@ __global__ __launch_bounds__(256) void sp_thresholds_kernel(const uint64_t *gthr
     }
     for (uint32_t i = q; i < n_cnt; i += blockDim.x) cand_cnt[i] = 0;
     if (q >= nq) { thr[q] = __builtin_inff(); band[q] = 0.0f; return; }
-    const float b = rel_band * row_norm_max * qnorm[q];
+    const float range = row_norm_max * qnorm[q];
+    const float b = rel_band * range + abs_band * (row_norm_max / qs + qnorm[q] / row_scale);
     const uint64_t k = gthr[q];
-    // no bound (the sample holds fewer than k live rows): no candidates for this query, and its infinite band sends it - alone - to the exact scan
-    band[q] = k ? b : __builtin_inff();
-    thr[q] = k ? (key_score(k) - b) * (row_scale * qs) : __builtin_inff();
+    // no bound (the sample holds fewer than k live rows), or no band that selects (a query too small beside the batch's largest, a zero query, a
+    // norm that is not finite): no candidates for this query, and its infinite band sends it - alone - to the exact scan
+    const bool ok = k != 0 && b < range;
+    band[q] = ok ? b : __builtin_inff();
+    thr[q] = ok ? (key_score(k) - b) * (row_scale * qs) : __builtin_inff();
 }
 
 typedef __attribute__((address_space(3))) unsigned char sp_lds_byte;
@@ -1130,7 +1135,8 @@ __global__ __launch_bounds__(256) void sp_plan_kernel(const uint32_t *ovf_q, uin
 }
 
 // ---- row statistics of an f32 block (once per segment): stats[0] = max |x|, stats[1] = max row sum of squares (uint bits) ----
-__global__ __launch_bounds__(256) void sp_row_stats_kernel(const unsigned char *rows, uint64_t row_stride, uint64_t n, uint32_t dim, uint32_t *stats) {
+// (the squares are those of x * scale, a power of two: a block far from unit scale neither underflows nor overflows them; stats[1] is in units of scale^2)
+__global__ __launch_bounds__(256) void sp_row_stats_kernel(const unsigned char *rows, uint64_t row_stride, uint64_t n, uint32_t dim, float scale, uint32_t *stats) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
     float mx = 0.0f, mss = 0.0f;
@@ -1140,7 +1146,7 @@ __global__ __launch_bounds__(256) void sp_row_stats_kernel(const unsigned char *
         for (uint32_t i = lane; i < dim; i += 64) {
             const float x = v[i];
             mx = __builtin_fmaxf(mx, __builtin_fabsf(x));
-            ss = __builtin_fmaf(x, x, ss);
+            ss = __builtin_fmaf(x * scale, x * scale, ss);
         }
         for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
         mss = __builtin_fmaxf(mss, ss);
@@ -2014,10 +2020,10 @@ size_t split_wlists_counts_bytes(int num_cus) { return ((size_t)num_cus * (SP3_T
 size_t split_wlists_bytes(int num_cus) { return split_wlists_counts_bytes(num_cus) + (size_t)num_cus * (SP3_THREADS / 64) * SP_WCAP * 16; }
 size_t split_query_bytes(uint32_t dim) { return (size_t)(dim / 32) * SP4_B_UNITS * 16; }   // (sized for the 256-query tile; the half mode needs half of it)
 
-int32_t launch_split_row_stats(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, uint32_t *d_stats) {
+int32_t launch_split_row_stats(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, float scale, uint32_t *d_stats) {
     if (n == 0) return QMX_OK;
     ::qmx::clear_stale_error();
-    hipLaunchKernelGGL(sp_row_stats_kernel, dim3(2048), dim3(256), 0, st, (const unsigned char *)rows, row_stride, n, dim, d_stats);
+    hipLaunchKernelGGL(sp_row_stats_kernel, dim3(2048), dim3(256), 0, st, (const unsigned char *)rows, row_stride, n, dim, scale, d_stats);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }
@@ -2040,11 +2046,11 @@ int32_t launch_split_pack_queries(hipStream_t st, const float *d_q, uint32_t nq,
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }
-int32_t launch_split_thresholds(hipStream_t st, const uint64_t *d_gthr, const float *d_qnorm, const float *d_qmax, uint32_t nq, float rel_band, float row_norm_max,
-                                float row_scale, float *d_scales, float *d_thr, float *d_band, uint32_t qt, uint32_t *d_cand_cnt, uint32_t n_cnt) {
+int32_t launch_split_thresholds(hipStream_t st, const uint64_t *d_gthr, const float *d_qnorm, const float *d_qmax, uint32_t nq, float rel_band, float abs_band,
+                                float row_norm_max, float row_scale, float *d_scales, float *d_thr, float *d_band, uint32_t qt, uint32_t *d_cand_cnt, uint32_t n_cnt) {
     ::qmx::clear_stale_error();
-    hipLaunchKernelGGL(sp_thresholds_kernel, dim3(1), dim3(qt), 0, st, d_gthr, d_qnorm, d_qmax, nq, rel_band, row_norm_max, row_scale, d_scales, d_thr, d_band,
-                       d_cand_cnt, n_cnt);
+    hipLaunchKernelGGL(sp_thresholds_kernel, dim3(1), dim3(qt), 0, st, d_gthr, d_qnorm, d_qmax, nq, rel_band, abs_band, row_norm_max, row_scale, d_scales, d_thr,
+                       d_band, d_cand_cnt, n_cnt);
     QMX_HIP(hipGetLastError());
     return QMX_OK;
 }
