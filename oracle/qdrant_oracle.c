@@ -1440,6 +1440,17 @@ float qo_bq_score_ex(int distance, int invert, uint32_t dim, int encoding, const
     if (dot_like) return invert ? xor_product - zeros_count : zeros_count - xor_product;
     return invert ? zeros_count - xor_product : xor_product - zeros_count;
 }
+/* one query against rows[ids[0..n)] of a block of row_stride-byte rows (ids NULL: rows 0..n): the per-pair functions above, called in a loop here
+ * instead of in the caller's interpreter */
+void qo_bq_score_ex_batch(int distance, int invert, uint32_t dim, int encoding, const uint8_t *q, const uint8_t *rows, size_t row_stride, const uint32_t *ids,
+                          size_t n, float *out) {
+    for (size_t i = 0; i < n; ++i) out[i] = qo_bq_score_ex(distance, invert, dim, encoding, q, rows + (size_t)(ids ? ids[i] : i) * row_stride);
+}
+void qo_bq_score_scalar_batch(int distance, int invert, uint32_t dim, int encoding, uint32_t bits, const uint8_t *scalar_query, const uint8_t *rows,
+                              size_t row_stride, const uint32_t *ids, size_t n, float *out) {
+    for (size_t i = 0; i < n; ++i)
+        out[i] = qo_bq_score_scalar(distance, invert, dim, encoding, bits, scalar_query, rows + (size_t)(ids ? ids[i] : i) * row_stride);
+}
 
 /* ---- Colbert MaxSim over multi-dense vectors: score_max_similarity (lib/segment/src/vector_storage/query_scorer/mod.rs:70-97) ----
  * sims[a * stride + b] = TMetric::similarity(dense_a, dense_b) (computed by the leaves above); the two loops of the reference. */

@@ -162,6 +162,11 @@ float qo_bq_score_ex(int distance, int invert, uint32_t dim, int encoding, const
 size_t qo_bq_encode_scalar_query(uint32_t dim, int encoding, uint32_t bits, const float *query, uint8_t *out);
 uint64_t qo_bq_xor_popcnt_scalar(const uint8_t *vector, const uint8_t *query, uint32_t n_u128, uint32_t bits);
 float qo_bq_score_scalar(int distance, int invert, uint32_t dim, int encoding, uint32_t bits, const uint8_t *scalar_query, const uint8_t *v);
+/* batched: one query against rows[ids[i]] (ids NULL: row i) of a block with row_stride bytes per row, out[i] = the per-pair function's result */
+void qo_bq_score_ex_batch(int distance, int invert, uint32_t dim, int encoding, const uint8_t *q, const uint8_t *rows, size_t row_stride, const uint32_t *ids,
+                          size_t n, float *out);
+void qo_bq_score_scalar_batch(int distance, int invert, uint32_t dim, int encoding, uint32_t bits, const uint8_t *scalar_query, const uint8_t *rows,
+                              size_t row_stride, const uint32_t *ids, size_t n, float *out);
 
 /* ---- TurboQuant: lib/quantization/src/turboquant/ behind EncodedVectorsTQ (oracle/qdrant_oracle_tq.c; TQMode::Normal) ----
  * bits: TQBits in the reference's order {Bits4 = 0, Bits2 = 1, Bits1_5 = 2, Bits1 = 3}; distance: QO_DOT | QO_COSINE | QO_EUCLID | QO_MANHATTAN (DistanceType::L1: the dequantise-and-rotate-back fallback). */

@@ -309,6 +309,8 @@ def sq_quantile_interval(sample, count, quantile):
 _sig("qo_bq_encode_scalar_query", C.c_size_t, [C.c_uint32, C.c_int, C.c_uint32, _P, _P])
 _sig("qo_bq_xor_popcnt_scalar", C.c_uint64, [_P, _P, C.c_uint32, C.c_uint32])
 _sig("qo_bq_score_scalar", _f, [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32, _P, _P])
+_sig("qo_bq_score_ex_batch", None, [C.c_int, C.c_int, C.c_uint32, C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, _P])
+_sig("qo_bq_score_scalar_batch", None, [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32, _P, _P, C.c_size_t, _P, C.c_size_t, _P])
 
 
 class BqOracle:
@@ -334,12 +336,32 @@ class BqOracle:
         self.rows = self.encode(vectors)
         return self.rows
 
+    def _block(self, ids):
+        """the stored rows as one contiguous block, the ids as u32 (checked here: the batched entries index the block unchecked)"""
+        rows = np.ascontiguousarray(self.rows, dtype=np.uint8)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        assert rows.ndim == 2 and rows.shape[1] == self.row_bytes and (len(ids) == 0 or int(ids.max()) < rows.shape[0])
+        return rows, ids
+
     def score_points(self, queries_preprocessed, ids):
+        """one qo_bq_score_ex_batch call per query (the per-pair qo_bq_score_ex in a C loop: tests/test_oracle_bq.py pins the equality)"""
         qs = self.encode(queries_preprocessed)
+        rows, ids = self._block(ids)
+        out = np.empty((qs.shape[0], len(ids)), dtype=np.float32)
+        for qi in range(qs.shape[0]):
+            _lib.qo_bq_score_ex_batch(self.distance, self.invert, self.dim, self.encoding, _p(qs[qi]), _p(rows), rows.strides[0], _p(ids), len(ids), _p(out[qi]))
+        return out
+
+    def score_points_per_pair(self, queries_preprocessed, ids, bits=1):
+        """the same scores one qo_bq_score_ex / qo_bq_score_scalar call per pair: what the batched entries are checked against"""
+        qs = self.encode(queries_preprocessed) if bits == 1 else self.encode_scalar_queries(queries_preprocessed, bits)
         out = np.empty((qs.shape[0], len(ids)), dtype=np.float32)
         for qi in range(qs.shape[0]):
             for j, i in enumerate(ids):
-                out[qi, j] = _lib.qo_bq_score_ex(self.distance, self.invert, self.dim, self.encoding, _p(qs[qi]), _p(self.rows[i]))
+                if bits == 1:
+                    out[qi, j] = _lib.qo_bq_score_ex(self.distance, self.invert, self.dim, self.encoding, _p(qs[qi]), _p(self.rows[i]))
+                else:
+                    out[qi, j] = _lib.qo_bq_score_scalar(self.distance, self.invert, self.dim, self.encoding, bits, _p(qs[qi]), _p(self.rows[i]))
         return out
 
     def encode_scalar_queries(self, queries_preprocessed, bits):
@@ -353,10 +375,11 @@ class BqOracle:
 
     def score_points_scalar(self, queries_preprocessed, ids, bits):
         qs = self.encode_scalar_queries(queries_preprocessed, bits)
+        rows, ids = self._block(ids)
         out = np.empty((qs.shape[0], len(ids)), dtype=np.float32)
         for qi in range(qs.shape[0]):
-            for j, i in enumerate(ids):
-                out[qi, j] = _lib.qo_bq_score_scalar(self.distance, self.invert, self.dim, self.encoding, bits, _p(qs[qi]), _p(self.rows[i]))
+            _lib.qo_bq_score_scalar_batch(self.distance, self.invert, self.dim, self.encoding, bits, _p(qs[qi]), _p(rows), rows.strides[0], _p(ids), len(ids),
+                                          _p(out[qi]))
         return out
 
     def score_internal(self, a, b):

@@ -163,3 +163,32 @@ def test_scalar_encoded_plus_minus_one_query_scores_like_the_one_bit_query(dim, 
     zero.encode_rows(vecs)
     z = zero.encode_scalar_queries(np.zeros((1, dim), np.float32), bits)[0]                 # delta = 0: every value quantises to 0
     assert not z.any()
+
+
+@pytest.mark.parametrize("encoding", [0, 1, 2])                 # OneBit, TwoBits, OneAndHalfBits
+@pytest.mark.parametrize("bits", [1, 4, 8])                     # SameAsStorage, Scalar4bits, Scalar8bits
+def test_batched_scores_equal_the_per_pair_ones(encoding, bits):
+    """BqOracle.score_points / score_points_scalar go through qo_bq_score_ex_batch / qo_bq_score_scalar_batch (one query against an array of row ids):
+    the same bits as one qo_bq_score_ex / qo_bq_score_scalar call per pair, for every encoding and query encoding, repeated and unordered ids, a
+    non-contiguous row array."""
+    rng = np.random.default_rng(encoding * 10 + bits)
+    for dist, dim in ((O.DOT, 33), (O.EUCLID, 129), (O.COSINE, 384), (O.MANHATTAN, 200)):
+        n, nq = 150, 3
+        vecs = rng.standard_normal((n, dim)).astype(np.float32)
+        mean = vecs.mean(axis=0).astype(np.float32) if encoding else None
+        stddev = vecs.std(axis=0).astype(np.float32) if encoding else None
+        obq = O.BqOracle(dist, dim, encoding=encoding, mean=mean, stddev=stddev)
+        obq.encode_rows(vecs)
+        queries = rng.standard_normal((nq, dim)).astype(np.float32)
+        ids = np.concatenate([rng.permutation(n)[:100], [0, n - 1, n - 1, 7, 7]]).astype(np.uint32)      # 315 pairs per combination
+        want = obq.score_points_per_pair(queries, ids.tolist(), bits)
+        got = obq.score_points(queries, ids) if bits == 1 else obq.score_points_scalar(queries, ids, bits)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+        assert len(np.unique(want)) > 10
+        padded = np.zeros((n, obq.row_bytes + 16), dtype=np.uint8)                                        # rows as a strided view
+        padded[:, :obq.row_bytes] = obq.rows
+        obq.rows = padded[:, :obq.row_bytes]
+        again = obq.score_points(queries, ids) if bits == 1 else obq.score_points_scalar(queries, ids, bits)
+        assert np.array_equal(again.view(np.uint32), want.view(np.uint32))
+        with pytest.raises(AssertionError):
+            obq.score_points(queries, [n])                                                                # an id past the block
