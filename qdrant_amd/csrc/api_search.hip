@@ -486,7 +486,7 @@ static int32_t wide_exact_search(SearchCall &c) {
     return QMX_OK;
 }
 
-// ---- the f32 prefilters (scan_split.hip): tiles of 128 / 256 queries; their verification and, if ever needed, the exact passes run once for all of them
+// ---- the f32 prefilters (scan_split.hip, scan_i8copy.hip, split_select.hip): tiles of 128 / 256 queries; their verification and, if ever needed, the exact passes run once for all of them
 // after the tile loop ----
 struct SplitTiles {
     SplitPlanLayout pl;

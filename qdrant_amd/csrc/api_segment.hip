@@ -95,7 +95,7 @@ static int32_t segment_pq_rot(qmx_segment *s) {
 
 // one pass over an f32 dot / cosine block that the split prefilter may serve: the power-of-two scale of its rows and the norm bound of
 // the verification band (4.5 ms per 30 GB; nothing for other storages)
-// ---- derived copies of an f32 dot / cosine block (scan_split.hip): what the prefilters stream instead of the f32 rows ----
+// ---- derived copies of an f32 dot / cosine block (scan_split.hip, scan_i8copy.hip): what the prefilters stream instead of the f32 rows ----
 static void segment_drop_copy(qmx_segment *s) {
     dev_free(s->d_rows_split);
     dev_free(s->d_i8_scale);

@@ -294,7 +294,7 @@ __global__ __launch_bounds__(CT_BLOCK) void custom_topk_small_kernel(const float
 }
 
 // The same selection once more, for the sample bound of the prefilters (n <= 16 384, top <= 64), in a block that starts on a CU whose other tenant is a
-// block of the resident int8 scan (2 waves and 320 registers per SIMD, 99 328 B of LDS: scan_split.hip sp8r_lds_bytes).  The kernel above cannot - 4 waves
+// block of the resident int8 scan (2 waves and 320 registers per SIMD, 99 328 B of LDS: scan_i8copy.hip sp8r_lds_bytes).  The kernel above cannot - 4 waves
 // per SIMD at 100 registers, a uint64 per score in LDS (65 680 B at 8 192 scores) - and waited for a CU without a scan block.  This one: 256 threads
 // (one wave per SIMD), no LDS per score.  A thread keeps the ORDER WORD (score_to_ord, 0 = dead / no such entry) of its <= 64 scores in registers.  The
 // largest word that at least `top` lanes of one wave reach with their maxima is a lower bound of the k-th best key's word; the entries that reach the

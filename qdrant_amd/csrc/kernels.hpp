@@ -333,7 +333,7 @@ int32_t launch_scan_f32_mfma16(hipStream_t st, int qt, const ScanArgs &a, int nu
 // (option fallback_beside_scan), and what such a block needs of a CU
 int32_t launch_scan_f32_mfma16_groups(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out);
 int32_t mfma16_groups_footprint(uint32_t dim, bool perq, size_t *lds_bytes, int *regs_per_simd);
-// f32 dot / cosine, 65..128 queries per pass: f16-split matrix-core prefilter + exact verification (scan_split.hip)
+// f32 dot / cosine, 65..128 queries per pass: f16-split matrix-core prefilter + exact verification (scan_split.hip; regroup, refine, select and plan: split_select.hip)
 bool split_scan_ok(const ScanArgs &a);
 size_t split_query_bytes(uint32_t dim);
 float split_row_scale(float row_maxabs);
@@ -383,7 +383,7 @@ struct VerifyPool {
 int32_t launch_split_select(hipStream_t st, const uint64_t *d_cand, const uint32_t *d_cand_cnt, uint32_t cap, const float *d_band, uint32_t nq, uint32_t top,
                             const VerifyPool &pool, uint32_t q_base, const int *d_tile_overflow, uint32_t *d_ovf_q, SplitStats *d_stats,
                             const float *d_t_exact = nullptr, bool tighten = false);
-// the int8 copy of an f32 block (QMX_SEG_I8_COPY) and its passes (scan_split.hip, "The INT8 copy")
+// the int8 copy of an f32 block (QMX_SEG_I8_COPY) and its passes (scan_i8copy.hip; the probe: split_select.hip)
 bool split_i8_dim_ok(uint32_t dim);
 size_t split_i8_copy_bytes(uint64_t n, uint32_t dim);
 size_t split_i8_query_bytes(uint32_t dim);

@@ -430,7 +430,7 @@ int32_t launch_scan_f32_mfma(hipStream_t st, int qt, ScanMode mode, const ScanAr
 }
 
 // The score matrix of a SHORT candidate list (the prefilters' sample: <= 16 384 ids) in a shape that starts on a CU whose other tenant is a block of
-// the resident int8 scan (scan_split.hip sp8r_lds_bytes: 2 waves and 320 registers per SIMD, 99 328 B of LDS - what is left is 192 registers per SIMD
+// the resident int8 scan (scan_i8copy.hip sp8r_lds_bytes: 2 waves and 320 registers per SIMD, 99 328 B of LDS - what is left is 192 registers per SIMD
 // and 64 512 B).  The 32-query tile of launch_scan_f32_mfma (8 waves at 176 registers, 107 264 B at 768 coordinates) waits for a CU without a scan block;
 // this one - 16 queries, 4 waves = one per SIMD, 53 760 B at 768 coordinates - does not.  Per (row, query) the same instruction sequence as the 16-query
 // slice of that tile (QW = 16 either way: QSPLIT only says which waves share a row stream), so the same bits; the block walks twice the query tiles.

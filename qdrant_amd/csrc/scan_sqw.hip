@@ -18,9 +18,7 @@
 // >= (T - query_offset) / multiplier, so with B[row] = ceil(vector_offset / multiplier) + 1 (an int32 column made once per segment) and A[query] = the
 // right side rounded down less a margin that covers the three f32 roundings of the expression, a pair can only reach the threshold when dot + B[row] >=
 // A[query].  (A bound on the segment's LARGEST vector_offset alone admits everything on rows whose offsets spread wider than their scores: iid unit rows.)
-#include <type_traits>
-
-#include "scan_common.hpp"
+#include "split_common.hpp"
 
 namespace qmx {
 
@@ -34,7 +32,7 @@ constexpr int SW_MAX_CODES = 1024;                           // sq_mfma_ok: 127^
 constexpr int SW_LDS_MAX = SW_MAX_CODES / 64 * SW_B_UNITS * 16 + SW_QT * 4;      // the queries' whole image (8 KiB per 64 codes) + the 128 integer bounds: 128.5 KiB
 constexpr uint32_t SW_WCAP = 8192;                           // candidates one wave may list per pass
 
-// unit index of (16-query tile t, piece kq, query-in-tile m) inside a stage of the queries' image: scan_split.hip sp_unit's swizzle, conflict-free for the operand reads
+// unit index of (16-query tile t, piece kq, query-in-tile m) inside a stage of the queries' image: split_common.hpp sp_unit's swizzle, conflict-free for the operand reads
 __device__ __forceinline__ uint32_t sw_unit(uint32_t t, uint32_t kq, uint32_t m) { return (t * 4 + kq) * 16 + (m ^ (2 * kq)); }
 
 struct SqWideArgs {
@@ -118,7 +116,7 @@ __global__ __launch_bounds__(256) void sqw_pack_kernel(const unsigned char *quer
 }
 
 // (default cache policy: a load instruction touches sixteen 64-byte HALF-lines whose other halves the group's next load is meant to hit - with `nt` the pass takes 1.49 ms
-// instead of 1.37, profiles/r6_nt_policy_experiment.txt; the int8-copy scans, whose loads consume whole lines, gain from it: scan_split.hip)
+// instead of 1.37, profiles/r6_nt_policy_experiment.txt; the int8-copy scans, whose loads consume whole lines, gain from it: scan_i8copy.hip)
 __device__ __forceinline__ void sw_gload16(i32x4q &dst, const unsigned char *sbase, uint32_t voff) {
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
 }
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(SW_THREADS, 1) void scan_sqw_kernel(const ScanArgs 
     const uint64_t n_tiles = (a.n_cand + BM - 1) / BM;
     const uint64_t my_tiles = blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
     if (my_tiles == 0) {
-        if (lane == 0) s.wcnt[blockIdx.x * (WAVES) + (uint32_t)w] = 0;
+        SpWaveList::none(s.wcnt, blockIdx.x * (WAVES) + (uint32_t)w, lane);
         return;
     }
 #pragma unroll 4
@@ -182,15 +180,11 @@ __global__ __launch_bounds__(SW_THREADS, 1) void scan_sqw_kernel(const ScanArgs 
     const uint32_t row_stride32 = (uint32_t)a.row_stride;
     const uint32_t rl0 = (uint32_t)w * 32u + m_r, rl1 = rl0 + 16u;
 
-    auto uniform_ptr = [&](uint64_t v) {
-        return reinterpret_cast<const unsigned char *>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
-                                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
-    };
     // One group's 2 G loads: the lane's code pieces of row tiles 0 and 1 of group b of the block's it-th tile (rows past the block: the last row's bytes,
     // their scores are dropped; stages past the row: the group's last piece again - the waits count loads)
     auto load_group = [&](uint64_t it, uint32_t b, i32x4q (&rc)[G][2]) __attribute__((always_inline)) {
         const uint64_t row0 = (blockIdx.x + it * gridDim.x) * BM;
-        const unsigned char *csrc = uniform_ptr((uint64_t)(uintptr_t)(rows + row0 * a.row_stride + b * (G * 64u)));
+        const unsigned char *csrc = sp_uniform_ptr((uint64_t)(uintptr_t)(rows + row0 * a.row_stride + b * (G * 64u)));
         const uint32_t gsz = nch - b * G < (uint32_t)G ? nch - b * G : (uint32_t)G;
         uint32_t r0 = rl0, r1 = rl1;
         const uint64_t room = last_row - row0;                      // (row0 <= last_row: the tile exists)
@@ -208,15 +202,14 @@ __global__ __launch_bounds__(SW_THREADS, 1) void scan_sqw_kernel(const ScanArgs 
     };
 
     i32x4q acc[2][8];
-    uint4 *const wl = s.wlist + (uint64_t)(blockIdx.x * (WAVES) + (uint32_t)w) * s.wcap;
-    uint32_t wcount = 0;
+    SpWaveList list(s.wlist, s.wcap, blockIdx.x * (WAVES) + (uint32_t)w);
     const uint32_t n_rows32 = (uint32_t)a.n_cand;
     // B of the lane's eight rows of the running tile (rows 4 kq_r .. + 3 of both 16-row tiles of the wave): entry j is row r + j's, also in the block's
     // last tile - the column is padded to whole tiles (sqw_bi_entries), so the 16 bytes stay inside it, and the epilogue drops rows past the block
     i32x4q bi8[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     auto load_bi = [&](uint64_t it) __attribute__((always_inline)) {
         const uint64_t row0 = (blockIdx.x + it * gridDim.x) * BM;
-        const unsigned char *src = uniform_ptr((uint64_t)(uintptr_t)(s.bi + row0));
+        const unsigned char *src = sp_uniform_ptr((uint64_t)(uintptr_t)(s.bi + row0));
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const uint32_t r = (uint32_t)w * 32u + (uint32_t)mt * 16u + 4 * kq_r;
@@ -253,13 +246,7 @@ __global__ __launch_bounds__(SW_THREADS, 1) void scan_sqw_kernel(const ScanArgs 
                 for (int j = 0; j < 4; ++j) {
                     const int v = acc[mt][nt][j];
                     const uint32_t row = row0 + (uint32_t)mt * 16 + (uint32_t)j;
-                    const bool c = v + bi8[mt][j] >= ti && row < n_rows32 && q < s.nq;
-                    const uint64_t hits = __ballot(c);
-                    if (hits) {
-                        const uint32_t at = wcount + __builtin_amdgcn_mbcnt_hi((uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0u));
-                        if (c && at < s.wcap) wl[at] = make_uint4((uint32_t)v, row, q, 0u);
-                        wcount += (uint32_t)__builtin_popcountll(hits);
-                    }
+                    list.append_raw(v + bi8[mt][j] >= ti && row < n_rows32 && q < s.nq, (uint32_t)v, row, q);
                 }
             }
         }
@@ -332,7 +319,7 @@ __global__ __launch_bounds__(SW_THREADS, 1) void scan_sqw_kernel(const ScanArgs 
     }
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(bi8[0]), "+v"(bi8[1]) : : "memory");
     epilogue(my_tiles - 1);
-    if (lane == 0) s.wcnt[blockIdx.x * (WAVES) + (uint32_t)w] = wcount;
+    list.finish(s.wcnt, blockIdx.x * (WAVES) + (uint32_t)w, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -351,12 +338,7 @@ __global__ __launch_bounds__(256) void sqw_finish_kernel(uint4 *wlist, const uin
         const float m1 = multiplier * (float)(int32_t)e.x;
         const float mq = m1 + qinfo[q];
         const float score = mq + row_offsets[row];
-        if (!(score < qinfo[SW_QT + q])) {
-            const uint64_t key = make_key(score, row);
-            list[i] = make_uint4((uint32_t)key, (uint32_t)(key >> 32), q, 0u);
-        } else {
-            list[i] = make_uint4(0u, 0u, 0xFFFFFFFFu, 0u);
-        }
+        list[i] = !(score < qinfo[SW_QT + q]) ? SpWaveList::entry(score, row, q) : SpWaveList::withdrawn();
     }
 }
 

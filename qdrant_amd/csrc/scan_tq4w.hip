@@ -21,9 +21,7 @@
 // zero.  The fast reject runs on integers: with sf in [sf_min, sf_max] over the segment (and l2 >= l2_min) a pair can only reach the threshold when
 // low + 128 high >= thr_i[q], a bound tq4w_pack_kernel derives per query with the rounding of finish() on its side; and since |low| <= 64 C1 (C1 = the
 // largest sum of |codebook bytes| of a row of the block), only when high >= (thr_i[q] - 64 C1) / 128 - the first test, on half the accumulators.
-#include <type_traits>
-
-#include "scan_common.hpp"
+#include "split_common.hpp"
 
 namespace qmx {
 
@@ -38,17 +36,17 @@ constexpr int TW_RP_UNITS = TW_BM * 8;                       // ... of a stage p
 constexpr int TW_LDS = (2 * TW_B_UNITS + 2 * TW_RP_UNITS) * 16 + 2 * TW_QT * 4;      // 64 + 64 + 1 = 129 KiB
 constexpr uint32_t TW_WCAP = 8192;                           // candidates one wave may list per pass
 
-// unit index of (16-row or 16-query tile t, half hl, k-group kq, row-in-tile m): scan_split.hip sp_unit, the layout both operand reads are conflict-free in
+// unit index of (16-row or 16-query tile t, half hl, k-group kq, row-in-tile m): split_common.hpp sp_unit, the layout both operand reads are conflict-free in
 __device__ __forceinline__ uint32_t tw_unit(uint32_t t, uint32_t hl, uint32_t kq, uint32_t m) { return ((t * 2 + hl) * 4 + kq) * 16 + (m ^ (2 * kq)); }
 
 typedef __attribute__((address_space(3))) unsigned char tw_lds_byte;
-// 1 KiB of global memory (wave-uniform base, lane i fetches bytes 16 i ..) straight into LDS at the wave-uniform byte address lds_dst (scan_split.hip sp_glds16)
+// 1 KiB of global memory (wave-uniform base, lane i fetches bytes 16 i ..) straight into LDS at the wave-uniform byte address lds_dst (split_common.hpp sp_glds16)
 __device__ __forceinline__ void tw_glds16(const unsigned char *src, uint32_t lane_off, uint32_t lds_dst) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(lane_off), "s"(src), "s"(lds_dst) : "memory");
 }
-// LDS traffic is all that crosses a stage barrier (scan_split.hip sp_stage_barrier: __syncthreads() would drain the row stream)
+// LDS traffic is all that crosses a stage barrier (split_common.hpp sp_stage_barrier: __syncthreads() would drain the row stream)
 __device__ __forceinline__ void tw_stage_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -244,7 +242,7 @@ __global__ __launch_bounds__(TW_THREADS, 1) void scan_tq4w_kernel(const ScanArgs
     const uint32_t nch = s.nch, npair = nch / 2;
     const uint64_t my_tiles = blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
     if (my_tiles == 0) {
-        if (lane == 0) s.wcnt[blockIdx.x * (TW_THREADS / 64) + (uint32_t)w] = 0;
+        SpWaveList::none(s.wcnt, blockIdx.x * (TW_THREADS / 64) + (uint32_t)w, lane);
         return;
     }
     if (tid < 2 * TW_QT) thr_lds[tid] = s.thr_i[tid];
@@ -261,17 +259,13 @@ __global__ __launch_bounds__(TW_THREADS, 1) void scan_tq4w_kernel(const ScanArgs
     const uint32_t rl0 = (uint32_t)w * 32u + m_r, rl1 = rl0 + 16u;
     const uint32_t coff0 = rl0 * row_stride32 + kq_r * 16u, coff1 = rl1 * row_stride32 + kq_r * 16u;
 
-    auto uniform_ptr = [&](uint64_t v) {
-        return reinterpret_cast<const unsigned char *>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
-                                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
-    };
     // the queries' images of stage kc -> B buffer `slot`: this wave's 4 KiB of the 32, four 1 KiB pieces
     const unsigned char *rq_src = nullptr;
     uint32_t rq_dst = 0;
     auto queries_begin = [&](uint32_t kc, uint32_t slot) {
         // (HO: the high digits' half of the image alone, 2 KiB per wave)
         const uint32_t off = HO ? TW_B_DIGIT_UNITS * 16u + (uint32_t)w * 2048u : (uint32_t)w * 4096u;
-        rq_src = uniform_ptr((uint64_t)(uintptr_t)(s.bq + (uint64_t)kc * TW_B_UNITS) + off);
+        rq_src = sp_uniform_ptr((uint64_t)(uintptr_t)(s.bq + (uint64_t)kc * TW_B_UNITS) + off);
         rq_dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + (slot * TW_B_UNITS) * 16u + off));
     };
     auto queries_piece = [&](int i) { tw_glds16(rq_src + i * 1024, lane_off, (uint32_t)__builtin_amdgcn_readfirstlane((int)(rq_dst + i * 1024))); };
@@ -281,7 +275,7 @@ __global__ __launch_bounds__(TW_THREADS, 1) void scan_tq4w_kernel(const ScanArgs
     uint32_t rc_dst = 0, rc_o0 = coff0, rc_o1 = coff1;
     auto codes_begin = [&](uint64_t it, uint32_t kp, uint32_t slot) {
         const uint64_t row0 = (blockIdx.x + it * gridDim.x) * TW_BM;
-        rc_src = uniform_ptr((uint64_t)(uintptr_t)(rows + row0 * a.row_stride + kp * 128u));
+        rc_src = sp_uniform_ptr((uint64_t)(uintptr_t)(rows + row0 * a.row_stride + kp * 128u));
         rc_dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + (2 * TW_B_UNITS + slot * TW_RP_UNITS) * 16u + (uint32_t)w * 1024u));
         rc_o0 = coff0;
         rc_o1 = coff1;
@@ -301,8 +295,7 @@ __global__ __launch_bounds__(TW_THREADS, 1) void scan_tq4w_kernel(const ScanArgs
     };
 
     i32x4w accl[2][8], acch[2][8];
-    uint4 *const wl = s.wlist + (uint64_t)(blockIdx.x * (TW_THREADS / 64) + (uint32_t)w) * s.wcap;
-    uint32_t wcount = 0;
+    SpWaveList list(s.wlist, s.wcap, blockIdx.x * (TW_THREADS / 64) + (uint32_t)w);
     const uint32_t n_rows32 = (uint32_t)a.n_cand;
 
     // The epilogue of a tile.  Level 1 on the high sums alone (64 of the lane's 128 accumulators): |low sum| <= 64 C1 whatever the row; then the whole
@@ -339,13 +332,7 @@ __global__ __launch_bounds__(TW_THREADS, 1) void scan_tq4w_kernel(const ScanArgs
                 for (int j = 0; j < 4; ++j) {
                     const int v = HO ? acch[mt][nt][j] : (acch[mt][nt][j] << 7) + accl[mt][nt][j];
                     const uint32_t row = row0 + (uint32_t)mt * 16 + (uint32_t)j;
-                    const bool c = v >= ti && row < n_rows32 && q < s.nq;
-                    const uint64_t hits = __ballot(c);
-                    if (hits) {
-                        const uint32_t at = wcount + __builtin_amdgcn_mbcnt_hi((uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0u));
-                        if (c && at < s.wcap) wl[at] = make_uint4((uint32_t)v, row, q, 0u);
-                        wcount += (uint32_t)__builtin_popcountll(hits);
-                    }
+                    list.append_raw(v >= ti && row < n_rows32 && q < s.nq, (uint32_t)v, row, q);
                 }
             }
         }
@@ -484,7 +471,7 @@ __global__ __launch_bounds__(TW_THREADS, 1) void scan_tq4w_kernel(const ScanArgs
         one_stage(1, ne, no, ae, ao);
     }
     epilogue(my_tiles - 1);
-    if (lane == 0) s.wcnt[blockIdx.x * (TW_THREADS / 64) + (uint32_t)w] = wcount;
+    list.finish(s.wcnt, blockIdx.x * (TW_THREADS / 64) + (uint32_t)w, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // nothing may land in LDS after the block is gone
 }
 
@@ -513,12 +500,7 @@ __global__ __launch_bounds__(256) void tq4w_finish_kernel(uint4 *wlist, const ui
             score = dot * sfr;
         }
         score = invert ? -score : score;
-        if (!(score < (band ? tf - band[q] : tf))) {
-            const uint64_t key = make_key(score, row);
-            list[i] = make_uint4((uint32_t)key, (uint32_t)(key >> 32), q, 0u);
-        } else {
-            list[i] = make_uint4(0u, 0u, 0xFFFFFFFFu, 0u);
-        }
+        list[i] = !(score < (band ? tf - band[q] : tf)) ? SpWaveList::entry(score, row, q) : SpWaveList::withdrawn();
     }
 }
 

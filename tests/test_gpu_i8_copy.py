@@ -1,4 +1,4 @@
-"""The int8 copy of an f32 block (QMX_SEG_I8_COPY; qdrant_amd/csrc/scan_split.hip, "The INT8 copy"): the prefilter streams one byte per element,
+"""The int8 copy of an f32 block (QMX_SEG_I8_COPY; qdrant_amd/csrc/scan_i8copy.hip): the prefilter streams one byte per element,
 multiplies on the int8 matrix cores and keeps every row whose approximate score lies within a worst-case band of an exact lower bound of the
 k-th best score; the survivors are re-scored with the exact gather kernel.  As with the f16 copies the approximate scores never leave the
 library: the result must be the exact scan's - the oracle's - ids and score bits, ties included, whatever the data does to the band."""
@@ -288,6 +288,25 @@ def test_int8_scan_with_resident_and_with_staged_queries_returns_the_exact_scan(
         qa.set_option("i8_resident", -1)
     _same(got, st, queries, top, live=~deleted)
     assert s.counters.prefilter_queries == nq and s.counters.fallback_queries == 0
+
+
+@pytest.mark.parametrize("stride", [2, 255])
+def test_int8_scan_with_another_sample_stride_returns_the_exact_scan(qa, stride):
+    """Option i8_sample_stride (2 .. 255; default 16): the first launch takes every stride-th tile, the second the complement (split_tiles.hpp).  At 2 the
+    launches halve the 1 055 tiles; at 255 the first launch has 5 tiles - fewer than blocks, most of which leave with an empty list - and the
+    complement skips one tile in 255.  The exact scan's lists either way."""
+    n, dim, nq, top = 270_000, 128, 5, 10
+    rows = O.preprocess(O.COSINE, O.synth(0x5EED07A0, 0, n, dim))
+    queries = O.synth(0x5EED07A1, 0, nq, dim)
+    vs = qa.VectorStorage(rows, qa.Distance.Cosine, flags=qa._ffi.SEG_I8_COPY)
+    qa.set_option("i8_sample_stride", stride)
+    try:
+        s = qa.BatchFilteredSearcher(queries, vs, top)
+        got = s.peek_top_all()
+        assert "scan_i8copy_kernel_res" in _kernel(qa, s), _kernel(qa, s)
+    finally:
+        qa.set_option("i8_sample_stride", -1)
+    _same(got, O.DenseStorage(O.F32, O.COSINE, rows), queries, top)
 
 
 def test_int8_scan_of_long_rows_keeps_the_staged_queries(qa):

@@ -1,5 +1,5 @@
 """The int8 prefilter's first launch (the strided sixteenth of the 256-row tiles, admitted on the sample's bound: tens of candidates per wave and tile)
-has an epilogue of its own since option `i8_dense_epilogue` (default 1; qdrant_amd/csrc/scan_split.hip, scan_i8copy_kernel_res_dense): a hit mask per
+has an epilogue of its own since option `i8_dense_epilogue` (default 1; qdrant_amd/csrc/scan_i8copy.hip, scan_i8copy_kernel_res_dense): a hit mask per
 lane and query tile and dense slots per wave instead of a ballot per row.  0 gives the one epilogue for both launches.  Every case runs with both
 values: the lists are the oracle's (ids and score bits) either way, and the candidate, verified-row and fallback counters are equal - the set of
 candidates a launch lists does not depend on which epilogue listed it.

@@ -1,6 +1,6 @@
 """Option `i8_sample_scan` (default 1): the int8 prefilter takes its first bound from the int8 copy itself.  Its sample is T = S / 16 whole 16-row
 tiles of the block (include/qdrant_amd.h states which; restated in `_sample_rows` below), scored by scan_i8copy_sample_kernel
-(qdrant_amd/csrc/scan_split.hip); the k best live sample rows of each query are scored exactly, and the smallest of those scores is the bound.
+(qdrant_amd/csrc/scan_i8copy.hip); the k best live sample rows of each query are scored exactly, and the smallest of those scores is the bound.
 0 = the exact f32 scores of every (n / S)-th row, as before.
 
 Every case compares ids and score bits with the exact scan (`no_split_scan` = 1) and between the two option values.  The candidate and

@@ -1,4 +1,4 @@
-"""The arithmetic of the int8 copy's prefilter (qdrant_amd/csrc/scan_split.hip, "The INT8 copy"), restated in numpy and checked on the CPU:
+"""The arithmetic of the int8 copy's prefilter (qdrant_amd/csrc/scan_i8copy.hip), restated in numpy and checked on the CPU:
 the band the device derives from the codes really bounds |exact score - approximate score| - on Gaussian rows and on the data that
 stretches it (outlier columns, sparse rows, rows of one repeated value, tiny and huge magnitudes) - and the pass built on it (thresholds from
 exact lower bounds, one band) keeps every member of the exact top k.  The device code follows these formulas line by line; the GPU tests
@@ -10,7 +10,7 @@ import pytest
 
 
 def choose_scales(colmax, colsq, n):
-    """split_i8_choose_scales (scan_split.hip), line by line: any s_i >= max |x_i| / 127 keeps the codes in range and |e_i| <= 1/2; raising the scales of
+    """split_i8_choose_scales (scan_i8copy.hip), line by line: any s_i >= max |x_i| / 127 keeps the codes in range and |e_i| <= 1/2; raising the scales of
     columns whose typical |q_i s_i| is below 1 / G of the largest moves range from their row codes to their query codes; the G of the smallest
     predicted band (queries distributed like the rows) is taken.  Returns (scales, G) - G = 0: every column at its floor."""
     dim = len(colmax)

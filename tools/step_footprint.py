@@ -11,7 +11,7 @@ sp8r_lds_bytes(dim / 128)) leaves on its CU: 163 840 B - its LDS, and 512 - 2 x 
 (threads / 256, rounded up) at r registers (rounded up to 8) fits when w * r and its LDS are within that - and it has no scratch to speak of.
 
 With --i8-sample-scan 1 (the default, as the option) the sample's bound comes from the int8 copy: scan_i8copy_sample_kernel<NQ> with NQ as
-scan_split.hip split_i8_sample_queries picks it, the picks and the sample's bound kernel; 0 lists the f32 pre-scan.
+scan_i8copy.hip split_i8_sample_queries picks it, the picks and the sample's bound kernel; 0 lists the f32 pre-scan.
 
 With --fallback-beside-scan 1 (the default, as the option) the conditional exact pass at the end of the step is the one-launch form of
 scan_mfma16.hip launch_scan_f32_mfma16_groups where its LDS fits beside the scan's (api_search.hip fallback_groups_fit); 0, and where it does not
@@ -28,7 +28,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-UNITS = ("preprocess", "scan_mfma", "custom_query", "scan_split", "scan_dense", "topk_merge", "scan_mfma16")
+UNITS = ("preprocess", "scan_mfma", "custom_query", "scan_i8copy", "split_select", "scan_dense", "topk_merge", "scan_mfma16")
 LDS_PER_CU, REGS_PER_SIMD, REG_UNIT = 163840, 512, 8
 
 
@@ -84,18 +84,18 @@ def step_kernels(a):
         ("preprocess", "cosine_preprocess_lds_kernel", r"cosine_preprocess_lds_kernelE", 256, dim * 16, "preprocess.hip launch_cosine_preprocess_f32"),
         ("pack", "pack_queries_kernel", r"pack_queries_kernelE", 64, 0, "preprocess.hip launch_pack_queries"),
     ]
-    res_lds = (dim // 128) * (128 * 2 * 4) * 16 + 2 * 128 * 4        # scan_split.hip sp8r_lds_bytes
+    res_lds = (dim // 128) * (128 * 2 * 4) * 16 + 2 * 128 * 4        # scan_i8copy.hip sp8r_lds_bytes
     if a.i8_sample_scan:
         S = S // 16 * 16
-        nch = dim // 128                                               # scan_split.hip split_i8_sample_queries
+        nch = dim // 128                                               # scan_i8copy.hip split_i8_sample_queries
         group = 16
         for c in (32, 64):
             if nch <= 8 and nch * (c // 16) * 2048 <= LDS_PER_CU - res_lds and c // 2 < nq:
                 group = c
         rows += [
-            ("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_split.hip launch_split_i8_pack"),
+            ("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_i8copy.hip launch_split_i8_pack"),
             ("sample scan", "scan_i8copy_sample_kernel<%d>" % group, r"scan_i8copy_sample_kernel" + targs(group), 256, nch * (group // 16) * 2048,
-             "scan_split.hip launch_scan_i8copy_sample"),
+             "scan_i8copy.hip launch_scan_i8copy_sample"),
         ]
     elif a.prescan_beside_scan and S <= 16384 and nq >= 16:
         d = 6
@@ -114,8 +114,8 @@ def step_kernels(a):
         rows.append(("top-k", "custom_topk_small_kernel", r"custom_topk_small_kernelE", 1024, S * 8, "custom_query.hip launch_custom_topk"))
     if a.i8_sample_scan:
         rows += [
-            ("sample picks", "sp_i8_picks_kernel", r"sp_i8_picks_kernelE", 64, 0, "scan_split.hip launch_split_i8_picks"),
-            ("sample bound", "sp_i8_sample_bound_kernel", r"sp_i8_sample_bound_kernelE", 64, 0, "scan_split.hip launch_split_i8_sample_bound"),
+            ("sample picks", "sp_i8_picks_kernel", r"sp_i8_picks_kernelE", 64, 0, "scan_i8copy.hip launch_split_i8_picks"),
+            ("sample bound", "sp_i8_sample_bound_kernel", r"sp_i8_sample_bound_kernelE", 64, 0, "scan_i8copy.hip launch_split_i8_sample_bound"),
         ]
     # scan_mfma16.hip M16Shape::LDS (ring stages of 16 rows x 1 KiB at pitch 1040; the half stages of odd row lengths come to the same)
     m16 = lambda nw, nt, ring=0: (ring or (4 if nw == 4 else 7)) * 16 * 1040 + nw * nt * 4 * 64 * 4 + 16 * 16 * 4
@@ -125,17 +125,17 @@ def step_kernels(a):
     # kernels' attributes; here: the LDS, which is what rules it out at 1 024 coordinates - the table's last column shows the registers)
     groups = a.fallback_beside_scan and m16(4, 1, 3) + res_lds <= LDS_PER_CU
     if not a.i8_sample_scan:
-        rows.append(("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_split.hip launch_split_i8_pack"))
+        rows.append(("sp_i8_pack", "sp_i8_pack_kernel", r"sp_i8_pack_kernelE", 256, dim * 4, "scan_i8copy.hip launch_split_i8_pack"))
     rows += [
-        ("first scan", "scan_i8copy_kernel_res_dense<1>", r"scan_i8copy_kernel_res_denseILi1EE", 512, res_lds, "scan_split.hip launch_scan_i8copy"),
-        ("second scan", "scan_i8copy_kernel_res<1>", r"scan_i8copy_kernel_resILi1EE", 512, res_lds, "scan_split.hip launch_scan_i8copy"),
-        ("regroup", "sp_regroup_kernel", r"sp_regroup_kernelE", 256, 0, "scan_split.hip launch_split_regroup"),
-        ("probe", "sp_i8_probe_kernel", r"sp_i8_probe_kernelE", 512, 0, "scan_split.hip launch_split_i8_probe"),
+        ("first scan", "scan_i8copy_kernel_res_dense<1>", r"scan_i8copy_kernel_res_denseILi1EE", 512, res_lds, "scan_i8copy.hip launch_scan_i8copy"),
+        ("second scan", "scan_i8copy_kernel_res<1>", r"scan_i8copy_kernel_resILi1EE", 512, res_lds, "scan_i8copy.hip launch_scan_i8copy"),
+        ("regroup", "sp_regroup_kernel", r"sp_regroup_kernelE", 256, 0, "split_select.hip launch_split_regroup"),
+        ("probe", "sp_i8_probe_kernel", r"sp_i8_probe_kernelE", 512, 0, "split_select.hip launch_split_i8_probe"),
         ("pair kernel", "pair_kernel<RowF32<dot>>", r"pair_kernelINS_6RowF32ILi0EEEE", 256, 0, "scan_common.hpp launch_pairs"),
-        ("bound", "sp_i8_bound_kernel", r"sp_i8_bound_kernelE", 64, 0, "scan_split.hip launch_split_i8_bound"),
-        ("select", "sp_select_kernel", r"sp_select_kernelE", 512, 0, "scan_split.hip launch_split_select"),
+        ("bound", "sp_i8_bound_kernel", r"sp_i8_bound_kernelE", 64, 0, "scan_i8copy.hip launch_split_i8_bound"),
+        ("select", "sp_select_kernel", r"sp_select_kernelE", 512, 0, "split_select.hip launch_split_select"),
         ("sort", "sort_scored_kernel", r"sort_scored_kernelE", 256, 0, "topk_merge.hip launch_sort_scored"),
-        ("plan", "sp_plan_kernel", r"sp_plan_kernelE", 256, 0, "scan_split.hip launch_split_plan"),
+        ("plan", "sp_plan_kernel", r"sp_plan_kernelE", 256, 0, "split_select.hip launch_split_plan"),
     ]
     if groups:
         rows += [
