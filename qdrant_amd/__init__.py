@@ -10,7 +10,7 @@ from .scorer import (BatchFilteredSearcher, Distance, EncodedVectorsPQ, EncodedV
                      new_raw_scorer_internal, pq_train, search_quantized, CustomQuery, CustomRawScorer, BinaryQuantizer, EncodedVectorsBin, load_quantizer, MultiDenseVectorStorage, QuantizedMultivectorStorage, TurboQuantizer, EncodedVectorsTQ, vector_stats,
                      SparseVectorStorage, pack_filters)
 from .groups import GroupKeys, search_groups  # noqa: F401
-from .hnsw import GraphLayers, decode_links_file  # noqa: F401
+from .hnsw import GraphLayers, decode_links_file, select_payload_blocks  # noqa: F401
 from .query import Dbsf, Mmr, Rrf, dbsf, hybrid_search, mmr, rrf, sparse_mmr  # noqa: F401
 from .query import (CompiledFormula, Formula, FormulaError, PayloadColumns, abs_, condition, const, datetime, decay_params_to_lambda,  # noqa: F401
                     div, exp, exp_decay, formula_eval, formula_rescore, gauss_decay, geo_distance, lin_decay, ln, log10, mult, neg, payload,

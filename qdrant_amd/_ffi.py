@@ -126,6 +126,15 @@ class HnswInfo(C.Structure):
                 ("n_extra_entry_points", C.c_uint32)]
 
 
+class HnswPayloadBlocks(C.Structure):
+    _fields_ = [("offsets", C.c_void_p), ("points", C.c_void_p), ("n_blocks", C.c_uint32), ("payload_m0", C.c_uint32),
+                ("ef_construct", C.c_uint32), ("max_batch", C.c_uint32)]
+
+
+class HnswPayloadInfo(C.Structure):
+    _fields_ = [("blocks_built", C.c_uint32), ("launches", C.c_uint32), ("links_added", C.c_uint64), ("longest_row", C.c_uint64)]
+
+
 class SearchParams(C.Structure):
     _fields_ = [("top", C.c_uint32), ("oversampling", C.c_float), ("rescore", C.c_uint8), ("acorn", C.c_uint8), ("pad_", C.c_uint8 * 2), ("hnsw_ef", C.c_uint32)]
 
@@ -283,6 +292,7 @@ SIGNATURES = {
     "qmx_hnsw_build": (C.c_int32, [_P, C.POINTER(HnswBuildParams), C.POINTER(_P)]),
     "qmx_hnsw_build_quantized": (C.c_int32, [_P, _P, C.POINTER(HnswBuildParams), C.POINTER(_P)]),
     "qmx_sharded_hnsw_build": (C.c_int32, [C.POINTER(_P), C.POINTER(_P), C.c_uint32, C.POINTER(HnswBuildParams), C.POINTER(_P), C.POINTER(C.c_int32)]),
+    "qmx_hnsw_build_payload_links": (C.c_int32, [_P, _P, _P, C.POINTER(HnswPayloadBlocks), C.POINTER(_P), C.POINTER(HnswPayloadInfo)]),
     "qmx_hnsw_get_info": (C.c_int32, [_P, C.POINTER(HnswInfo)]),
     "qmx_hnsw_export_plain": (C.c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qmx_hnsw_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.POINTER(Counters)]),

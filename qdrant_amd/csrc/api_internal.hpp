@@ -444,6 +444,7 @@ struct qmx_hnsw {
     uint64_t *d_level_offsets = nullptr, *d_offsets = nullptr;
     uint32_t *d_l0 = nullptr;     // packed level 0 [n_points][l0_stride]: count, links (built when every list fits 63 links)
     uint32_t l0_stride = 0;
+    uint32_t max_row0 = 0;        // the longest level-0 list (it may pass m0: merged payload links, graphs loaded from files)
     // the same table with the SQ vector_offset of every linked row behind the links ([n_points][2 m0]), made at the first plain walk of an SQ segment
     // over this graph and kept for that segment (its uid): searches share the graph across threads, hence the lock
     mutable std::mutex l0x_mu;

@@ -35,7 +35,7 @@
 
 namespace qmx {
 
-// bytes of the ACORN walk's list of nodes to explore (one per link of the popped candidate: m0 ids, 64 at least)
+// bytes of the ACORN walk's list of nodes to explore (one per link of the popped candidate: HnswArgs::explore_cap ids - the graph's longest level-0 list -, 64 at least)
 __host__ __device__ static inline uint32_t hnsw_acorn_lds(uint32_t acorn, uint32_t m0) { return acorn ? 4u * (((m0 < 64u ? 64u : m0) + 63u) / 64u * 64u) : 0u; }
 
 // ---- hop scorers: LPI lanes score one stored row; the score is valid in the lane with sub == 0 ----
@@ -1249,7 +1249,7 @@ __global__ __launch_bounds__(64) QMX_WALK_KERNEL_ATTR void hnsw_search_kernel(co
     // [hop ids: hop_cap u32][hop scores: hop_cap f32][ACORN: 64 ids to explore][query entry]
     uint32_t *hop_ids = reinterpret_cast<uint32_t *>(smem);
     float *hop_scores = reinterpret_cast<float *>(smem + 4 * (size_t)h.hop_cap);
-    unsigned char *q_lds = smem + 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.m0);
+    unsigned char *q_lds = smem + 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap);
     unsigned char *beam_lds = q_lds + (QLDS ? ((size_t)h.lds_query_bytes + 15) / 16 * 16 : 0);      // E == 0: the LDS beam behind the query entry (E == HNSW_E_REF: `nearest`)
     uint32_t *vis = h.visited + (uint64_t)blockIdx.x * h.vis_words;
     uint32_t *vlog = h.vis_log + (uint64_t)blockIdx.x * h.log_cap;
@@ -1393,7 +1393,7 @@ int32_t hnsw_occupancy_inst(uint32_t lds_query_bytes, size_t hop_lds, int *per_c
 template <class H, int E, bool QLDS>
 int32_t launch_hnsw_inst(hipStream_t st, const ScanArgs &a, const HnswArgs &h, uint32_t grid) {
     const uint32_t ef = h.ef > h.top ? h.ef : h.top;
-    const size_t lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.m0) + (QLDS ? ((size_t)h.lds_query_bytes + 15) / 16 * 16 : 0) + (E <= 0 ? hnsw_beam_lds(ef) : 0) +
+    const size_t lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + (QLDS ? ((size_t)h.lds_query_bytes + 15) / 16 * 16 : 0) + (E <= 0 ? hnsw_beam_lds(ef) : 0) +
                        (E == HNSW_E_REF ? (size_t)HNSW_REF_CAND_LDS * 8 : 0) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
     QMX_REQUIRE(lds <= 160 * 1024, QMX_ERR_NOT_SUPPORTED, "hnsw walk: %zu bytes of LDS (query entry + a list of %u)", lds, ef);
     ::qmx::clear_stale_error();
@@ -1435,18 +1435,18 @@ int32_t launch_hnsw_hop(hipStream_t st, const ScanArgs &a, const HnswArgs &h, ui
     }
     if (ef > HNSW_MAX_EF_REG) {        // the LDS beam: one instantiation per policy, the query entry staged
         QMX_REQUIRE(qlds, QMX_ERR_NOT_SUPPORTED, "hnsw ef %u > %u needs the query entry in LDS (it does not fit)", ef, HNSW_MAX_EF_REG);
-        if (grid == 0) return hnsw_occupancy_inst<H, 0, true>(h.lds_query_bytes, 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.m0) + hnsw_beam_lds(ef) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0), per_cu);
+        if (grid == 0) return hnsw_occupancy_inst<H, 0, true>(h.lds_query_bytes, 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + hnsw_beam_lds(ef) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0), per_cu);
         return launch_hnsw_inst<H, 0, true>(st, a, h, grid);
     }
     if constexpr (is_custom<H>::value || is_maxsim<H>::value) {      // (always staged: no instantiation that reads the entry from global memory)
         if (grid == 0) {
-            const size_t hop_lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.m0) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
+            const size_t hop_lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
             return ef <= 128 ? hnsw_occupancy_inst<H, 2, true>(h.lds_query_bytes, hop_lds, per_cu) : hnsw_occupancy_inst<H, 8, true>(h.lds_query_bytes, hop_lds, per_cu);
         }
         return ef <= 128 ? launch_hnsw_inst<H, 2, true>(st, a, h, grid) : launch_hnsw_inst<H, 8, true>(st, a, h, grid);
     } else {
     if (grid == 0) {
-        const size_t hop_lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.m0) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
+        const size_t hop_lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
         if (ef <= 128) return qlds ? hnsw_occupancy_inst<H, 2, true>(h.lds_query_bytes, hop_lds, per_cu) : hnsw_occupancy_inst<H, 2, false>(0, hop_lds, per_cu);
         return qlds ? hnsw_occupancy_inst<H, 8, true>(h.lds_query_bytes, hop_lds, per_cu) : hnsw_occupancy_inst<H, 8, false>(0, hop_lds, per_cu);
     }

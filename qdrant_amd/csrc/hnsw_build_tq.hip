@@ -1,5 +1,6 @@
 // hnsw_build_tq.hip - the HNSW build through the TurboQuant scorer (hnsw_build.hpp).
 #include "tq_internal_policy.hpp"
+#include "hnsw_build_payload.hpp"
 
 namespace qmx {
 
@@ -27,6 +28,28 @@ int32_t launch_hnsw_build_tq(hipStream_t st, const ScanArgs &a, const HnswBuildA
                       : launch_hnsw_build_hop<HopRow<RowTQ1<false, 16>>, HopTQInternal<1, false>>(st, a, h, phase, grid, per_cu);
         return l2 ? launch_hnsw_build_hop<HopRow<RowTQ1<true>>, HopTQInternal<1, true>>(st, a, h, phase, grid, per_cu)
                   : launch_hnsw_build_hop<HopRow<RowTQ1<false>>, HopTQInternal<1, false>>(st, a, h, phase, grid, per_cu);
+    }
+    set_error("TurboQuant build: %u bits per value not supported", a.tq_bits);
+    return QMX_ERR_NOT_SUPPORTED;
+}
+
+// the payload-block sub-graphs (hnsw_build_payload.hpp) through the same scorers
+int32_t launch_hnsw_payload_tq(hipStream_t st, const ScanArgs &a, const HnswPayloadArgs &h, int phase, uint32_t grid, int *per_cu) {
+    QMX_REQUIRE(h.batch_queries, QMX_ERR_BAD_ARG, "TurboQuant build needs the round's query entries");
+    const bool l2 = a.tq_l2 != nullptr;
+#define QMX_TQB(B, L, ROW)                                                                                                      \
+    if (a.tq_bits == B && l2 == L) return launch_hnsw_payload_hop<HopRow<ROW>, HopTQInternal<B, L>>(st, a, h, phase, grid, per_cu);
+    QMX_TQB(4, false, RowTQ4<false>)
+    QMX_TQB(4, true, RowTQ4<true>)
+    QMX_TQB(2, false, RowTQ2<false>)
+    QMX_TQB(2, true, RowTQ2<true>)
+#undef QMX_TQB
+    if (a.tq_bits == 1) {
+        if (a.tq_planes == 16)
+            return l2 ? launch_hnsw_payload_hop<HopRow<RowTQ1<true, 16>>, HopTQInternal<1, true>>(st, a, h, phase, grid, per_cu)
+                      : launch_hnsw_payload_hop<HopRow<RowTQ1<false, 16>>, HopTQInternal<1, false>>(st, a, h, phase, grid, per_cu);
+        return l2 ? launch_hnsw_payload_hop<HopRow<RowTQ1<true>>, HopTQInternal<1, true>>(st, a, h, phase, grid, per_cu)
+                  : launch_hnsw_payload_hop<HopRow<RowTQ1<false>>, HopTQInternal<1, false>>(st, a, h, phase, grid, per_cu);
     }
     set_error("TurboQuant build: %u bits per value not supported", a.tq_bits);
     return QMX_ERR_NOT_SUPPORTED;

@@ -144,6 +144,7 @@ struct HnswArgs {
     uint32_t ref_heaps;
     uint32_t ref_cap;               // entries of a slot's candidates heap; a search that needs more raises err_flag = 2
     uint2 *ref_cands;               // [slots][ref_cap]  (x = idx, y = score bits)
+    uint32_t explore_cap;           // ACORN: entries of the list of nodes to explore = the graph's longest level-0 list, m0 at least (merged / loaded graphs have longer ones)
 };
 
 // The PQ walk without LUTs (pq.hip HopPQDirect): the query entry is the preprocessed f32 vector, a LUT entry is recomputed from the codebook where it is needed

@@ -14,6 +14,7 @@
 // chain, so <= 1e-5 relative to the reference's mul+add chain; the exact-order VALU kernel is the
 // bit-parity variant).
 #include "hnsw_build.hpp"
+#include "hnsw_build_payload.hpp"
 #include "dev_mem.hpp"
 
 namespace qmx {
@@ -810,6 +811,18 @@ int32_t launch_hnsw_build_pq(hipStream_t st, const ScanArgs &a, const HnswBuildA
     }
     QMX_REQUIRE(a.pq_pair && h.batch_queries, QMX_ERR_BAD_ARG, "PQ build needs the centroid pair table and the batch LUTs");
     return launch_hnsw_build_hop<HopPQBuild, HopPQInternal>(st, a, h, phase, grid, per_cu);
+}
+
+// the payload-block sub-graphs (hnsw_build_payload.hpp) through the same scorers: the round's entries are its items' original vectors (or their LUTs)
+int32_t launch_hnsw_payload_pq(hipStream_t st, const ScanArgs &a, const HnswPayloadArgs &h, int phase, uint32_t grid, int *per_cu) {
+    if (h.lds_query_bytes != 0 && pq_direct_build_ok(a)) {
+        QMX_REQUIRE(h.batch_queries, QMX_ERR_BAD_ARG, "PQ build needs the round's original vectors");
+        if (a.pq_chunk == 16) return launch_hnsw_payload_hop<HopPQDirectBuild<16, 4, 2>, HopPQInternalDirect<16>>(st, a, h, phase, grid, per_cu);
+        if (a.pq_chunk == 8) return launch_hnsw_payload_hop<HopPQDirectBuild<8, 4, 4>, HopPQInternalDirect<8>>(st, a, h, phase, grid, per_cu);
+        return launch_hnsw_payload_hop<HopPQDirectBuild<4, 4, 8>, HopPQInternalDirect<4>>(st, a, h, phase, grid, per_cu);
+    }
+    QMX_REQUIRE(a.pq_pair && h.batch_queries, QMX_ERR_BAD_ARG, "PQ build needs the centroid pair table and the round's LUTs");
+    return launch_hnsw_payload_hop<HopPQBuild, HopPQInternal>(st, a, h, phase, grid, per_cu);
 }
 
 // ... over multi-vector points: the searches of an insertion through the LUTs of the new point's ORIGINAL inner vectors (HopMaxSimQ), stored <-> stored pairs

@@ -14,6 +14,7 @@
 // The rows are 16-byte multiples: the lane policies of the dense scan apply unchanged (8 lanes per row, 16 bytes per
 // lane per 128-byte step) and with them the tiled scan, pair scoring, rescoring plumbing and the HNSW walk.
 #include "hnsw_build.hpp"
+#include "hnsw_build_payload.hpp"
 
 namespace qmx {
 
@@ -276,6 +277,9 @@ int32_t launch_hnsw_maxsim_bq(hipStream_t st, const ScanArgs &a, const HnswArgs 
 // whatever the segment's QueryEncoding (score_internal :892-917)
 int32_t launch_hnsw_build_bq(hipStream_t st, const ScanArgs &a, const HnswBuildArgs &h, int phase, uint32_t grid, int *per_cu) {
     return HnswBuildLauncher{st, &h, phase, grid, per_cu}.template row<RowBQ>(a);
+}
+int32_t launch_hnsw_payload_bq(hipStream_t st, const ScanArgs &a, const HnswPayloadArgs &h, int phase, uint32_t grid, int *per_cu) {      // (hnsw_build_payload.hpp)
+    return HnswPayloadLauncher{st, &h, phase, grid, per_cu}.template row<RowBQ>(a);
 }
 int32_t launch_hnsw_build_maxsim_bq(hipStream_t st, const ScanArgs &a, const HnswBuildArgs &h, int phase, uint32_t grid, int *per_cu) {
     return HnswBuildMaxSimLauncher{st, &h, phase, grid, per_cu}.template row<RowBQ>(a);

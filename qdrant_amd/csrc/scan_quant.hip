@@ -12,6 +12,7 @@
 // 4-byte aligned) is split at upload into a 16-byte aligned code block [n][actual_dim] and an
 // offset column [n] f32; algorithmic bytes per scored row stay 4 + actual_dim.
 #include "hnsw_build.hpp"
+#include "hnsw_build_payload.hpp"
 
 namespace qmx {
 
@@ -158,6 +159,15 @@ int32_t launch_hnsw_maxsim_sq(hipStream_t st, int distance, const ScanArgs &a, c
 }
 int32_t launch_hnsw_build_sq(hipStream_t st, int distance, const ScanArgs &a, const HnswBuildArgs &h, int phase, uint32_t grid, int *per_cu) {
     const HnswBuildLauncher l{st, &h, phase, grid, per_cu};
+    const bool l1 = distance == QMX_DISTANCE_MANHATTAN;
+    const bool sep = (uint64_t)127 * 127 * a.dim >= (1ull << 24);
+    if (l1) return l.template row<RowSQInternal<true, false>>(a);
+    if (sep) return l.template row<RowSQInternal<false, true>>(a);
+    return l.template row<RowSQInternal<false, false>>(a);
+}
+// the payload-block sub-graphs (hnsw_build_payload.hpp) through the same internal scorer
+int32_t launch_hnsw_payload_sq(hipStream_t st, int distance, const ScanArgs &a, const HnswPayloadArgs &h, int phase, uint32_t grid, int *per_cu) {
+    const HnswPayloadLauncher l{st, &h, phase, grid, per_cu};
     const bool l1 = distance == QMX_DISTANCE_MANHATTAN;
     const bool sep = (uint64_t)127 * 127 * a.dim >= (1ull << 24);
     if (l1) return l.template row<RowSQInternal<true, false>>(a);

@@ -162,6 +162,41 @@ class GraphLayers:
         self.counters = F.Counters()
         return self
 
+    @classmethod
+    def build_payload_links(cls, storage, blocks, payload_m: int = 16, payload_m0: Optional[int] = None, ef_construct: int = 100,
+                            max_batch: int = 0, main: Optional["GraphLayers"] = None, original=None):
+        """The additional links of payload blocks (hnsw/build.rs:408-531; qmx_hnsw_build_payload_links): a flat graph of `payload_m0` links per
+        point over every block's points alone, all blocks built side by side on the storage's GPU, their links appended to level 0 of `main`
+        (`merge_from_other`) and their first points to its entry points.  `blocks`: a list of point-id arrays (insertion order), or an
+        `(offsets, points)` pair.  `main=None` is the reference's `m = 0` index - payload links only.  Returns a new GraphLayers; `main` is
+        untouched.  What the build did is in `.payload_info` (blocks_built, launches, links_added, longest_row)."""
+        if isinstance(blocks, tuple) and len(blocks) == 2:      # (a tuple is the CSR pair, a list is a list of blocks)
+            offsets, points = _u64(blocks[0]), _u32(blocks[1])
+        else:
+            lists = [_u32(b).ravel() for b in blocks]
+            offsets = np.zeros(len(lists) + 1, dtype=np.uint64)
+            if lists:
+                offsets[1:] = np.cumsum([len(b) for b in lists])
+            points = np.concatenate(lists) if lists else np.zeros(0, dtype=np.uint32)
+        if len(offsets) == 0:
+            offsets = np.zeros(1, dtype=np.uint64)
+        self = cls.__new__(cls)
+        b = F.HnswPayloadBlocks()
+        b.offsets, b.points = F.ptr(offsets).value, (F.ptr(points).value if len(points) else None)
+        b.n_blocks = len(offsets) - 1
+        b.payload_m0 = int(2 * payload_m if payload_m0 is None else payload_m0)
+        b.ef_construct, b.max_batch = int(ef_construct), int(max_batch)
+        self._keep = []
+        self._h = C.c_void_p()
+        self.payload_info = F.HnswPayloadInfo()
+        F.check(F.lib().qmx_hnsw_build_payload_links(storage._h, original._h if original is not None else None, main._h if main is not None else None,
+                                                     C.byref(b), C.byref(self._h), C.byref(self.payload_info)))
+        info = F.HnswInfo()
+        F.check(F.lib().qmx_hnsw_get_info(self._h, C.byref(info)))
+        self.m, self.m0, self.n_points = info.m, info.m0, info.n_points
+        self.counters = F.Counters()
+        return self
+
     def export_plain(self):
         """The plain GraphLinks arrays + entry points of a graph built on the device (an object with the fields
         `from_plain` takes)."""
@@ -243,6 +278,26 @@ class GraphLayers:
             self.close()
         except Exception:
             pass
+
+
+def select_payload_blocks(blocks, total: int, main_links0_average: int, full_scan_threshold: int):
+    """Which payload blocks get a graph of their own (hnsw/build.rs:441-478), the two deterministic rules: a block is skipped when its
+    cardinality exceeds `max_block_size = total / main_links0_average * 4` (integer division; below 1 / m of the points the main graph is
+    expected to disconnect, times four for safety - no bound without a main graph, `main_links0_average == 0`), or when it holds no more
+    than `full_scan_threshold / 4` points (such a block is scanned, not walked).  `blocks`: a list of point-id arrays, the points WITH an
+    available vector (`condition_points`); the cardinality tested by the first rule is the length of the list.  Returns the indices of the
+    blocks to build, in order.  The reference's third rule - a randomised estimate of the sub-graph's connectivity that may skip
+    non-tenant fields - is not restated."""
+    max_block_size = None if main_links0_average <= 0 else int(total) // int(main_links0_average) * 4
+    keep = []
+    for i, b in enumerate(blocks):
+        n = len(b)
+        if max_block_size is not None and n > max_block_size:
+            continue
+        if n <= int(full_scan_threshold) // 4:
+            continue
+        keep.append(i)
+    return keep
 
 
 def decode_links_file(data: bytes):
