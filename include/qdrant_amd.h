@@ -1057,6 +1057,52 @@ QMX_API int32_t qmx_group_search(qmx_query *q, const qmx_group_keys *keys, uint3
                                  const float *score_threshold, uint32_t *out_group_keys, uint32_t *out_group_sizes, qmx_scored_point *out_hits,
                                  uint32_t *out_n_groups, qmx_group_counters *counters);
 
+/* ---- distance matrix API (/points/search/matrix/pairs and /offsets) ------------------------------ */
+
+/* `Collection::search_points_matrix` (lib/collection/src/collection/distance_matrix.rs:141-289): "sample `sample` points under a filter and return,
+ * for each of them, its `limit` nearest among the other sampled points".  The reference builds it above the segment from two shard queries and a loop:
+ * `ScoringQuery::Sample(SampleInternal::Random)` with limit = sample under the filter and `HasVector` (:168-187), then a batch of Nearest searches
+ * with limit + 1 under `HasId(sample)` (:217-246), then per row `remove` of the row's own entry or `pop` of the last one (:270-284).  Here it is
+ * two calls on one device; ids are point OFFSETS of one segment, the filter is an allow bitmap the caller's payload index evaluated.
+ *
+ * qmx_sample_points = the first query.  A candidate is an offset below the segment's rows that is live under the segment's deleted flags (point-deleted
+ * or vector-deleted - the reference's `HasVector` - excludes it) and, with `allowed` != NULL, below n_allowed_bits with its bit set.  The reference's
+ * sample is random and not reproducible; this one is deterministic in `seed`: with (all arithmetic mod 2^64)
+ *     z = seed + (offset + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     key = z ^ (z >> 31)
+ * the sample is the n candidates of smallest (key, offset), written in ASCENDING OFFSET order (the reference's `sort_unstable_by_key(|p| p.id)`, :210);
+ * *out_count = min(n, candidates).  So n >= the number of candidates returns every live allowed offset in ascending order.
+ * n <= 65536 (QMX_ERR_NOT_SUPPORTED beyond), n == 0: count 0.  Every dtype but QMX_DTYPE_SPARSE (QMX_ERR_NOT_SUPPORTED).  out_ids [n] and out_count:
+ * host or device memory; `allowed`: host or device.  Synchronises (an exact radix select over the keys: per 12-bit level one pass over the
+ * liveness words and a few words read back; no host loop over points). */
+QMX_API int32_t qmx_sample_points(const qmx_segment *seg, const uint64_t *allowed, uint64_t n_allowed_bits, uint32_t n, uint64_t seed,
+                                  uint32_t *out_ids, uint32_t *out_count);
+
+/* qmx_search_matrix = the second query and the loop.  Row i is the Nearest search of STORED row sample_ids[i], used as the query, over the candidates
+ * sample_ids[j] with j != i that are live under the segment's deleted flags; cut to `limit`; ordered as qmx_search_topk orders (score descending, the
+ * lower offset first among equal scores).  That is what the reference converges to: with exact scores "take limit + 1, remove the row's own id if it
+ * is there, otherwise pop the last of a full list" leaves the `limit` best of the others.
+ *   - the row's own entry is dropped by POSITION, not by score: an exact duplicate of the row stays in its list;
+ *   - a deleted sample point still gets a row (its vector is stored) and never appears as a neighbour.
+ * Scores: the bits of qmx_query_create_internal([a]) + qmx_score_points([b]) on this segment (`FilteredScorer::new_internal`: the row as stored is the
+ * encoded query).  The reference retrieves the vector and preprocesses it again; under Cosine `is_length_zero_or_normalized` leaves alone a row whose
+ * squared length is within 1e-6 of 1, which every row `cosine_preprocess` produced is, and the widened row of an f16 / u8 storage casts back exactly:
+ * the contract is the stored row as the query.  Every score has the bits of the reference's `Metric::similarity` (f32, f16 and u8 alike).  For f16 rows
+ * of 32 and more elements that is the order of metric_f16/avx/dot.rs:13-69 (euclid.rs, manhattan.rs), which the call's own scan keeps; qmx_score_points
+ * on an f16 segment sums in another order (within 1e-5 of the reference) and may differ from these scores in the last place.
+ *   sample_ids : [n_sample] strictly ascending (QMX_ERR_BAD_ARG otherwise: unsorted or repeated), each below the rows (QMX_ERR_OUT_OF_BOUNDS); validated
+ *                on the host wherever they live.  n_sample <= 65536 (QMX_ERR_NOT_SUPPORTED beyond).
+ *   out        : [n_sample][limit] hits, idx = the neighbour's offset;   out_cols : [n_sample][limit] its position in sample_ids (the `offsets_col` of
+ *                SearchMatrixOffsetsResponse, :64-94), may be NULL;   out_counts : [n_sample].  Entries behind a row's count are zeros.
+ *   n_sample < 2 or limit == 0: every count 0 and QMX_OK (the reference's empty response; `out` is not touched).  limit > n_sample - 1 is served: counts are
+ *   at most n_sample - 1, the stride of out / out_cols stays `limit`.
+ * f32 / f16 / u8 segments, all four metrics.  Quantized and sparse segments: QMX_ERR_NOT_SUPPORTED (the reference rescored a quantized search with the
+ * original vectors anyway: hand over the original storage); multi-vector points have no entry here.  counters may be NULL.  Host or device memory;
+ * synchronises.  The sample's rows are gathered once on the device into a transient block, searched by the exact scans in chunks of at most 4096
+ * queries (staging lists of at most 256 MiB), and never visit the host. */
+QMX_API int32_t qmx_search_matrix(const qmx_segment *seg, const uint32_t *sample_ids, uint32_t n_sample, uint32_t limit, qmx_scored_point *out,
+                                  uint32_t *out_cols, uint32_t *out_counts, qmx_counters *counters);
+
 /* ---- HNSW search on device -------------------------------------------------------------------- */
 
 /* One built graph = `GraphLayers` (lib/segment/src/index/hnsw_index/graph_layers.rs:58-72): the

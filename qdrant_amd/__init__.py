@@ -10,6 +10,7 @@ from .scorer import (BatchFilteredSearcher, Distance, EncodedVectorsPQ, EncodedV
                      new_raw_scorer_internal, pq_train, search_quantized, CustomQuery, CustomRawScorer, BinaryQuantizer, EncodedVectorsBin, load_quantizer, MultiDenseVectorStorage, QuantizedMultivectorStorage, TurboQuantizer, EncodedVectorsTQ, vector_stats,
                      SparseVectorStorage, pack_filters)
 from .groups import GroupKeys, search_groups  # noqa: F401
+from .matrix import SearchMatrix, sample_points, search_matrix, search_matrix_offsets, search_matrix_pairs  # noqa: F401
 from .hnsw import GraphLayers, decode_links_file, select_payload_blocks  # noqa: F401
 from .query import Dbsf, Mmr, Rrf, dbsf, hybrid_search, mmr, rrf, sparse_mmr  # noqa: F401
 from .query import (CompiledFormula, Formula, FormulaError, PayloadColumns, abs_, condition, const, datetime, decay_params_to_lambda,  # noqa: F401

@@ -277,6 +277,8 @@ SIGNATURES = {
     "qmx_group_keys_create": (C.c_int32, [C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(_P)]),
     "qmx_group_keys_destroy": (C.c_int32, [_P]),
     "qmx_group_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_float), _P, _P, _P, _P, C.POINTER(GroupCounters)]),
+    "qmx_sample_points": (C.c_int32, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, _P]),
+    "qmx_search_matrix": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.POINTER(Counters)]),
     "qmx_sharded_search_topk": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),
     "qmx_sharded_search_topk_async": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "qmx_sharded_hnsw_search": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(Counters)]),

@@ -99,6 +99,7 @@ struct qmx_segment {
     float auto_i8_ms = 0.0f, auto_half_ms = 0.0f, auto_i8_verified = 0.0f;
     uint32_t auto_i8_fallback = 0;
     SparseSeg *sparse = nullptr;      // QMX_DTYPE_SPARSE only
+    bool f16_avx_order = false;       // the f16 block of a qmx_search_matrix call: rows in the layout of RowF16Avx, scanned by launch_scan_f16_avx alone
 
     qmx_segment() = default;
     qmx_segment(const qmx_segment &) = delete;
@@ -261,6 +262,7 @@ static inline int32_t refuse_filters(const char *fn) {
 static bool mfma_scan_ok(const qmx_segment *s) {
     if (s->dtype == QMX_DTYPE_SQ_U8) return sq_mfma_ok(s->distance, s->scan_dim) && !option(OPT_NO_MFMA_SCAN);
     if (s->dtype == QMX_DTYPE_TQ) return !option(OPT_NO_MFMA_SCAN);   // scan_sq_mfma.hip TqOps / Tq1Ops
+    if (s->f16_avx_order) return false;                               // (the matrix cores sum in their own order)
     return (s->dtype == QMX_DTYPE_F32 || s->dtype == QMX_DTYPE_F16) && (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) && s->dim >= 32 &&
            s->fast_layout() && !option(OPT_NO_MFMA_SCAN);
 }
@@ -532,6 +534,7 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
                               qmx_scored_point *d_out, uint32_t *d_counts, const volatile uint8_t *is_stopped,
                               qmx_counters *counters, bool timed);
 int32_t fold_split_counters(qmx_query *q, qmx_counters *c);
+int32_t query_encode_internal(qmx_query *q, const uint32_t *point_ids);      // api_query.hip: the stored rows `point_ids` (host or device) as the queries of an internal batch; synchronises
 // api_custom.hip: the descriptors of a custom-query request against a batch of `n_examples` examples
 int32_t custom_validate(const qmx_query *ex, const qmx_custom_query *queries, uint32_t n_queries, uint32_t n_examples, uint32_t *max_examples);
 TqRotationHost tq_rotation(const qmx_segment *s);

@@ -123,8 +123,8 @@ int32_t qmx_query_update(qmx_query *q, const float *queries) {
     return query_encode(q, queries);
 }
 
-// the stored rows `point_ids` as the batch's queries
-static int32_t internal_encode(qmx_query *q, const uint32_t *point_ids) {
+// the stored rows `point_ids` as the batch's queries (q->nq of them; again for a batch made over other rows: the chunks of qmx_search_matrix)
+int32_t query_encode_internal(qmx_query *q, const uint32_t *point_ids) {
     const qmx_segment *seg = q->seg;
     const uint32_t nq = q->nq;
     const void *d_ids = nullptr;
@@ -157,7 +157,7 @@ int32_t qmx_query_create_internal(const qmx_segment *seg, const uint32_t *point_
                 seg->dtype);
     qmx_query *q = nullptr;
     QMX_TRY(query_alloc(seg, nq, &q, true));
-    const int32_t rc = nq ? internal_encode(q, point_ids) : QMX_OK;
+    const int32_t rc = nq ? query_encode_internal(q, point_ids) : QMX_OK;
     if (rc != QMX_OK) {
         qmx_query_destroy(q);
         return rc;
@@ -350,6 +350,7 @@ int32_t launch_scan(const qmx_query *q, int qt, ScanMode mode, const ScanArgs &a
         QMX_REQUIRE(s->fast_layout(), QMX_ERR_NOT_SUPPORTED,
                     "dtype %u dim %u: an adopted device block needs a 16-byte aligned base and row stride (got stride %llu); "
                     "let qmx_segment_create upload it instead", s->dtype, s->dim, (unsigned long long)s->row_stride);
+        if (s->f16_avx_order) return launch_scan_f16_avx(q->stream, (int)s->distance, qt, mode, a, s->num_cus, grid);
         if (qt >= 8 && mfma_scan_ok(s))
             return s->dtype == QMX_DTYPE_F32 ? launch_scan_f32_mfma(q->stream, qt, mode, a, s->num_cus, grid)
                                               : launch_scan_f16_mfma(q->stream, qt, mode, a, s->num_cus, grid);

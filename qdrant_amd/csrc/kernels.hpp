@@ -721,4 +721,26 @@ int32_t launch_group_select(hipStream_t st, const GroupKeysDev &gk, const GroupS
 int32_t launch_group_final(hipStream_t st, const GroupState &gs, uint32_t nq, uint32_t *out_keys, uint32_t *out_sizes, qmx_scored_point *out_hits,
                            uint32_t *out_n_groups);
 
+// the distance matrix API (matrix.hip): the sampler of qmx_sample_points and the gather / finish of qmx_search_matrix; the logic both share with the host: matrix_plan.hpp
+struct SampleState;
+// one level of the radix select over the keys of the candidates of `del` (its `allowed` is the caller's bitmap): histogram + decision; hist [4096], zero before level 0
+int32_t launch_sample_level(hipStream_t st, const DeletedView &del, uint64_t n_words, uint64_t seed, uint32_t level, SampleState *state, uint32_t *hist);
+// the candidates at or below state->threshold, ascending, into out[0 .. cap); block_counts : [sample_count_blocks(n_words)] scratch
+uint32_t sample_count_blocks(uint64_t n_words);
+int32_t launch_sample_write(hipStream_t st, const DeletedView &del, uint64_t n_words, uint64_t seed, const SampleState *state, uint32_t *block_counts,
+                            uint32_t *out, uint32_t cap);
+// block row i = stored row ids[i] (ids below the rows: the caller validated them) at `pitch` bytes, a multiple of 16, zero behind row_bytes; bit i of `deleted`
+// (zeros on entry) set where ids[i] is not live under `del`; positions[i] = i
+int32_t launch_matrix_gather(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t row_bytes, const uint32_t *ids, uint32_t n, const DeletedView &del,
+                             void *block, uint64_t pitch, uint64_t *deleted, uint32_t *positions);
+// f16 rows of 32 and more elements: the same block in the layout of RowF16Avx (matrix_f16.hip) - the SIMD body as whole 128-byte segments of two AVX
+// iterations each (matrix_plan.hpp matrix_f16_avx_dim: `block_dim` elements per row), the scalar tail behind them.  Rows and stride: multiples of 2 bytes.
+int32_t launch_matrix_gather_f16_avx(hipStream_t st, const void *rows, uint64_t row_stride, uint32_t dim, const uint32_t *ids, uint32_t n, const DeletedView &del,
+                                     void *block, uint64_t pitch, uint32_t block_dim, uint64_t *deleted, uint32_t *positions);
+// ... and its exact top-k scan: `qt` (1 .. 16, a power of two) queries of such rows per pass, no id list; the sums in the order of the reference's f16 AVX leaf
+int32_t launch_scan_f16_avx(hipStream_t st, int distance, int qt, ScanMode mode, const ScanArgs &a, int num_cus, uint32_t *grid_out);
+// lists : [n_chunk][top] of the queries at positions c0 .. c0 + n_chunk, idx = position in the sample -> rows c0 .. of out / out_cols [.][limit] and out_counts
+int32_t launch_matrix_finish(hipStream_t st, const qmx_scored_point *lists, const uint32_t *counts, uint32_t top, uint32_t c0, uint32_t n_chunk,
+                             const uint32_t *sample_ids, uint32_t n_sample, uint32_t limit, qmx_scored_point *out, uint32_t *out_cols, uint32_t *out_counts);
+
 }  // namespace qmx
