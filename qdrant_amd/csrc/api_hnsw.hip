@@ -1,10 +1,7 @@
-// api_hnsw.hip — the C-ABI of include/qdrant_amd.h, HNSW graphs: create / import, the walks, the device build.
-// (One of the api_*.hip translation units; what they share: api_internal.hpp.)
-#include "api_internal.hpp"
-#include "hnsw_payload_args.hpp"
+// api_hnsw.hip — the C-ABI of include/qdrant_amd.h, HNSW graphs: create / import / export, the walks.  (The device builds: api_hnsw_build.hip,
+// api_hnsw_payload.hip.)  (One of the api_*.hip translation units; what they share: api_internal.hpp.)
+#include "api_hnsw_build.hpp"
 #include <algorithm>
-#include <atomic>
-#include <functional>
 
 extern "C" {
 
@@ -181,82 +178,23 @@ int32_t qmx_hnsw_create_from_plain_file(const void *bytes, uint64_t n_bytes, con
     return hnsw_create_checked(&d, out, false);
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// HNSW build on device (hnsw_build.hpp)
-// ---------------------------------------------------------------------------------------------
-static inline uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-static void fill_args_segment(const qmx_segment *s, ScanArgs &a) {
-    memset(&a, 0, sizeof(a));
-    a.rows = s->d_rows;
-    a.n_rows = s->n;
-    a.row_stride = s->row_stride;
-    a.dim = s->scan_dim;
-    const uint32_t eb = elem_bytes(s->dtype);
-    const uint32_t full = s->dtype <= QMX_DTYPE_U8 ? s->scan_dim - s->scan_dim % 32 : s->scan_dim;   // as fill_args
-    a.nseg = full * eb / 128;
-    a.rem_pieces = (full * eb % 128) / 16;
-    a.tail_start = full;
-    a.del = s->deleted_view();
-    a.flags = s->flags;
-    if (s->dtype == QMX_DTYPE_SQ_U8) {
-        a.sq_multiplier = s->sq.multiplier;
-        a.row_offsets = s->d_row_offsets;
-        // get_shift (encoded_vectors_u8.rs:116-134)
-        float shift = (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE)
-                          ? (float)s->sq.actual_dim * s->sq.offset * s->sq.offset : 0.0f;
-        a.sq_shift = s->sq.invert ? -shift : shift;
-    }
-    if (s->dtype == QMX_DTYPE_PQ) {
-        a.pq_m = s->pq_m;
-        a.pq_ncent = s->pq.n_centroids;
-        a.pq_pair = s->d_pq_pair;
-        a.pq_invert = s->pq.invert;
-        a.pq_centroids = s->d_centroids;      // the codebook itself (the table-free build, pq.hip)
-        a.pq_dim = s->dim;
-        a.pq_chunk = s->pq.chunk_size;
-        a.pq_kind = (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) ? 0u : s->distance == QMX_DISTANCE_MANHATTAN ? 1u : 2u;
-    }
-    if (s->dtype == QMX_DTYPE_BQ) {   // as fill_args; stored <-> stored scores are one-bit
-        a.bq_dim = s->dim;
-        a.bq_flip = (s->flags & QMX_SEG_BQ_TOGGLE_INVERT) ? 1 : 0;
-        a.bq_qbits = 1;
-    }
-    if (s->dtype == QMX_DTYPE_TQ) {   // as fill_args + the layout of the entries the build makes per batch + score_symmetric's inputs
-        uint32_t pieces;
-        a.tq_sf = s->d_tq_sf;
-        a.tq_l2 = s->d_tq_l2;
-        a.tq_bits = s->tq_value_bits;
-        a.tq_invert = s->tq_invert ? 1 : 0;
-        a.tq_planes = (s->tq_value_bits == 1 && s->d_tq_shift) ? 16 : 8;
-        tq_entry_layout(s, &pieces, &a.tq_qbytes_off, &a.aux_off);
-        a.q_stride = lds_tile_stride(a.aux_off + QUERY_AUX_BYTES);
-        a.bq_qbits = pieces;
-        a.tq_code_bytes = s->tq_code_bytes;
-        a.tq_ec = TqEc{s->d_tq_weights, s->d_tq_xm, s->tq_weight_scale, s->tq_mm_const};
-    }
-}
-
-static int32_t launch_hnsw_build_any(const qmx_segment *seg, const ScanArgs &a, const HnswBuildArgs &h, int phase, uint32_t grid, int *per_cu) {
-    if (a.mv_offsets) {   // multi-vector points (qmx_multi_hnsw_build)
-        if (seg->dtype == QMX_DTYPE_SQ_U8) return launch_hnsw_build_maxsim_sq(nullptr, (int)seg->distance, a, h, phase, grid, per_cu);
-        if (seg->dtype == QMX_DTYPE_BQ) return launch_hnsw_build_maxsim_bq(nullptr, a, h, phase, grid, per_cu);
-        if (seg->dtype == QMX_DTYPE_PQ) return launch_hnsw_build_maxsim_pq(nullptr, a, h, phase, grid, per_cu);
-        if (seg->dtype == QMX_DTYPE_TQ) return launch_hnsw_build_maxsim_tq(nullptr, a, h, phase, grid, per_cu);
-        return launch_hnsw_build_maxsim_dense(nullptr, (int)seg->dtype, (int)seg->distance, a, h, phase, grid, per_cu);
-    }
-    if (seg->dtype == QMX_DTYPE_SQ_U8) return launch_hnsw_build_sq(nullptr, (int)seg->distance, a, h, phase, grid, per_cu);
-    if (seg->dtype == QMX_DTYPE_BQ) return launch_hnsw_build_bq(nullptr, a, h, phase, grid, per_cu);
-    if (seg->dtype == QMX_DTYPE_PQ) return launch_hnsw_build_pq(nullptr, a, h, phase, grid, per_cu);
-    if (tq_l1(seg)) return launch_hnsw_build_tq_l1(nullptr, a, h, phase, grid, per_cu, seg->tq_rot_dim, seg->tq_padded_dim);
-    if (seg->dtype == QMX_DTYPE_TQ) return launch_hnsw_build_tq(nullptr, a, h, phase, grid, per_cu);
-    return launch_hnsw_build_dense(nullptr, (int)seg->dtype, (int)seg->distance, a, h, phase, grid, per_cu);
+int32_t hnsw_finish_graph(qmx_hnsw &g, uint32_t m, uint32_t m0, uint32_t n, uint32_t n_levels, int device, qmx_hnsw **out) {
+    qmx_hnsw_desc d;
+    memset(&d, 0, sizeof(d));
+    d.m = m; d.m0 = m0; d.n_points = n; d.n_levels = n_levels;
+    d.reindex = g.h_reindex.data(); d.level_offsets = g.h_level_offsets.data(); d.offsets = g.h_offsets.data();
+    d.n_offsets = g.h_offsets.size(); d.neighbors = g.h_neighbors.data(); d.n_neighbors = g.h_neighbors.size();
+    d.entry_point_ids = g.h_ep_ids.data(); d.entry_point_levels = g.h_ep_levels.data(); d.n_entry_points = (uint32_t)g.h_ep_ids.size();
+    d.extra_entry_point_ids = g.h_xp_ids.data(); d.extra_entry_point_levels = g.h_xp_levels.data();
+    d.n_extra_entry_points = (uint32_t)g.h_xp_ids.size();
+    d.device_id = device;
+    QMX_TRY(qmx_hnsw_create(&d, out));
+    qmx_hnsw *dev = *out;
+    dev->h_reindex = std::move(g.h_reindex); dev->h_neighbors = std::move(g.h_neighbors);
+    dev->h_ep_ids = std::move(g.h_ep_ids); dev->h_ep_levels = std::move(g.h_ep_levels);
+    dev->h_xp_ids = std::move(g.h_xp_ids); dev->h_xp_levels = std::move(g.h_xp_levels);
+    dev->h_level_offsets = std::move(g.h_level_offsets); dev->h_offsets = std::move(g.h_offsets);
+    return QMX_OK;
 }
 
 int32_t qmx_hnsw_get_info(const qmx_hnsw *g, qmx_hnsw_info *out) {
@@ -281,798 +219,6 @@ int32_t qmx_hnsw_export_plain(const qmx_hnsw *g, uint32_t *reindex, uint64_t *le
     cp(xp_ids, g->h_xp_ids.data(), g->h_xp_ids.size() * 4);
     cp(xp_levels, g->h_xp_levels.data(), g->h_xp_levels.size() * 4);
     return QMX_OK;
-}
-
-int32_t qmx_hnsw_build(const qmx_segment *seg, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
-    QMX_REFUSE_SPARSE(seg);
-    return qmx_hnsw_build_quantized(seg, nullptr, bp, out);
-}
-
-static int32_t hnsw_build_impl(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, qmx_hnsw **out, const MultiBuild *mb);
-
-int32_t qmx_hnsw_build_quantized(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
-    QMX_REFUSE_SPARSE(seg);
-    QMX_REFUSE_SPARSE(original);
-    return hnsw_build_impl(seg, original, bp, out, nullptr);
-}
-
-// Build fan-out over independent segments (gpu_devices_manager.rs:120-143 + hnsw/build.rs:53: one device locked per segment build, builds share nothing):
-// one host thread per segment, each driving its segment's device; the thread's own error text travels back with its status.
-static int32_t sharded_hnsw_build_body(const qmx_segment *const *segments, const qmx_segment *const *originals, uint32_t n_segments,
-                                       const qmx_hnsw_build_params *bp, qmx_hnsw **out_graphs, int32_t *out_status);
-int32_t qmx_sharded_hnsw_build(const qmx_segment *const *segments, const qmx_segment *const *originals, uint32_t n_segments,
-                               const qmx_hnsw_build_params *bp, qmx_hnsw **out_graphs, int32_t *out_status) {
-    for (uint32_t i = 0; segments && i < n_segments; ++i) {
-        QMX_REFUSE_SPARSE(segments[i]);
-        if (originals) QMX_REFUSE_SPARSE(originals[i]);
-    }
-    try {
-        return sharded_hnsw_build_body(segments, originals, n_segments, bp, out_graphs, out_status);
-    } catch (...) {         // nothing C++ crosses the C ABI
-        set_error("qmx_sharded_hnsw_build: out of host memory");
-        return QMX_ERR_OUT_OF_MEMORY;
-    }
-}
-static int32_t sharded_hnsw_build_body(const qmx_segment *const *segments, const qmx_segment *const *originals, uint32_t n_segments,
-                                       const qmx_hnsw_build_params *bp, qmx_hnsw **out_graphs, int32_t *out_status) {
-    QMX_REQUIRE(segments && bp && out_graphs && n_segments >= 1, QMX_ERR_BAD_ARG, "NULL argument");
-    for (uint32_t i = 0; i < n_segments; ++i) {
-        out_graphs[i] = nullptr;
-        if (out_status) out_status[i] = QMX_OK;
-    }
-    for (uint32_t i = 0; i < n_segments; ++i) QMX_REQUIRE(segments[i], QMX_ERR_BAD_ARG, "segment %u: NULL", i);
-    std::vector<int32_t> rcs(n_segments, QMX_OK);
-    std::vector<std::string> errs(n_segments);
-    auto work = [&](uint32_t i) {
-        try {
-            rcs[i] = hnsw_build_impl(segments[i], originals ? originals[i] : nullptr, bp, &out_graphs[i], nullptr);
-            if (rcs[i] != QMX_OK) errs[i] = last_error_text();          // (thread-local: copied out before the thread ends)
-        } catch (...) {     // (bad_alloc of a host vector inside the build: a status, not a terminate)
-            rcs[i] = QMX_ERR_OUT_OF_MEMORY;
-        }
-    };
-    if (n_segments == 1) {
-        work(0);
-    } else {
-        // One worker thread per DEVICE x QMX_BUILDS_PER_DEVICE (the reference locks one GPU of its pool per segment build, gpu_devices_manager.rs:120-143;
-        // here a device takes up to two builds at once: each holds its full scratch - visited bitmaps, selection buffers - so the count is bounded).
-        // Workers draw segments of their device from a shared cursor.  No C++ exception leaves this extern "C" function: a thread that cannot be
-        // started leaves its share to the calling thread, which runs whatever is left inline after joining the rest.
-        constexpr uint32_t QMX_BUILDS_PER_DEVICE = 2;
-        std::vector<int> devs;
-        for (uint32_t i = 0; i < n_segments; ++i)
-            if (std::find(devs.begin(), devs.end(), segments[i]->device) == devs.end()) devs.push_back(segments[i]->device);
-        std::vector<std::atomic<uint32_t>> cursor(devs.size());
-        for (auto &c : cursor) c.store(0);
-        auto drain = [&](size_t d) {      // the next unbuilt segment of device d, until none is left
-            for (;;) {
-                const uint32_t start = cursor[d].fetch_add(1);
-                uint32_t seen = 0, pick = n_segments;
-                for (uint32_t i = 0; i < n_segments; ++i)
-                    if (segments[i]->device == devs[d] && seen++ == start) { pick = i; break; }
-                if (pick == n_segments) return;
-                work(pick);
-            }
-        };
-        std::vector<std::thread> pool;
-        try {
-            pool.reserve(devs.size() * QMX_BUILDS_PER_DEVICE);
-            for (size_t d = 0; d < devs.size(); ++d)
-                for (uint32_t k = 0; k < QMX_BUILDS_PER_DEVICE; ++k) pool.emplace_back(drain, d);
-        } catch (...) {
-            // (std::system_error from the thread constructor, bad_alloc: keep what started)
-        }
-        for (auto &t : pool)
-            if (t.joinable()) t.join();
-        for (size_t d = 0; d < devs.size(); ++d) drain(d);      // whatever no worker took (all of it if no thread could be started)
-    }
-    int32_t first = QMX_OK;
-    for (uint32_t i = 0; i < n_segments; ++i) {
-        if (out_status) out_status[i] = rcs[i];
-        if (rcs[i] != QMX_OK && first == QMX_OK) {
-            first = rcs[i];
-            set_error("segment %u: %s", i, errs[i].c_str());
-        }
-    }
-    return first;
-}
-
-int32_t qmx_multi_hnsw_build_quantized(const qmx_segment *inner, const qmx_segment *original_inner, const uint64_t *point_offsets, uint32_t n_points,
-                                       const uint64_t *point_deleted, uint64_t n_deleted_bits, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
-    QMX_REFUSE_SPARSE(inner);
-    QMX_REFUSE_SPARSE(original_inner);
-    QMX_REQUIRE(inner && point_offsets && bp && out, QMX_ERR_BAD_ARG, "NULL argument");
-    *out = nullptr;
-    QMX_REQUIRE(inner->dtype == QMX_DTYPE_F32 || inner->dtype == QMX_DTYPE_F16 || inner->dtype == QMX_DTYPE_SQ_U8 || inner->dtype == QMX_DTYPE_BQ ||
-                    inner->dtype == QMX_DTYPE_PQ || (inner->dtype == QMX_DTYPE_TQ && !tq_l1(inner)),
-                QMX_ERR_NOT_SUPPORTED, "device HNSW build over multi-vectors: inner dtype %u not supported (f32, f16, SQ, BQ, PQ, TurboQuant except over Manhattan)",
-                inner->dtype);
-    QMX_REQUIRE(!is_device_ptr(point_offsets) && !is_device_ptr(point_deleted), QMX_ERR_BAD_ARG, "point_offsets and point_deleted are host arrays");
-    for (uint32_t p = 0; p < n_points; ++p)
-        QMX_REQUIRE(point_offsets[p] <= point_offsets[p + 1], QMX_ERR_BAD_ARG, "point_offsets is not ascending at %u", p);
-    QMX_REQUIRE(point_offsets[n_points] <= inner->n, QMX_ERR_OUT_OF_BOUNDS, "point_offsets reach past the %llu inner rows of the segment",
-                (unsigned long long)inner->n);
-    const MultiBuild mb{point_offsets, n_points, (point_deleted && n_deleted_bits) ? point_deleted : nullptr, point_deleted ? n_deleted_bits : 0};
-    return hnsw_build_impl(inner, (inner->dtype == QMX_DTYPE_PQ || inner->dtype == QMX_DTYPE_TQ) ? original_inner : nullptr, bp, out, &mb);
-}
-int32_t qmx_multi_hnsw_build(const qmx_segment *inner, const uint64_t *point_offsets, uint32_t n_points, const uint64_t *point_deleted,
-                             uint64_t n_deleted_bits, const qmx_hnsw_build_params *bp, qmx_hnsw **out) {
-    QMX_REFUSE_SPARSE(inner);
-    return qmx_multi_hnsw_build_quantized(inner, nullptr, point_offsets, n_points, point_deleted, n_deleted_bits, bp, out);
-}
-
-// what the device phase of a build leaves on the host: the fixed-capacity link lists and the entry points
-struct BuiltLinks {
-    std::vector<uint32_t> links0, cnt0, linksU, cntU;
-    bool have_ep = false;
-    uint32_t ep_id = 0, ep_level = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> extra;   // (level, id)
-};
-
-// the insertions of a build on the device; its scratch lives as long as this call
-static int32_t hnsw_build_links(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, const MultiBuild *mb, uint32_t n,
-                                uint32_t max_batch, const std::vector<uint8_t> &level, const std::vector<uint32_t> &up_off, uint64_t n_up,
-                                const std::vector<uint64_t> &pdel, const std::function<bool(uint32_t)> &live, BuiltLinks &r) {
-    const uint32_t m = bp->m, m0 = bp->m0;
-    const bool from_original = seg->dtype == QMX_DTYPE_PQ || seg->dtype == QMX_DTYPE_TQ;
-    DevBuf b_level, b_upoff, b_links0, b_cnt0, b_linksU, b_cntU, b_lock, b_vis, b_log, b_sel, b_sels, b_selc, b_normf, b_normi, b_bq, b_bqsrc, b_rot, b_next, b_mvoff,
-        b_mvdel;
-    const size_t nn = std::max<uint32_t>(n, 1);
-    QMX_TRY(b_level.reserve(nn)); QMX_TRY(b_upoff.reserve(nn * 4));
-    QMX_TRY(b_links0.reserve(nn * m0 * 4)); QMX_TRY(b_cnt0.reserve(nn * 4));
-    QMX_TRY(b_linksU.reserve(std::max<uint64_t>(n_up, 1) * m * 4)); QMX_TRY(b_cntU.reserve(std::max<uint64_t>(n_up, 1) * 4));
-    QMX_TRY(b_lock.reserve(nn * 4));
-    QMX_HIP(hipMemcpy(b_level.p, level.data(), nn, hipMemcpyHostToDevice));
-    QMX_HIP(hipMemcpy(b_upoff.p, up_off.data(), nn * 4, hipMemcpyHostToDevice));
-    QMX_HIP(hipMemset(b_cnt0.p, 0, nn * 4));
-    QMX_HIP(hipMemset(b_cntU.p, 0, std::max<uint64_t>(n_up, 1) * 4));
-    QMX_HIP(hipMemset(b_lock.p, 0, nn * 4));
-    QMX_TRY(b_sel.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * m0 * 4));
-    QMX_TRY(b_sels.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * m0 * 4));
-    QMX_TRY(b_selc.reserve((size_t)max_batch * HNSW_BUILD_MAX_LEVELS * 4));
-
-    ScanArgs a;
-    fill_args_segment(seg, a);
-    if (mb) {   // the graph's points are multi-vectors: offsets into the inner rows, deletion per POINT (the inner rows carry no flags of their own)
-        QMX_TRY(b_mvoff.reserve((size_t)(n + 1) * 8));
-        QMX_HIP(hipMemcpy(b_mvoff.p, mb->h_offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
-        a.mv_offsets = (const uint64_t *)b_mvoff.p;
-        DeletedView dv;
-        memset(&dv, 0, sizeof(dv));
-        dv.n_rows = n;
-        if (!pdel.empty()) {
-            QMX_TRY(b_mvdel.reserve(pdel.size() * 8));
-            QMX_HIP(hipMemcpy(b_mvdel.p, pdel.data(), pdel.size() * 8, hipMemcpyHostToDevice));
-            dv.point_deleted = (const uint64_t *)b_mvdel.p;
-            dv.n_point_bits = mb->n_deleted_bits;
-        }
-        a.del = dv;
-    }
-    HnswBuildArgs h;
-    memset(&h, 0, sizeof(h));
-    h.g.links0 = (uint32_t *)b_links0.p; h.g.cnt0 = (uint32_t *)b_cnt0.p; h.g.linksU = (uint32_t *)b_linksU.p; h.g.cntU = (uint32_t *)b_cntU.p;
-    h.g.up_off = (const uint32_t *)b_upoff.p; h.g.m = m; h.g.m0 = m0;
-    h.level = (const uint8_t *)b_level.p;
-    h.n_points = n;
-    h.ef_construct = bp->ef_construct;
-    h.sel_ids = (uint32_t *)b_sel.p; h.sel_scores = (float *)b_sels.p; h.sel_cnt = (uint32_t *)b_selc.p;
-    h.lock = (uint32_t *)b_lock.p;
-    // bytes of a row as it lies in HBM: the SQ block holds the codes only (the vector_offset column is separate)
-    const uint64_t dev_row_bytes = seg->dtype == QMX_DTYPE_SQ_U8 ? (uint64_t)seg->sq.actual_dim : seg->row_bytes;
-    h.row_bytes = (uint32_t)dev_row_bytes;
-    h.lds_query_bytes = (uint32_t)((dev_row_bytes + 127) / 128 * 128 + 128);
-    uint64_t lut_stride = 0;
-    uint64_t max_entries = max_batch;      // query entries a batch may need: one per point - or, multi-vector points, one per inner vector
-    bool pq_direct_build = false;
-    if (seg->dtype == QMX_DTYPE_PQ) {   // query entries = LUTs of the batch's original vectors, read through L2 (as the PQ walk does)
-        lut_stride = ((uint64_t)seg->pq_m * seg->pq.n_centroids * sizeof(float) + 15) & ~15ull;
-        if (mb) {   // at least the longest point, at most 1 GiB of LUTs (the insertion loop shortens a batch that would need more)
-            uint64_t longest = 1;
-            for (uint32_t p = 0; p < n; ++p) longest = std::max<uint64_t>(longest, mb->h_offsets[p + 1] - mb->h_offsets[p]);
-            max_entries = std::max<uint64_t>(longest, std::min<uint64_t>(mb->h_offsets[n] ? mb->h_offsets[n] : 1, (1ull << 30) / lut_stride));
-            a.q_stride = (uint32_t)lut_stride;
-        }
-        // the table-free build (pq.hip HopPQDirectBuild + HopPQInternalDirect; the default where the codebook allows, option hnsw_pq_table_build for the
-        // other): the entries are the preprocessed original vectors themselves, staged in LDS per insertion - no LUTs are made, and none are reserved
-        // (max_entries x lut_stride is 1.6 GB at m = 96: several builds on one device would multiply it for nothing)
-        pq_direct_build = !mb && !option(OPT_HNSW_PQ_TABLE_BUILD) && pq_direct_walk_ok(seg->dim, seg->pq_m, seg->pq.chunk_size, seg->pq.n_centroids);
-        if (!pq_direct_build) QMX_TRY(b_bq.reserve((size_t)max_entries * lut_stride));
-        QMX_TRY(b_bqsrc.reserve((size_t)max_entries * seg->dim * sizeof(float)));
-        h.batch_queries = (const unsigned char *)b_bq.p;
-        h.batch_q_stride = lut_stride;
-        h.lds_query_bytes = 0;
-        if (pq_direct_build) {
-            h.batch_queries = (const unsigned char *)b_bqsrc.p;
-            h.batch_q_stride = (uint64_t)seg->dim * 4;
-            h.lds_query_bytes = seg->dim * 4;
-            // (round 5 tried an 8-bit LUT image per new point behind its vector, to prefilter the hops of the insertion searches: the same graph,
-            // 25.6 s against 24.9 s at 2 M x 1536 points - gone from the code since round 6, profiles/r5_walk_variants_pq_hop_prefilter.jsonl)
-        }
-    }
-    if (seg->dtype == QMX_DTYPE_TQ) {   // query entries = precompute_query of the batch's original vectors, staged in LDS per insertion
-        if (mb) {   // one entry per inner vector of the batch: at least the longest point, at most 256 MiB of rotated vectors
-            uint64_t longest = 1;
-            for (uint32_t p = 0; p < n; ++p) longest = std::max<uint64_t>(longest, mb->h_offsets[p + 1] - mb->h_offsets[p]);
-            max_entries = std::max<uint64_t>(longest, std::min<uint64_t>(mb->h_offsets[n] ? mb->h_offsets[n] : 1,
-                                                                         (1ull << 28) / ((uint64_t)seg->tq_padded_dim * sizeof(double))));
-        }
-        QMX_TRY(b_bq.reserve((size_t)max_entries * a.q_stride));
-        QMX_TRY(b_bqsrc.reserve((size_t)max_entries * seg->dim * sizeof(float)));
-        QMX_TRY(b_rot.reserve((size_t)max_entries * seg->tq_padded_dim * sizeof(double)));
-        h.batch_queries = (const unsigned char *)b_bq.p;
-        h.batch_q_stride = a.q_stride;
-        h.lds_query_bytes = a.q_stride;
-        if (tq_l1(seg)) {   // over Manhattan the entry is the original vector as given (quantization.rs:532-535), its hop scratch behind it in LDS (tq_l1_policy.hpp)
-            a.tq_l1 = seg->d_tq_l1;
-            a.q_stride = tq_l1_query_bytes(seg->dim);
-            QMX_TRY(b_bq.reserve((size_t)max_batch * a.q_stride));
-            h.batch_queries = (const unsigned char *)b_bq.p;
-            h.batch_q_stride = a.q_stride;
-            h.lds_query_bytes = tq_l1_lds_bytes(seg->dim, seg->tq_rot_dim);
-        }
-    }
-    if (mb) h.lds_query_bytes = 0;      // nothing staged: the inner rows of the new point are read where they lie
-    if (seg->dtype == QMX_DTYPE_U8 && seg->distance == QMX_DISTANCE_COSINE && seg->dim >= 32) {   // the per-pair cosine's query norm of a stored row
-        QMX_TRY(b_normf.reserve(nn * 4)); QMX_TRY(b_normi.reserve(nn * 4));
-        QMX_TRY(launch_u8_row_norms(nullptr, seg->d_rows, seg->row_stride, n, seg->dim, seg->flags, (float *)b_normf.p, (int32_t *)b_normi.p));
-        a.row_norms_f = (const float *)b_normf.p;
-        a.row_norms_i = (const int32_t *)b_normi.p;
-    }
-    QMX_REQUIRE(h.lds_query_bytes <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "rows of %llu bytes do not fit the LDS query slot",
-                (unsigned long long)dev_row_bytes);
-    h.log_cap = 16384;
-    h.vis_words = ((uint64_t)n + 31) / 32;
-    if (h.vis_words == 0) h.vis_words = 1;
-    int per_cu1 = 1, per_cu2 = 1;
-    QMX_TRY(launch_hnsw_build_any(seg, a, h, 1, 0, &per_cu1));
-    QMX_TRY(launch_hnsw_build_any(seg, a, h, 2, 0, &per_cu2));
-    uint64_t slots1 = std::min<uint64_t>({(uint64_t)seg->num_cus * per_cu1, (uint64_t)HNSW_SLOT_CAP, (uint64_t)max_batch});
-    slots1 = std::max<uint64_t>(1, std::min<uint64_t>(slots1, HNSW_VIS_BUDGET / (h.vis_words * 4)));
-    const uint64_t slots2 = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)seg->num_cus * per_cu2, max_batch));
-    QMX_TRY(b_next.reserve(8));
-    h.next = (uint32_t *)b_next.p;
-    QMX_TRY(b_vis.reserve((size_t)slots1 * h.vis_words * 4));
-    QMX_TRY(b_log.reserve((size_t)slots1 * h.log_cap * 4));
-    QMX_HIP(hipMemset(b_vis.p, 0, (size_t)slots1 * h.vis_words * 4));
-    h.visited = (uint32_t *)b_vis.p;
-    h.vis_log = (uint32_t *)b_log.p;
-
-    // ---- insertion loop ----
-    // EntryPoints (entry_points.rs:46-94) kept on the host: the live point of the highest level seen first is the
-    // entry; the `entry_points_num` highest others are the extra entries
-    bool &have_ep = r.have_ep;
-    uint32_t &ep_id = r.ep_id, &ep_level = r.ep_level, inserted = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> &extra = r.extra;
-    auto note_point = [&](uint32_t id) {
-        const uint32_t lv = level[id];
-        if (!have_ep) { have_ep = true; ep_id = id; ep_level = lv; return; }
-        std::pair<uint32_t, uint32_t> other(lv, id);
-        if (lv > ep_level) { other = {ep_level, ep_id}; ep_id = id; ep_level = lv; }
-        if (bp->entry_points_num == 0) return;
-        if (extra.size() < bp->entry_points_num) { extra.push_back(other); return; }
-        size_t lo = 0;
-        for (size_t i = 1; i < extra.size(); ++i) if (extra[i].first < extra[lo].first) lo = i;
-        if (extra[lo].first < other.first) extra[lo] = other;
-    };
-    uint32_t next = 0;
-    while (next < n) {
-        if (!have_ep) {                      // the first live point: nothing to link to
-            if (live(next)) { note_point(next); ++inserted; }
-            ++next;
-            continue;
-        }
-        uint32_t count = std::min<uint32_t>({max_batch, std::max<uint32_t>(1, inserted / 32), n - next});
-        // a point above the current top level ends its batch: the next batch starts from it
-        for (uint32_t i = 0; i < count; ++i)
-            if (level[next + i] > ep_level && live(next + i)) { count = i + 1; break; }
-        if (mb && from_original)      // the batch's inner vectors must fit the entries (a single point always does)
-            while (count > 1 && mb->h_offsets[next + count] - mb->h_offsets[next] > max_entries) --count;
-        h.first = next; h.count = count; h.ep_id = ep_id; h.ep_level = ep_level;
-        if (seg->dtype == QMX_DTYPE_PQ) {
-            // quantized_vectors.raw_scorer(original vector): Metric::preprocess (quantized_query_scorer.rs:39-41; identity for a row
-            // normalised at insert, up to the reference's 1e-6 rule), then EncodedVectorsPQ::encode_query for every point of the batch
-            // (multi-vector points: for every inner vector of the batch's points, in storage order)
-            const uint64_t r0 = mb ? mb->h_offsets[next] : next, nr = mb ? mb->h_offsets[next + count] - r0 : count;
-            float *src = (float *)b_bqsrc.p;
-            if (nr) {
-                QMX_HIP(hipMemcpy2DAsync(src, (size_t)seg->dim * 4, (const char *)original->d_rows + r0 * original->row_stride, original->row_stride,
-                                    (size_t)seg->dim * 4, nr, hipMemcpyDeviceToDevice, nullptr));
-                if (seg->distance == QMX_DISTANCE_COSINE) QMX_TRY(launch_cosine_preprocess_f32(nullptr, src, src, nr, seg->dim));
-                if (!pq_direct_build) QMX_TRY(launch_pq_lut(nullptr, seg->distance, seg->dim, seg->pq, seg->d_centroids, src, (uint32_t)nr, (float *)b_bq.p));
-            }
-        }
-        if (tq_l1(seg)) {   // EncodedVectorsTQ over Manhattan: no preprocessing, no rotation - the rows themselves, zero padded to whole 16 bytes
-            QMX_HIP(hipMemsetAsync(b_bq.p, 0, (size_t)count * a.q_stride, nullptr));
-            QMX_HIP(hipMemcpy2DAsync(b_bq.p, a.q_stride, (const char *)original->d_rows + (uint64_t)next * original->row_stride, original->row_stride,
-                                (size_t)seg->dim * 4, count, hipMemcpyDeviceToDevice, nullptr));
-        } else if (seg->dtype == QMX_DTYPE_TQ) {   // the same for EncodedVectorsTQ: preprocess, rotate, TurboQuantizer::precompute_query
-            const uint64_t r0 = mb ? mb->h_offsets[next] : next, nr = mb ? mb->h_offsets[next + count] - r0 : count;      // (multi-vector points: every inner vector)
-            float *src = (float *)b_bqsrc.p;
-            if (nr) {
-                QMX_HIP(hipMemcpy2DAsync(src, (size_t)seg->dim * 4, (const char *)original->d_rows + r0 * original->row_stride, original->row_stride,
-                                    (size_t)seg->dim * 4, nr, hipMemcpyDeviceToDevice, nullptr));
-                if (seg->distance == QMX_DISTANCE_COSINE) QMX_TRY(launch_cosine_preprocess_f32(nullptr, src, src, nr, seg->dim));
-                QMX_TRY(launch_tq_rotate(nullptr, src, (uint32_t)nr, tq_rotation(seg), (double *)b_rot.p));
-                QMX_TRY(launch_tq_query_encode(nullptr, (double *)b_rot.p, (uint32_t)nr, seg->tq_padded_dim, seg->tq_value_bits, seg->distance == QMX_DISTANCE_EUCLID ? 1 : 0,
-                                          b_bq.p, a.q_stride, a.aux_off, seg->d_tq_shift, seg->d_tq_scale, a.tq_qbytes_off));
-            }
-        }
-        const uint32_t grid1 = (uint32_t)std::min<uint64_t>(slots1, count), grid2 = (uint32_t)std::min<uint64_t>(slots2, count);
-        if (h.next) {
-            const uint32_t start[2] = {grid1, grid2};
-            QMX_HIP(hipMemcpyAsync(h.next, start, sizeof(start), hipMemcpyHostToDevice, nullptr));      // (pageable source: the copy is staged before the call returns)
-        }
-        QMX_TRY(launch_hnsw_build_any(seg, a, h, 1, grid1, &per_cu1));
-        QMX_TRY(launch_hnsw_build_any(seg, a, h, 2, grid2, &per_cu2));
-        for (uint32_t i = 0; i < count; ++i)
-            if (live(next + i)) { note_point(next + i); ++inserted; }
-        next += count;
-    }
-    QMX_HIP(hipDeviceSynchronize());
-
-    r.links0.resize((size_t)nn * m0);
-    r.cnt0.resize(nn);
-    r.linksU.resize(std::max<uint64_t>(n_up, 1) * m);
-    r.cntU.resize(std::max<uint64_t>(n_up, 1));
-    QMX_HIP(hipMemcpy(r.links0.data(), b_links0.p, r.links0.size() * 4, hipMemcpyDeviceToHost));
-    QMX_HIP(hipMemcpy(r.cnt0.data(), b_cnt0.p, r.cnt0.size() * 4, hipMemcpyDeviceToHost));
-    QMX_HIP(hipMemcpy(r.linksU.data(), b_linksU.p, r.linksU.size() * 4, hipMemcpyDeviceToHost));
-    QMX_HIP(hipMemcpy(r.cntU.data(), b_cntU.p, r.cntU.size() * 4, hipMemcpyDeviceToHost));
-    return QMX_OK;
-}
-
-static int32_t hnsw_build_impl(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw_build_params *bp, qmx_hnsw **out, const MultiBuild *mb) {
-    QMX_REQUIRE(seg && bp && out, QMX_ERR_BAD_ARG, "NULL argument");
-    *out = nullptr;
-    QMX_REQUIRE(seg->dtype <= QMX_DTYPE_BQ || seg->dtype == QMX_DTYPE_TQ, QMX_ERR_NOT_SUPPORTED, "device HNSW build: dtype %u not supported", seg->dtype);
-    const bool from_original = seg->dtype == QMX_DTYPE_PQ || seg->dtype == QMX_DTYPE_TQ;
-    if (from_original) {   // point_scorer.rs:197-212: the insertion searches score through the query (PQ: LUT) of the ORIGINAL vector
-        QMX_REQUIRE(original, QMX_ERR_NOT_SUPPORTED,
-                    "a PQ / TurboQuant segment cannot score a stored row as a query (encode_internal_vector -> None): pass the original f32 segment to qmx_hnsw_build_quantized");
-        QMX_REQUIRE(original->dtype == QMX_DTYPE_F32 && original->dim == seg->dim && original->n >= seg->n && original->device == seg->device,
-                    QMX_ERR_BAD_ARG, "the original segment must be f32, of the same dim, on the same device and hold every row of the quantized segment");
-        QMX_REQUIRE(seg->dtype != QMX_DTYPE_PQ || seg->d_pq_pair ||
-                        (!mb && !option(OPT_HNSW_PQ_TABLE_BUILD) && pq_direct_walk_ok(seg->dim, seg->pq_m, seg->pq.chunk_size, seg->pq.n_centroids)),
-                    QMX_ERR_NOT_SUPPORTED,
-                    "PQ build: the centroid pair table (m x n_centroids^2 floats) exceeds 256 MB");
-    }
-    QMX_REQUIRE(seg->dtype == QMX_DTYPE_SQ_U8 || seg->dtype == QMX_DTYPE_PQ || seg->fast_layout(), QMX_ERR_NOT_SUPPORTED,
-                "adopted device block is not 16-byte aligned");
-    QMX_REQUIRE(bp->m >= 1 && bp->m0 >= bp->m && bp->m0 <= HNSW_BUILD_MAX_M0, QMX_ERR_BAD_ARG, "need 1 <= m <= m0 <= %u", HNSW_BUILD_MAX_M0);
-    QMX_REQUIRE(bp->ef_construct >= 1 && bp->ef_construct <= HNSW_MAX_EF, QMX_ERR_NOT_SUPPORTED, "ef_construct %u not in 1..%u",
-                bp->ef_construct, HNSW_MAX_EF);
-    QMX_REQUIRE(seg->n <= 0xFFFFFFFFull, QMX_ERR_BAD_ARG, "too many rows");
-    QMX_HIP(hipSetDevice(seg->device));
-    const uint32_t n = mb ? mb->n_points : (uint32_t)seg->n, m = bp->m, m0 = bp->m0;
-    const uint32_t max_batch = bp->max_batch ? bp->max_batch : 16384;
-
-    // ---- levels (graph_layers_builder.rs:388-396), the same draw as the CPU oracle ----
-    std::vector<uint8_t> level(std::max<uint32_t>(n, 1));
-    std::vector<uint32_t> up_off(std::max<uint32_t>(n, 1));
-    const double level_factor = 1.0 / log((double)(m > 2 ? m : 2));
-    uint64_t n_up = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t r = splitmix64(bp->seed ^ (0xA0761D6478BD642Full * ((uint64_t)i + 1)));
-        const double u = ((double)(r >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-        double lv = round(-log(u) * level_factor);
-        if (lv > (double)(HNSW_BUILD_MAX_LEVELS - 1)) lv = HNSW_BUILD_MAX_LEVELS - 1;
-        level[i] = (uint8_t)lv;
-        up_off[i] = (uint32_t)n_up;
-        n_up += level[i];
-    }
-    QMX_REQUIRE(n_up <= 0xFFFFFFFFull, QMX_ERR_BAD_ARG, "too many upper-level lists");
-    // deleted flags on the host: deleted points are never indexed and never entry points
-    std::vector<uint64_t> pdel, vdel;
-    if (mb) {
-        if (mb->h_deleted) pdel.assign(mb->h_deleted, mb->h_deleted + (mb->n_deleted_bits + 63) / 64);
-    } else
-    if (seg->d_point_deleted) { pdel.resize((seg->n_point_bits + 63) / 64); QMX_HIP(hipMemcpy(pdel.data(), seg->d_point_deleted, pdel.size() * 8, hipMemcpyDeviceToHost)); }
-    if (!mb && seg->d_vec_deleted) { vdel.resize((seg->n_vec_bits + 63) / 64); QMX_HIP(hipMemcpy(vdel.data(), seg->d_vec_deleted, vdel.size() * 8, hipMemcpyDeviceToHost)); }
-    const uint64_t n_point_bits = mb ? mb->n_deleted_bits : seg->n_point_bits;
-    auto live = [&](uint32_t id) {
-        const bool vd = (!vdel.empty() && id < seg->n_vec_bits) ? ((vdel[id >> 6] >> (id & 63)) & 1) : false;
-        const bool pd = !pdel.empty() ? (id < n_point_bits ? ((pdel[id >> 6] >> (id & 63)) & 1) : true) : false;
-        return !vd && !pd;
-    };
-
-    // ---- device state and the insertion loop ----
-    BuiltLinks r;
-    QMX_TRY(hnsw_build_links(seg, original, bp, mb, n, max_batch, level, up_off, n_up, pdel, live, r));
-    const std::vector<uint32_t> &links0 = r.links0, &cnt0 = r.cnt0, &linksU = r.linksU, &cntU = r.cntU;
-    const bool have_ep = r.have_ep;
-    const uint32_t ep_id = r.ep_id, ep_level = r.ep_level;
-    const std::vector<std::pair<uint32_t, uint32_t>> &extra = r.extra;
-    const size_t nn = std::max<uint32_t>(n, 1);
-
-    // ---- export: fixed-capacity lists -> plain GraphLinks arrays (graph_links/serializer.rs:52-209) ----
-    uint32_t maxl = 0;
-    for (uint32_t i = 0; i < n; ++i) maxl = std::max<uint32_t>(maxl, level[i]);
-    const uint32_t L = n ? maxl + 1 : 0;
-    qmx_hnsw host;      // (the plain arrays only: qmx_hnsw_create below makes the handle, which then takes them over for qmx_hnsw_export_plain)
-    qmx_hnsw *g = &host;
-    std::vector<uint64_t> count_ge(L + 1, 0);
-    for (uint32_t i = 0; i < n; ++i) for (uint32_t l = 0; l <= level[i]; ++l) count_ge[l]++;
-    // back_index: points by descending level, ties by id
-    std::vector<uint32_t> back(nn);
-    {
-        std::vector<uint64_t> start(L + 1, 0);
-        uint64_t acc = 0;
-        for (int32_t l = (int32_t)L - 1; l >= 0; --l) { start[l] = acc; acc += count_ge[l] - (l + 1 < (int32_t)L ? count_ge[l + 1] : 0); }
-        for (uint32_t i = 0; i < n; ++i) back[start[level[i]]++] = i;
-    }
-    g->h_reindex.resize(n);
-    for (uint32_t i = 0; i < n; ++i) g->h_reindex[back[i]] = i;
-    uint64_t total_slots = 0;
-    for (uint32_t l = 0; l < L; ++l) total_slots += count_ge[l];
-    g->h_level_offsets.assign(L + 1, 0);
-    g->h_offsets.assign(total_slots + 1, 0);
-    uint64_t nnb = 0;
-    for (uint32_t i = 0; i < n; ++i) { nnb += cnt0[i]; for (uint32_t l = 1; l <= level[i]; ++l) nnb += cntU[up_off[i] + l - 1]; }
-    g->h_neighbors.resize(nnb);
-    uint64_t off = 0, slot = 0;
-    for (uint32_t l = 0; l < L; ++l) {
-        g->h_level_offsets[l] = slot;
-        for (uint64_t j = 0; j < count_ge[l]; ++j) {
-            const uint32_t id = l == 0 ? (uint32_t)j : back[j];
-            g->h_offsets[slot++] = off;
-            const uint32_t len = l == 0 ? cnt0[id] : cntU[up_off[id] + l - 1];
-            const uint32_t *src = l == 0 ? &links0[(size_t)id * m0] : &linksU[((size_t)up_off[id] + l - 1) * m];
-            memcpy(g->h_neighbors.data() + off, src, (size_t)len * 4);
-            off += len;
-        }
-    }
-    g->h_level_offsets[L] = slot;
-    g->h_offsets[slot] = off;
-    if (have_ep) { g->h_ep_ids.push_back(ep_id); g->h_ep_levels.push_back(ep_level); }
-    for (auto &e : extra) { g->h_xp_ids.push_back(e.second); g->h_xp_levels.push_back(e.first); }
-    qmx_hnsw_desc d;
-    memset(&d, 0, sizeof(d));
-    d.m = m; d.m0 = m0; d.n_points = n; d.n_levels = L;
-    d.reindex = g->h_reindex.data(); d.level_offsets = g->h_level_offsets.data(); d.offsets = g->h_offsets.data();
-    d.n_offsets = g->h_offsets.size(); d.neighbors = g->h_neighbors.data(); d.n_neighbors = g->h_neighbors.size();
-    d.entry_point_ids = g->h_ep_ids.data(); d.entry_point_levels = g->h_ep_levels.data(); d.n_entry_points = (uint32_t)g->h_ep_ids.size();
-    d.extra_entry_point_ids = g->h_xp_ids.data(); d.extra_entry_point_levels = g->h_xp_levels.data();
-    d.n_extra_entry_points = (uint32_t)g->h_xp_ids.size();
-    d.device_id = seg->device;
-    QMX_TRY(qmx_hnsw_create(&d, out));
-    qmx_hnsw *dev = *out;
-    dev->h_reindex = std::move(g->h_reindex); dev->h_neighbors = std::move(g->h_neighbors);
-    dev->h_ep_ids = std::move(g->h_ep_ids); dev->h_ep_levels = std::move(g->h_ep_levels);
-    dev->h_xp_ids = std::move(g->h_xp_ids); dev->h_xp_levels = std::move(g->h_xp_levels);
-    dev->h_level_offsets = std::move(g->h_level_offsets); dev->h_offsets = std::move(g->h_offsets);
-    return QMX_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// payload-block sub-graphs merged into the graph (hnsw_build_payload.hpp)
-// ---------------------------------------------------------------------------------------------
-static int32_t launch_hnsw_payload_any(const qmx_segment *seg, const ScanArgs &a, const HnswPayloadArgs &h, int phase, uint32_t grid, int *per_cu) {
-    if (seg->dtype == QMX_DTYPE_SQ_U8) return launch_hnsw_payload_sq(nullptr, (int)seg->distance, a, h, phase, grid, per_cu);
-    if (seg->dtype == QMX_DTYPE_BQ) return launch_hnsw_payload_bq(nullptr, a, h, phase, grid, per_cu);
-    if (seg->dtype == QMX_DTYPE_PQ) return launch_hnsw_payload_pq(nullptr, a, h, phase, grid, per_cu);
-    if (seg->dtype == QMX_DTYPE_TQ) return launch_hnsw_payload_tq(nullptr, a, h, phase, grid, per_cu);
-    return launch_hnsw_payload_dense(nullptr, (int)seg->dtype, (int)seg->distance, a, h, phase, grid, per_cu);
-}
-
-static int32_t hnsw_payload_links_body(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw *main_graph, const qmx_hnsw_payload_blocks *bl, qmx_hnsw **out,
-                                       qmx_hnsw_payload_info *info) {
-    QMX_REQUIRE(seg->dtype <= QMX_DTYPE_BQ || seg->dtype == QMX_DTYPE_TQ, QMX_ERR_NOT_SUPPORTED, "payload links: dtype %u not supported", seg->dtype);
-    QMX_REQUIRE(!tq_l1(seg), QMX_ERR_NOT_SUPPORTED, "payload links through a TurboQuant storage over Manhattan are not built");
-    const bool from_original = seg->dtype == QMX_DTYPE_PQ || seg->dtype == QMX_DTYPE_TQ;
-    if (from_original) {   // as qmx_hnsw_build_quantized: the insertion searches score through the query of the ORIGINAL vector (point_scorer.rs:197-212)
-        QMX_REQUIRE(original, QMX_ERR_NOT_SUPPORTED,
-                    "a PQ / TurboQuant segment cannot score a stored row as a query (encode_internal_vector -> None): pass the original f32 segment");
-        QMX_REQUIRE(original->dtype == QMX_DTYPE_F32 && original->dim == seg->dim && original->n >= seg->n && original->device == seg->device,
-                    QMX_ERR_BAD_ARG, "the original segment must be f32, of the same dim, on the same device and hold every row of the quantized segment");
-        QMX_REQUIRE(seg->dtype != QMX_DTYPE_PQ || seg->d_pq_pair ||
-                        (!option(OPT_HNSW_PQ_TABLE_BUILD) && pq_direct_walk_ok(seg->dim, seg->pq_m, seg->pq.chunk_size, seg->pq.n_centroids)),
-                    QMX_ERR_NOT_SUPPORTED, "PQ build: the centroid pair table (m x n_centroids^2 floats) exceeds 256 MB");
-    }
-    QMX_REQUIRE(seg->dtype == QMX_DTYPE_SQ_U8 || seg->dtype == QMX_DTYPE_PQ || seg->fast_layout(), QMX_ERR_NOT_SUPPORTED, "adopted device block is not 16-byte aligned");
-    QMX_REQUIRE(bl->payload_m0 >= 1 && bl->payload_m0 <= HNSW_BUILD_MAX_M0, QMX_ERR_BAD_ARG, "payload_m0 %u not in 1..%u", bl->payload_m0, HNSW_BUILD_MAX_M0);
-    QMX_REQUIRE(bl->ef_construct >= 1 && bl->ef_construct <= HNSW_MAX_EF, QMX_ERR_BAD_ARG, "ef_construct %u not in 1..%u", bl->ef_construct, HNSW_MAX_EF);
-    QMX_REQUIRE(seg->n <= 0xFFFFFFFFull, QMX_ERR_BAD_ARG, "too many rows");
-    QMX_REQUIRE(bl->n_blocks == 0 || bl->offsets, QMX_ERR_BAD_ARG, "block offsets missing");
-    QMX_REQUIRE(bl->n_blocks < 0xFFFFFFFFu, QMX_ERR_BAD_ARG, "too many blocks");
-    QMX_REQUIRE(!is_device_ptr(bl->offsets) && !is_device_ptr(bl->points), QMX_ERR_BAD_ARG, "block offsets and points are host arrays");
-    const uint32_t n = (uint32_t)seg->n, n_blocks = bl->n_blocks, pm0 = bl->payload_m0;
-    const uint32_t max_batch = bl->max_batch ? bl->max_batch : 16384;
-    if (n_blocks) {
-        QMX_REQUIRE(bl->offsets[0] == 0, QMX_ERR_BAD_ARG, "block offsets must start at 0");
-        for (uint32_t b = 0; b < n_blocks; ++b)
-            QMX_REQUIRE(bl->offsets[b] <= bl->offsets[b + 1], QMX_ERR_BAD_ARG, "block offsets decrease at block %u", b);
-        QMX_REQUIRE(bl->offsets[n_blocks] == 0 || bl->points, QMX_ERR_BAD_ARG, "block points missing");
-    }
-    if (main_graph) {
-        QMX_REQUIRE(main_graph->n_points == n && main_graph->device == seg->device, QMX_ERR_BAD_ARG,
-                    "the main graph must hold the segment's %u points on its device (it has %u)", n, main_graph->n_points);
-        QMX_REQUIRE(n == 0 || (!main_graph->h_offsets.empty() && main_graph->h_offsets.size() > n), QMX_ERR_NOT_SUPPORTED,
-                    "payload links: the main graph keeps no host copy of its plain arrays (graphs built by qmx_hnsw_build do)");
-    }
-    QMX_HIP(hipSetDevice(seg->device));
-
-    // ---- liveness on the host, as the main build's ----
-    std::vector<uint64_t> pdel, vdel;
-    if (seg->d_point_deleted) { pdel.resize((seg->n_point_bits + 63) / 64); QMX_HIP(hipMemcpy(pdel.data(), seg->d_point_deleted, pdel.size() * 8, hipMemcpyDeviceToHost)); }
-    if (seg->d_vec_deleted) { vdel.resize((seg->n_vec_bits + 63) / 64); QMX_HIP(hipMemcpy(vdel.data(), seg->d_vec_deleted, vdel.size() * 8, hipMemcpyDeviceToHost)); }
-    auto live = [&](uint32_t id) {
-        const bool vd = (!vdel.empty() && id < seg->n_vec_bits) ? ((vdel[id >> 6] >> (id & 63)) & 1) : false;
-        const bool pd = !pdel.empty() ? (id < seg->n_point_bits ? ((pdel[id >> 6] >> (id & 63)) & 1) : true) : false;
-        return !vd && !pd;
-    };
-
-    // ---- the membership slots: the live points of every block, block after block ----
-    std::vector<uint32_t> pts;
-    std::vector<uint64_t> blk_off(n_blocks + 1, 0);
-    {
-        std::vector<uint32_t> stamp(n, 0);      // block + 1 that listed the point last
-        for (uint32_t b = 0; b < n_blocks; ++b) {
-            for (uint64_t i = bl->offsets[b]; i < bl->offsets[b + 1]; ++i) {
-                const uint32_t p = bl->points[i];
-                QMX_REQUIRE(p < n, QMX_ERR_BAD_ARG, "block %u lists point %u of %u", b, p, n);
-                QMX_REQUIRE(stamp[p] != b + 1, QMX_ERR_BAD_ARG, "block %u lists point %u twice", b, p);
-                stamp[p] = b + 1;
-                if (live(p)) pts.push_back(p);
-            }
-            blk_off[b + 1] = pts.size();
-        }
-    }
-    const uint64_t n_slots = pts.size();
-    uint32_t largest = 0, blocks_built = 0;
-    for (uint32_t b = 0; b < n_blocks; ++b) {
-        const uint64_t len = blk_off[b + 1] - blk_off[b];
-        largest = (uint32_t)std::max<uint64_t>(largest, len);
-        blocks_built += len ? 1 : 0;
-    }
-
-    // ---- the schedule: a round holds the next batch of every block that still has points (batch rule per block: <= max(1, inserted / 32), <= max_batch);
-    // position 0 of a block is its entry point and needs no search.  The rounds of a block depend on its size alone, so there are as many rounds as
-    // the largest block needs by itself
-    std::vector<uint32_t> item_block, item_pos;
-    std::vector<uint64_t> round_first(1, 0);
-    {
-        item_block.reserve(n_slots);
-        item_pos.reserve(n_slots);
-        std::vector<uint32_t> active, done_pos(n_blocks, 1);
-        for (uint32_t b = 0; b < n_blocks; ++b) if (blk_off[b + 1] - blk_off[b] > 1) active.push_back(b);
-        while (!active.empty()) {
-            size_t keep = 0;
-            for (size_t k = 0; k < active.size(); ++k) {
-                const uint32_t b = active[k], len = (uint32_t)(blk_off[b + 1] - blk_off[b]);
-                const uint32_t count = std::min<uint32_t>({max_batch, std::max<uint32_t>(1, done_pos[b] / 32), len - done_pos[b]});
-                for (uint32_t i = 0; i < count; ++i) { item_block.push_back(b); item_pos.push_back(done_pos[b] + i); }
-                done_pos[b] += count;
-                if (done_pos[b] < len) active[keep++] = b;
-            }
-            active.resize(keep);
-            round_first.push_back(item_block.size());
-        }
-    }
-    const size_t n_rounds = round_first.size() - 1;
-    uint64_t max_round = 1;
-    for (size_t r = 0; r < n_rounds; ++r) max_round = std::max<uint64_t>(max_round, round_first[r + 1] - round_first[r]);
-    QMX_REQUIRE(max_round <= 0xFFFFFFFFull, QMX_ERR_BAD_ARG, "too many insertions in one round");
-
-    // ---- device state ----
-    DevBuf b_pts, b_blk, b_iblk, b_ipos, b_links, b_cnt, b_lock, b_sel, b_sels, b_selc, b_vis, b_log, b_next, b_normf, b_normi, b_ipt, b_bq, b_bqsrc, b_rot;
-    QMX_TRY(dev_upload(b_pts, pts.data(), pts.size()));
-    QMX_TRY(dev_upload(b_blk, blk_off.data(), blk_off.size()));
-    QMX_TRY(dev_upload(b_iblk, item_block.data(), item_block.size()));
-    QMX_TRY(dev_upload(b_ipos, item_pos.data(), item_pos.size()));
-    const size_t ns1 = std::max<uint64_t>(n_slots, 1);
-    QMX_TRY(b_links.reserve(ns1 * pm0 * 4)); QMX_TRY(b_cnt.reserve(ns1 * 4)); QMX_TRY(b_lock.reserve(ns1 * 4));
-    QMX_HIP(hipMemset(b_cnt.p, 0, ns1 * 4));
-    QMX_HIP(hipMemset(b_lock.p, 0, ns1 * 4));
-    uint32_t launches = 0;
-    if (n_rounds) {
-        QMX_TRY(b_sel.reserve((size_t)max_round * pm0 * 4)); QMX_TRY(b_sels.reserve((size_t)max_round * pm0 * 4)); QMX_TRY(b_selc.reserve((size_t)max_round * 4));
-        ScanArgs a;
-        fill_args_segment(seg, a);
-        HnswPayloadArgs h;
-        memset(&h, 0, sizeof(h));
-        h.points = (const uint32_t *)b_pts.p; h.blk_off = (const uint64_t *)b_blk.p;
-        h.item_block = (const uint32_t *)b_iblk.p; h.item_pos = (const uint32_t *)b_ipos.p;
-        h.pm0 = pm0; h.links = (uint32_t *)b_links.p; h.cnt = (uint32_t *)b_cnt.p; h.lock = (uint32_t *)b_lock.p;
-        h.ef_construct = bl->ef_construct;
-        h.sel_pos = (uint32_t *)b_sel.p; h.sel_scores = (float *)b_sels.p; h.sel_cnt = (uint32_t *)b_selc.p;
-        const uint64_t dev_row_bytes = seg->dtype == QMX_DTYPE_SQ_U8 ? (uint64_t)seg->sq.actual_dim : seg->row_bytes;      // (as the main build)
-        h.row_bytes = (uint32_t)dev_row_bytes;
-        h.lds_query_bytes = (uint32_t)((dev_row_bytes + 127) / 128 * 128 + 128);
-        QMX_REQUIRE(h.lds_query_bytes <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "rows of %llu bytes do not fit the LDS query slot", (unsigned long long)dev_row_bytes);
-        if (seg->dtype == QMX_DTYPE_U8 && seg->distance == QMX_DISTANCE_COSINE && seg->dim >= 32) {
-            const size_t nn = std::max<uint32_t>(n, 1);
-            QMX_TRY(b_normf.reserve(nn * 4)); QMX_TRY(b_normi.reserve(nn * 4));
-            QMX_TRY(launch_u8_row_norms(nullptr, seg->d_rows, seg->row_stride, n, seg->dim, seg->flags, (float *)b_normf.p, (int32_t *)b_normi.p));
-            a.row_norms_f = (const float *)b_normf.p;
-            a.row_norms_i = (const int32_t *)b_normi.p;
-        }
-        // PQ / TurboQuant: the query entries of a round's items, made from their original vectors before phase 1 (as the main build does per batch; the
-        // items' rows are gathered by id instead of copied as a range)
-        bool pq_direct_build = false;
-        if (from_original) {
-            std::vector<uint32_t> item_point(item_block.size());
-            for (size_t i = 0; i < item_point.size(); ++i) item_point[i] = pts[blk_off[item_block[i]] + item_pos[i]];
-            QMX_TRY(dev_upload(b_ipt, item_point.data(), item_point.size()));
-            QMX_TRY(b_bqsrc.reserve((size_t)max_round * seg->dim * sizeof(float)));
-        }
-        if (seg->dtype == QMX_DTYPE_PQ) {
-            const uint64_t lut_stride = ((uint64_t)seg->pq_m * seg->pq.n_centroids * sizeof(float) + 15) & ~15ull;
-            pq_direct_build = !option(OPT_HNSW_PQ_TABLE_BUILD) && pq_direct_walk_ok(seg->dim, seg->pq_m, seg->pq.chunk_size, seg->pq.n_centroids);
-            if (!pq_direct_build) QMX_TRY(b_bq.reserve((size_t)max_round * lut_stride));
-            h.batch_queries = (const unsigned char *)b_bq.p;
-            h.batch_q_stride = lut_stride;
-            h.lds_query_bytes = 0;
-            if (pq_direct_build) {
-                h.batch_queries = (const unsigned char *)b_bqsrc.p;
-                h.batch_q_stride = (uint64_t)seg->dim * 4;
-                h.lds_query_bytes = seg->dim * 4;
-            }
-        }
-        if (seg->dtype == QMX_DTYPE_TQ) {
-            QMX_TRY(b_bq.reserve((size_t)max_round * a.q_stride));
-            QMX_TRY(b_rot.reserve((size_t)max_round * seg->tq_padded_dim * sizeof(double)));
-            h.batch_queries = (const unsigned char *)b_bq.p;
-            h.batch_q_stride = a.q_stride;
-            h.lds_query_bytes = a.q_stride;
-        }
-        QMX_REQUIRE(h.lds_query_bytes <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "query entries of %u bytes do not fit the LDS query slot", h.lds_query_bytes);
-        h.log_cap = 16384;
-        h.vis_words = std::max<uint64_t>(1, ((uint64_t)largest + 31) / 32);     // the visited set of an insertion search: one bit per position of the largest BLOCK
-        int per_cu1 = 1, per_cu2 = 1;
-        QMX_TRY(launch_hnsw_payload_any(seg, a, h, 1, 0, &per_cu1));
-        QMX_TRY(launch_hnsw_payload_any(seg, a, h, 2, 0, &per_cu2));
-        uint64_t slots1 = std::min<uint64_t>({(uint64_t)seg->num_cus * per_cu1, (uint64_t)HNSW_SLOT_CAP, max_round});
-        slots1 = std::max<uint64_t>(1, std::min<uint64_t>(slots1, HNSW_VIS_BUDGET / (h.vis_words * 4)));
-        const uint64_t slots2 = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)seg->num_cus * per_cu2, max_round));
-        QMX_TRY(b_next.reserve(8));
-        h.next = (uint32_t *)b_next.p;
-        QMX_TRY(b_vis.reserve((size_t)slots1 * h.vis_words * 4));
-        QMX_TRY(b_log.reserve((size_t)slots1 * h.log_cap * 4));
-        QMX_HIP(hipMemset(b_vis.p, 0, (size_t)slots1 * h.vis_words * 4));
-        h.visited = (uint32_t *)b_vis.p;
-        h.vis_log = (uint32_t *)b_log.p;
-        for (size_t r = 0; r < n_rounds; ++r) {
-            h.first_item = round_first[r];
-            h.count = (uint32_t)(round_first[r + 1] - round_first[r]);
-            const uint32_t grid1 = (uint32_t)std::min<uint64_t>(slots1, h.count), grid2 = (uint32_t)std::min<uint64_t>(slots2, h.count);
-            const uint32_t start[2] = {grid1, grid2};
-            QMX_HIP(hipMemcpyAsync(h.next, start, sizeof(start), hipMemcpyHostToDevice, nullptr));      // (pageable source: staged before the call returns)
-            if (from_original) {
-                float *src = (float *)b_bqsrc.p;
-                QMX_TRY(launch_gather_rows(nullptr, original->d_rows, original->row_stride, (const uint32_t *)b_ipt.p + h.first_item, h.count, seg->dim * 4, src,
-                                           (uint64_t)seg->dim * 4));
-                if (seg->distance == QMX_DISTANCE_COSINE) QMX_TRY(launch_cosine_preprocess_f32(nullptr, src, src, h.count, seg->dim));
-                if (seg->dtype == QMX_DTYPE_PQ) {
-                    if (!pq_direct_build) QMX_TRY(launch_pq_lut(nullptr, seg->distance, seg->dim, seg->pq, seg->d_centroids, src, h.count, (float *)b_bq.p));
-                } else {
-                    QMX_TRY(launch_tq_rotate(nullptr, src, h.count, tq_rotation(seg), (double *)b_rot.p));
-                    QMX_TRY(launch_tq_query_encode(nullptr, (double *)b_rot.p, h.count, seg->tq_padded_dim, seg->tq_value_bits, seg->distance == QMX_DISTANCE_EUCLID ? 1 : 0,
-                                                   b_bq.p, a.q_stride, a.aux_off, seg->d_tq_shift, seg->d_tq_scale, a.tq_qbytes_off));
-                }
-            }
-            QMX_TRY(launch_hnsw_payload_any(seg, a, h, 1, grid1, &per_cu1));
-            QMX_TRY(launch_hnsw_payload_any(seg, a, h, 2, grid2, &per_cu2));
-            launches += 2;
-        }
-    }
-
-    // ---- merge_from_other on level 0, every point at once ----
-    // the memberships of every point in block order (a counting sort of the slots by point: slots ascend with their blocks)
-    std::vector<uint64_t> mem_off((size_t)n + 1, 0), mem_slot(n_slots), mem_slot0(n_slots);
-    for (uint64_t s = 0; s < n_slots; ++s) mem_off[pts[s] + 1]++;
-    for (uint32_t p = 0; p < n; ++p) mem_off[p + 1] += mem_off[p];
-    {
-        std::vector<uint64_t> fill(mem_off.begin(), mem_off.end() - 1);
-        for (uint32_t b = 0; b < n_blocks; ++b)
-            for (uint64_t s = blk_off[b]; s < blk_off[b + 1]; ++s) {
-                const uint64_t at = fill[pts[s]]++;
-                mem_slot[at] = s;
-                mem_slot0[at] = blk_off[b];
-            }
-    }
-    DevBuf b_moff, b_mslot, b_mslot0, b_cap, b_len, b_tmp, b_out;
-    QMX_TRY(dev_upload(b_moff, mem_off.data(), mem_off.size()));
-    QMX_TRY(dev_upload(b_mslot, mem_slot.data(), mem_slot.size()));
-    QMX_TRY(dev_upload(b_mslot0, mem_slot0.data(), mem_slot0.size()));
-    QMX_TRY(b_cap.reserve(((size_t)n + 1) * 8)); QMX_TRY(b_len.reserve(((size_t)n + 1) * 8));
-    HnswPayloadMergeArgs mg;
-    memset(&mg, 0, sizeof(mg));
-    mg.n_points = n;
-    if (main_graph && n) { mg.main_off = main_graph->d_offsets; mg.main_nb = main_graph->d_neighbors; }
-    mg.mem_off = (const uint64_t *)b_moff.p; mg.mem_slot = (const uint64_t *)b_mslot.p; mg.mem_slot0 = (const uint64_t *)b_mslot0.p;
-    mg.points = (const uint32_t *)b_pts.p; mg.links = (const uint32_t *)b_links.p; mg.cnt = (const uint32_t *)b_cnt.p; mg.pm0 = pm0;
-    mg.cap = (uint64_t *)b_cap.p; mg.len = (uint64_t *)b_len.p;
-    uint64_t cap_total = 0, l0_total = 0;
-    std::vector<uint64_t> l0_off((size_t)n + 1, 0);
-    std::vector<uint32_t> l0_nb;
-    if (n) {
-        QMX_TRY(launch_hnsw_payload_merge_caps(nullptr, mg));
-        QMX_TRY(launch_exclusive_scan_u64(nullptr, mg.cap, n));
-        QMX_HIP(hipMemcpy(&cap_total, mg.cap + n, 8, hipMemcpyDeviceToHost));
-        QMX_TRY(b_tmp.reserve(std::max<uint64_t>(cap_total, 1) * 4));
-        mg.tmp = (uint32_t *)b_tmp.p;
-        QMX_TRY(launch_hnsw_payload_merge_rows(nullptr, mg));
-        QMX_TRY(launch_exclusive_scan_u64(nullptr, mg.len, n));
-        QMX_HIP(hipMemcpy(l0_off.data(), mg.len, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
-        l0_total = l0_off[n];
-        QMX_REQUIRE(l0_total <= cap_total, QMX_ERR_OTHER, "payload links: the merge wrote %llu links into %llu slots", (unsigned long long)l0_total,
-                    (unsigned long long)cap_total);
-        QMX_TRY(b_out.reserve(std::max<uint64_t>(l0_total, 1) * 4));
-        mg.out = (uint32_t *)b_out.p;
-        QMX_TRY(launch_hnsw_payload_merge_compact(nullptr, mg));
-        l0_nb.resize(l0_total);
-        if (l0_total) QMX_HIP(hipMemcpy(l0_nb.data(), mg.out, l0_total * 4, hipMemcpyDeviceToHost));
-    }
-    QMX_HIP(hipDeviceSynchronize());
-
-    // ---- the plain arrays of the result: the merged level 0, the main graph's upper levels behind it ----
-    qmx_hnsw host;
-    qmx_hnsw *g = &host;
-    const uint32_t L = main_graph ? main_graph->n_levels : (n ? 1u : 0u);
-    uint64_t main_l0 = 0;
-    if (main_graph && n) {
-        main_l0 = main_graph->h_offsets[n];
-        g->h_reindex = main_graph->h_reindex;
-        g->h_level_offsets = main_graph->h_level_offsets;
-        g->h_offsets.resize(main_graph->h_offsets.size());
-        std::copy(l0_off.begin(), l0_off.end(), g->h_offsets.begin());
-        for (size_t s = (size_t)n + 1; s < g->h_offsets.size(); ++s) g->h_offsets[s] = main_graph->h_offsets[s] - main_l0 + l0_total;
-        g->h_neighbors = std::move(l0_nb);
-        g->h_neighbors.insert(g->h_neighbors.end(), main_graph->h_neighbors.begin() + (ptrdiff_t)main_l0, main_graph->h_neighbors.end());
-        g->h_ep_ids = main_graph->h_ep_ids; g->h_ep_levels = main_graph->h_ep_levels;
-        g->h_xp_ids = main_graph->h_xp_ids; g->h_xp_levels = main_graph->h_xp_levels;
-    } else if (n) {
-        g->h_reindex.resize(n);
-        for (uint32_t i = 0; i < n; ++i) g->h_reindex[i] = i;
-        g->h_level_offsets = {0, n};
-        g->h_offsets = std::move(l0_off);
-        g->h_neighbors = std::move(l0_nb);
-    }
-    for (uint32_t b = 0; b < n_blocks; ++b)      // EntryPoints::merge_from_other: the block graphs' entry points behind the main graph's, in block order
-        if (blk_off[b + 1] > blk_off[b]) { g->h_ep_ids.push_back(pts[blk_off[b]]); g->h_ep_levels.push_back(0); }
-    uint64_t longest = 0;
-    for (uint32_t p = 0; p < n; ++p) longest = std::max<uint64_t>(longest, g->h_offsets[p + 1] - g->h_offsets[p]);
-    qmx_hnsw_desc d;
-    memset(&d, 0, sizeof(d));
-    if (main_graph) { d.m = main_graph->m; d.m0 = main_graph->m0; }
-    else { d.m = 0; d.m0 = pm0; }
-    d.n_points = n; d.n_levels = L;
-    d.reindex = g->h_reindex.data(); d.level_offsets = g->h_level_offsets.data(); d.offsets = g->h_offsets.data();
-    d.n_offsets = g->h_offsets.size(); d.neighbors = g->h_neighbors.data(); d.n_neighbors = g->h_neighbors.size();
-    d.entry_point_ids = g->h_ep_ids.data(); d.entry_point_levels = g->h_ep_levels.data(); d.n_entry_points = (uint32_t)g->h_ep_ids.size();
-    d.extra_entry_point_ids = g->h_xp_ids.data(); d.extra_entry_point_levels = g->h_xp_levels.data();
-    d.n_extra_entry_points = (uint32_t)g->h_xp_ids.size();
-    d.device_id = seg->device;
-    QMX_TRY(hnsw_create_checked(&d, out, true));
-    qmx_hnsw *dev = *out;
-    dev->h_reindex = std::move(g->h_reindex); dev->h_neighbors = std::move(g->h_neighbors);
-    dev->h_ep_ids = std::move(g->h_ep_ids); dev->h_ep_levels = std::move(g->h_ep_levels);
-    dev->h_xp_ids = std::move(g->h_xp_ids); dev->h_xp_levels = std::move(g->h_xp_levels);
-    dev->h_level_offsets = std::move(g->h_level_offsets); dev->h_offsets = std::move(g->h_offsets);
-    if (info) {
-        info->blocks_built = blocks_built;
-        info->launches = launches;
-        info->links_added = l0_total - main_l0;
-        info->longest_row = longest;
-    }
-    return QMX_OK;
-}
-
-int32_t qmx_hnsw_build_payload_links(const qmx_segment *seg, const qmx_segment *original, const qmx_hnsw *main_graph, const qmx_hnsw_payload_blocks *blocks,
-                                     qmx_hnsw **out, qmx_hnsw_payload_info *info) {
-    if (out) *out = nullptr;
-    if (info) memset(info, 0, sizeof(*info));
-    QMX_REFUSE_SPARSE(seg);
-    QMX_REFUSE_SPARSE(original);
-    QMX_REQUIRE(seg && blocks && out, QMX_ERR_BAD_ARG, "NULL argument");
-    try {
-        const int32_t rc = hnsw_payload_links_body(seg, original, main_graph, blocks, out, info);
-        if (rc != QMX_OK && *out) { qmx_hnsw_destroy(*out); *out = nullptr; }
-        return rc;
-    } catch (...) {         // nothing C++ crosses the C ABI
-        set_error("qmx_hnsw_build_payload_links: out of host memory");
-        return QMX_ERR_OUT_OF_MEMORY;
-    }
 }
 
 static int32_t launch_hnsw(const qmx_query *q, const ScanArgs &a, const HnswArgs &h, uint32_t grid, int *per_cu) {

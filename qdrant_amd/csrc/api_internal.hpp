@@ -520,6 +520,7 @@ int32_t hnsw_check(const qmx_hnsw *g, const qmx_query *q, uint32_t top, uint32_t
 int32_t hnsw_search_sync(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts,
                                 const volatile uint8_t *is_stopped, qmx_counters *counters, bool acorn);
 void fill_args(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, ScanArgs &a);
+void fill_args_storage(const qmx_segment *s, ScanArgs &a);      // (api_query.hip) the part of fill_args that is the segment's alone
 int32_t launch_scan(const qmx_query *q, int qt, ScanMode mode, const ScanArgs &a, uint32_t *grid);
 int32_t tq_l1_scores_device(qmx_query *q, uint32_t q0, uint32_t nq, const uint32_t *d_ids, uint64_t n, float *d_scores, uint64_t stride, const PairSel *sel);
 // (short_list: an id list of at most PRESCAN_BESIDE_MAX_N rows - a prefilter's sample, the ids of qmx_score_points - may take the shape that fits beside a

@@ -285,17 +285,15 @@ int32_t qmx_query_read_encoded(const qmx_query *q, uint32_t query_index, void *o
 // ---------------------------------------------------------------------------------------------
 // scoring
 // ---------------------------------------------------------------------------------------------
-void fill_args(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, ScanArgs &a) {
-    const qmx_segment *s = q->seg;
+// What a scan or a hop reads of the segment itself, whoever asks (a query batch: fill_args; a build, whose queries are stored rows: api_hnsw_build.hpp):
+// `a` zeroed, then the rows, the body / tail split, the deleted view, the flags, and the SQ / PQ / TurboQuant storage fields - which are zero or null in a
+// segment of another dtype (qmx_segment_create sets them for their own dtype alone).
+void fill_args_storage(const qmx_segment *s, ScanArgs &a) {
     memset(&a, 0, sizeof(a));
     a.rows = s->d_rows;
     a.n_rows = s->n;
     a.row_stride = s->row_stride;
     a.dim = s->scan_dim;
-    a.nq = nq_tile;
-    a.queries = (const char *)q->d_queries + (size_t)tile0 * q->q_stride;
-    a.q_stride = q->q_stride;
-    a.aux_off = q->aux_off;
     {   // SIMD body / scalar tail split of the reference leaf (AVX loops step 32 elements)
         const uint32_t eb = elem_bytes(s->dtype);
         const uint32_t full = s->dtype <= QMX_DTYPE_U8 ? s->scan_dim - s->scan_dim % 32 : s->scan_dim;
@@ -305,6 +303,32 @@ void fill_args(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, ScanArgs &a
         a.tail_start = full;
     }
     a.del = s->deleted_view();
+    a.flags = s->flags;
+    a.sq_multiplier = s->sq.multiplier;
+    a.row_offsets = s->d_row_offsets;
+    a.pq_m = s->pq_m;
+    a.pq_ncent = s->pq.n_centroids;
+    a.pq_pair = s->d_pq_pair;
+    a.pq_invert = s->pq.invert;
+    if (s->dtype == QMX_DTYPE_PQ) {      // the codebook itself (the LUT-free walk, pq.hip HopPQDirect; the table-free build)
+        a.pq_centroids = s->d_centroids;
+        a.pq_dim = s->dim;
+        a.pq_chunk = s->pq.chunk_size;
+        a.pq_kind = (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) ? 0u : s->distance == QMX_DISTANCE_MANHATTAN ? 1u : 2u;
+    }
+    a.tq_sf = s->d_tq_sf;
+    a.tq_l2 = s->d_tq_l2;
+    a.tq_bits = s->tq_value_bits;
+    a.tq_invert = s->tq_invert ? 1 : 0;
+}
+
+void fill_args(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, ScanArgs &a) {
+    const qmx_segment *s = q->seg;
+    fill_args_storage(s, a);
+    a.nq = nq_tile;
+    a.queries = (const char *)q->d_queries + (size_t)tile0 * q->q_stride;
+    a.q_stride = q->q_stride;
+    a.aux_off = q->aux_off;
     if (q->has_filter) {
         a.del.allowed = (const uint64_t *)q->filter.p;
         a.del.n_allowed_bits = q->n_filter_bits;
@@ -317,27 +341,10 @@ void fill_args(const qmx_query *q, uint32_t tile0, uint32_t nq_tile, ScanArgs &a
     }
     a.err_flag = q->d_err;
     a.tq_l1 = s->d_tq_l1;
-    a.flags = s->flags;
-    a.sq_multiplier = s->sq.multiplier;
-    a.row_offsets = s->d_row_offsets;
-    a.pq_m = s->pq_m;
-    a.pq_ncent = s->pq.n_centroids;
-    a.pq_pair = s->d_pq_pair;
-    a.pq_invert = s->pq.invert;
-    if (s->dtype == QMX_DTYPE_PQ) {      // the codebook itself (the LUT-free walk, pq.hip HopPQDirect)
-        a.pq_centroids = s->d_centroids;
-        a.pq_dim = s->dim;
-        a.pq_chunk = s->pq.chunk_size;
-        a.pq_kind = (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) ? 0u : s->distance == QMX_DISTANCE_MANHATTAN ? 1u : 2u;
-    }
     a.bq_dim = s->dim;
     // calculate_metric's match: (Dot | Cosine, invert = false) and (L1 | L2, invert = true) -> zeros - xor; the toggled pairs -> xor - zeros
     a.bq_flip = (s->flags & QMX_SEG_BQ_TOGGLE_INVERT) ? 1 : 0;
     a.bq_qbits = q->bq_bits;
-    a.tq_sf = s->d_tq_sf;
-    a.tq_l2 = s->d_tq_l2;
-    a.tq_bits = s->tq_value_bits;
-    a.tq_invert = s->tq_invert ? 1 : 0;
     a.tq_planes = (s->tq_value_bits == 1 && s->d_tq_shift) ? 16 : 8;
     a.tq_qbytes_off = q->tq_qbytes_off;
     // |low + 128 high| <= 8127 * 128 * dims (4 / 2 bits); |2 v.q - sum q| <= 3 * 32767 * dims (1 bit, 16-bit TQ+ queries)

@@ -1,4 +1,4 @@
-// hnsw_payload_args.hpp — arguments and launchers of the payload-block build (hnsw_build_payload.hpp, hnsw_build_payload.hip): what api_hnsw.hip sees of it.
+// hnsw_payload_args.hpp — arguments and launchers of the payload-block build (hnsw_build_payload.hpp, hnsw_build_payload.hip): what api_hnsw_payload.hip sees of it.
 #pragma once
 #include "kernels.hpp"
 

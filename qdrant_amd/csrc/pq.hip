@@ -655,7 +655,7 @@ int32_t launch_hnsw_custom_pq(hipStream_t st, const ScanArgs &a, const HnswArgs 
 // ------------------------------------------------------------------------------------------
 // HNSW build over a PQ segment (hnsw/build.rs:334-341 + point_scorer.rs:183-218).  EncodedVectorsPQ cannot turn a stored row
 // into a query (encode_internal_vector -> None), so the searches of an insertion score through the LUT of the point's ORIGINAL
-// vector (HopPQ over the batch's LUTs, made by api_hnsw.hip before phase 1) while everything stored <-> stored — the heuristic, the
+// vector (HopPQ over the batch's LUTs, made by api_hnsw_build.hpp BuildQueryEntries before phase 1) while everything stored <-> stored — the heuristic, the
 // back links, an entry point at or below the new point's level — is EncodedVectorsPQ::score_internal (:574-618): the sum over
 // chunks of the distance between the two rows' centroids.  Those chunk distances are tabulated once per segment
 // (pair[c][i][j], m x 256 x 256 f32 = 25 MB at m = 96) with the reference's own inner loop, so a pair score is m table gathers
@@ -803,7 +803,7 @@ static bool pq_direct_build_ok(const ScanArgs &a) {
 template <int CHUNK, int SPLIT, int R>
 struct HopPQDirectBuild : HopPQDirect<CHUNK, SPLIT, R> {};
 int32_t launch_hnsw_build_pq(hipStream_t st, const ScanArgs &a, const HnswBuildArgs &h, int phase, uint32_t grid, int *per_cu) {
-    if (h.lds_query_bytes != 0 && pq_direct_build_ok(a)) {      // the batch's entries are the original vectors themselves (api_hnsw.hip): no table of any kind
+    if (h.lds_query_bytes != 0 && pq_direct_build_ok(a)) {      // the batch's entries are the original vectors themselves (api_hnsw_build.hpp BuildQueryEntries): no table of any kind
         QMX_REQUIRE(h.batch_queries, QMX_ERR_BAD_ARG, "PQ build needs the batch's original vectors");
         if (a.pq_chunk == 16) return launch_hnsw_build_hop<HopPQDirectBuild<16, 4, 2>, HopPQInternalDirect<16>>(st, a, h, phase, grid, per_cu);
         if (a.pq_chunk == 8) return launch_hnsw_build_hop<HopPQDirectBuild<8, 4, 4>, HopPQInternalDirect<8>>(st, a, h, phase, grid, per_cu);
