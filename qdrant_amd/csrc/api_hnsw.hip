@@ -1,6 +1,7 @@
 // api_hnsw.hip — the C-ABI of include/qdrant_amd.h, HNSW graphs: create / import / export, the walks.  (The device builds: api_hnsw_build.hip,
 // api_hnsw_payload.hip.)  (One of the api_*.hip translation units; what they share: api_internal.hpp.)
 #include "api_hnsw_build.hpp"
+#include "hnsw_layout.hpp"
 #include <algorithm>
 
 extern "C" {
@@ -381,7 +382,7 @@ int32_t hnsw_enqueue(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef,
         }
     }
     if (std::max(top, ef) > HNSW_MAX_EF_REG && !mw && !cw && !tq_l1(s)) {   // a list this long lives in LDS behind the query entry, which is then always staged (a PQ LUT too)
-        const size_t beam = ((size_t)std::max(top, ef) * 9 + 15) / 16 * 16;
+        const size_t beam = hnsw_beam_lds(std::max(top, ef));
         QMX_REQUIRE((size_t)a.q_stride + beam + 2048 <= 160 * 1024, QMX_ERR_NOT_SUPPORTED,
                     "hnsw max(top, ef) = %u: the query entry (%u bytes) and the list do not fit the LDS together", std::max(top, ef), a.q_stride);
         h.lds_query_bytes = a.q_stride;

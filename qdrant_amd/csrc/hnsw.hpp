@@ -29,647 +29,15 @@
 //     log overflows).
 //   * links = the plain GraphLinks arrays (graph_links/view.rs: reindex, level_offsets, offsets,
 //     neighbors) as serialised by graph_links/serializer.rs:52-176.
+//
+// Files: hnsw_hop.hpp (the hop scorers and hop_score), hnsw_sets.hpp (beam, visited table, reference heaps), hnsw_layout.hpp (the dynamic LDS of a
+// launch), and here the walk: hnsw_search_one, the staging of a search's query entry, the kernel and its launchers.
 #pragma once
-#include "custom_combine.hpp"
-#include "scan_common.hpp"
+#include "hnsw_hop.hpp"
+#include "hnsw_layout.hpp"
+#include "hnsw_sets.hpp"
 
 namespace qmx {
-
-// bytes of the ACORN walk's list of nodes to explore (one per link of the popped candidate: HnswArgs::explore_cap ids - the graph's longest level-0 list -, 64 at least)
-__host__ __device__ static inline uint32_t hnsw_acorn_lds(uint32_t acorn, uint32_t m0) { return acorn ? 4u * (((m0 < 64u ? 64u : m0) + 63u) / 64u * 64u) : 0u; }
-
-// ---- hop scorers: LPI lanes score one stored row; the score is valid in the lane with sub == 0 ----
-// a policy whose query offset comes from ScanArgs::sq_qoff instead of the query entry's aux block (a stored SQ row as the query)
-template <class P, class = void>
-struct has_internal_qoff { static constexpr bool value = false; };
-template <class P>
-struct has_internal_qoff<P, decltype((void)P::INTERNAL_QOFF)> { static constexpr bool value = P::INTERNAL_QOFF; };
-
-// ... or whose query norm comes from ScanArgs::u8_qnorm_* (a stored u8 row as the query of the per-pair cosine)
-template <class P, class = void>
-struct has_internal_norm { static constexpr bool value = false; };
-template <class P>
-struct has_internal_norm<P, decltype((void)P::INTERNAL_NORM)> { static constexpr bool value = P::INTERNAL_NORM; };
-// a hop scorer whose stored <-> stored score is NOT the score of the search (PQ: LUT of the original vector vs centroid <-> centroid)
-template <class H, class = void>
-struct is_asymmetric { static constexpr bool value = false; };
-template <class H>
-struct is_asymmetric<H, decltype((void)H::ASYMMETRIC)> { static constexpr bool value = H::ASYMMETRIC; };
-
-template <class P, class = void>
-struct offset_by_caller { static constexpr bool value = false; };
-template <class P>
-struct offset_by_caller<P, decltype((void)P::OFFSET_BY_CALLER)> { static constexpr bool value = P::OFFSET_BY_CALLER; };
-
-template <class P>
-struct HopRow {
-    static constexpr int LPI = 8;
-    static constexpr bool ADDS_OFFSET = offset_by_caller<P>::value;      // the policy's score lacks the row's offset: hop_score adds hop_scores[j]'s prefilled value
-    static constexpr bool INTERNAL_QOFF = has_internal_qoff<P>::value;
-    static constexpr bool INTERNAL_NORM = has_internal_norm<P>::value;
-    static constexpr bool MULTI = true;     // score_multi<R>: R rows per 8-lane group in one pass
-    static __device__ __forceinline__ float score(const ScanArgs &a, const unsigned char *qp, uint32_t id, int sub) {
-        return group_score<P>(a, qp, id, sub);
-    }
-    template <int R>
-    static __device__ __forceinline__ void score_multi(const ScanArgs &a, const unsigned char *qp, const uint32_t (&ids)[R], int sub, float (&out)[R]) {
-        group_score_multi<P, R>(a, qp, ids, sub, out);
-    }
-};
-template <class S>
-struct HopSmall {
-    static constexpr int LPI = 1;
-    static constexpr bool INTERNAL_QOFF = false;
-    static constexpr bool INTERNAL_NORM = false;
-    static constexpr bool MULTI = false;
-    static __device__ __forceinline__ float score(const ScanArgs &a, const unsigned char *qp, uint32_t id, int) {
-        return S::score(qp, reinterpret_cast<const unsigned char *>(a.rows) + (uint64_t)id * a.row_stride, id, a);
-    }
-};
-
-// Multi-vector points with the MaxSim comparator (MultiMetricQueryScorer, query_scorer/multi_metric_query_scorer.rs + score_max_similarity,
-// query_scorer/mod.rs:70-97; quantized: QuantizedMultivectorStorage::score_point_max_similarity, quantized_multivector_storage/mod.rs:339-363):
-// the graph's points are multi-vectors, a hop candidate's score is the sum over the query's inner vectors (in order, from 0.0) of the max
-// over the point's inner vectors (`if max_sim < sim`, from -inf) of the inner policy's score.  The query entry in LDS is
-// [16-byte header: number of inner query vectors, pad, pointer to the first entry][the entries, when they fit the launch's LDS share - else the header points
-// at them in global memory (PQ: every inner query vector is a LUT)]; qp points behind the header.
-template <class H, class = void>
-struct is_maxsim { static constexpr bool value = false; };
-template <class H>
-struct is_maxsim<H, decltype((void)H::MAXSIM)> { static constexpr bool value = H::MAXSIM; };
-template <class HI>
-struct HopMaxSim {
-    static constexpr int LPI = HI::LPI;
-    static constexpr bool INTERNAL_QOFF = false;
-    static constexpr bool INTERNAL_NORM = false;
-    static constexpr bool MULTI = false;
-    static constexpr bool MAXSIM = true;
-    static __device__ __forceinline__ float score(const ScanArgs &a, const unsigned char *qp, uint32_t id, int sub) {
-        const uint32_t n_tokens = *reinterpret_cast<const uint32_t *>(qp - 16);
-        const unsigned char *toks = *reinterpret_cast<const unsigned char *const *>(qp - 8);
-        const uint64_t b0 = a.mv_offsets[id], b1 = a.mv_offsets[id + 1];
-        float sum = 0.0f;
-        for (uint32_t t = 0; t < n_tokens; ++t) {
-            const unsigned char *qe = toks + (size_t)t * a.q_stride;
-            float max_sim = -__builtin_inff();
-            for (uint64_t b = b0; b < b1; ++b) {
-                const float sim = HI::score(a, qe, (uint32_t)b, sub);
-                if (max_sim < sim) max_sim = sim;
-            }
-            sum += max_sim;
-        }
-        return sum;
-    }
-};
-
-// The insertion searches of a build over multi-vector points whose inner storage cannot turn a stored row into a query (PQ, TurboQuant:
-// QuantizedMultivectorStorage::encode_internal_vector -> None, quantized_multivector_storage/mod.rs:458-470; point_scorer.rs:183-218 then takes the query
-// scorer of the point's ORIGINAL multi-vector): HopMaxSim over the batch's query entries - the new point's tokens are a.mv_q_tokens entries, a.q_stride
-// apart, from `qp` on (hnsw_build.hpp points it at the first; no header).
-template <class H, class = void>
-struct is_maxsim_q { static constexpr bool value = false; };
-template <class H>
-struct is_maxsim_q<H, decltype((void)H::MAXSIM_Q)> { static constexpr bool value = H::MAXSIM_Q; };
-template <class HI>
-struct HopMaxSimQ {
-    static constexpr int LPI = HI::LPI;
-    static constexpr bool INTERNAL_QOFF = false;
-    static constexpr bool INTERNAL_NORM = false;
-    static constexpr bool MULTI = false;
-    static constexpr bool MAXSIM_Q = true;
-    static __device__ __forceinline__ float score(const ScanArgs &a, const unsigned char *qp, uint32_t id, int sub) {
-        const uint32_t n_tokens = a.mv_q_tokens;
-        const uint64_t b0 = a.mv_offsets[id], b1 = a.mv_offsets[id + 1];
-        float sum = 0.0f;
-        for (uint32_t t = 0; t < n_tokens; ++t) {
-            const unsigned char *qe = qp + (size_t)t * a.q_stride;
-            float max_sim = -__builtin_inff();
-            for (uint64_t b = b0; b < b1; ++b) {
-                const float sim = HI::score(a, qe, (uint32_t)b, sub);
-                if (max_sim < sim) max_sim = sim;
-            }
-            sum += max_sim;
-        }
-        return sum;
-    }
-};
-
-// The same points scored stored <-> stored (HNSW build over multi-vector points, hnsw/build.rs:334-341 through FilteredScorer::new_internal:
-// MultiMetricQueryScorer::score_internal, multi_metric_query_scorer.rs; quantized: score_internal_max_similarity,
-// quantized_multivector_storage/mod.rs:366-393): sum over the inner vectors of point a (in order, from 0.0) of the max over the inner vectors of
-// point b (`if sim > max_sim`, from -inf) of the inner storage's score_internal.  The "query entry" of a stored multi-vector is its point id
-// (stored_query in hnsw_build.hpp hands it over in the pointer); the inner rows are read from HBM / L2 on every pair.  Not symmetric.
-template <class H, class = void>
-struct is_maxsim_internal { static constexpr bool value = false; };
-template <class H>
-struct is_maxsim_internal<H, decltype((void)H::MAXSIM_INTERNAL)> { static constexpr bool value = H::MAXSIM_INTERNAL; };
-template <class HI>
-struct HopMaxSimInternal {
-    static constexpr int LPI = HI::LPI;
-    static constexpr bool INTERNAL_QOFF = false;     // the inner rows' offsets / norms are looked up per inner row below
-    static constexpr bool INTERNAL_NORM = false;
-    static constexpr bool MULTI = false;
-    static constexpr bool ASYMMETRIC = true;
-    static constexpr bool MAXSIM_INTERNAL = true;
-    static __device__ __forceinline__ float score(const ScanArgs &a, const unsigned char *qp, uint32_t id, int sub) {
-        const uint32_t p = (uint32_t)reinterpret_cast<uintptr_t>(qp);
-        const unsigned char *rows = reinterpret_cast<const unsigned char *>(a.rows);
-        const uint64_t a0 = a.mv_offsets[p], a1 = a.mv_offsets[p + 1];
-        const uint64_t b0 = a.mv_offsets[id], b1 = a.mv_offsets[id + 1];
-        float sum = 0.0f;
-        for (uint64_t i = a0; i < a1; ++i) {
-            ScanArgs b = a;
-            if constexpr (HI::INTERNAL_QOFF) b.sq_qoff = a.row_offsets[i] - a.sq_shift;
-            if constexpr (HI::INTERNAL_NORM) {
-                b.u8_qnorm_f = a.row_norms_f[i];
-                b.u8_qnorm_i = a.row_norms_i[i];
-            }
-            const unsigned char *qe = rows + i * a.row_stride;
-            float max_sim = -__builtin_inff();
-            for (uint64_t j = b0; j < b1; ++j) {
-                const float sim = HI::score(b, qe, (uint32_t)j, sub);
-                if (sim > max_sim) max_sim = sim;
-            }
-            sum += max_sim;
-        }
-        return sum;
-    }
-};
-
-// a hop policy that can drop candidates on an upper bound of their score before the exact scoring (H::prefilter): HopPQ's 8-bit LUT image, pq.hip
-template <class H, class = void>
-struct hop_adds_offset { static constexpr bool value = false; };
-template <class H>
-struct hop_adds_offset<H, decltype((void)H::ADDS_OFFSET)> { static constexpr bool value = H::ADDS_OFFSET; };
-template <class H, class = void>
-struct has_hop_prefilter { static constexpr bool value = false; };
-template <class H>
-struct has_hop_prefilter<H, decltype((void)H::HOP_PREFILTER)> { static constexpr bool value = H::HOP_PREFILTER; };
-
-// a hop policy that scores a whole hop itself, wave-cooperatively (H::hop): TurboQuant over Manhattan, tq_l1_policy.hpp
-template <class H, class = void>
-struct is_tql1 { static constexpr bool value = false; };
-template <class H>
-struct is_tql1<H, decltype((void)H::TQL1)> { static constexpr bool value = H::TQL1; };
-
-// Custom queries as the scorer of the walk (raw_scorer.rs:228-333 builds a CustomQueryScorer / QuantizedCustomQueryScorer / TurboCustomQueryScorer for
-// whatever storage the segment has; graph_layers.rs:108-149 walks with whatever scorer it gets): a hop candidate's score is
-// query.score_by(|example| inner policy's score(example, candidate)) - the examples of ONE custom query, in flat_iter() order, are what the search stages.
-// The query block in LDS is [32-byte CustomHeader][the examples' entries, when they fit: else the header points at them in global memory]; qp points
-// behind the header.
-struct CustomHeader {
-    uint32_t kind, n_a, n_b, coef_first;
-    const unsigned char *entries;       // the examples' query entries, a.q_stride apart (LDS or global) ...
-    const uint32_t *ex_off;             // ... or, when the examples are multi-vectors of different lengths: byte offset of example e's first token from `entries`
-};
-static_assert(sizeof(CustomHeader) == 32, "the custom walk's LDS header");
-template <class H, class = void>
-struct is_custom { static constexpr bool value = false; };
-template <class H>
-struct is_custom<H, decltype((void)H::CUSTOM)> { static constexpr bool value = H::CUSTOM; };
-
-// Per-request payload filters (qmx_query_set_filters) in the walk: the same hop policy under another name, instantiated beside the plain one and launched
-// only for a batch that carries such filters (launch_hnsw_hop).  The walks of every other batch are the instantiations they were: their liveness test does
-// not know of a second index.
-template <class H>
-struct HopPerQuery : H { static constexpr bool PER_QUERY_FILTER = true; };
-template <class H, class = void>
-struct per_query_filter { static constexpr bool value = false; };
-template <class H>
-struct per_query_filter<H, decltype((void)H::PER_QUERY_FILTER)> { static constexpr bool value = H::PER_QUERY_FILTER; };
-// filters().check_vector(id) of search qi
-template <class H>
-__device__ __forceinline__ bool walk_live(const DeletedView &d, uint32_t id, uint32_t qi) {
-    if constexpr (per_query_filter<H>::value) return d.live(id, qi);
-    else return d.live(id);
-}
-template <class HI>
-struct HopCustom {
-    static constexpr int LPI = HI::LPI;
-    static constexpr bool INTERNAL_QOFF = false;
-    static constexpr bool INTERNAL_NORM = false;
-    static constexpr bool MULTI = false;
-    static constexpr bool CUSTOM = true;
-    static constexpr bool MULTI_EXAMPLES = is_maxsim<HI>::value;      // MultiCustomQueryScorer: every example is a multi-vector scored by MaxSim
-    static __device__ __forceinline__ float score(const ScanArgs &a, const unsigned char *qp, uint32_t id, int sub) {
-        const CustomHeader *hd = reinterpret_cast<const CustomHeader *>(qp - sizeof(CustomHeader));
-        const unsigned char *ent = hd->entries;
-        const uint32_t *off = hd->ex_off;
-        return custom_score_by(hd->kind, hd->n_a, hd->n_b, a.cq_coefs + hd->coef_first, [&](uint32_t e) {
-            return HI::score(a, MULTI_EXAMPLES ? ent + off[e] : ent + (size_t)e * a.q_stride, id, sub);
-        });
-    }
-    // an inner policy that scores a hop as a wave (TurboQuant over Manhattan): the hop against every example in turn - scores parked per example in LDS -
-    // then lane j combines candidate j's.  The examples are always staged; behind them [the inner policy's hop scratch][n_examples x 64 floats]
-    // (custom_tql1_lds_bytes sizes it; instantiated for such policies only)
-    static constexpr bool TQL1 = is_tql1<HI>::value;
-    static __device__ __forceinline__ void hop(const ScanArgs &a, const unsigned char *qp, const uint32_t *hop_ids, float *hop_scores, uint32_t k, int lane) {
-        const CustomHeader *hd = reinterpret_cast<const CustomHeader *>(qp - sizeof(CustomHeader));
-        const uint32_t ne = hd->kind <= QMX_CUSTOM_RECO_SUM_SCORES ? hd->n_a + hd->n_b : hd->n_a + 2 * hd->n_b;
-        unsigned char *scratch = const_cast<unsigned char *>(qp) + (size_t)ne * a.q_stride;
-        float *ex = reinterpret_cast<float *>(scratch + HI::scratch_bytes(a));
-        for (uint32_t e = 0; e < ne; ++e) HI::hop_at(a, hd->entries + (size_t)e * a.q_stride, scratch, hop_ids, ex + (size_t)e * 64, k, lane);
-        if ((uint32_t)lane < k)
-            hop_scores[lane] = custom_score_by(hd->kind, hd->n_a, hd->n_b, a.cq_coefs + hd->coef_first, [&](uint32_t e) { return ex[(size_t)e * 64 + (uint32_t)lane]; });
-        __syncthreads();
-    }
-};
-
-// bytes of the LDS beam of a walk with max(top, ef) = ef > HNSW_MAX_EF_REG: keys + expanded flags
-__host__ __device__ static inline size_t hnsw_beam_lds(uint32_t ef) { return ((size_t)ef * 9 + 15) / 16 * 16; }
-
-// ---- the beam: sorted descending, entry index = e * 64 + lane ------------------------------------
-template <int E>
-struct Beam {
-    uint64_t key[E];
-    uint32_t done[E];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int e = 0; e < E; ++e) { key[e] = 0; done[e] = 0; }
-    }
-    __device__ __forceinline__ uint64_t at(uint32_t idx) const {   // idx uniform
-        uint64_t r = 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-            if ((idx >> 6) == (uint32_t)e) r = readlane_u64(key[e], (int)(idx & 63));
-        return r;
-    }
-    // insert nk (uniform, non-zero), keep the first `cap` entries
-    __device__ __forceinline__ void insert(uint64_t nk, uint32_t cap, int lane) {
-        uint32_t p = 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) p += (uint32_t)__popcll(__ballot(key[e] > nk));
-        uint64_t carry_k = 0;
-        uint32_t carry_d = 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            uint64_t up = shfl_up1_u64(key[e]);
-            uint32_t upd = (uint32_t)__shfl_up((int)done[e], 1, 64);
-            const uint64_t last_k = readlane_u64(key[e], 63);
-            const uint32_t last_d = (uint32_t)__builtin_amdgcn_readlane((int)done[e], 63);
-            if (lane == 0) { up = carry_k; upd = carry_d; }
-            const uint32_t idx = (uint32_t)e * 64 + (uint32_t)lane;
-            if (idx == p) { key[e] = nk; done[e] = 0; }
-            else if (idx > p) { key[e] = up; done[e] = upd; }
-            if (idx >= cap) { key[e] = 0; done[e] = 0; }
-            carry_k = last_k;
-            carry_d = last_d;
-        }
-    }
-    __device__ __forceinline__ bool done_at(uint32_t idx) const {   // idx uniform
-        uint32_t r = 0;
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-            if ((idx >> 6) == (uint32_t)e) r = (uint32_t)__builtin_amdgcn_readlane((int)done[e], (int)(idx & 63));
-        return r != 0;
-    }
-    // best unexpanded entry -> its key (0 if none); marks it expanded
-    __device__ __forceinline__ uint64_t pop_best(int lane) {
-        uint64_t ck = 0;
-        bool found = false;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const uint64_t m = __ballot(key[e] != 0 && done[e] == 0);
-            if (!found && m) {
-                const int l = __builtin_ctzll(m);
-                ck = readlane_u64(key[e], l);
-                if (lane == l) done[e] = 1;
-                found = true;
-            }
-        }
-        return ck;
-    }};
-
-// The same list for ef > 512, kept in LDS (the walk kernel appends `cap` keys + `cap` flag bytes to its dynamic LDS): the same interface, every
-// operation wave-cooperative.  insert: the position by a two-level search (64 block ends, then the block), then the tail moves up one entry, 64
-// at a time from the end; pop_best scans from a hint below which every entry is expanded.  Slower per operation than the register beam, and meant
-// to be: searches this wide are rare.
-template <>
-struct Beam<0> {
-    uint64_t *key;
-    unsigned char *done;
-    uint32_t len, hint;
-    __device__ __forceinline__ void init(unsigned char *lds, uint32_t cap) {
-        key = reinterpret_cast<uint64_t *>(lds);
-        done = lds + 8 * (size_t)cap;
-    }
-    __device__ __forceinline__ void clear() { len = 0; hint = 0; }
-    __device__ __forceinline__ uint64_t at(uint32_t idx) const { return idx < len ? key[idx] : 0ull; }        // idx uniform
-    __device__ __forceinline__ bool done_at(uint32_t idx) const { return idx < len && done[idx] != 0; }
-    __device__ __forceinline__ void insert(uint64_t nk, uint32_t cap, int lane) {
-        // p = number of keys above nk (descending, distinct keys)
-        uint32_t p = 0;
-        if (len) {
-            const uint32_t stride = (len + 63) / 64;                       // <= 64 while cap <= 4096
-            const uint32_t last = (uint32_t)lane * stride + stride - 1;     // the end of the lane's block
-            const bool whole = last < len && key[last] > nk;                // the block lies above nk as a whole
-            const uint32_t b = (uint32_t)__popcll(__ballot(whole));         // (monotone: the first b blocks)
-            const uint32_t i = b * stride + (uint32_t)lane;
-            const bool above = (uint32_t)lane < stride && i < len && key[i] > nk;
-            p = b * stride + (uint32_t)__popcll(__ballot(above));
-        }
-        const uint32_t new_len = len < cap ? len + 1 : cap;
-        if (p >= new_len) return;                                           // (below a full list: the callers test against at(cap - 1) first)
-        for (uint32_t hi = new_len - 1; hi > p;) {                          // entries [p, new_len - 1) move up by one, the last of a full list drops out
-            const uint32_t lo = hi - p > 64 ? hi - 63 : p + 1;
-            const uint32_t i = lo + (uint32_t)lane;
-            uint64_t k = 0;
-            unsigned char d = 0;
-            if (i <= hi) { k = key[i - 1]; d = done[i - 1]; }
-            if (i <= hi) { key[i] = k; done[i] = d; }
-            hi = lo - 1;
-        }
-        if (lane == 0) { key[p] = nk; done[p] = 0; }
-        len = new_len;
-        if (p < hint) hint = p;
-    }
-    __device__ __forceinline__ uint64_t pop_best(int lane) {
-        for (uint32_t base = hint; base < len; base += 64) {
-            const uint32_t i = base + (uint32_t)lane;
-            const uint64_t m = __ballot(i < len && done[i] == 0);
-            if (m) {
-                const uint32_t at = base + (uint32_t)__builtin_ctzll(m);
-                if (i == at) done[i] = 1;
-                hint = at + 1;
-                return key[at];
-            }
-        }
-        hint = len;
-        return 0ull;
-    }
-};
-
-// ---- the visited set of a search, in LDS ----------------------------------------------------------------------------------------------
-// One bit per point in a per-slot HBM bitmap costs the walk a third of its time at 10 M points: every test-and-set is an L2 atomic on a random word of a
-// 1.25 MB bitmap (5 GB over the slots in flight), i.e. an HBM read-modify-write per link - tools/micro/gather_roof measures the row gathers of a hop at
-// 6.2 TB/s alone and at 3.4 TB/s with those atomics beside them, which is where the walk sat (profiles/r5_sq_walk_visited.md).  A search inserts a few
-// thousand ids, so its set fits the LDS: 1024 buckets (id & 1023) of eight 16-bit tags ((id >> 10) + 1; 0 = empty, 0xFFFF = taken back) = 16 KiB per search.  test_and_set looks
-// the tag up in its bucket (one ds_read_b128), claims the first empty half-word with a compare-and-swap on the word that holds it (lanes of the wave insert
-// side by side; a lost race re-reads), and when the bucket is full - about 1 % of the inserts of an ef = 128 search, more for wide ones - falls back to the
-// HBM bitmap for that id.  An id is recorded in exactly one of the two places (the bucket is consulted first, and a full bucket never frees a slot while the
-// search runs: unset() marks the slot instead of emptying it), so the set is exact: same fresh / visited answers as the bitmap alone, hence the same
-// walk.  Graphs of more than 65534 x 1024 points (tags would not fit), ACORN and the reference-heap mode keep the bitmap.
-// (One search = one wave = one work-group of 64 threads - `__launch_bounds__(64)` on the walk kernels: the plain 16-byte read of a bucket below races with
-// nobody but the lanes of its own wave, whose LDS operations execute in order.  A launch with more than one wave per group would need atomic bucket reads.)
-struct LdsVisited {
-    uint32_t *tab;      // LDS, 4096 words; nullptr: the bitmap only
-    // -> true when `id` was visited before; *in_bitmap: the id lives (now or already) in the HBM bitmap, not in the table
-    __device__ __forceinline__ bool test_and_set(uint32_t id, uint32_t *vis, bool *in_bitmap) const {
-        const uint32_t bit = 1u << (id & 31);
-        *in_bitmap = false;
-        if (tab) {
-            uint32_t *b = tab + (id & 1023u) * 4u;
-            const uint32_t tag = (id >> 10) + 1u;
-            for (;;) {
-                const uint4 w4 = *reinterpret_cast<const uint4 *>(b);
-                const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-                int empty = -1;
-                bool found = false;
-#pragma unroll
-                for (int d = 3; d >= 0; --d) {
-                    const uint32_t lo = w[d] & 0xFFFFu, hi = w[d] >> 16;
-                    found = found || lo == tag || hi == tag;
-                    if (hi == 0) empty = 2 * d + 1;
-                    if (lo == 0) empty = 2 * d;
-                }
-                if (found) return true;
-                if (empty < 0) break;                                    // the bucket is full: this id is the bitmap's
-                const int d = empty >> 1;
-                const uint32_t expected = w[d], desired = expected | (tag << (16 * (empty & 1)));
-                if (atomicCAS(&b[d], expected, desired) == expected) return false;
-            }
-        }
-        *in_bitmap = true;
-        return (atomicOr(&vis[id >> 5], bit) & bit) != 0;
-    }
-    // takes back an insert this search made (a link behind the level's limit: the reference never looked at it)
-    __device__ __forceinline__ void unset(uint32_t id, uint32_t *vis, bool in_bitmap) const {
-        if (in_bitmap || !tab) { atomicAnd(&vis[id >> 5], ~(1u << (id & 31))); return; }
-        // The slot is not freed but marked (tag 0xFFFF: no id of a graph this table serves has it): a bucket that was ever full stays full, so an id that
-        // went to the bitmap because its bucket was full can never be mistaken for a fresh one by a later lookup that finds room in that bucket.
-        uint32_t *b = tab + (id & 1023u) * 4u;
-        const uint32_t tag = (id >> 10) + 1u;
-        for (int d = 0; d < 4; ++d) {
-            for (;;) {
-                const uint32_t w = b[d];
-                uint32_t nw = w;
-                if ((w & 0xFFFFu) == tag) nw = w | 0xFFFFu;
-                else if ((w >> 16) == tag) nw = w | 0xFFFF0000u;
-                else break;
-                if (atomicCAS(&b[d], w, nw) == w) return;
-            }
-        }
-    }
-    __device__ __forceinline__ void clear(int lane) const {               // wave-cooperative; the caller barriers
-        if (!tab) return;
-        uint4 *t = reinterpret_cast<uint4 *>(tab);
-        for (uint32_t i = (uint32_t)lane; i < HNSW_VIS_LDS_BYTES / 16; i += 64) t[i] = make_uint4(0, 0, 0, 0);
-    }
-};
-
-// ---- option hnsw_reference_heap_order: the reference's two binary heaps, worked by ONE lane in std's exact sift order ---------------------
-// `nearest` = FixedLengthPriorityQueue<ScoredPointOffset> = BinaryHeap<Reverse<T>> of at most ef entries (lib/common/common/src/
-// fixed_length_priority_queue.rs:20-65; push :47-59 replaces the root only on strict root < value, through PeekMut = sift_down(0));
-// `candidates` = BinaryHeap<ScoredPointOffset> (search_context.rs:8-40; pop = swap with the last + sift_down_to_bottom(0) + sift_up).
-// ScoredPointOffset orders by OrderedFloat(score) alone, so which of two equal scores a sift moves depends on where they sit in the array:
-// reproducing the arrays is the only way to reproduce the reference's lists among equal scores (integer scorers: SQ, u8, BQ, 1-bit TQ).
-// Every heap operation is a chain of dependent loads of one lane; `nearest` sits in LDS, and so do the first HNSW_REF_CAND_LDS entries of
-// `candidates` (round 6: the levels every sift touches; rounds 5's heap lived in HBM whole: a pop was a dozen dependent trips to memory); the rest of
-// the array (unbounded in the reference) is a per-slot HBM scratch of ref_cap entries.
-struct RefHeaps {
-    uint2 *nd;                 // nearest: x = idx, y = score bits
-    uint2 *cd;                 // candidates: entries [c_lds, c_cap) live here ...
-    uint2 *cl;                 // ... entries [0, c_lds) in LDS
-    uint32_t n_len, n_cap, c_len, c_cap, c_lds;
-    bool overflow;
-    __device__ __forceinline__ uint2 cget(uint32_t i) const { return i < c_lds ? cl[i] : cd[i]; }
-    __device__ __forceinline__ void cset(uint32_t i, uint2 v) { if (i < c_lds) cl[i] = v; else cd[i] = v; }
-    // OrderedFloat::cmp: NaN is the greatest value and equal to itself
-    static __device__ __forceinline__ int of_cmp(float a, float b) {
-        if (a < b) return -1;
-        if (a > b) return 1;
-        if (a == b) return 0;
-        const bool an = a != a, bn = b != b;
-        if (an && bn) return 0;
-        return an ? 1 : -1;
-    }
-    static __device__ __forceinline__ float sc(uint2 v) { return __uint_as_float(v.y); }
-    static __device__ __forceinline__ int rev_cmp(uint2 a, uint2 b) { return of_cmp(sc(b), sc(a)); }      // Reverse<T>
-    __device__ __forceinline__ void init(unsigned char *lds, uint32_t ef, uint2 *scratch, uint32_t cap, unsigned char *cand_lds, uint32_t cand_lds_entries) {
-        nd = reinterpret_cast<uint2 *>(lds);
-        cd = scratch;
-        cl = reinterpret_cast<uint2 *>(cand_lds);
-        c_lds = cand_lds_entries;
-        n_len = 0; n_cap = ef ? ef : 1; c_len = 0; c_cap = cap;
-        overflow = false;
-    }
-    // BinaryHeap::sift_up(0, pos) under Reverse
-    __device__ void n_sift_up(uint32_t pos) {
-        const uint2 elt = nd[pos];
-        while (pos > 0) {
-            const uint32_t parent = (pos - 1) / 2;
-            if (rev_cmp(elt, nd[parent]) <= 0) break;
-            nd[pos] = nd[parent];
-            pos = parent;
-        }
-        nd[pos] = elt;
-    }
-    // BinaryHeap::sift_down_range(pos, end) under Reverse
-    __device__ void n_sift_down_range(uint32_t pos, uint32_t end) {
-        const uint2 elt = nd[pos];
-        uint32_t child = 2 * pos + 1;
-        while (end >= 2 && child <= end - 2) {
-            child += rev_cmp(nd[child], nd[child + 1]) <= 0 ? 1u : 0u;
-            if (rev_cmp(elt, nd[child]) >= 0) { nd[pos] = elt; return; }
-            nd[pos] = nd[child];
-            pos = child;
-            child = 2 * pos + 1;
-        }
-        if (end >= 1 && child == end - 1 && rev_cmp(elt, nd[child]) < 0) {
-            nd[pos] = nd[child];
-            pos = child;
-        }
-        nd[pos] = elt;
-    }
-    // FixedLengthPriorityQueue::push -> was the value kept (SearchContext::process_candidate's `was_added`)
-    __device__ bool n_push(uint2 v) {
-        if (n_len < n_cap) {
-            nd[n_len] = v;
-            n_sift_up(n_len);
-            ++n_len;
-            return true;                                   // None
-        }
-        if (of_cmp(sc(nd[0]), sc(v)) < 0) {
-            const uint2 removed = nd[0];
-            nd[0] = v;
-            n_sift_down_range(0, n_len);
-            return removed.x != v.x;                       // Some(removed): removed.idx != score_point.idx
-        }
-        return false;                                      // Some(value): rejected
-    }
-    __device__ void c_push(uint2 v) {
-        if (c_len == c_cap) { overflow = true; return; }
-        uint32_t pos = c_len++;
-        while (pos > 0) {                                  // sift_up(0, pos)
-            const uint32_t parent = (pos - 1) / 2;
-            const uint2 pv = cget(parent);
-            if (of_cmp(sc(v), sc(pv)) <= 0) break;
-            cset(pos, pv);
-            pos = parent;
-        }
-        cset(pos, v);
-    }
-    __device__ bool c_pop(uint2 *out) {
-        if (c_len == 0) return false;
-        uint2 item = cget(--c_len);
-        if (c_len > 0) {
-            const uint2 root = cget(0);
-            // sift_down_to_bottom(0) of `item`, then sift_up from where it landed
-            const uint32_t end = c_len;
-            uint32_t pos = 0, child = 1;
-            while (end >= 2 && child <= end - 2) {
-                const uint2 l = cget(child), r = cget(child + 1);
-                const bool right = of_cmp(sc(l), sc(r)) <= 0;
-                cset(pos, right ? r : l);
-                pos = child + (right ? 1u : 0u);
-                child = 2 * pos + 1;
-            }
-            if (child == end - 1) { cset(pos, cget(child)); pos = child; }
-            while (pos > 0) {
-                const uint32_t parent = (pos - 1) / 2;
-                const uint2 pv = cget(parent);
-                if (of_cmp(sc(item), sc(pv)) <= 0) break;
-                cset(pos, pv);
-                pos = parent;
-            }
-            cset(pos, item);
-            item = root;
-        }
-        *out = item;
-        return true;
-    }
-    // SearchContext::process_candidate (search_context.rs:32-40)
-    __device__ void process_candidate(uint32_t idx, float score) {
-        const uint2 v = make_uint2(idx, __float_as_uint(score));
-        if (n_push(v)) c_push(v);
-    }
-    // into_iter_sorted(): BinaryHeap::into_sorted_vec under Reverse = descending score, in place
-    __device__ uint32_t n_into_sorted() {
-        uint32_t end = n_len;
-        while (end > 1) {
-            --end;
-            const uint2 t = nd[0]; nd[0] = nd[end]; nd[end] = t;
-            n_sift_down_range(0, end);
-        }
-        return n_len;
-    }
-};
-constexpr int HNSW_E_REF = -1;       // the template value of the walk's E that selects this mode
-
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// scores hop_ids[0..k) into hop_scores[0..k); uniform control flow, k <= 64
-template <class H, int R>
-__device__ __forceinline__ void hop_score_pass(const ScanArgs &a, const unsigned char *qp, const uint32_t *hop_ids, float *hop_scores,
-                                               uint32_t base, uint32_t k, int sub, int g) {
-    constexpr int IPP = 64 / H::LPI;
-    uint32_t ids[R];
-    float sc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t j = base + (uint32_t)(r * IPP + g);
-        ids[r] = hop_ids[j < k ? j : 0];
-    }
-    H::template score_multi<R>(a, qp, ids, sub, sc);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t j = base + (uint32_t)(r * IPP + g);
-        if (j < k && sub == 0) hop_scores[j] = hop_adds_offset<H>::value ? sc[r] + hop_scores[j] : sc[r];
-    }
-}
-
-// (policies whose score lacks the row's offset - hop_adds_offset: RowSQX - find it in hop_scores[j]: put there by the caller with the links
-// (`have_offsets`), or gathered here from the offsets column)
-template <class H>
-__device__ __forceinline__ void hop_score(const ScanArgs &a, const unsigned char *qp, const uint32_t *hop_ids,
-                                          float *hop_scores, uint32_t k, int lane, bool have_offsets = false) {
-    constexpr int IPP = 64 / H::LPI;
-    const int sub = lane % H::LPI, g = lane / H::LPI;
-    __syncthreads();   // hop_ids written by other lanes
-    if constexpr (hop_adds_offset<H>::value) {
-        if (!have_offsets) {
-            for (uint32_t j = (uint32_t)lane; j < k; j += 64) hop_scores[j] = a.row_offsets[hop_ids[j]];
-            __syncthreads();
-        }
-    }
-    if constexpr (is_tql1<H>::value) {      // the policy scores the hop as a wave (it ends on a barrier, like the loop below)
-        H::hop(a, qp, hop_ids, hop_scores, k, lane);
-        return;
-    }
-    uint32_t base = 0;
-    if constexpr (H::MULTI) {
-        // the usual hop (9..32 fresh neighbours) in ONE pass with 2 or 4 rows per lane group: one round of gathers
-        for (; base + 2 * IPP < k; base += 4 * IPP) hop_score_pass<H, 4>(a, qp, hop_ids, hop_scores, base, k, sub, g);
-        for (; base + IPP < k; base += 2 * IPP) hop_score_pass<H, 2>(a, qp, hop_ids, hop_scores, base, k, sub, g);
-    }
-    for (; base < k; base += IPP) {
-        const uint32_t j = base + (uint32_t)g;
-        const bool on = j < k;
-        const uint32_t id = hop_ids[on ? j : 0];
-        const float s = H::score(a, qp, id, sub);
-        if (on && sub == 0) hop_scores[j] = hop_adds_offset<H>::value ? s + hop_scores[j] : s;
-    }
-    __syncthreads();
-}
 
 // One search.  `qp` = the query entry (LDS or global).
 template <class H, int E>
@@ -910,7 +278,7 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
     if (h.acorn) {
         // ---- search_on_level_acorn (graph_layers.rs:154-243): links that fail the filters are explored instead of scored ----
         const uint32_t half = (uint32_t)(h.vis_words / 2);           // vis = hop1_visited_list, vis + half = hop2_visited_list
-        uint32_t *to_explore = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(hop_ids) + 8 * (size_t)h.hop_cap);
+        uint32_t *to_explore = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(hop_ids) + hnsw_hop_lds(h.hop_cap));
         const uint32_t hop_limit = h.m0;                                // hop1_limit = hop2_limit = get_m(0)
         auto mask_le = [](int l) -> uint64_t { return l >= 63 ? ~0ull : ((2ull << l) - 1ull); };
         auto nth_set = [](uint64_t m, uint32_t nth) -> int {            // lane of the nth (1-based) set bit
@@ -1239,6 +607,94 @@ __device__ __forceinline__ void hnsw_search_one(const ScanArgs &a, const HnswArg
     }   // E != HNSW_E_REF
 }
 
+// the dynamic LDS of the instantiation <E, QLDS> for a launch with arguments h
+template <int E, bool QLDS>
+__host__ __device__ __forceinline__ HnswLds hnsw_lds_layout(const HnswArgs &h) {
+    return hnsw_lds_layout(E, QLDS, h.hop_cap, h.acorn, h.explore_cap, h.lds_query_bytes, h.ef > h.top ? h.ef : h.top, h.vis_lds, h.pq8 != nullptr, h.pq8_stride);
+}
+
+// ---- the query entry of a search, staged ------------------------------------------------------------------------------------------------------
+// the wave copies n16 pieces of 16 bytes from global memory into LDS
+__device__ __forceinline__ void stage_copy(unsigned char *dst, const unsigned char *src, uint32_t n16, int lane) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+    uint4 *d = reinterpret_cast<uint4 *>(dst);
+    for (uint32_t i = (uint32_t)lane; i < n16; i += 64) d[i] = s[i];
+}
+// the 16-byte header in front of a multi-query's tokens (HopMaxSim); one lane writes it
+__device__ __forceinline__ void write_maxsim_header(unsigned char *at, uint32_t n_tokens, const unsigned char *tokens) {
+    *reinterpret_cast<uint32_t *>(at) = n_tokens;
+    *reinterpret_cast<const unsigned char **>(at + 8) = tokens;
+}
+// the header in front of a custom query's examples (HopCustom); one lane writes it
+__device__ __forceinline__ void write_custom_header(unsigned char *at, const qmx_custom_query &cq, const unsigned char *entries, const uint32_t *ex_off) {
+    CustomHeader *hd = reinterpret_cast<CustomHeader *>(at);
+    hd->kind = cq.kind; hd->n_a = cq.n_a; hd->n_b = cq.n_b; hd->coef_first = cq.coef_first;
+    hd->entries = entries;
+    hd->ex_off = ex_off;
+}
+
+// Stages the query entry of search qi in q_lds (QLDS; a header always sits there) -> where the entry lies: behind the header in LDS, or in global memory.
+template <class H, bool QLDS>
+__device__ __forceinline__ const unsigned char *stage_search_entry(const ScanArgs &a, const HnswArgs &h, unsigned char *q_lds, uint32_t qi, int lane) {
+    const unsigned char *queries = reinterpret_cast<const unsigned char *>(a.queries);
+    if constexpr (is_maxsim<H>::value) {
+        // (the header always sits in LDS; the entries follow when the launch's budget holds them, else they are read where they lie)
+        const uint32_t t0 = a.mv_qfirst[qi], n_tokens = a.mv_qfirst[qi + 1] - t0;
+        const unsigned char *qg = queries + (uint64_t)t0 * a.q_stride;
+        const bool fits = 16 + (uint64_t)n_tokens * a.q_stride <= h.lds_query_bytes;
+        __syncthreads();
+        if (fits) stage_copy(q_lds + 16, qg, n_tokens * (a.q_stride / 16), lane);
+        if (lane == 0) write_maxsim_header(q_lds, n_tokens, fits ? q_lds + 16 : qg);
+        __syncthreads();
+        return q_lds + 16;
+    } else if constexpr (is_custom<H>::value) {
+        // (the header always sits in LDS: launch_hnsw_hop grants at least its 32 bytes; the examples follow when the launch's budget holds them)
+        const qmx_custom_query cq = a.cq_desc[qi];
+        const uint32_t ne = cq.kind <= QMX_CUSTOM_RECO_SUM_SCORES ? cq.n_a + cq.n_b : cq.n_a + 2 * cq.n_b;
+        unsigned char *base = q_lds + sizeof(CustomHeader);
+        if constexpr (H::MULTI_EXAMPLES) {
+            // [header][offset table, 16-byte padded][per example: 16-byte MaxSim header (its token count) + its tokens]; the API sized the launch for it
+            uint32_t *tab = reinterpret_cast<uint32_t *>(base);
+            uint32_t off = (4 * ne + 15u) & ~15u;
+            __syncthreads();
+            for (uint32_t e = 0; e < ne; ++e) {
+                const uint32_t t0 = a.mv_qfirst[cq.first + e], nt = a.mv_qfirst[cq.first + e + 1] - t0;
+                // (the visited table and the PQ image sit right behind the query entry: an example that did not fit the launch's entry must not be
+                // staged over them - the search is refused instead)
+                if (sizeof(CustomHeader) + (uint64_t)off + 16 + (uint64_t)nt * a.q_stride > h.lds_query_bytes) {
+                    if (lane == 0) *a.err_flag = 1;
+                    break;
+                }
+                if (lane == 0) {
+                    tab[e] = off + 16;
+                    write_maxsim_header(base + off, nt, base + off + 16);
+                }
+                stage_copy(base + off + 16, queries + (uint64_t)t0 * a.q_stride, nt * (a.q_stride / 16), lane);
+                off += 16 + nt * a.q_stride;
+            }
+            if (lane == 0) write_custom_header(q_lds, cq, base, tab);
+        } else {
+            const unsigned char *qg = queries + (uint64_t)cq.first * a.q_stride;
+            const bool fits = sizeof(CustomHeader) + (uint64_t)ne * a.q_stride <= h.lds_query_bytes;
+            __syncthreads();
+            if (fits) stage_copy(base, qg, ne * (a.q_stride / 16), lane);
+            if (lane == 0) write_custom_header(q_lds, cq, fits ? base : qg, nullptr);
+        }
+        __syncthreads();
+        return base;
+    } else {
+        const unsigned char *qg = queries + (uint64_t)qi * a.q_stride;
+        if constexpr (QLDS) {
+            __syncthreads();
+            stage_copy(q_lds, qg, (h.lds_query_bytes < a.q_stride ? h.lds_query_bytes : a.q_stride) / 16, lane);     // (a policy may own scratch behind its entry)
+            __syncthreads();
+            return q_lds;
+        } else {
+            return qg;
+        }
+    }
+}
+
 #ifndef QMX_WALK_KERNEL_ATTR
 #define QMX_WALK_KERNEL_ATTR
 #endif
@@ -1246,15 +702,18 @@ template <class H, int E, bool QLDS>
 __global__ __launch_bounds__(64) QMX_WALK_KERNEL_ATTR void hnsw_search_kernel(const ScanArgs a, const HnswArgs h) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
-    // [hop ids: hop_cap u32][hop scores: hop_cap f32][ACORN: 64 ids to explore][query entry]
-    uint32_t *hop_ids = reinterpret_cast<uint32_t *>(smem);
-    float *hop_scores = reinterpret_cast<float *>(smem + 4 * (size_t)h.hop_cap);
-    unsigned char *q_lds = smem + 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap);
-    unsigned char *beam_lds = q_lds + (QLDS ? ((size_t)h.lds_query_bytes + 15) / 16 * 16 : 0);      // E == 0: the LDS beam behind the query entry (E == HNSW_E_REF: `nearest`)
+    const HnswLds at = hnsw_lds_layout<E, QLDS>(h);
+    uint32_t *hop_ids = reinterpret_cast<uint32_t *>(smem + at.hop_ids);
+    float *hop_scores = reinterpret_cast<float *>(smem + at.hop_scores);
+    // every region by the layout: the query entry and the beam found from the region in front of them, the two regions behind the beam looked up
+    // where the launch has them
+    unsigned char *q_lds = smem + at.explore + (at.query - at.explore);
     uint32_t *vis = h.visited + (uint64_t)blockIdx.x * h.vis_words;
     uint32_t *vlog = h.vis_log + (uint64_t)blockIdx.x * h.log_cap;
-    // the search's visited table (LdsVisited), behind everything else: zero once here, every search leaves it zero
-    uint32_t *vtab = h.vis_lds ? reinterpret_cast<uint32_t *>(beam_lds + (E <= 0 ? hnsw_beam_lds(h.ef > h.top ? h.ef : h.top) : 0) + (E == HNSW_E_REF ? (size_t)HNSW_REF_CAND_LDS * 8 : 0)) : nullptr;
+    unsigned char *beam_lds = q_lds + (at.beam - at.query);      // E == 0: the LDS beam behind the query entry (E == HNSW_E_REF: `nearest`)
+    // the search's visited table (LdsVisited): zero once here, every search leaves it zero
+    uint32_t *vtab = nullptr;
+    if (h.vis_lds) vtab = reinterpret_cast<uint32_t *>(smem + hnsw_lds_layout<E, QLDS>(h).visited);
     if (vtab) {
         LdsVisited{vtab}.clear(lane);
         __syncthreads();
@@ -1268,124 +727,35 @@ __global__ __launch_bounds__(64) QMX_WALK_KERNEL_ATTR void hnsw_search_kernel(co
         if (lane == 0) v = atomicAdd(h.next_query, 1u);
         return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
     };
-    // HopPQ's 8-bit LUT image of the search (HnswArgs::pq8), behind the visited table
+    // HopPQ's 8-bit LUT image of the search (HnswArgs::pq8)
     unsigned char *pq8_lds = nullptr;
     if constexpr (has_hop_prefilter<H>::value) {
-        if (h.pq8) pq8_lds = beam_lds + (E <= 0 ? hnsw_beam_lds(h.ef > h.top ? h.ef : h.top) : 0) + h.vis_lds;
+        if (h.pq8) pq8_lds = smem + hnsw_lds_layout<E, QLDS>(h).pq8;
     }
     for (uint32_t qi = blockIdx.x; qi < h.nq; qi = next_search(qi)) {
         if constexpr (has_hop_prefilter<H>::value) {
             if (pq8_lds) {
                 __syncthreads();
-                const uint4 *src = reinterpret_cast<const uint4 *>(h.pq8 + (uint64_t)qi * h.pq8_stride);
-                uint4 *dst = reinterpret_cast<uint4 *>(pq8_lds);
-                for (uint32_t i = (uint32_t)lane; i < h.pq8_stride / 16; i += 64) dst[i] = src[i];
+                stage_copy(pq8_lds, h.pq8 + (uint64_t)qi * h.pq8_stride, h.pq8_stride / 16, lane);
                 __syncthreads();
             }
         }
-        if constexpr (is_maxsim<H>::value) {
-            // (the header always sits in LDS; the entries follow when the launch's budget holds them, else they are read where they lie)
-            const uint32_t t0 = a.mv_qfirst[qi], n_tokens = a.mv_qfirst[qi + 1] - t0;
-            const unsigned char *qg = reinterpret_cast<const unsigned char *>(a.queries) + (uint64_t)t0 * a.q_stride;
-            const bool fits = 16 + (uint64_t)n_tokens * a.q_stride <= h.lds_query_bytes;
-            __syncthreads();
-            if (fits) {
-                const uint4 *src = reinterpret_cast<const uint4 *>(qg);
-                uint4 *dst = reinterpret_cast<uint4 *>(q_lds + 16);
-                for (uint32_t i = (uint32_t)lane; i < n_tokens * (a.q_stride / 16); i += 64) dst[i] = src[i];
-            }
-            if (lane == 0) {
-                *reinterpret_cast<uint32_t *>(q_lds) = n_tokens;
-                *reinterpret_cast<const unsigned char **>(q_lds + 8) = fits ? q_lds + 16 : qg;
-            }
-            __syncthreads();
-            hnsw_search_one<H, E>(a, h, q_lds + 16, hop_ids, hop_scores, vis, vlog, qi, lane, beam_lds, vtab, pq8_lds);
-            continue;
-        }
-        if constexpr (is_custom<H>::value) {
-            // (the header always sits in LDS: launch_hnsw_hop grants at least its 32 bytes; the examples follow when the launch's budget holds them)
-            const qmx_custom_query cq = a.cq_desc[qi];
-            const uint32_t ne = cq.kind <= QMX_CUSTOM_RECO_SUM_SCORES ? cq.n_a + cq.n_b : cq.n_a + 2 * cq.n_b;
-            const unsigned char *qg = reinterpret_cast<const unsigned char *>(a.queries) + (uint64_t)cq.first * a.q_stride;
-            if constexpr (H::MULTI_EXAMPLES) {
-                // [header][offset table, 16-byte padded][per example: 16-byte MaxSim header (its token count) + its tokens]; the API sized the launch for it
-                unsigned char *base = q_lds + sizeof(CustomHeader);
-                uint32_t *tab = reinterpret_cast<uint32_t *>(base);
-                uint32_t off = (4 * ne + 15u) & ~15u;
-                __syncthreads();
-                for (uint32_t e = 0; e < ne; ++e) {
-                    const uint32_t t0 = a.mv_qfirst[cq.first + e], nt = a.mv_qfirst[cq.first + e + 1] - t0;
-                    // (the visited table and the PQ image sit right behind the query entry: an example that did not fit the launch's entry must not be
-                    // staged over them - the search is refused instead)
-                    if (sizeof(CustomHeader) + (uint64_t)off + 16 + (uint64_t)nt * a.q_stride > h.lds_query_bytes) {
-                        if (lane == 0) *a.err_flag = 1;
-                        break;
-                    }
-                    if (lane == 0) {
-                        tab[e] = off + 16;
-                        *reinterpret_cast<uint32_t *>(base + off) = nt;
-                        *reinterpret_cast<const unsigned char **>(base + off + 8) = base + off + 16;
-                    }
-                    const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned char *>(a.queries) + (uint64_t)t0 * a.q_stride);
-                    uint4 *dst = reinterpret_cast<uint4 *>(base + off + 16);
-                    for (uint32_t i = (uint32_t)lane; i < nt * (a.q_stride / 16); i += 64) dst[i] = src[i];
-                    off += 16 + nt * a.q_stride;
-                }
-                if (lane == 0) {
-                    CustomHeader *hd = reinterpret_cast<CustomHeader *>(q_lds);
-                    hd->kind = cq.kind; hd->n_a = cq.n_a; hd->n_b = cq.n_b; hd->coef_first = cq.coef_first;
-                    hd->entries = base;
-                    hd->ex_off = tab;
-                }
-                __syncthreads();
-                hnsw_search_one<H, E>(a, h, q_lds + sizeof(CustomHeader), hop_ids, hop_scores, vis, vlog, qi, lane, beam_lds, vtab, pq8_lds);
-                continue;
-            }
-            const bool fits = sizeof(CustomHeader) + (uint64_t)ne * a.q_stride <= h.lds_query_bytes;
-            __syncthreads();
-            if (fits) {
-                const uint4 *src = reinterpret_cast<const uint4 *>(qg);
-                uint4 *dst = reinterpret_cast<uint4 *>(q_lds + sizeof(CustomHeader));
-                for (uint32_t i = (uint32_t)lane; i < ne * (a.q_stride / 16); i += 64) dst[i] = src[i];
-            }
-            if (lane == 0) {
-                CustomHeader *hd = reinterpret_cast<CustomHeader *>(q_lds);
-                hd->kind = cq.kind; hd->n_a = cq.n_a; hd->n_b = cq.n_b; hd->coef_first = cq.coef_first;
-                hd->entries = fits ? q_lds + sizeof(CustomHeader) : qg;
-                hd->ex_off = nullptr;
-            }
-            __syncthreads();
-            hnsw_search_one<H, E>(a, h, q_lds + sizeof(CustomHeader), hop_ids, hop_scores, vis, vlog, qi, lane, beam_lds, vtab, pq8_lds);
-            continue;
-        }
-        const unsigned char *qg = reinterpret_cast<const unsigned char *>(a.queries) + (uint64_t)qi * a.q_stride;
-        if constexpr (QLDS) {
-            __syncthreads();
-            const uint4 *src = reinterpret_cast<const uint4 *>(qg);
-            uint4 *dst = reinterpret_cast<uint4 *>(q_lds);
-            const uint32_t q_units = (h.lds_query_bytes < a.q_stride ? h.lds_query_bytes : a.q_stride) / 16;     // (a policy may own scratch behind its entry)
-            for (uint32_t i = (uint32_t)lane; i < q_units; i += 64) dst[i] = src[i];
-            __syncthreads();
-            hnsw_search_one<H, E>(a, h, q_lds, hop_ids, hop_scores, vis, vlog, qi, lane, beam_lds, vtab, pq8_lds);
-        } else {
-            hnsw_search_one<H, E>(a, h, qg, hop_ids, hop_scores, vis, vlog, qi, lane, beam_lds, vtab, pq8_lds);
-        }
+        const unsigned char *qp = stage_search_entry<H, QLDS>(a, h, q_lds, qi, lane);
+        hnsw_search_one<H, E>(a, h, qp, hop_ids, hop_scores, vis, vlog, qi, lane, beam_lds, vtab, pq8_lds);
     }
 }
 
-
-// occupancy of an instantiation (blocks of one wave per CU) — used by the API to size the scratch
+// occupancy of an instantiation (blocks of one wave per CU) for a launch with arguments h — used by the API to size the scratch
 template <class H, int E, bool QLDS>
-int32_t hnsw_occupancy_inst(uint32_t lds_query_bytes, size_t hop_lds, int *per_cu) {
+int32_t hnsw_occupancy_inst(const HnswArgs &h, int *per_cu) {
     auto kfn = hnsw_search_kernel<H, E, QLDS>;
     static thread_local DeviceOnce attr_once;
     if (attr_once.need()) {
         QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_once.mark();
     }
-    const size_t lds = hop_lds + (QLDS ? ((size_t)lds_query_bytes + 15) / 16 * 16 : 0);     // (hop_lds carries the LDS beam of an E == 0 instantiation)
     int n = 0;
-    QMX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kfn, 64, lds));
+    QMX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kfn, 64, hnsw_lds_layout<E, QLDS>(h).total));
     *per_cu = n < 1 ? 1 : n;
     return QMX_OK;
 }
@@ -1393,8 +763,7 @@ int32_t hnsw_occupancy_inst(uint32_t lds_query_bytes, size_t hop_lds, int *per_c
 template <class H, int E, bool QLDS>
 int32_t launch_hnsw_inst(hipStream_t st, const ScanArgs &a, const HnswArgs &h, uint32_t grid) {
     const uint32_t ef = h.ef > h.top ? h.ef : h.top;
-    const size_t lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + (QLDS ? ((size_t)h.lds_query_bytes + 15) / 16 * 16 : 0) + (E <= 0 ? hnsw_beam_lds(ef) : 0) +
-                       (E == HNSW_E_REF ? (size_t)HNSW_REF_CAND_LDS * 8 : 0) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
+    const size_t lds = hnsw_lds_layout<E, QLDS>(h).total;
     QMX_REQUIRE(lds <= 160 * 1024, QMX_ERR_NOT_SUPPORTED, "hnsw walk: %zu bytes of LDS (query entry + a list of %u)", lds, ef);
     ::qmx::clear_stale_error();
     QMX_NOTE_KERNEL((hnsw_search_kernel<H, E, QLDS>));
@@ -1409,6 +778,36 @@ struct ref_heaps_built {
     static constexpr bool value = !is_custom<H>::value && !is_maxsim<H>::value && !is_maxsim_q<H>::value && !is_maxsim_internal<H>::value && !is_tql1<H>::value;
 };
 
+// the instantiation <H, E, QLDS> that serves a launch, handed to `with` as a tag
+template <int E, bool QLDS>
+struct WalkInst {
+    static constexpr int e = E;
+    static constexpr bool qlds = QLDS;
+};
+template <class H, class With>
+int32_t choose_hnsw_inst(const HnswArgs &h, uint32_t ef, With &&with) {
+    const bool qlds = h.lds_query_bytes > 0;
+    if (h.ref_heaps) {      // option hnsw_reference_heap_order: the plain walk of the policies a stored graph is walked with
+        if constexpr (ref_heaps_built<H>::value) {
+            QMX_REQUIRE(!h.acorn && !h.expanded, QMX_ERR_NOT_SUPPORTED, "hnsw_reference_heap_order: the plain walk only (not ACORN, not search_with_vectors)");
+            return qlds ? with(WalkInst<HNSW_E_REF, true>{}) : with(WalkInst<HNSW_E_REF, false>{});
+        } else {
+            set_error("hnsw_reference_heap_order: not built for this scorer (custom queries, multi-vector points, TurboQuant over Manhattan)");
+            return QMX_ERR_NOT_SUPPORTED;
+        }
+    }
+    if (ef > HNSW_MAX_EF_REG) {        // the LDS beam: one instantiation per policy, the query entry staged
+        QMX_REQUIRE(qlds, QMX_ERR_NOT_SUPPORTED, "hnsw ef %u > %u needs the query entry in LDS (it does not fit)", ef, HNSW_MAX_EF_REG);
+        return with(WalkInst<0, true>{});
+    }
+    if constexpr (is_custom<H>::value || is_maxsim<H>::value) {      // (always staged: no instantiation that reads the entry from global memory)
+        return ef <= 128 ? with(WalkInst<2, true>{}) : with(WalkInst<8, true>{});
+    } else {
+        if (ef <= 128) return qlds ? with(WalkInst<2, true>{}) : with(WalkInst<2, false>{});
+        return qlds ? with(WalkInst<8, true>{}) : with(WalkInst<8, false>{});
+    }
+}
+
 // grid == 0: only report the occupancy in *per_cu (no launch)
 template <class H>
 int32_t launch_hnsw_hop(hipStream_t st, const ScanArgs &a, const HnswArgs &h, uint32_t grid, int *per_cu) {
@@ -1419,74 +818,31 @@ int32_t launch_hnsw_hop(hipStream_t st, const ScanArgs &a, const HnswArgs &h, ui
     } else if constexpr (!per_query_filter<H>::value) {
         QMX_REQUIRE(!a.del.filter_of, QMX_ERR_NOT_SUPPORTED, "this walk does not serve per-request filters (qmx_query_set_filters)");
     }
-    const bool qlds = h.lds_query_bytes > 0;
-    if constexpr (is_maxsim<H>::value) QMX_REQUIRE(qlds, QMX_ERR_NOT_SUPPORTED, "the inner vectors of a multi-query must fit the LDS");
+    if constexpr (is_maxsim<H>::value) QMX_REQUIRE(h.lds_query_bytes > 0, QMX_ERR_NOT_SUPPORTED, "the inner vectors of a multi-query must fit the LDS");
     if constexpr (is_custom<H>::value) QMX_REQUIRE(h.lds_query_bytes >= sizeof(CustomHeader), QMX_ERR_OTHER, "the custom walk keeps its header in LDS");
-    if (h.ref_heaps) {      // option hnsw_reference_heap_order: the plain walk of the policies a stored graph is walked with
-        if constexpr (ref_heaps_built<H>::value) {
-            QMX_REQUIRE(!h.acorn && !h.expanded, QMX_ERR_NOT_SUPPORTED, "hnsw_reference_heap_order: the plain walk only (not ACORN, not search_with_vectors)");
-            const size_t hop_lds = 8 * (size_t)h.hop_cap + hnsw_beam_lds(ef) + (size_t)HNSW_REF_CAND_LDS * 8 + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
-            if (grid == 0) return qlds ? hnsw_occupancy_inst<H, HNSW_E_REF, true>(h.lds_query_bytes, hop_lds, per_cu) : hnsw_occupancy_inst<H, HNSW_E_REF, false>(0, hop_lds, per_cu);
-            return qlds ? launch_hnsw_inst<H, HNSW_E_REF, true>(st, a, h, grid) : launch_hnsw_inst<H, HNSW_E_REF, false>(st, a, h, grid);
-        } else {
-            set_error("hnsw_reference_heap_order: not built for this scorer (custom queries, multi-vector points, TurboQuant over Manhattan)");
-            return QMX_ERR_NOT_SUPPORTED;
-        }
-    }
-    if (ef > HNSW_MAX_EF_REG) {        // the LDS beam: one instantiation per policy, the query entry staged
-        QMX_REQUIRE(qlds, QMX_ERR_NOT_SUPPORTED, "hnsw ef %u > %u needs the query entry in LDS (it does not fit)", ef, HNSW_MAX_EF_REG);
-        if (grid == 0) return hnsw_occupancy_inst<H, 0, true>(h.lds_query_bytes, 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + hnsw_beam_lds(ef) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0), per_cu);
-        return launch_hnsw_inst<H, 0, true>(st, a, h, grid);
-    }
-    if constexpr (is_custom<H>::value || is_maxsim<H>::value) {      // (always staged: no instantiation that reads the entry from global memory)
-        if (grid == 0) {
-            const size_t hop_lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
-            return ef <= 128 ? hnsw_occupancy_inst<H, 2, true>(h.lds_query_bytes, hop_lds, per_cu) : hnsw_occupancy_inst<H, 8, true>(h.lds_query_bytes, hop_lds, per_cu);
-        }
-        return ef <= 128 ? launch_hnsw_inst<H, 2, true>(st, a, h, grid) : launch_hnsw_inst<H, 8, true>(st, a, h, grid);
-    } else {
-    if (grid == 0) {
-        const size_t hop_lds = 8 * (size_t)h.hop_cap + hnsw_acorn_lds(h.acorn, h.explore_cap) + h.vis_lds + (h.pq8 ? h.pq8_stride : 0);
-        if (ef <= 128) return qlds ? hnsw_occupancy_inst<H, 2, true>(h.lds_query_bytes, hop_lds, per_cu) : hnsw_occupancy_inst<H, 2, false>(0, hop_lds, per_cu);
-        return qlds ? hnsw_occupancy_inst<H, 8, true>(h.lds_query_bytes, hop_lds, per_cu) : hnsw_occupancy_inst<H, 8, false>(0, hop_lds, per_cu);
-    }
-    if (ef <= 128) return qlds ? launch_hnsw_inst<H, 2, true>(st, a, h, grid) : launch_hnsw_inst<H, 2, false>(st, a, h, grid);
-    return qlds ? launch_hnsw_inst<H, 8, true>(st, a, h, grid) : launch_hnsw_inst<H, 8, false>(st, a, h, grid);
-    }
+    return choose_hnsw_inst<H>(h, ef, [&](auto inst) -> int32_t {
+        constexpr int E = decltype(inst)::e;
+        constexpr bool QLDS = decltype(inst)::qlds;
+        if (grid == 0) return hnsw_occupancy_inst<H, E, QLDS>(h, per_cu);
+        return launch_hnsw_inst<H, E, QLDS>(st, a, h, grid);
+    });
 }
 
-// launch functor for the per-dtype dispatchers (dispatch_dense / dispatch_sq)
-struct HnswLauncher {
+// launch functors for the per-dtype dispatchers (dispatch_dense / dispatch_sq): the storage's hop policy under the wrapper of the walk's scorer
+template <template <class> class Wrap>
+struct HnswLauncherOf {
     hipStream_t st;
     const HnswArgs *h;
     uint32_t grid;
     int *per_cu;
-    template <class P> int32_t row(const ScanArgs &a) const { return launch_hnsw_hop<HopRow<P>>(st, a, *h, grid, per_cu); }
-    template <class S> int32_t small(const ScanArgs &a) const { return launch_hnsw_hop<HopSmall<S>>(st, a, *h, grid, per_cu); }
+    template <class P> int32_t row(const ScanArgs &a) const { return launch_hnsw_hop<Wrap<HopRow<P>>>(st, a, *h, grid, per_cu); }
+    template <class S> int32_t small(const ScanArgs &a) const { return launch_hnsw_hop<Wrap<HopSmall<S>>>(st, a, *h, grid, per_cu); }
 };
-struct HnswCustomLauncher {
-    hipStream_t st;
-    const HnswArgs *h;
-    uint32_t grid;
-    int *per_cu;
-    template <class P> int32_t row(const ScanArgs &a) const { return launch_hnsw_hop<HopCustom<HopRow<P>>>(st, a, *h, grid, per_cu); }
-    template <class S> int32_t small(const ScanArgs &a) const { return launch_hnsw_hop<HopCustom<HopSmall<S>>>(st, a, *h, grid, per_cu); }
-};
-struct HnswCustomMaxSimLauncher {
-    hipStream_t st;
-    const HnswArgs *h;
-    uint32_t grid;
-    int *per_cu;
-    template <class P> int32_t row(const ScanArgs &a) const { return launch_hnsw_hop<HopCustom<HopMaxSim<HopRow<P>>>>(st, a, *h, grid, per_cu); }
-    template <class S> int32_t small(const ScanArgs &a) const { return launch_hnsw_hop<HopCustom<HopMaxSim<HopSmall<S>>>>(st, a, *h, grid, per_cu); }
-};
-struct HnswMaxSimLauncher {
-    hipStream_t st;
-    const HnswArgs *h;
-    uint32_t grid;
-    int *per_cu;
-    template <class P> int32_t row(const ScanArgs &a) const { return launch_hnsw_hop<HopMaxSim<HopRow<P>>>(st, a, *h, grid, per_cu); }
-    template <class S> int32_t small(const ScanArgs &a) const { return launch_hnsw_hop<HopMaxSim<HopSmall<S>>>(st, a, *h, grid, per_cu); }
-};
+template <class H> using HopPlain = H;
+template <class H> using HopCustomMaxSim = HopCustom<HopMaxSim<H>>;
+using HnswLauncher = HnswLauncherOf<HopPlain>;
+using HnswCustomLauncher = HnswLauncherOf<HopCustom>;
+using HnswCustomMaxSimLauncher = HnswLauncherOf<HopCustomMaxSim>;
+using HnswMaxSimLauncher = HnswLauncherOf<HopMaxSim>;
 
 }  // namespace qmx
