@@ -109,35 +109,12 @@ int32_t qmx_custom_hnsw_search(const qmx_hnsw *g, qmx_query *ex, const qmx_custo
     QMX_CHECK_CANCELLED(is_stopped);
     uint32_t max_examples = 0;
     QMX_TRY(custom_validate(ex, queries, n_queries, ex->nq, &max_examples));
-    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
-    if (g->n_points == 0) {   // get_entry_point() -> None
-        if (cnt_dev) QMX_HIP(hipMemset(out_counts, 0, (size_t)n_queries * 4));
-        else memset(out_counts, 0, (size_t)n_queries * 4);
-        return QMX_OK;
-    }
     QMX_TRY(ex->cq_desc.reserve((size_t)n_queries * sizeof(qmx_custom_query)));
     QMX_HIP(hipMemcpyAsync(ex->cq_desc.p, queries, (size_t)n_queries * sizeof(qmx_custom_query), hipMemcpyHostToDevice, ex->stream));
-    CustomWalk cw{(const qmx_custom_query *)ex->cq_desc.p, (const float *)ex->cq_coefs.p, n_queries, max_examples};
-    qmx_scored_point *d_out = out;
-    uint32_t *d_counts = out_counts;
-    if (!out_dev) { QMX_TRY(ex->out.reserve((size_t)n_queries * top * sizeof(qmx_scored_point))); d_out = (qmx_scored_point *)ex->out.p; }
-    if (!cnt_dev) { QMX_TRY(ex->counts.reserve((size_t)n_queries * 4)); d_counts = (uint32_t *)ex->counts.p; }
-    QMX_TRY(ex->hnsw_scored.reserve((size_t)n_queries * 4));
-    const bool timed = ex->timing || (ex->seg->flags & QMX_SEG_TIME_KERNELS) != 0;
-    QMX_TRY(hnsw_enqueue(g, ex, top, ef, d_out, d_counts, (uint32_t *)ex->hnsw_scored.p, timed, false, nullptr, nullptr, &cw));
-    if (!out_dev) QMX_TRY(copy_out(ex->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
-    if (!cnt_dev) QMX_TRY(copy_out(ex->stream, out_counts, d_counts, (size_t)n_queries * 4));
-    QMX_TRY(check_err_flag(ex));    // synchronises (the caller's descriptors may go away)
-    if (counters) {
-        std::vector<uint32_t> sc(n_queries);
-        QMX_HIP(hipMemcpy(sc.data(), ex->hnsw_scored.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost));
-        uint64_t total = 0;
-        for (uint32_t v : sc) total += v;
-        counters->vectors_scored = total;            // POINTS scored (each costs one similarity per example of its query)
-        counters->kernel_launches = 1;
-        if (timed) { const float before = ex->timing_ms; QMX_TRY(timing_fold(ex)); counters->kernel_ms = ex->timing_ms - before; }
-    }
-    return QMX_OK;
+    const CustomWalk cw{(const qmx_custom_query *)ex->cq_desc.p, (const float *)ex->cq_coefs.p, n_queries, max_examples};
+    WalkRequest r;
+    r.top = top; r.ef = ef; r.custom = &cw;
+    return hnsw_walk_to_caller(g, ex, r, n_queries, out, out_counts, counters, false);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -310,8 +287,10 @@ int32_t qmx_multi_custom_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const 
     if (n_queries == 0) return QMX_OK;
     QMX_REQUIRE(example_first[n_examples] <= inner->nq, QMX_ERR_OUT_OF_BOUNDS, "examples reach past the %u inner query vectors of the batch", inner->nq);
     for (uint32_t e = 0; e < n_examples; ++e) QMX_REQUIRE(example_first[e] <= example_first[e + 1], QMX_ERR_BAD_ARG, "example_first is not ascending at %u", e);
-    for (uint32_t p = 0; p < n_points; ++p) QMX_REQUIRE(point_offsets[p] <= point_offsets[p + 1], QMX_ERR_BAD_ARG, "point_offsets is not ascending at %u", p);
-    QMX_REQUIRE(point_offsets[n_points] <= s->n, QMX_ERR_OUT_OF_BOUNDS, "point_offsets reach past the %llu inner rows of the segment", (unsigned long long)s->n);
+    MultiWalk mw;
+    QMX_TRY(stage_multi_walk(inner, example_first, n_examples, point_offsets, n_points, point_deleted, n_deleted_bits, &mw));
+    mw.n_queries = n_queries;
+    mw.max_tokens = 1;
     uint32_t max_examples = 0;
     QMX_TRY(custom_validate(inner, queries, n_queries, n_examples, &max_examples));
     uint64_t lds_need = 0;        // the largest staged block: header + offset table + per example (16-byte MaxSim header + its tokens)
@@ -324,53 +303,12 @@ int32_t qmx_multi_custom_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const 
     }
     QMX_REQUIRE(lds_need <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "a custom query of %llu bytes of example tokens does not fit the LDS",
                 (unsigned long long)lds_need);
-    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
-    if (g->n_points == 0) {
-        if (cnt_dev) QMX_HIP(hipMemset(out_counts, 0, (size_t)n_queries * 4));
-        else memset(out_counts, 0, (size_t)n_queries * 4);
-        return QMX_OK;
-    }
-    QMX_TRY(inner->mv_qfirst.reserve((size_t)(n_examples + 1) * 4));
-    QMX_TRY(inner->mv_offsets.reserve((size_t)(n_points + 1) * 8));
     QMX_TRY(inner->cq_desc.reserve((size_t)n_queries * sizeof(qmx_custom_query)));
-    QMX_HIP(hipMemcpyAsync(inner->mv_qfirst.p, example_first, (size_t)(n_examples + 1) * 4, hipMemcpyHostToDevice, inner->stream));
-    QMX_HIP(hipMemcpyAsync(inner->mv_offsets.p, point_offsets, (size_t)(n_points + 1) * 8, hipMemcpyHostToDevice, inner->stream));
     QMX_HIP(hipMemcpyAsync(inner->cq_desc.p, queries, (size_t)n_queries * sizeof(qmx_custom_query), hipMemcpyHostToDevice, inner->stream));
-    MultiWalk mw;
-    memset(&mw, 0, sizeof(mw));
-    mw.d_qfirst = (const uint32_t *)inner->mv_qfirst.p;
-    mw.d_offsets = (const uint64_t *)inner->mv_offsets.p;
-    mw.n_queries = n_queries;
-    mw.max_tokens = 1;
-    mw.del.n_rows = n_points;
-    if (point_deleted && n_deleted_bits) {
-        const void *d_bits = nullptr;
-        QMX_TRY(stage_in(inner, inner->mv_deleted, point_deleted, (size_t)((n_deleted_bits + 63) / 64) * 8, &d_bits));
-        mw.del.point_deleted = (const uint64_t *)d_bits;
-        mw.del.n_point_bits = n_deleted_bits;
-    }
-    if (inner->has_filter) { mw.del.allowed = (const uint64_t *)inner->filter.p; mw.del.n_allowed_bits = inner->n_filter_bits; }
-    CustomWalk cw{(const qmx_custom_query *)inner->cq_desc.p, (const float *)inner->cq_coefs.p, n_queries, max_examples, (uint32_t)lds_need};
-    qmx_scored_point *d_out = out;
-    uint32_t *d_counts = out_counts;
-    if (!out_dev) { QMX_TRY(inner->out.reserve((size_t)n_queries * top * sizeof(qmx_scored_point))); d_out = (qmx_scored_point *)inner->out.p; }
-    if (!cnt_dev) { QMX_TRY(inner->counts.reserve((size_t)n_queries * 4)); d_counts = (uint32_t *)inner->counts.p; }
-    QMX_TRY(inner->hnsw_scored.reserve((size_t)n_queries * 4));
-    const bool timed = inner->timing || (s->flags & QMX_SEG_TIME_KERNELS) != 0;
-    QMX_TRY(hnsw_enqueue(g, inner, top, ef, d_out, d_counts, (uint32_t *)inner->hnsw_scored.p, timed, false, &mw, nullptr, &cw));
-    if (!out_dev) QMX_TRY(copy_out(inner->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
-    if (!cnt_dev) QMX_TRY(copy_out(inner->stream, out_counts, d_counts, (size_t)n_queries * 4));
-    QMX_TRY(check_err_flag(inner));
-    if (counters) {
-        std::vector<uint32_t> sc(n_queries);
-        QMX_HIP(hipMemcpy(sc.data(), inner->hnsw_scored.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost));
-        uint64_t total = 0;
-        for (uint32_t v : sc) total += v;
-        counters->vectors_scored = total;
-        counters->kernel_launches = 1;
-        if (timed) { const float before = inner->timing_ms; QMX_TRY(timing_fold(inner)); counters->kernel_ms = inner->timing_ms - before; }
-    }
-    return QMX_OK;
+    const CustomWalk cw{(const qmx_custom_query *)inner->cq_desc.p, (const float *)inner->cq_coefs.p, n_queries, max_examples, (uint32_t)lds_need};
+    WalkRequest r;
+    r.top = top; r.ef = ef; r.multi = &mw; r.custom = &cw;
+    return hnsw_walk_to_caller(g, inner, r, n_queries, out, out_counts, counters, false);
 }
 
 }  // extern "C"

@@ -275,66 +275,113 @@ static int32_t launch_hnsw(const qmx_query *q, const ScanArgs &a, const HnswArgs
 }
 
 
-int32_t hnsw_enqueue(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *d_out,
-                            uint32_t *d_counts, uint32_t *d_scored, bool timed, bool acorn, const MultiWalk *mw,
-                            const ExpandedOut *xo, const CustomWalk *cw, const PopTrace *pt) {
+// ---- one walk (hnsw_enqueue): describe it, plan it (hnsw_walk_plan.hpp), set up what the plan names, launch ----
+static WalkShape walk_shape(const qmx_hnsw *g, const qmx_query *q, const WalkRequest &r, const ScanArgs &a) {
     const qmx_segment *s = q->seg;
-    QMX_REQUIRE(!tq_l1(s) || !mw, QMX_ERR_NOT_SUPPORTED, "multi-vector walks through a TurboQuant storage over Manhattan are not built");
-    // (per-request filters index the walk's searches as the batch's queries: custom and multi-vector walks, whose searches are not the batch's entries, and
-    // the expanded-candidates walk of search_with_vectors refuse at their entry points - this is the backstop)
-    QMX_REQUIRE(!q->has_filters || (!mw && !cw && !xo), QMX_ERR_NOT_SUPPORTED, "this walk does not serve per-request filters (qmx_query_set_filters)");
-    ScanArgs a;
-    fill_args(q, 0, q->nq, a);
+    WalkShape w;
+    w.acorn = r.acorn; w.expanded = r.expanded != nullptr; w.multi = r.multi != nullptr; w.custom = r.custom != nullptr; w.traced = r.trace != nullptr;
+    w.filters = q->has_filters;
+    w.storage = s->dtype == QMX_DTYPE_PQ ? WalkStorage::PQ : tq_l1(s) ? WalkStorage::TqL1 : WalkStorage::Other;
+    w.dim = s->dim;
+    if (w.storage == WalkStorage::PQ) {
+        w.pq_m = s->pq_m;
+        w.n_centroids = s->pq.n_centroids;
+        w.pq_direct_ok = s->d_centroids && pq_direct_walk_ok(s->dim, s->pq_m, s->pq.chunk_size, s->pq.n_centroids);
+    }
+    if (w.storage == WalkStorage::TqL1) {
+        w.tq_l1_entry_bytes = tq_l1_query_bytes(s->dim);
+        w.tq_l1_lds_bytes = tq_l1_lds_bytes(s->dim, s->tq_rot_dim);
+    }
+    w.q_stride = q->q_stride; w.top = r.top; w.ef = r.ef;
+    w.batch_entries = a.queries == q->d_queries;
+    w.n_points = g->n_points; w.m0 = g->m0; w.max_row0 = g->max_row0;
+    if (r.multi) w.max_tokens = r.multi->max_tokens;
+    if (r.custom) { w.max_examples = r.custom->max_examples; w.custom_lds_bytes = r.custom->lds_bytes; }
+    w.opt_pq_direct_walk = option(OPT_HNSW_PQ_DIRECT_WALK) > 0;
+    w.opt_reference_heap_order = option(OPT_HNSW_REFERENCE_HEAP_ORDER) > 0;
+    w.opt_no_lds_visited = option(OPT_HNSW_NO_LDS_VISITED) != 0;
+    w.opt_no_pq_prefilter = option(OPT_HNSW_NO_PQ_PREFILTER) != 0;
+    w.opt_log_cap = option(OPT_HNSW_LOG_CAP);
+    return w;
+}
+
+static int32_t walk_refused(const WalkPlan &p, const WalkShape &w) {
+    const unsigned long long bytes = p.refused_bytes;
+    switch (p.refusal) {
+    case WalkRefusal::None: return QMX_OK;
+    case WalkRefusal::TqL1Multi: set_error("multi-vector walks through a TurboQuant storage over Manhattan are not built"); break;
+    // (custom and multi-vector walks, whose searches are not the batch's entries, and the expanded-candidates walk of search_with_vectors refuse a batch
+    // with per-request filters at their entry points - this is the backstop)
+    case WalkRefusal::Filters: set_error("this walk does not serve per-request filters (qmx_query_set_filters)"); break;
+    case WalkRefusal::Trace: set_error("the pop trace is the plain walk's"); break;
+    case WalkRefusal::TqL1Lds: set_error("TurboQuant over Manhattan, the walk: %u bytes of LDS per search", (uint32_t)bytes); break;
+    case WalkRefusal::CustomTqL1Lds: set_error("a custom query of %u examples over TurboQuant / Manhattan needs %llu bytes of LDS", w.max_examples, bytes); break;
+    case WalkRefusal::CustomTokensLds: set_error("a custom query of %u bytes of example tokens does not fit the LDS", (uint32_t)bytes); break;
+    case WalkRefusal::BeamLds:
+        set_error("hnsw max(top, ef) = %u: the query entry (%u bytes) and the list do not fit the LDS together", std::max(w.top, w.ef), p.entry_stride);
+        break;
+    case WalkRefusal::AcornM0: set_error("ACORN walk: m0 = %u not in 1..128", w.m0); break;
+    case WalkRefusal::AcornRow: set_error("ACORN walk: a level-0 list of %u links does not fit the LDS", w.max_row0); break;
+    }
+    return QMX_ERR_NOT_SUPPORTED;
+}
+
+// the query entries as the walk reads them, where they are not the batch's
+static int32_t stage_walk_entries(qmx_query *q, const WalkPlan &p, ScanArgs &a) {
+    const qmx_segment *s = q->seg;
     if (tq_l1(s)) {   // the walk scores against the query as given (tq_l1_policy.hpp): f32 entries of dim floats, 16-byte padded
-        const uint32_t qs = tq_l1_query_bytes(s->dim);
+        const size_t qs = p.entry_stride;
         QMX_TRY(q->tq_rot.reserve((size_t)q->nq * qs));
         QMX_HIP(hipMemsetAsync(q->tq_rot.p, 0, (size_t)q->nq * qs, q->stream));
         QMX_HIP(hipMemcpy2DAsync(q->tq_rot.p, qs, q->enc.p, (size_t)s->dim * 4, (size_t)s->dim * 4, q->nq, hipMemcpyDeviceToDevice, q->stream));
         a.queries = q->tq_rot.p;
-        a.q_stride = qs;
     }
-    // PQ: the LUT-free walk (pq.hip HopPQDirect) - the entry of a search is its preprocessed vector (q->enc keeps them), staged in LDS
-    const bool pq_direct = s->dtype == QMX_DTYPE_PQ && !cw && !mw && option(OPT_HNSW_PQ_DIRECT_WALK) > 0 &&
-                           s->d_centroids &&
-                           pq_direct_walk_ok(s->dim, s->pq_m, s->pq.chunk_size, s->pq.n_centroids);
-    if (pq_direct) {
-        a.queries = q->enc.p;
-        a.q_stride = s->dim * 4;
+    // PQ: the LUT-free walk (pq.hip HopPQDirect) - the entry of a search is its preprocessed vector (q->enc keeps them)
+    if (p.pq_direct) a.queries = q->enc.p;
+    a.q_stride = p.entry_stride;
+    return QMX_OK;
+}
+
+static int32_t fill_sq_level0(const qmx_segment *s, const uint32_t *d_l0, uint32_t n_points, uint32_t l0_stride, hipStream_t st, uint32_t *table) {
+    QMX_TRY(launch_hnsw_pack_level0_aux(st, d_l0, n_points, l0_stride, s->d_row_offsets, s->n, table));
+    QMX_HIP(hipStreamSynchronize(st));      // (other threads' streams read it once the lock is gone)
+    return QMX_OK;
+}
+int32_t SqLevel0Table::for_segment(const qmx_segment *s, const uint32_t *d_l0, uint32_t n_points, uint32_t l0_stride, hipStream_t st, const uint32_t **table) {
+    *table = nullptr;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!d_table && !failed) {      // the first SQ segment walked over this graph
+        uint32_t *fresh = nullptr;
+        if (hipMalloc((void **)&fresh, (size_t)n_points * (2 * (l0_stride - 1)) * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            failed = true;
+            return QMX_OK;
+        }
+        const int32_t rc = fill_sq_level0(s, d_l0, n_points, l0_stride, st, fresh);
+        if (rc != QMX_OK) {         // (a table that was not completed is nobody's)
+            (void)hipFree(fresh);
+            failed = true;
+            return rc;
+        }
+        d_table = fresh;
+        owner_uid = s->uid;
     }
-    const uint32_t n_searches = cw ? cw->n_queries : mw ? mw->n_queries : q->nq;
-    if (cw) {
-        a.cq_desc = cw->d_desc;
-        a.cq_coefs = cw->d_coefs;
-    }
-    if (mw) {
-        a.mv_offsets = mw->d_offsets;
-        a.mv_qfirst = mw->d_qfirst;
-        a.del = mw->del;
-    }
-    HnswArgs h;
-    memset(&h, 0, sizeof(h));
+    if (d_table && owner_uid == s->uid) *table = d_table;
+    return QMX_OK;
+}
+
+// the graph's tables, its shape, and the capacities the plan chose
+static int32_t bind_graph(const qmx_hnsw *g, const qmx_query *q, const WalkRequest &r, const WalkPlan &p, HnswArgs &h) {
+    const qmx_segment *s = q->seg;
     h.reindex = g->d_reindex; h.level_offsets = g->d_level_offsets; h.offsets = g->d_offsets; h.neighbors = g->d_neighbors;
     h.l0 = g->d_l0; h.l0_stride = g->l0_stride;
-    // SQ segments, plain walk over a packed level 0: the link rows bring the linked rows' vector_offset along (scan_quant.hip RowSQX): the table is made once
-    // per (graph, segment) - 10 M points x 64 dwords = 2.56 GB, one gather pass - and costs the walk one more line per hop instead of a random request per row
-    if (s->dtype == QMX_DTYPE_SQ_U8 && g->d_l0 && !acorn && !xo && !mw && !cw && !(option(OPT_HNSW_REFERENCE_HEAP_ORDER) > 0) && s->d_row_offsets && g->n_points <= s->n) {
-        std::lock_guard<std::mutex> lock(g->l0x_mu);
-        // (the table belongs to the first SQ segment walked over this graph: another segment - another quantization of the same points - keeps the column;
-        // nothing is ever freed under a running kernel)
-        if (!g->d_l0x && !g->l0x_failed) {
-            const size_t bytes = (size_t)g->n_points * (2 * (g->l0_stride - 1)) * 4;
-            if (hipMalloc((void **)&g->d_l0x, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                g->d_l0x = nullptr;
-                g->l0x_failed = true;
-            } else {
-                QMX_TRY(launch_hnsw_pack_level0_aux(q->stream, g->d_l0, g->n_points, g->l0_stride, s->d_row_offsets, s->n, g->d_l0x));
-                QMX_HIP(hipStreamSynchronize(q->stream));      // (other threads' streams read it once the lock is gone)
-                g->l0x_segment_uid = s->uid;
-            }
-        }
-        if (g->d_l0x && g->l0x_segment_uid == s->uid) {
-            h.l0 = g->d_l0x;
+    // SQ segments, plain walk over a packed level 0: the link rows bring the linked rows' vector_offset along, where the graph's table is this segment's
+    const bool plain = !r.acorn && !r.expanded && !r.multi && !r.custom && !p.ref_heaps;
+    if (s->dtype == QMX_DTYPE_SQ_U8 && g->d_l0 && plain && s->d_row_offsets && g->n_points <= s->n) {
+        const uint32_t *l0x = nullptr;
+        QMX_TRY(g->l0x.for_segment(s, g->d_l0, g->n_points, g->l0_stride, q->stream, &l0x));
+        if (l0x) {
+            h.l0 = l0x;
             h.l0_aux_off = g->l0_stride - 1;               // = m0: the row is [m0 link slots][m0 offsets]
             h.l0_stride = 2 * (g->l0_stride - 1);
         }
@@ -343,148 +390,111 @@ int32_t hnsw_enqueue(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef,
     h.n_points = g->n_points; h.n_levels = g->n_levels; h.m = g->m; h.m0 = g->m0;
     h.ep_ids = g->d_ep_ids; h.ep_levels = g->d_ep_levels; h.n_ep = g->n_ep;
     h.xp_ids = g->d_xp_ids; h.xp_levels = g->d_xp_levels; h.n_xp = g->n_xp;
-    h.ef = ef; h.top = top; h.nq = n_searches;
-    h.out = d_out; h.out_counts = d_counts; h.out_scored = d_scored;
-    if (xo) { h.expanded = xo->d_ids; h.expanded_cnt = xo->d_cnt; h.xcap = xo->xcap; }
-    if (pt) {
-        QMX_REQUIRE(!xo && !acorn && !mw && !cw, QMX_ERR_NOT_SUPPORTED, "the pop trace is the plain walk's");
-        h.pops = pt->d_pops; h.pop_cnt = pt->d_cnt; h.pop_cap = pt->cap;
-    }
-    // option hnsw_reference_heap_order: the plain walk keeps the reference's two binary heaps (hnsw.hpp RefHeaps); other walks are unaffected
-    h.ref_heaps = (option(OPT_HNSW_REFERENCE_HEAP_ORDER) > 0 && !acorn && !xo && !mw && !cw && !tq_l1(s)) ? 1 : 0;
+    h.acorn = r.acorn ? 1 : 0;
+    h.ref_heaps = p.ref_heaps ? 1 : 0;      // option hnsw_reference_heap_order: the plain walk keeps the reference's two binary heaps (hnsw.hpp RefHeaps)
     h.ref_cap = HNSW_REF_CAND_CAP;
-    h.lds_query_bytes = q->q_stride <= HNSW_LDS_QUERY_MAX ? q->q_stride : 0;
-    if (tq_l1(s)) {
-        h.lds_query_bytes = tq_l1_lds_bytes(s->dim, s->tq_rot_dim);
-        QMX_REQUIRE(h.lds_query_bytes <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "TurboQuant over Manhattan, the walk: %u bytes of LDS per search", h.lds_query_bytes);
-    }
-    if (mw) {   // [16-byte header][the multi-query's inner vectors, when the longest fits a modest share of the LDS; else every search reads its own through L2]
-        const uint64_t need = 16 + (uint64_t)std::max<uint32_t>(mw->max_tokens, 1) * q->q_stride;
-        h.lds_query_bytes = need <= 64 * 1024 ? (uint32_t)need : 16;
-    }
-    // A PQ LUT of more than half the LDS leaves one search per CU; the walk is a chain of dependent memory round trips,
-    // so many searches per CU with the LUT read through L2 win (measured: tools/bench_hnsw.py)
-    if (s->dtype == QMX_DTYPE_PQ && q->q_stride > 16 * 1024 && !mw) h.lds_query_bytes = 0;      // (a multi-query's LUTs are always staged)
-    if (pq_direct) h.lds_query_bytes = a.q_stride;
-    if (cw) {   // [32-byte header][the examples' entries]: staged when they fit a modest share of the LDS, read through L2 otherwise (PQ LUTs always)
-        const uint64_t need = 32 + (uint64_t)std::max<uint32_t>(cw->max_examples, 1) * q->q_stride;
-        h.lds_query_bytes = (need <= 48 * 1024 && h.lds_query_bytes != 0) ? (uint32_t)need : 32;
-        if (tq_l1(s)) {   // TurboQuant over Manhattan: [header][the examples, always staged][the hop scratch][64 scores per example] (hnsw.hpp HopCustom::hop)
-            const uint64_t ne = std::max<uint32_t>(cw->max_examples, 1);
-            const uint64_t need_l1 = 32 + ne * a.q_stride + (tq_l1_lds_bytes(s->dim, s->tq_rot_dim) - tq_l1_query_bytes(s->dim)) + ne * 256;
-            QMX_REQUIRE(need_l1 <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "a custom query of %u examples over TurboQuant / Manhattan needs %llu bytes of LDS",
-                        cw->max_examples, (unsigned long long)need_l1);
-            h.lds_query_bytes = (uint32_t)need_l1;
-        }
-        if (cw->lds_bytes) {      // multi-vector examples: always staged (the MaxSim policy reads its tokens from LDS)
-            QMX_REQUIRE(cw->lds_bytes <= HNSW_LDS_QUERY_MAX, QMX_ERR_NOT_SUPPORTED, "a custom query of %u bytes of example tokens does not fit the LDS", cw->lds_bytes);
-            h.lds_query_bytes = cw->lds_bytes;
-        }
-    }
-    if (std::max(top, ef) > HNSW_MAX_EF_REG && !mw && !cw && !tq_l1(s)) {   // a list this long lives in LDS behind the query entry, which is then always staged (a PQ LUT too)
-        const size_t beam = hnsw_beam_lds(std::max(top, ef));
-        QMX_REQUIRE((size_t)a.q_stride + beam + 2048 <= 160 * 1024, QMX_ERR_NOT_SUPPORTED,
-                    "hnsw max(top, ef) = %u: the query entry (%u bytes) and the list do not fit the LDS together", std::max(top, ef), a.q_stride);
-        h.lds_query_bytes = a.q_stride;
-    }
-    // the visited set in LDS (hnsw.hpp LdsVisited) where the search has room for it beside its query entry; the bitmap below stays allocated for what the
-    // table's buckets cannot hold
-    h.vis_lds = (!acorn && !h.ref_heaps && !option(OPT_HNSW_NO_LDS_VISITED) && g->n_points <= HNSW_VIS_LDS_MAX_POINTS && h.lds_query_bytes <= 32 * 1024) ? HNSW_VIS_LDS_BYTES : 0;
-    // the PQ walk through per-search LUTs (HopPQ, not the LUT-free walk): the LUTs' 8-bit images for the hop prefilter (pq.hip HopPQ::prefilter), built
-    // here from the batch's f32 LUTs.  Its 24 KiB per search take the LDS the visited table would: that walk keeps the bitmap
-    if (s->dtype == QMX_DTYPE_PQ && !pq_direct && !acorn && !mw && !cw && !h.ref_heaps && !option(OPT_HNSW_NO_PQ_PREFILTER) && a.queries == q->d_queries &&
-        s->pq_m <= 128 && s->pq.n_centroids <= 256 && q->q_stride > 16 * 1024 && h.lds_query_bytes == 0) {
-        const uint32_t st8 = pq_walk_lut8_stride(s->pq_m);
-        QMX_TRY(q->hnsw_pq8.reserve((size_t)n_searches * st8));
-        QMX_TRY(launch_pq_walk_lut8(q->stream, q->d_queries, q->q_stride, n_searches, s->pq_m, s->pq.n_centroids, q->hnsw_pq8.p));
-        h.pq8 = (const unsigned char *)q->hnsw_pq8.p;
-        h.pq8_stride = st8;
-        h.vis_lds = 0;
-    }
-    // ... and the LUT-free walk (HopPQDirect) prefilters its hops on the image of the EXACT-ORDER LUT - the entries it recomputes; a batch whose LUTs came
-    // from the matrix cores (<= 1e-5 off that order) gets exact-order LUTs made for the image alone
-    if (pq_direct && !acorn && !xo && !h.ref_heaps && !option(OPT_HNSW_NO_PQ_PREFILTER) && s->pq_m <= 128 && s->pq.n_centroids <= 256) {
-        const uint32_t st8 = pq_walk_lut8_stride(s->pq_m);
+    h.lds_query_bytes = p.lds_query_bytes;
+    h.vis_lds = p.vis_lds;                  // the visited set in LDS (hnsw.hpp LdsVisited)
+    h.vis_words = p.vis_words; h.log_cap = p.log_cap; h.hop_cap = p.hop_cap; h.explore_cap = p.explore_cap; h.ev_cap = p.ev_cap;
+    return QMX_OK;
+}
+
+// the 8-bit images of the searches' LUTs for the PQ walk's hop prefilter (pq.hip HopPQ::prefilter); their 24 KiB per search take the LDS the visited table
+// would.  The LUT-free walk (HopPQDirect) prefilters on the image of the EXACT-ORDER LUT - the entries it recomputes: a batch whose LUTs came from the
+// matrix cores (<= 1e-5 off that order) gets exact-order LUTs made for the image alone
+static int32_t build_pq_image(qmx_query *q, const WalkPlan &p, uint32_t n_searches, HnswArgs &h) {
+    if (p.pq_image == PqImage::None) return QMX_OK;
+    const qmx_segment *s = q->seg;
+    const void *luts = q->d_queries;
+    uint32_t lstride = q->q_stride;
+    const bool dotlike = s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE;
+    if (p.pq_image == PqImage::ExactOrderLuts && s->pq.lut_mfma && dotlike) {
         const size_t lut_bytes = (size_t)s->pq_m * s->pq.n_centroids * sizeof(float);
-        const void *luts = q->d_queries;
-        uint32_t lstride = q->q_stride;
-        const bool dotlike = s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE;
-        if (s->pq.lut_mfma && dotlike) {
-            qmx_pq_params exact = s->pq;
-            exact.lut_mfma = 0;
-            QMX_TRY(q->hnsw_lutx.reserve((size_t)n_searches * lut_bytes));
-            QMX_TRY(launch_pq_lut(q->stream, s->distance, s->dim, exact, s->d_centroids, (const float *)q->enc.p, n_searches, (float *)q->hnsw_lutx.p));
-            luts = q->hnsw_lutx.p;
-            lstride = (uint32_t)lut_bytes;
-        }
-        QMX_TRY(q->hnsw_pq8.reserve((size_t)n_searches * st8));
-        QMX_TRY(launch_pq_walk_lut8(q->stream, luts, lstride, n_searches, s->pq_m, s->pq.n_centroids, q->hnsw_pq8.p));
-        h.pq8 = (const unsigned char *)q->hnsw_pq8.p;
-        h.pq8_stride = st8;
-        h.vis_lds = 0;
+        qmx_pq_params exact = s->pq;
+        exact.lut_mfma = 0;
+        QMX_TRY(q->hnsw_lutx.reserve((size_t)n_searches * lut_bytes));
+        QMX_TRY(launch_pq_lut(q->stream, s->distance, s->dim, exact, s->d_centroids, (const float *)q->enc.p, n_searches, (float *)q->hnsw_lutx.p));
+        luts = q->hnsw_lutx.p;
+        lstride = (uint32_t)lut_bytes;
     }
-    h.log_cap = HNSW_LOG_CAP;
-    {   // tests: force the whole-bitmap clear path
-        const int64_t v = option(OPT_HNSW_LOG_CAP);
-        if (v >= 1 && v <= (int64_t)HNSW_LOG_CAP) h.log_cap = (uint32_t)v;
-    }
-    h.vis_words = ((uint64_t)g->n_points + 31) / 32;
-    if (h.vis_words == 0) h.vis_words = 1;
-    h.acorn = acorn ? 1 : 0;
-    h.hop_cap = 64;
-    if (acorn) {   // two visited lists; every explored node may add m0 points to one scoring batch
-        QMX_REQUIRE(g->m0 >= 1 && g->m0 <= 128, QMX_ERR_NOT_SUPPORTED, "ACORN walk: m0 = %u not in 1..128", g->m0);
-        h.vis_words *= 2;
-        // every unvisited link of the popped candidate that fails the filter is explored: a list as long as the candidate's, which m0 does not bound
-        QMX_REQUIRE(g->max_row0 <= 8192, QMX_ERR_NOT_SUPPORTED, "ACORN walk: a level-0 list of %u links does not fit the LDS", g->max_row0);
-        h.explore_cap = std::max<uint32_t>(g->m0, g->max_row0);
-        h.hop_cap = std::min<uint32_t>((g->m0 * (g->m0 + 1) + 63) / 64 * 64, 4160);    // (m0 > 64: the kernel scores what it holds before the buffer could overflow)
-    }
-    int per_cu = 1;
-    QMX_TRY(launch_hnsw(q, a, h, 0, &per_cu));
-    if (s->dtype == QMX_DTYPE_PQ && h.lds_query_bytes == 0 && option(OPT_HNSW_PQ_PER_CU) > 0) per_cu = (int)std::min<int64_t>(per_cu, option(OPT_HNSW_PQ_PER_CU));
-    // whole waves per SIMD: with 9 searches per CU one SIMD carries three waves and the others two, and the slowest SIMD sets the pace
-    // (measured on the SQ walk at 10 M points: 5.76 ms with 8 per CU, 6.09 with 9, 6.23 with 7: profiles/r5_sq_walk_visited.md)
-    if (per_cu >= 8) per_cu -= per_cu % 4;
-    if (option(OPT_HNSW_PER_CU) > 0) per_cu = (int)std::min<int64_t>(per_cu, option(OPT_HNSW_PER_CU));
-    uint64_t slots = std::min<uint64_t>({(uint64_t)n_searches, (uint64_t)s->num_cus * per_cu, (uint64_t)HNSW_SLOT_CAP});
-    const uint64_t by_budget = std::max<uint64_t>(1, HNSW_VIS_BUDGET / (h.vis_words * 4));
-    slots = std::max<uint64_t>(1, std::min(slots, by_budget));
-    if (xo) {      // search_with_vectors: a slot's stack of evicted candidates that tie with the bound (hnsw.hpp; the reference keeps every one of them in `candidates`)
-        h.ev_cap = HNSW_EV_SPILL_CAP;
-        QMX_TRY(q->hnsw_refc.reserve((size_t)slots * h.ev_cap * sizeof(uint64_t)));
+    const uint32_t st8 = pq_walk_lut8_stride(s->pq_m);
+    QMX_TRY(q->hnsw_pq8.reserve((size_t)n_searches * st8));
+    QMX_TRY(launch_pq_walk_lut8(q->stream, luts, lstride, n_searches, s->pq_m, s->pq.n_centroids, q->hnsw_pq8.p));
+    h.pq8 = (const unsigned char *)q->hnsw_pq8.p;
+    h.pq8_stride = st8;
+    return QMX_OK;
+}
+
+// the handle's scratch for `ws.slots` searches in flight: visited bitmaps and logs, the spill / reference candidates, the work counter
+static int32_t bind_walk_scratch(qmx_query *q, const WalkSlots &ws, HnswArgs &h) {
+    if (h.ev_cap) {      // search_with_vectors: a slot's stack of evicted candidates that tie with the bound (hnsw.hpp; the reference keeps every one of them in `candidates`)
+        QMX_TRY(q->hnsw_refc.reserve((size_t)ws.slots * h.ev_cap * sizeof(uint64_t)));
         h.ev_spill = (uint64_t *)q->hnsw_refc.p;
     }
     if (h.ref_heaps) {
-        slots = std::min<uint64_t>(slots, HNSW_REF_SLOT_CAP);
-        QMX_TRY(q->hnsw_refc.reserve((size_t)slots * h.ref_cap * sizeof(uint2)));
+        QMX_TRY(q->hnsw_refc.reserve((size_t)ws.slots * h.ref_cap * sizeof(uint2)));
         h.ref_cands = (uint2 *)q->hnsw_refc.p;
     }
-    if (q->hnsw_slots < slots || q->hnsw_vis_words != h.vis_words) {
+    if (q->hnsw_slots < ws.slots || q->hnsw_vis_words != h.vis_words) {
         // (re)allocate for the largest slot count this handle can use, zero once: the kernel returns the bitmaps all-zero
-        const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)std::max<uint32_t>(std::max(q->nq, n_searches), 1), (uint64_t)s->num_cus * per_cu,
-                                                                       (uint64_t)HNSW_SLOT_CAP, by_budget}));
         QMX_HIP(hipStreamSynchronize(q->stream));
         q->hnsw_slots = 0;
-        QMX_TRY(q->hnsw_vis.reserve((size_t)want * h.vis_words * 4));
-        QMX_TRY(q->hnsw_log.reserve((size_t)want * HNSW_LOG_CAP * 4));
-        QMX_HIP(hipMemsetAsync(q->hnsw_vis.p, 0, (size_t)want * h.vis_words * 4, q->stream));
-        q->hnsw_slots = (uint32_t)want;
+        QMX_TRY(q->hnsw_vis.reserve((size_t)ws.want * h.vis_words * 4));
+        QMX_TRY(q->hnsw_log.reserve((size_t)ws.want * HNSW_LOG_CAP * 4));
+        QMX_HIP(hipMemsetAsync(q->hnsw_vis.p, 0, (size_t)ws.want * h.vis_words * 4, q->stream));
+        q->hnsw_slots = (uint32_t)ws.want;
         q->hnsw_vis_words = h.vis_words;
     }
     h.visited = (uint32_t *)q->hnsw_vis.p;
     h.vis_log = (uint32_t *)q->hnsw_log.p;
     // the slots draw their searches from a counter that starts behind the first `slots` (hnsw.hpp)
     QMX_TRY(q->hnsw_next.reserve(32));         // [u32 next search][pad][u64 hop candidates offered to the PQ prefilter][u64 scored exactly]
-    QMX_HIP(hipMemsetD32Async((hipDeviceptr_t)q->hnsw_next.p, (int)slots, 1, q->stream));
+    QMX_HIP(hipMemsetD32Async((hipDeviceptr_t)q->hnsw_next.p, (int)ws.slots, 1, q->stream));
     QMX_HIP(hipMemsetAsync((char *)q->hnsw_next.p + 8, 0, 16, q->stream));
     h.next_query = (uint32_t *)q->hnsw_next.p;
     h.pq_stats = h.pq8 ? (unsigned long long *)((char *)q->hnsw_next.p + 8) : nullptr;
+    return QMX_OK;
+}
+
+int32_t hnsw_enqueue(const qmx_hnsw *g, qmx_query *q, const WalkRequest &r) {
+    const qmx_segment *s = q->seg;
+    ScanArgs a;
+    fill_args(q, 0, q->nq, a);
+    const WalkShape shape = walk_shape(g, q, r, a);
+    const WalkPlan plan = hnsw_walk_plan(shape);
+    QMX_TRY(walk_refused(plan, shape));
+    QMX_TRY(stage_walk_entries(q, plan, a));
+    const uint32_t n_searches = r.custom ? r.custom->n_queries : r.multi ? r.multi->n_queries : q->nq;
+    if (r.custom) {
+        a.cq_desc = r.custom->d_desc;
+        a.cq_coefs = r.custom->d_coefs;
+    }
+    if (r.multi) {
+        a.mv_offsets = r.multi->d_offsets;
+        a.mv_qfirst = r.multi->d_qfirst;
+        a.del = r.multi->del;
+    }
+    HnswArgs h;
+    memset(&h, 0, sizeof(h));
+    QMX_TRY(bind_graph(g, q, r, plan, h));
+    h.ef = r.ef; h.top = r.top; h.nq = n_searches;
+    h.out = r.d_out; h.out_counts = r.d_counts; h.out_scored = r.d_scored;
+    if (r.expanded) { h.expanded = r.expanded->d_ids; h.expanded_cnt = r.expanded->d_cnt; h.xcap = r.expanded->xcap; }
+    if (r.trace) { h.pops = r.trace->d_pops; h.pop_cnt = r.trace->d_cnt; h.pop_cap = r.trace->cap; }
+    QMX_TRY(build_pq_image(q, plan, n_searches, h));
+    int per_cu = 1;
+    QMX_TRY(launch_hnsw(q, a, h, 0, &per_cu));      // (grid 0: the occupancy of the kernel this launch takes)
+    WalkSlotOptions so;
+    so.pq_per_cu = option(OPT_HNSW_PQ_PER_CU);
+    so.per_cu = option(OPT_HNSW_PER_CU);
+    const WalkSlots ws = hnsw_walk_slots(plan, per_cu, n_searches, q->nq, s->num_cus, so);
+    per_cu = ws.per_cu;
+    QMX_TRY(bind_walk_scratch(q, ws, h));
     size_t slot = 0;
-    if (timed) QMX_TRY(timing_begin(q, &slot));
-    QMX_TRY(launch_hnsw(q, a, h, (uint32_t)slots, &per_cu));
+    if (r.timed) QMX_TRY(timing_begin(q, &slot));
+    QMX_TRY(launch_hnsw(q, a, h, (uint32_t)ws.slots, &per_cu));
     q->last_kernel = last_noted_kernel();
-    if (timed) QMX_TRY(timing_end(q, slot));
+    if (r.timed) QMX_TRY(timing_end(q, slot));
     return QMX_OK;
 }
 
@@ -498,6 +508,51 @@ int32_t hnsw_check(const qmx_hnsw *g, const qmx_query *q, uint32_t top, uint32_t
     return QMX_OK;
 }
 
+int32_t hnsw_walk_to_caller(const qmx_hnsw *g, qmx_query *q, WalkRequest r, uint32_t n_searches, qmx_scored_point *out, uint32_t *out_counts,
+                            qmx_counters *counters, bool plain) {
+    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
+    const size_t out_bytes = (size_t)n_searches * r.top * sizeof(qmx_scored_point), cnt_bytes = (size_t)n_searches * 4;
+    if (g->n_points == 0) {   // get_entry_point() -> None -> empty result (graph_layers.rs:539-542)
+        if (cnt_dev) QMX_HIP(hipMemset(out_counts, 0, cnt_bytes));
+        else memset(out_counts, 0, cnt_bytes);
+        QMX_HIP(hipStreamSynchronize(q->stream));      // (what the caller staged for the walk may go away)
+        return QMX_OK;
+    }
+    r.d_out = out;
+    r.d_counts = out_counts;
+    if (!out_dev) { QMX_TRY(q->out.reserve(out_bytes)); r.d_out = (qmx_scored_point *)q->out.p; }
+    if (!cnt_dev) { QMX_TRY(q->counts.reserve(cnt_bytes)); r.d_counts = (uint32_t *)q->counts.p; }
+    QMX_TRY(q->hnsw_scored.reserve(cnt_bytes));
+    r.d_scored = (uint32_t *)q->hnsw_scored.p;
+    r.timed = q->timing || (q->seg->flags & QMX_SEG_TIME_KERNELS) != 0;
+    QMX_TRY(hnsw_enqueue(g, q, r));
+    if (!out_dev) QMX_TRY(copy_out(q->stream, out, r.d_out, out_bytes));
+    if (!cnt_dev) QMX_TRY(copy_out(q->stream, out_counts, r.d_counts, cnt_bytes));
+    std::vector<uint32_t> scored(counters ? n_searches : 0);
+    unsigned long long pq_stats[2] = {0, 0};
+    if (counters) QMX_HIP(hipMemcpyAsync(scored.data(), r.d_scored, cnt_bytes, hipMemcpyDeviceToHost, q->stream));
+    if (counters && plain) QMX_HIP(hipMemcpyAsync(pq_stats, (char *)q->hnsw_next.p + 8, 16, hipMemcpyDeviceToHost, q->stream));
+    QMX_TRY(check_err_flag(q));   // synchronises the stream (what the caller staged for the walk may go away)
+    if (counters) {
+        uint64_t total = 0;
+        for (uint32_t v : scored) total += v;
+        counters->vectors_scored = total;      // custom / MaxSim walks: POINTS scored (each costs one similarity per example, |query| x |point| inner scores)
+        counters->kernel_launches = 1;
+        if (plain) {
+            // the PQ walk's hop prefilter (hnsw.hpp HopPQ::prefilter): level-0 hop candidates that met the 8-bit bound / those that survived it and were scored exactly
+            counters->prefilter_candidates = pq_stats[0];
+            counters->verified_rows = pq_stats[1];
+            counters->bytes_read = total * q->seg->row_bytes;
+        }
+    }
+    if (r.timed && (counters || plain)) {      // (the plain walk folds its time into the batch's at once; the others leave it to the next fold when nobody asks)
+        const float before = q->timing_ms;
+        QMX_TRY(timing_fold(q));
+        if (counters) counters->kernel_ms = q->timing_ms - before;
+    }
+    return QMX_OK;
+}
+
 int32_t hnsw_search_sync(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts,
                                 const volatile uint8_t *is_stopped, qmx_counters *counters, bool acorn) {
     QMX_REQUIRE(g && q && out && out_counts, QMX_ERR_BAD_ARG, "NULL argument");
@@ -506,42 +561,9 @@ int32_t hnsw_search_sync(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t
     if (counters) memset(counters, 0, sizeof(*counters));
     if (q->nq == 0) return QMX_OK;
     QMX_CHECK_CANCELLED(is_stopped);
-    if (g->n_points == 0) {   // get_entry_point() -> None -> empty result (graph_layers.rs:539-542)
-        if (is_device_ptr(out_counts)) QMX_HIP(hipMemset(out_counts, 0, (size_t)q->nq * 4));
-        else memset(out_counts, 0, (size_t)q->nq * 4);
-        return QMX_OK;
-    }
-    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
-    qmx_scored_point *d_out = out;
-    uint32_t *d_counts = out_counts;
-    if (!out_dev) { QMX_TRY(q->out.reserve((size_t)q->nq * top * sizeof(qmx_scored_point))); d_out = (qmx_scored_point *)q->out.p; }
-    if (!cnt_dev) { QMX_TRY(q->counts.reserve((size_t)q->nq * 4)); d_counts = (uint32_t *)q->counts.p; }
-    QMX_TRY(q->hnsw_scored.reserve((size_t)q->nq * 4));
-    const bool timed = q->timing || (q->seg->flags & QMX_SEG_TIME_KERNELS) != 0;
-    QMX_TRY(hnsw_enqueue(g, q, top, ef, d_out, d_counts, (uint32_t *)q->hnsw_scored.p, timed, acorn));
-    if (!out_dev) QMX_TRY(copy_out(q->stream, out, d_out, (size_t)q->nq * top * sizeof(qmx_scored_point)));
-    if (!cnt_dev) QMX_TRY(copy_out(q->stream, out_counts, d_counts, (size_t)q->nq * 4));
-    std::vector<uint32_t> scored(counters ? q->nq : 0);
-    unsigned long long pq_stats[2] = {0, 0};
-    if (counters) QMX_HIP(hipMemcpyAsync(scored.data(), q->hnsw_scored.p, (size_t)q->nq * 4, hipMemcpyDeviceToHost, q->stream));
-    if (counters && q->hnsw_next.p) QMX_HIP(hipMemcpyAsync(pq_stats, (char *)q->hnsw_next.p + 8, 16, hipMemcpyDeviceToHost, q->stream));
-    QMX_TRY(check_err_flag(q));   // synchronises the stream
-    if (counters) {
-        uint64_t total = 0;
-        for (uint32_t v : scored) total += v;
-        counters->vectors_scored = total;
-        // the PQ walk's hop prefilter (hnsw.hpp HopPQ::prefilter): level-0 hop candidates that met the 8-bit bound / those that survived it and were scored exactly
-        counters->prefilter_candidates = pq_stats[0];
-        counters->verified_rows = pq_stats[1];
-        counters->bytes_read = total * q->seg->row_bytes;
-        counters->kernel_launches = 1;
-    }
-    if (timed) {
-        const float before = q->timing_ms;
-        QMX_TRY(timing_fold(q));
-        if (counters) counters->kernel_ms = q->timing_ms - before;
-    }
-    return QMX_OK;
+    WalkRequest r;
+    r.top = top; r.ef = ef; r.acorn = acorn;
+    return hnsw_walk_to_caller(g, q, r, q->nq, out, out_counts, counters, true);
 }
 
 int32_t qmx_hnsw_search(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts,
@@ -574,7 +596,10 @@ int32_t qmx_hnsw_search_traced(const qmx_hnsw *g, qmx_query *q, uint32_t top, ui
     PopTrace pt{(qmx_scored_point *)q->cand.p, (uint32_t *)q->xcnt.p, pop_cap};
     // (a search without a live entry point - every point deleted, or rejected by the search's own filter - returns before it counts its pops)
     QMX_HIP(hipMemsetAsync(q->xcnt.p, 0, (size_t)q->nq * 4, q->stream));
-    QMX_TRY(hnsw_enqueue(g, q, top, ef, (qmx_scored_point *)q->out.p, (uint32_t *)q->counts.p, nullptr, false, false, nullptr, nullptr, nullptr, &pt));
+    WalkRequest r;
+    r.d_out = (qmx_scored_point *)q->out.p; r.d_counts = (uint32_t *)q->counts.p;
+    r.top = top; r.ef = ef; r.trace = &pt;
+    QMX_TRY(hnsw_enqueue(g, q, r));
     QMX_TRY(copy_out(q->stream, out, q->out.p, (size_t)q->nq * top * sizeof(qmx_scored_point)));
     QMX_TRY(copy_out(q->stream, out_counts, q->counts.p, (size_t)q->nq * 4));
     QMX_TRY(copy_out(q->stream, pops, q->cand.p, (size_t)q->nq * pop_cap * sizeof(qmx_scored_point)));
@@ -593,8 +618,11 @@ int32_t qmx_hnsw_search_async(const qmx_hnsw *g, qmx_query *q, uint32_t top, uin
         QMX_HIP(hipMemsetAsync(out_counts_dev, 0, (size_t)q->nq * 4, q->stream));
         return QMX_OK;
     }
-    const bool timed = q->timing || (q->seg->flags & QMX_SEG_TIME_KERNELS) != 0;
-    return hnsw_enqueue(g, q, top, ef, out_dev, out_counts_dev, out_scored_dev, timed);
+    WalkRequest r;
+    r.d_out = out_dev; r.d_counts = out_counts_dev; r.d_scored = out_scored_dev;
+    r.top = top; r.ef = ef;
+    r.timed = q->timing || (q->seg->flags & QMX_SEG_TIME_KERNELS) != 0;
+    return hnsw_enqueue(g, q, r);
 }
 
 int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_query *base, uint32_t top, uint32_t ef, qmx_scored_point *out,
@@ -634,8 +662,10 @@ int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_qu
     while (true) {
         QMX_TRY(links->cand_ids.reserve((size_t)nq * xcap * 4));
         ExpandedOut xo{(uint32_t *)links->cand_ids.p, (uint32_t *)links->xcnt.p, xcap};
-        QMX_TRY(hnsw_enqueue(g, links, std::min(top, beam_ef), ef, (qmx_scored_point *)links->cand.p, (uint32_t *)links->cand_cnt.p,
-                             (uint32_t *)links->hnsw_scored.p, timed, false, nullptr, &xo));
+        WalkRequest r;
+        r.d_out = (qmx_scored_point *)links->cand.p; r.d_counts = (uint32_t *)links->cand_cnt.p; r.d_scored = (uint32_t *)links->hnsw_scored.p;
+        r.top = std::min(top, beam_ef); r.ef = ef; r.timed = timed; r.expanded = &xo;
+        QMX_TRY(hnsw_enqueue(g, links, r));
         ++walks;
         QMX_HIP(hipMemcpyAsync(cnt.data(), links->xcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, links->stream));
         QMX_HIP(hipMemcpyAsync(sc.data(), links->hnsw_scored.p, (size_t)nq * 4, hipMemcpyDeviceToHost, links->stream));
@@ -664,6 +694,30 @@ int32_t qmx_hnsw_search_with_vectors(const qmx_hnsw *g, qmx_query *links, qmx_qu
     return QMX_OK;
 }
 
+int32_t stage_multi_walk(qmx_query *inner, const uint32_t *first, uint32_t n_first, const uint64_t *point_offsets, uint32_t n_points,
+                         const uint64_t *point_deleted, uint64_t n_deleted_bits, MultiWalk *mw) {
+    for (uint32_t p = 0; p < n_points; ++p)
+        QMX_REQUIRE(point_offsets[p] <= point_offsets[p + 1], QMX_ERR_BAD_ARG, "point_offsets is not ascending at %u", p);
+    QMX_REQUIRE(point_offsets[n_points] <= inner->seg->n, QMX_ERR_OUT_OF_BOUNDS, "point_offsets reach past the %llu inner rows of the segment",
+                (unsigned long long)inner->seg->n);
+    QMX_TRY(inner->mv_qfirst.reserve((size_t)(n_first + 1) * 4));
+    QMX_TRY(inner->mv_offsets.reserve((size_t)(n_points + 1) * 8));
+    QMX_HIP(hipMemcpyAsync(inner->mv_qfirst.p, first, (size_t)(n_first + 1) * 4, hipMemcpyHostToDevice, inner->stream));
+    QMX_HIP(hipMemcpyAsync(inner->mv_offsets.p, point_offsets, (size_t)(n_points + 1) * 8, hipMemcpyHostToDevice, inner->stream));
+    memset(mw, 0, sizeof(*mw));
+    mw->d_qfirst = (const uint32_t *)inner->mv_qfirst.p;
+    mw->d_offsets = (const uint64_t *)inner->mv_offsets.p;
+    mw->del.n_rows = n_points;      // deletion is per POINT (the id tracker's bitslice over multi-vector points), not per inner row
+    if (point_deleted && n_deleted_bits) {
+        const void *d_bits = nullptr;
+        QMX_TRY(stage_in(inner, inner->mv_deleted, point_deleted, (size_t)((n_deleted_bits + 63) / 64) * 8, &d_bits));
+        mw->del.point_deleted = (const uint64_t *)d_bits;
+        mw->del.n_point_bits = n_deleted_bits;
+    }
+    if (inner->has_filter) { mw->del.allowed = (const uint64_t *)inner->filter.p; mw->del.n_allowed_bits = inner->n_filter_bits; }
+    return QMX_OK;
+}
+
 int32_t qmx_multi_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const uint32_t *query_first, uint32_t n_queries, const uint64_t *point_offsets,
                               uint32_t n_points, const uint64_t *point_deleted, uint64_t n_deleted_bits, uint32_t top, uint32_t ef,
                               qmx_scored_point *out, uint32_t *out_counts, qmx_counters *counters) {
@@ -680,59 +734,18 @@ int32_t qmx_multi_hnsw_search(const qmx_hnsw *g, qmx_query *inner, const uint32_
     if (counters) memset(counters, 0, sizeof(*counters));
     if (n_queries == 0) return QMX_OK;
     QMX_REQUIRE(query_first[n_queries] <= inner->nq, QMX_ERR_OUT_OF_BOUNDS, "multi-queries reach past the %u inner query vectors of the batch", inner->nq);
+    MultiWalk mw;
     uint32_t max_tokens = 0;
     for (uint32_t j = 0; j < n_queries; ++j) {
         QMX_REQUIRE(query_first[j] <= query_first[j + 1], QMX_ERR_BAD_ARG, "query_first is not ascending at %u", j);
         max_tokens = std::max(max_tokens, query_first[j + 1] - query_first[j]);
     }
-    for (uint32_t p = 0; p < n_points; ++p)
-        QMX_REQUIRE(point_offsets[p] <= point_offsets[p + 1], QMX_ERR_BAD_ARG, "point_offsets is not ascending at %u", p);
-    QMX_REQUIRE(point_offsets[n_points] <= s->n, QMX_ERR_OUT_OF_BOUNDS, "point_offsets reach past the %llu inner rows of the segment",
-                (unsigned long long)s->n);
-    const bool out_dev = is_device_ptr(out), cnt_dev = is_device_ptr(out_counts);
-    if (g->n_points == 0) {   // get_entry_point() -> None
-        if (cnt_dev) QMX_HIP(hipMemset(out_counts, 0, (size_t)n_queries * 4));
-        else memset(out_counts, 0, (size_t)n_queries * 4);
-        return QMX_OK;
-    }
-    QMX_TRY(inner->mv_qfirst.reserve((size_t)(n_queries + 1) * 4));
-    QMX_TRY(inner->mv_offsets.reserve((size_t)(n_points + 1) * 8));
-    QMX_HIP(hipMemcpyAsync(inner->mv_qfirst.p, query_first, (size_t)(n_queries + 1) * 4, hipMemcpyHostToDevice, inner->stream));
-    QMX_HIP(hipMemcpyAsync(inner->mv_offsets.p, point_offsets, (size_t)(n_points + 1) * 8, hipMemcpyHostToDevice, inner->stream));
-    MultiWalk mw;
-    memset(&mw, 0, sizeof(mw));
-    mw.d_qfirst = (const uint32_t *)inner->mv_qfirst.p;
-    mw.d_offsets = (const uint64_t *)inner->mv_offsets.p;
+    QMX_TRY(stage_multi_walk(inner, query_first, n_queries, point_offsets, n_points, point_deleted, n_deleted_bits, &mw));
     mw.n_queries = n_queries;
     mw.max_tokens = max_tokens;
-    mw.del.n_rows = n_points;      // deletion is per POINT (the id tracker's bitslice over multi-vector points), not per inner row
-    if (point_deleted && n_deleted_bits) {
-        const void *d_bits = nullptr;
-        QMX_TRY(stage_in(inner, inner->mv_deleted, point_deleted, (size_t)((n_deleted_bits + 63) / 64) * 8, &d_bits));
-        mw.del.point_deleted = (const uint64_t *)d_bits;
-        mw.del.n_point_bits = n_deleted_bits;
-    }
-    if (inner->has_filter) { mw.del.allowed = (const uint64_t *)inner->filter.p; mw.del.n_allowed_bits = inner->n_filter_bits; }
-    qmx_scored_point *d_out = out;
-    uint32_t *d_counts = out_counts;
-    if (!out_dev) { QMX_TRY(inner->out.reserve((size_t)n_queries * top * sizeof(qmx_scored_point))); d_out = (qmx_scored_point *)inner->out.p; }
-    if (!cnt_dev) { QMX_TRY(inner->counts.reserve((size_t)n_queries * 4)); d_counts = (uint32_t *)inner->counts.p; }
-    QMX_TRY(inner->hnsw_scored.reserve((size_t)n_queries * 4));
-    const bool timed = inner->timing || (s->flags & QMX_SEG_TIME_KERNELS) != 0;
-    QMX_TRY(hnsw_enqueue(g, inner, top, ef, d_out, d_counts, (uint32_t *)inner->hnsw_scored.p, timed, false, &mw));
-    if (!out_dev) QMX_TRY(copy_out(inner->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
-    if (!cnt_dev) QMX_TRY(copy_out(inner->stream, out_counts, d_counts, (size_t)n_queries * 4));
-    QMX_TRY(check_err_flag(inner));    // synchronises (the staged partitions may go away)
-    if (counters) {
-        std::vector<uint32_t> sc(n_queries);
-        QMX_HIP(hipMemcpy(sc.data(), inner->hnsw_scored.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost));
-        uint64_t total = 0;
-        for (uint32_t v : sc) total += v;
-        counters->vectors_scored = total;            // POINTS scored (each costs |query| x |point| inner scores)
-        counters->kernel_launches = 1;
-        if (timed) { const float before = inner->timing_ms; QMX_TRY(timing_fold(inner)); counters->kernel_ms = inner->timing_ms - before; }
-    }
-    return QMX_OK;
+    WalkRequest r;
+    r.top = top; r.ef = ef; r.multi = &mw;
+    return hnsw_walk_to_caller(g, inner, r, n_queries, out, out_counts, counters, false);
 }
 
 }  // extern "C"

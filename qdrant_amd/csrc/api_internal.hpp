@@ -20,6 +20,7 @@
 
 #include "kernels.hpp"
 #include "dev_mem.hpp"
+#include "hnsw_walk_plan.hpp"
 #include "tq_rotate.hpp"
 
 namespace qmx {
@@ -437,6 +438,25 @@ struct SplitF32 {
 // ---------------------------------------------------------------------------------------------
 // HNSW search on device
 // ---------------------------------------------------------------------------------------------
+// The packed level-0 table of a graph with the SQ vector_offset of every linked row behind the links ([n_points][2 m0]; scan_quant.hip RowSQX): made at
+// the first plain walk of an SQ segment over the graph and kept for that segment (its uid) - 10 M points x 64 dwords = 2.56 GB, one gather pass - it costs
+// the walk one more line per hop instead of a random request per row.  Another segment - another quantization of the same points - keeps the offsets
+// column, and so does every segment once the table could not be made.  Nothing is ever freed under a running kernel.
+struct SqLevel0Table {
+    // *table: the table where it is segment s's, else nullptr; d_l0 / n_points / l0_stride: the graph's packed level 0 (api_hnsw.hip)
+    int32_t for_segment(const qmx_segment *s, const uint32_t *d_l0, uint32_t n_points, uint32_t l0_stride, hipStream_t st, const uint32_t **table);
+    SqLevel0Table() = default;
+    SqLevel0Table(const SqLevel0Table &) = delete;
+    SqLevel0Table &operator=(const SqLevel0Table &) = delete;
+    ~SqLevel0Table() { dev_free(d_table); }
+
+private:
+    std::mutex mu;
+    uint32_t *d_table = nullptr;     // non-null only once it is complete ...
+    uint64_t owner_uid = 0;          // ... for this segment
+    bool failed = false;             // it could not be made: not tried again
+};
+
 struct qmx_hnsw {
     int device = 0;
     uint32_t m = 0, m0 = 0, n_points = 0, n_levels = 0, n_ep = 0, n_xp = 0;
@@ -447,12 +467,7 @@ struct qmx_hnsw {
     uint32_t *d_l0 = nullptr;     // packed level 0 [n_points][l0_stride]: count, links (built when every list fits 63 links)
     uint32_t l0_stride = 0;
     uint32_t max_row0 = 0;        // the longest level-0 list (it may pass m0: merged payload links, graphs loaded from files)
-    // the same table with the SQ vector_offset of every linked row behind the links ([n_points][2 m0]), made at the first plain walk of an SQ segment
-    // over this graph and kept for that segment (its uid): searches share the graph across threads, hence the lock
-    mutable std::mutex l0x_mu;
-    mutable uint32_t *d_l0x = nullptr;
-    mutable uint64_t l0x_segment_uid = 0;
-    mutable bool l0x_failed = false;     // no memory for it: the walk keeps the offsets column
+    mutable SqLevel0Table l0x;    // (searches share the graph across threads: the table locks itself)
     // host copy of the plain arrays (graphs built by qmx_hnsw_build; empty otherwise) for qmx_hnsw_export_plain
     std::vector<uint32_t> h_reindex, h_neighbors, h_ep_ids, h_ep_levels, h_xp_ids, h_xp_levels;
     std::vector<uint64_t> h_level_offsets, h_offsets;
@@ -462,13 +477,9 @@ struct qmx_hnsw {
     qmx_hnsw &operator=(const qmx_hnsw &) = delete;
     ~qmx_hnsw() {
         dev_free(d_reindex); dev_free(d_neighbors); dev_free(d_ep_ids); dev_free(d_ep_levels); dev_free(d_xp_ids); dev_free(d_xp_levels);
-        dev_free(d_level_offsets); dev_free(d_offsets); dev_free(d_l0); dev_free(d_l0x);
+        dev_free(d_level_offsets); dev_free(d_offsets); dev_free(d_l0);
     }
 };
-
-constexpr uint32_t HNSW_SLOT_CAP = 4096;
-constexpr uint32_t HNSW_LOG_CAP = 16384;                    // words logged per search before falling back to a full clear
-constexpr uint64_t HNSW_VIS_BUDGET = 8ull << 30;            // bytes of visited bitmaps per query handle
 
 // the points of a build over multi-vectors (qmx_multi_hnsw_build): point p = inner rows [offsets[p], offsets[p + 1]) of the segment, deleted flags per POINT
 struct MultiBuild {
@@ -508,14 +519,32 @@ struct CustomWalk {
     uint32_t lds_bytes = 0;      // multi-vector examples: bytes of the largest staged query block (header + offset table + the examples' tokens)
 };
 
+// one walk as hnsw_enqueue takes it: where the lists go, how long they are, and what makes it other than the plain walk; a caller fills what it uses
+struct WalkRequest {
+    qmx_scored_point *d_out = nullptr;
+    uint32_t *d_counts = nullptr, *d_scored = nullptr;      // (d_scored may stay null)
+    uint32_t top = 0, ef = 0;
+    bool timed = false, acorn = false;
+    const MultiWalk *multi = nullptr;
+    const ExpandedOut *expanded = nullptr;
+    const CustomWalk *custom = nullptr;
+    const PopTrace *trace = nullptr;
+};
+
 // EncodedVectorsTQ over Distance::Manhattan: no integer kernel, every score dequantises and rotates the row back (tq_l1.hip)
 static bool tq_l1(const qmx_segment *s) { return s->dtype == QMX_DTYPE_TQ && s->distance == QMX_DISTANCE_MANHATTAN; }
 
 // ---- internal functions one family calls in another (defined in the file named) ----
 extern "C" {
-int32_t hnsw_enqueue(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *d_out,
-                            uint32_t *d_counts, uint32_t *d_scored, bool timed, bool acorn = false, const MultiWalk *mw = nullptr,
-                            const ExpandedOut *xo = nullptr, const CustomWalk *cw = nullptr, const PopTrace *pt = nullptr);
+int32_t hnsw_enqueue(const qmx_hnsw *g, qmx_query *q, const WalkRequest &r);
+// a synchronous walk of `n_searches` searches into the caller's arrays (host or device): the empty graph's answer, the staged outputs, the walk, the counters
+// (plain: the plain / ACORN walk's, which also reports the bytes read and the PQ hop prefilter's counts)
+int32_t hnsw_walk_to_caller(const qmx_hnsw *g, qmx_query *q, WalkRequest r, uint32_t n_searches, qmx_scored_point *out, uint32_t *out_counts,
+                            qmx_counters *counters, bool plain);
+// the partitions of a walk over multi-vector points on the device (`first`: the n_first + 1 bounds of the query-side multi-vectors), the POINT-level deleted
+// view and the batch's allow-list; checks point_offsets.  n_queries and max_tokens are the caller's to set
+int32_t stage_multi_walk(qmx_query *inner, const uint32_t *first, uint32_t n_first, const uint64_t *point_offsets, uint32_t n_points,
+                         const uint64_t *point_deleted, uint64_t n_deleted_bits, MultiWalk *mw);
 int32_t hnsw_check(const qmx_hnsw *g, const qmx_query *q, uint32_t top, uint32_t ef);
 int32_t hnsw_search_sync(const qmx_hnsw *g, qmx_query *q, uint32_t top, uint32_t ef, qmx_scored_point *out, uint32_t *out_counts,
                                 const volatile uint8_t *is_stopped, qmx_counters *counters, bool acorn);

@@ -48,8 +48,11 @@ static int32_t sharded_enqueue(qmx_query *const *queries, const qmx_hnsw *const 
         const bool timed = q->timing || (q->seg->flags & QMX_SEG_TIME_KERNELS) != 0;
         qmx_counters local{};
         if (graphs) {
+            WalkRequest r;
+            r.d_out = (qmx_scored_point *)q->out.p; r.d_counts = (uint32_t *)q->counts.p;
+            r.top = top; r.ef = ef; r.timed = timed;
             if (graphs[i]->n_points == 0) QMX_HIP(hipMemsetAsync(q->counts.p, 0, cbytes, q->stream));
-            else QMX_TRY(hnsw_enqueue(graphs[i], q, top, ef, (qmx_scored_point *)q->out.p, (uint32_t *)q->counts.p, nullptr, timed));
+            else QMX_TRY(hnsw_enqueue(graphs[i], q, r));
             local.kernel_launches = 1;
         } else {
             QMX_TRY(search_enqueue(q, top, nullptr, 0, (qmx_scored_point *)q->out.p, (uint32_t *)q->counts.p, is_stopped, &local, timed));

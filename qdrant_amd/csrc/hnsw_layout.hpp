@@ -1,6 +1,7 @@
 // hnsw_layout.hpp — the dynamic LDS of one walk (hnsw.hpp hnsw_search_kernel): where each region starts, and the total.  The kernel carves its LDS by it,
 // the launcher and the occupancy query ask it for the bytes: a region exists in one place only.  Integer logic a host compiler reads without HIP
-// (tools/hnsw_layout_check.cpp sweeps it under the sanitizers).
+// (tools/hnsw_layout_check.cpp sweeps it under the sanitizers).  The integer limits of a walk's launch live here too: the kernels (through kernels.hpp),
+// the host code and hnsw_walk_plan.hpp read the one definition.
 //
 //   [hop ids][hop scores][ACORN explore list][query entry, padded to 16][LDS beam / `nearest`][reference candidates][visited table][PQ 8-bit image]
 #pragma once
@@ -18,6 +19,17 @@ namespace qmx {
 
 constexpr int HNSW_E_REF = -1;                     // the template value of the walk's E that selects option hnsw_reference_heap_order (hnsw.hpp RefHeaps)
 constexpr uint32_t HNSW_REF_CAND_LDS = 1024;       // ... entries of its `candidates` heap kept in LDS (8 KiB per search): the ten levels every sift touches
+constexpr uint32_t HNSW_REF_CAND_CAP = 1u << 16;   // ... entries of one search's whole `candidates` heap (512 KiB per slot)
+constexpr uint32_t HNSW_REF_SLOT_CAP = 4096;       // ... searches in flight in that mode (1 024 until round 5: fewer than the default walk keeps in flight)
+constexpr uint32_t HNSW_EV_SPILL_CAP = 4096;       // search_with_vectors: evicted candidates of ONE score a slot can hold beyond four (32 KiB per slot; more raises err_flag = 2)
+constexpr uint32_t HNSW_MAX_EF = 4096;             // max(top, ef) of a walk: up to HNSW_MAX_EF_REG in a register beam, beyond it in an LDS beam (hnsw.hpp Beam<0>)
+constexpr uint32_t HNSW_MAX_EF_REG = 512;          // ... the register beam's; and the largest ef_construct (the build keeps its beam in registers)
+constexpr uint32_t HNSW_LDS_QUERY_MAX = 150 * 1024;            // bytes of query entry a search stages at most
+constexpr uint32_t HNSW_VIS_LDS_BYTES = 16384;                 // the walk's visited table in LDS (hnsw.hpp LdsVisited): 1024 buckets x 8 tags of 16 bits
+constexpr uint32_t HNSW_VIS_LDS_MAX_POINTS = 65534u * 1024u;   // ... graphs whose (id >> 10) + 1 fits a tag below the "taken back" mark 0xFFFF
+constexpr uint32_t HNSW_SLOT_CAP = 4096;                       // searches in flight per launch
+constexpr uint32_t HNSW_LOG_CAP = 16384;                       // visited words logged per search before falling back to a full clear
+constexpr uint64_t HNSW_VIS_BUDGET = 8ull << 30;               // bytes of visited bitmaps per query handle
 
 // bytes of the ACORN walk's list of nodes to explore (one per link of the popped candidate: HnswArgs::explore_cap ids - the graph's longest level-0 list -, 64 at least)
 QMX_LAYOUT_HD uint32_t hnsw_acorn_lds(uint32_t acorn, uint32_t m0) { return acorn ? 4u * (((m0 < 64u ? 64u : m0) + 63u) / 64u * 64u) : 0u; }

@@ -1,6 +1,7 @@
 // kernels.hpp — host-callable launchers of the HIP kernels (internal to libqdrant_amd.so).
 #pragma once
 #include "common.hpp"
+#include "hnsw_layout.hpp"      // the walk's integer constants (HNSW_*): a header the host compiler reads too
 
 namespace qmx {
 
@@ -210,14 +211,7 @@ int32_t launch_hnsw_bq(hipStream_t st, const ScanArgs &a, const HnswArgs &h, uin
 int32_t launch_hnsw_pack_level0(hipStream_t st, const uint64_t *offsets, const uint32_t *neighbors, uint32_t n_points, uint32_t stride, uint32_t *l0);
 // the table again, each row followed by one f32 per link slot: aux[linked row] (SQ: the offsets column travels with the links)
 int32_t launch_hnsw_pack_level0_aux(hipStream_t st, const uint32_t *l0, uint32_t n_points, uint32_t stride, const float *aux, uint64_t n_aux, uint32_t *l0x);
-constexpr uint32_t HNSW_VIS_LDS_BYTES = 16384;                 // the walk's visited table in LDS (hnsw.hpp LdsVisited): 1024 buckets x 8 tags of 16 bits
-constexpr uint32_t HNSW_VIS_LDS_MAX_POINTS = 65534u * 1024u;    // ... graphs whose (id >> 10) + 1 fits a tag below the "taken back" mark 0xFFFF
-constexpr uint32_t HNSW_REF_CAND_CAP = 1u << 16;   // option hnsw_reference_heap_order: entries of one search's `candidates` heap (512 KiB per slot)
-constexpr uint32_t HNSW_EV_SPILL_CAP = 4096;      // search_with_vectors: evicted candidates of ONE score a slot can hold beyond four (32 KiB per slot; more raises err_flag = 2)
-constexpr uint32_t HNSW_REF_SLOT_CAP = 4096;       // ... searches in flight in that mode (1 024 until round 5: fewer than the default walk keeps in flight)
-constexpr uint32_t HNSW_MAX_EF = 4096;          // max(top, ef) of a walk: up to 512 in a register beam, beyond it in an LDS beam (hnsw.hpp Beam<0>)
 constexpr uint32_t HNSW_BUILD_MAX_M0 = 128;     // links per level-0 list of a device build (m <= m0 <= 128)
-constexpr uint32_t HNSW_MAX_EF_REG = 512;       // ... and of ef_construct (the build keeps its beam in registers)
 // HNSW build (hnsw_build.hpp)
 constexpr uint32_t HNSW_BUILD_MAX_LEVELS = 16;   // levels 0..15 (P(level >= 16) ~ m^-15.5)
 struct BuildLinks {
@@ -277,7 +271,6 @@ int32_t launch_hnsw_build_maxsim_tq(hipStream_t st, const ScanArgs &a, const Hns
 int32_t launch_pq_pair_table(hipStream_t st, uint32_t distance, uint32_t dim, const qmx_pq_params &pq, const float *d_centroids, float *d_pair);
 // norms[r] = sum of squares of u8 row r as the cosine leaf computes it for a stored row (metric_uint/avx2/cosine.rs, simple_cosine.rs)
 int32_t launch_u8_row_norms(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, uint32_t flags, float *norms_f, int32_t *norms_i);
-constexpr uint32_t HNSW_LDS_QUERY_MAX = 150 * 1024;
 
 // dense f32 / f16 / u8 (scan_dense.hip)
 int32_t launch_scan_dense(hipStream_t st, int dtype, int distance, int qt, ScanMode mode,

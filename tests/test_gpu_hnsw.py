@@ -713,3 +713,35 @@ def test_lds_visited_table_answers_like_the_bitmap_with_full_buckets_and_over_lo
                     qa.set_option("hnsw_no_lds_visited", -1)
                 assert scored == want_scored
                 _same(got, want)
+
+
+def test_sq_level0_table_belongs_to_the_first_segment_walked(qa):
+    """The packed level-0 table with the SQ rows' vector_offset behind the links (api_internal.hpp SqLevel0Table) is made at the first plain walk of an SQ
+    segment over a graph handle and kept for THAT segment: another quantization of the same points walked over the same handle keeps its own offsets column.
+    One handle walked with segment A, then B, then A again: every result is, bit for bit, the walk of a fresh handle that saw that storage alone."""
+    n, dim, nq, top, ef = 2000, 48, 48, 10, 64
+    rng = np.random.default_rng(1)
+    centers = rng.standard_normal((16, dim)).astype(np.float32) * 2.0
+    rows = (centers[rng.integers(0, 16, n)] + rng.standard_normal((n, dim)).astype(np.float32) * 0.6).astype(np.float32)
+    queries = (centers[rng.integers(0, 16, nq)] + rng.standard_normal((nq, dim)).astype(np.float32) * 0.6).astype(np.float32)
+    plain = O.Hnsw(O.DenseStorage(O.F32, O.DOT, rows), m=16, ef_construct=64, seed=7, threads=0).export_plain()
+    assert plain.m0 <= 63      # (level 0 is packed: the table exists)
+    storages = {}
+    for name, fit_on in (("a", rows), ("b", rows * np.float32(0.5))):
+        quant = qa.ScalarQuantizer.from_min_max(fit_on, dim, qa.Distance.Euclid)
+        codes = quant.encode(rows)
+        storages[name] = (qa.EncodedVectorsU8(codes, quant), np.ascontiguousarray(codes[:, :4]).view(np.float32).ravel())
+    assert not np.array_equal(storages["a"][1], storages["b"][1])      # the two vector_offset columns differ
+
+    def walk(graph, name):
+        res, scored = graph.search(top, ef, qa.new_raw_scorer(queries, storages[name][0]), with_scored=True)
+        assert any(len(r) for r in res)
+        return res, scored
+
+    shared = qa.GraphLayers.from_plain(plain)
+    for name in ("a", "b", "a"):
+        got, got_scored = walk(shared, name)
+        want, want_scored = walk(qa.GraphLayers.from_plain(plain), name)      # (for b: a handle that never saw a)
+        assert [len(r) for r in got] == [len(r) for r in want]
+        _same(got, want)
+        assert got_scored == want_scored
