@@ -149,6 +149,15 @@ typedef struct qmx_counters {
  * queries scans (pq_prefilter.hip).  It is built by default when it at most doubles the codes' footprint (m >= 16); this flag asks for it on narrower
  * codes too (m = 8: 32 bytes per row beside the 8 of the codes). */
 #define QMX_SEG_PQ_PREFILTER_COPY 0x100u
+/* f32 EUCLID blocks: keep a CENTRED int8 copy of the block - the codes of x - mu (mu: the column means, f64 sums on the device), one scale per column, in the
+ * int8 copy's layout (1 byte per element) - and one f32 per row, |x - mu|^2.  Top-k searches of the whole block (no id list, top <= 64) then take 128
+ * queries per pass of that copy on the int8 matrix cores (qdrant_amd/csrc/scan_l2i8.hip): |q - x|^2 = |q - mu|^2 + |x - mu|^2 - 2 (q - mu).(x - mu), the
+ * rows within a worst-case band of the k-th best score of a sample are re-scored exactly, and a query whose candidate lists overflow takes the exact Euclid
+ * scan alone: the results stay the reference's ids and score bits.  Built only for dim a multiple of 128 up to 1 024, 2^18 rows and more, the 16-byte
+ * aligned layout, every element finite; where it cannot be built (memory included) the segment is created without it.  Honoured on f32 Euclid segments
+ * only: on any other segment it does nothing, as QMX_SEG_I8_COPY and QMX_SEG_AUTO_COPY do nothing on a Euclid one.  Option "no_l2_prefilter" switches the
+ * route off. */
+#define QMX_SEG_L2_I8_COPY 0x200u
 
 /* SQ-int8 parameters = `MetadataInt8` (lib/quantization/src/encoded_vectors_u8.rs:84-91).
  * Parity is defined on GIVEN (alpha, offset): the reference's quantile estimate samples
@@ -315,7 +324,7 @@ QMX_API uint32_t qmx_abi_version(void);
  * which wait for a CU without a scan block.  A batch with more than 16 overflowed queries then streams the block once per 16 of them instead of once
  * per 64: 10 M x 768 Student-t rows through a forced int8 copy, where all 128 queries of every batch overflow, take 39.9 ms per batch against 22.0
  * with the former passes - a block the library's own choice of copy keeps away from the int8 copy; the headline step, where nothing overflows, is
- * 1.4 - 1.5 % faster), "group_matrix_bytes", "debug"
+ * 1.4 - 1.5 % faster), "group_matrix_bytes", "no_l2_prefilter" (an f32 Euclid segment with QMX_SEG_L2_I8_COPY keeps the exact Euclid scans), "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -
  * (qdrant_amd/csrc/common.hpp says what each selects; round 6 removed the experiments that had measured slower twice: their numbers stay under
  * profiles/).  Initial values come from the environment variables QMX_<NAME> read
@@ -420,7 +429,7 @@ QMX_API int32_t qmx_sparse_query_create_idf(const qmx_segment *seg, const uint64
  * trial at create measured.  (The reference's counterpart is the segment telemetry, `VectorIndexSearchesTelemetry` / `SegmentInfo`: which index and
  * quantization serve a segment is reported, not guessed.) */
 typedef struct qmx_segment_info {
-    uint32_t derived_copy;          /* 0 = none, else ONE of QMX_SEG_I8_COPY / QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY: the copy the prefilter streams */
+    uint32_t derived_copy;          /* 0 = none, else ONE of QMX_SEG_I8_COPY / QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY / QMX_SEG_L2_I8_COPY: the copy the prefilter streams */
     uint32_t chosen_by_trial;       /* 1 = QMX_SEG_AUTO_COPY decided it                                                                            */
     uint64_t derived_copy_bytes;    /* HBM the copy takes                                                                                          */
     float i8_scale_balance;         /* int8 copy: the range ratio G the column scales were balanced to (0 = every column at max |x| / 127)         */

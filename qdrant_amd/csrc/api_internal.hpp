@@ -99,6 +99,12 @@ struct qmx_segment {
     bool auto_choice = false;         // QMX_SEG_AUTO_COPY: the copy was chosen by the trial of segment_auto_copy; what it measured:
     float auto_i8_ms = 0.0f, auto_half_ms = 0.0f, auto_i8_verified = 0.0f;
     uint32_t auto_i8_fallback = 0;
+    // f32 Euclid blocks, QMX_SEG_L2_I8_COPY (scan_l2i8.hip): the centred int8 copy, what its pack and scan read beside it
+    void *d_l2_rows = nullptr;        // the codes of x - mu in the int8 copy's layout (split_i8_copy_bytes); nullptr: no copy
+    float *d_l2_norms = nullptr;      // ... |x_r - mu|^2 per row, padded to whole 256-row tiles (l2i8_norm_entries)
+    float *d_l2_mu = nullptr, *d_l2_scale = nullptr;      // ... the column means and the columns' scales [dim]
+    uint32_t *d_l2_stats = nullptr;   // ... {C1, C2^2, -, max_r N_r (f32 bits)}
+    uint64_t l2_bytes = 0;            // bytes of the copy and the norm column
     SparseSeg *sparse = nullptr;      // QMX_DTYPE_SPARSE only
     bool f16_avx_order = false;       // the f16 block of a qmx_search_matrix call: rows in the layout of RowF16Avx, scanned by launch_scan_f16_avx alone
 
@@ -115,6 +121,7 @@ struct qmx_segment {
         dev_free(d_tq_sf); dev_free(d_tq_l2); dev_free(d_tq_xm); dev_free(d_tq_shift); dev_free(d_tq_scale); dev_free(d_tq_weights);
         dev_free(d_tq_tables); dev_free(d_tq_l1); dev_free(d_tq_norms);
         dev_free(d_rows_split); dev_free(d_i8_scale); dev_free(d_i8_stats);
+        dev_free(d_l2_rows); dev_free(d_l2_norms); dev_free(d_l2_mu); dev_free(d_l2_scale); dev_free(d_l2_stats);
         sparse_delete(sparse);
     }
     bool fast_layout() const {

@@ -1,6 +1,6 @@
 // api_search.hip — the C-ABI of include/qdrant_amd.h, brute-force top-k: the exact scans, the prefilters, the merge, the oversampled quantized search.
 // (One of the api_*.hip translation units; what they share: api_internal.hpp.)
-// search_enqueue: search_plan decides the route once, then one function per route runs - tq_l1_search, pq_prefilter_search, wide_exact_search (SQ / TQ), and per
+// search_enqueue: search_plan decides the route once, then one function per route runs - tq_l1_search, pq_prefilter_search, wide_exact_search (SQ / TQ), l2_i8_search, and per
 // tile of the f32 / exact driver split_tile (f16_split_scan | i8_copy_scan) or exact_tile.  The prefilter routes share one skeleton, each step written once:
 // prefilter_begin (plan block, verification pool, sample), bound_enqueue, the route's approximate pass, verify_and_sort, overflow_passes, close_counters.
 #include "api_internal.hpp"
@@ -54,6 +54,7 @@ enum SearchRoute {
     ROUTE_SPLIT_ROWS,     // scan_split.hip over the f32 rows themselves (more than 64 queries)
     ROUTE_SPLIT_F16,      // ... over an f16 copy (QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY)
     ROUTE_I8_COPY,        // ... over the int8 copy (QMX_SEG_I8_COPY)
+    ROUTE_L2_I8,          // scan_l2i8.hip: f32 Euclid over the centred int8 copy (QMX_SEG_L2_I8_COPY)
     ROUTE_EXACT,          // tiles of the exact scans
 };
 struct SearchPlan {
@@ -87,6 +88,11 @@ static SearchPlan search_plan(const qmx_query *q, uint32_t top, const uint32_t *
     if (s->dtype == QMX_DTYPE_SQ_U8 && s->sq_wide && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && mfma_scan_ok(s) && option(OPT_SQ_WIDE_MIN_QUERIES) > 0 &&
         q->nq >= (uint32_t)option(OPT_SQ_WIDE_MIN_QUERIES) && sqw_shape_ok(tile_args(q, top, n_cand, 0, std::min<uint32_t>(q->nq, SPLIT_QT))))
         return whole(ROUTE_SQ_WIDE, SPLIT_QT);
+    // f32 Euclid with the centred int8 copy, whole block: 128 queries per pass of the copy, whatever the batch size (everything else about a Euclid search -
+    // an id list, top > 64, a small block, no copy - keeps the exact tiles below)
+    if (s->dtype == QMX_DTYPE_F32 && s->distance == QMX_DISTANCE_EUCLID && s->d_l2_rows && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && n_cand <= s->n &&
+        !option(OPT_NO_L2_PREFILTER))
+        return whole(ROUTE_L2_I8, SPLIT_QT);
     // f32 dot / cosine rows of 256, 512 or 768 floats, whole block: 64 queries per pass (scan_mfma16.hip); everything else 32 / 16
     const bool q64 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && q->nq > MAX_QT_MFMA && mfma16_dim_ok(64, s->dim) && !option(OPT_NO_MFMA16);
     // ... and rows of 1024 .. 1536 floats 32 per pass: that kernel keeps the queries in registers, not in an LDS tile (tile_qt's limit)
@@ -486,6 +492,93 @@ static int32_t wide_exact_search(SearchCall &c) {
     return QMX_OK;
 }
 
+// ---- f32 Euclid over the centred int8 copy (scan_l2i8.hip): 128 queries per pass of the copy.  The skeleton of the wide routes with a band: the sample's exact
+// k-th best score T_q (a lower bound of the final one), the pack (codes, Q, band, the compare's coefficients), the pass, regroup, the selection - it keeps
+// A >= max(T_q - band, A_k - 2 band) -, the pair kernel (the reference's bits) and sort; the queries whose lists overflowed take the exact Euclid scan in ONE
+// conditional launch of 16-query block rows (launch_scan_l2_exact_groups) and one merge ----
+constexpr uint32_t L2_FQT = 16;             // queries per block row of that launch
+static size_t l2_overflow_partial_bytes(const qmx_query *q, uint32_t top) {
+    return (size_t)q->seg->num_cus * ((q->nq + L2_FQT - 1) / L2_FQT) * L2_FQT * top * sizeof(uint64_t);
+}
+static int32_t l2_overflow_pass(const SearchCall &c, const SplitPlanLayout &pl) {
+    qmx_query *q = c.q;
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
+    if (q->has_filters) QMX_TRY(q->filter_of_packed.reserve((size_t)pl.list_cap * 4));
+    QMX_TRY(launch_split_plan(q->stream, (const uint32_t *)(plan + pl.ovf_q), q->nq, (const uint64_t *)q->gthr.p, ovf_list, (uint64_t *)(plan + pl.gthr_packed), pl.list_cap,
+                              (uint32_t *)(plan + pl.count), (int *)(plan + pl.run16), (int *)(plan + pl.run64), pl.n_run64, (SplitStats *)plan, q->d_queries,
+                              q->q_stride, q->sp_fq.p, q->has_filters ? (const uint32_t *)q->filter_of.p : nullptr, (uint32_t *)q->filter_of_packed.p));
+    ScanArgs a = tile_args(c, 0, q->nq);      // (nq: the packed slots; a block row takes 16 of them and reads how many are filled)
+    a.queries = q->sp_fq.p;
+    if (q->has_filters) a.del.filter_of = (const uint32_t *)q->filter_of_packed.p;
+    a.partial = (uint64_t *)q->partial.p;
+    a.partial_qt = L2_FQT;
+    a.run_if = (const int *)(plan + pl.count);
+    uint32_t grid = (uint32_t)q->seg->num_cus;      // (the cap the reservation was made for)
+    QMX_REQUIRE(l2_overflow_partial_bytes(q, c.top) <= q->partial.cap, QMX_ERR_OTHER, "Euclid fallback: partial lists");
+    QMX_TRY(launch_scan_l2_exact_groups(q->stream, a, q->seg->num_cus, &grid));
+    QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, L2_FQT, q->nq, c.top, c.d_out, c.d_counts, c.top, 0, nullptr, a.run_if, ovf_list, 0, true));
+    return split_stage(q, "Euclid fallback (conditional, one launch)");
+}
+static int32_t l2_i8_search(SearchCall &c) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    const SplitPlanLayout pl(q->nq, L2_FQT);
+    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT) * sizeof(uint64_t)));
+    QMX_TRY(q->sp_bq.reserve(split_i8_query_bytes(s->dim)));
+    QMX_TRY(q->sp_f32.reserve(SplitF32::floats * sizeof(float)));
+    QMX_TRY(q->sp_cand.reserve((size_t)SPLIT_QT * SPLIT_CAND_CAP * sizeof(uint64_t)));
+    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
+    QMX_TRY(q->sp_wl.reserve(l2i8_wlists_bytes(s->num_cus)));
+    QMX_TRY(q->sp_fq.reserve((size_t)pl.list_cap * q->q_stride));
+    QMX_TRY(q->partial.reserve(l2_overflow_partial_bytes(q, c.top)));
+    // the sample: every 256-th row (prescan_shift - 2; at least 8 192 rows), scored exactly
+    VerifyPool vp;
+    uint64_t S = 0;
+    QMX_TRY(prefilter_begin(q, pl, c.n_cand, -2, &vp, &S));
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    // the tile's per-query terms: T_q, band and the compare's a where the int8 route keeps them; b and Q share the scales' array, 2 t the query scales'
+    const SplitF32 f(q->sp_f32.p);
+    float *t_exact = f.i8_texact, *ca = f.thr, *cb = f.scales, *qn = f.scales + SPLIT_QT, *q2t = f.i8_qscale;
+    uint32_t n_tiles = 0;
+    c.launches = 2;     // (the verification's two launches up front, as the wide routes count)
+    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += SPLIT_QT, ++n_tiles) {
+        const uint32_t nq_tile = std::min<uint32_t>(SPLIT_QT, q->nq - tile0);
+        QMX_CHECK_CANCELLED(c.is_stopped);
+        const ScanArgs a = tile_args(c, tile0, nq_tile);
+        // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best
+        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches, true));
+        // 2. the shifted queries' codes as operand images, Q, the band, the compare's coefficients
+        QMX_TRY(launch_l2i8_pack(q->stream, a, s->d_l2_mu, s->d_l2_scale, (const uint64_t *)q->gthr.p + tile0, s->d_l2_stats, q->sp_bq.p, t_exact, f.band, ca, cb, q2t, qn,
+                                 (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+        QMX_TRY(split_stage(q, "Euclid int8 pack"));
+        // 3. the pass
+        uint32_t grid = 0;
+        QMX_TIMED_SCAN(c, launch_scan_l2i8(q->stream, a, s->d_l2_rows, s->d_l2_norms, q->sp_bq.p, ca, cb, q2t, qn, s->num_cus, q->sp_wl.p, &grid));
+        QMX_TRY(split_stage(q, "Euclid int8 scan"));
+        // 4. per-wave lists -> per-query lists (deleted rows dropped), then the rows worth an exact score
+        int *tile_ovf = (int *)(plan + pl.tile_ovf) + n_tiles;
+        QMX_TRY(launch_regroup_lists(q->stream, a.del, (const unsigned char *)q->sp_wl.p + l2i8_wlists_counts_bytes(s->num_cus), (const uint32_t *)q->sp_wl.p, l2i8_wcap(),
+                                     grid * 8, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf));
+        QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, vp, tile0, tile_ovf,
+                                    (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan, t_exact, true));
+        QMX_TRY(split_stage(q, "select"));
+        c.launches += 4;
+    }
+    // 5. the selected rows through the pair kernel (the reference's bits), sorted; 6. the exact Euclid scan of the queries whose lists overflowed
+    QMX_TRY(verify_and_sort(c, vp, q->nq));
+    QMX_TRY(l2_overflow_pass(c, pl));
+    c.launches += 3;
+    q->last_split = true;
+    q->last_pq = false;
+    q->last_fqt = L2_FQT;
+    // streamed: the copy and the norm column once per tile of queries + the sample's rows per group of the score kernel's queries
+    close_counters(c, (uint64_t)q->nq * c.n_cand,
+                   (uint64_t)n_tiles * l2i8_norm_entries(c.n_cand) * ((uint64_t)s->dim + 4) + (uint64_t)((q->nq + tile_qt(s, q) - 1) / tile_qt(s, q)) * S * s->row_bytes,
+                   c.launches, q->nq);
+    return QMX_OK;
+}
+
 // ---- the f32 prefilters (scan_split.hip, scan_i8copy.hip, split_select.hip): tiles of 128 / 256 queries; their verification and, if ever needed, the exact passes run once for all of them
 // after the tile loop ----
 struct SplitTiles {
@@ -731,6 +824,7 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
     if (plan.route == ROUTE_TQ_L1) return tq_l1_search(c, plan);
     if (plan.route == ROUTE_PQ_PREFILTER) return pq_prefilter_search(c);
     if (plan.route == ROUTE_TQ_WIDE || plan.route == ROUTE_SQ_WIDE) return wide_exact_search(c);
+    if (plan.route == ROUTE_L2_I8) return l2_i8_search(c);
     // tiles of plan.tile_q queries: the split tiles first, then - a remainder without a copy, or the whole batch - the exact ones
     const uint32_t TQ = plan.tile_q;
     QMX_TRY(q->partial.reserve((size_t)s->num_cus * 8 * std::min<uint32_t>(TQ, MAX_QT_TOPK) * std::min<uint32_t>(top, MAX_TOP_FAST) * sizeof(uint64_t)));

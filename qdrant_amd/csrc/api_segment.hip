@@ -283,6 +283,58 @@ static int32_t segment_split_stats(qmx_segment *s) {
     return QMX_OK;
 }
 
+// ---- the centred int8 copy of an f32 Euclid block (QMX_SEG_L2_I8_COPY; scan_l2i8.hip): the column means (f64 sums on the device; the mean as an f32 number
+// is what rows and queries are shifted by - any mu serves the identity, the mean makes the codes small), the statistics of y = x - mu (a pass), the scales
+// (host: split_i8_choose_scales, which is metric-agnostic), the worst row's code norms and the row-norm column (a pass), the codes (a pass).  Where it
+// cannot be built - dims, memory, an element that is not finite - the segment is created without it and every search keeps today's route. ----
+static bool l2_copy_passes(qmx_segment *s) {
+    uint32_t h[4] = {0, 0, 1, 0};
+    std::vector<float> colmax(s->dim), colsq(s->dim), scale(s->dim), mu(s->dim);
+    std::vector<double> colsum(s->dim);
+    DevBuf bcolsum, bcolmax, bcolsq;      // (filled by bare hipMalloc: a failure here is no error and leaves no error text)
+    bool ok = hipMalloc(&bcolsum.p, (size_t)s->dim * 8) == hipSuccess && hipMalloc(&bcolmax.p, (size_t)s->dim * 4) == hipSuccess &&
+              hipMalloc(&bcolsq.p, (size_t)s->dim * 4) == hipSuccess && hipMalloc((void **)&s->d_l2_mu, (size_t)s->dim * 4) == hipSuccess &&
+              hipMalloc((void **)&s->d_l2_scale, (size_t)s->dim * 4) == hipSuccess && hipMalloc((void **)&s->d_l2_stats, 16) == hipSuccess &&
+              hipMalloc((void **)&s->d_l2_norms, (size_t)l2i8_norm_entries(s->n) * 4) == hipSuccess;
+    if (ok) ok = launch_l2i8_colsum(nullptr, s->d_rows, s->row_stride, s->n, s->dim, (double *)bcolsum.p) == QMX_OK &&
+                 hipMemcpy(colsum.data(), bcolsum.p, (size_t)s->dim * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok) {
+        for (uint32_t i = 0; i < s->dim && ok; ++i) {
+            mu[i] = (float)(colsum[i] / (double)s->n);
+            ok = std::fabs(mu[i]) < 3.0e38f;      // (NaN / inf rows: no copy)
+        }
+    }
+    if (ok) ok = hipMemcpy(s->d_l2_mu, mu.data(), (size_t)s->dim * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                 launch_l2i8_colstats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, s->d_l2_mu, (uint32_t *)bcolmax.p, (float *)bcolsq.p) == QMX_OK &&
+                 hipMemcpy(colmax.data(), bcolmax.p, (size_t)s->dim * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(colsq.data(), bcolsq.p, (size_t)s->dim * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok) {
+        (void)split_i8_choose_scales(colmax.data(), colsq.data(), s->n, s->dim, scale.data());
+        ok = hipMemcpy(s->d_l2_scale, scale.data(), (size_t)s->dim * 4, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (ok) ok = launch_l2i8_rowstats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, s->d_l2_mu, s->d_l2_scale, s->d_l2_norms, s->d_l2_stats) == QMX_OK &&
+                 hipMemcpy(h, s->d_l2_stats, 16, hipMemcpyDeviceToHost) == hipSuccess && h[2] == 0;
+    if (ok) ok = hipMalloc(&s->d_l2_rows, split_i8_copy_bytes(s->n, s->dim)) == hipSuccess;
+    if (ok) ok = launch_l2i8_copy(nullptr, s->d_rows, s->row_stride, s->n, s->dim, s->d_l2_mu, s->d_l2_scale, s->d_l2_rows) == QMX_OK &&
+                 hipDeviceSynchronize() == hipSuccess;
+    return ok;
+}
+static int32_t segment_l2_copy(qmx_segment *s) {
+    if (!(s->flags & QMX_SEG_L2_I8_COPY) || s->dtype != QMX_DTYPE_F32 || s->distance != QMX_DISTANCE_EUCLID || !l2i8_dim_ok(s->dim) || s->n < (1u << 18) ||
+        s->n >= 0xFFFFFFFFull || !s->fast_layout())
+        return QMX_OK;
+    const bool ok = l2_copy_passes(s);
+    (void)hipGetLastError();
+    ::qmx::clear_stale_error();
+    if (!ok) {
+        dev_free(s->d_l2_rows); dev_free(s->d_l2_norms); dev_free(s->d_l2_mu); dev_free(s->d_l2_scale); dev_free(s->d_l2_stats);
+        (void)hipGetLastError();
+        return QMX_OK;
+    }
+    s->l2_bytes = split_i8_copy_bytes(s->n, s->dim) + l2i8_norm_entries(s->n) * 4;
+    return QMX_OK;
+}
+
 // SQ blocks large enough for the 128-query pass (scan_sqw.hip): the largest vector_offset, which its integer reject bound rests on
 static int32_t segment_sq_stats(qmx_segment *s) {
     if (s->dtype != QMX_DTYPE_SQ_U8 || s->n < (1u << 18) || !s->d_row_offsets || !sq_mfma_ok(s->distance, s->scan_dim) || !(s->sq.multiplier > 0.f) ||
@@ -612,6 +664,7 @@ int32_t qmx_segment_create(const qmx_segment_desc *desc, qmx_segment **out) {
     }
     if (rc == QMX_OK) rc = segment_upload(s, desc);
     if (rc == QMX_OK) rc = segment_split_stats(s);
+    if (rc == QMX_OK) rc = segment_l2_copy(s);
     if (rc == QMX_OK) rc = segment_pq_rot(s);
     if (rc == QMX_OK) rc = segment_tq_stats(s);
     if (rc == QMX_OK) rc = segment_sq_stats(s);
@@ -824,9 +877,9 @@ int32_t qmx_segment_get_info(const qmx_segment *seg, qmx_segment_info *out) {
     QMX_REFUSE_SPARSE(seg);
     QMX_REQUIRE(seg && out, QMX_ERR_BAD_ARG, "NULL argument");
     memset(out, 0, sizeof(*out));
-    out->derived_copy = !seg->d_rows_split ? 0u : seg->split_i8 ? QMX_SEG_I8_COPY : seg->split_half ? QMX_SEG_HALF_COPY : QMX_SEG_SPLIT_COPY;
+    out->derived_copy = seg->d_l2_rows ? QMX_SEG_L2_I8_COPY : !seg->d_rows_split ? 0u : seg->split_i8 ? QMX_SEG_I8_COPY : seg->split_half ? QMX_SEG_HALF_COPY : QMX_SEG_SPLIT_COPY;
     out->chosen_by_trial = seg->auto_choice ? 1u : 0u;
-    out->derived_copy_bytes = seg->d_rows_split ? seg->copy_bytes : 0;
+    out->derived_copy_bytes = seg->d_l2_rows ? seg->l2_bytes : seg->d_rows_split ? seg->copy_bytes : 0;
     out->i8_scale_balance = seg->split_i8 ? seg->i8_balance : 0.0f;
     out->trial_i8_ms = seg->auto_i8_ms;
     out->trial_half_ms = seg->auto_half_ms;

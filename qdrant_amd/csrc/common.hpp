@@ -77,6 +77,7 @@ enum Option {
                               // passes of 64, three launch pairs per 128 queries, whose blocks wait for a CU without a scan block even to find that nothing
                               // overflowed.  The same lists; a batch with more than 16 overflowed queries streams the block once per 16 of them, not per 64
     OPT_GROUP_MATRIX_BYTES,   // qmx_group_search: byte budget of the fallback's score matrix, which tiles the unfinished queries (0 = 1 GiB)
+    OPT_NO_L2_PREFILTER,      // f32 Euclid segments with the centred int8 copy (QMX_SEG_L2_I8_COPY) keep the exact Euclid scans (no scan_l2i8.hip prefilter + verification)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT
 };

@@ -403,6 +403,23 @@ int32_t launch_split_i8_picks(hipStream_t st, const qmx_scored_point *d_lists, c
                               uint32_t *d_probe_ids, uint32_t *d_probe_cnt);
 int32_t launch_split_i8_sample_bound(hipStream_t st, const float *d_scores, const uint32_t *d_probe_ids, uint32_t *d_probe_cnt, uint32_t nq, uint32_t top,
                                      float *d_band, const float *d_qscale, float *d_thr, float *d_t_exact, uint64_t *d_gthr);
+// the centred int8 copy of an f32 Euclid block (QMX_SEG_L2_I8_COPY), its pack, its 128-query pass and the conditional exact Euclid pass (scan_l2i8.hip; the
+// band: l2i8_band.hpp).  The copy's layout and size are the int8 copy's (split_i8_copy_bytes, split_i8_query_bytes); the scales come from split_i8_choose_scales
+bool l2i8_dim_ok(uint32_t dim);
+uint64_t l2i8_norm_entries(uint64_t n);      // entries of the row-norm column: n rounded up to whole 256-row tiles
+size_t l2i8_wlists_counts_bytes(int num_cus);
+size_t l2i8_wlists_bytes(int num_cus);       // d_wlists of launch_scan_l2i8: [counts][lists], 8 lists per block
+uint32_t l2i8_wcap();
+int32_t launch_l2i8_colsum(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, double *d_colsum);
+int32_t launch_l2i8_colstats(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, const float *d_mu, uint32_t *d_colmax, float *d_colsq);
+int32_t launch_l2i8_rowstats(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, const float *d_mu, const float *d_scale, float *d_norms,
+                             uint32_t *d_stats);
+int32_t launch_l2i8_copy(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, const float *d_mu, const float *d_scale, void *d_out);
+int32_t launch_l2i8_pack(hipStream_t st, const ScanArgs &a, const float *d_mu, const float *d_scale, const uint64_t *d_gthr, const uint32_t *d_row_stats, void *d_bq,
+                         float *d_t_exact, float *d_band, float *d_ca, float *d_cb, float *d_q2t, float *d_qn, uint32_t *d_cand_cnt, uint32_t n_cnt);
+int32_t launch_scan_l2i8(hipStream_t st, const ScanArgs &a, const void *d_rows_i8, const float *d_norms, const void *d_bq, const float *d_ca, const float *d_cb,
+                         const float *d_q2t, const float *d_qn, int num_cus, void *d_wlists, uint32_t *grid_out);
+int32_t launch_scan_l2_exact_groups(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid_out);
 // TurboQuant 4 bits, 128 queries per pass: codes decoded once per tile into the matrix cores' operand images, exact scores, candidate lists (scan_tq4w.hip)
 bool tq4w_shape_ok(const ScanArgs &a);
 size_t tq4w_query_bytes(uint32_t code_bytes);
