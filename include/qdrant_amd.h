@@ -153,7 +153,8 @@ typedef struct qmx_counters {
  * int8 copy's layout (1 byte per element) - and one f32 per row, |x - mu|^2.  Top-k searches of the whole block (no id list, top <= 64) then take 128
  * queries per pass of that copy on the int8 matrix cores (qdrant_amd/csrc/scan_l2i8.hip): |q - x|^2 = |q - mu|^2 + |x - mu|^2 - 2 (q - mu).(x - mu), the
  * rows within a worst-case band of the k-th best score of a sample are re-scored exactly, and a query whose candidate lists overflow takes the exact Euclid
- * scan alone: the results stay the reference's ids and score bits.  Built only for dim a multiple of 128 up to 1 024, 2^18 rows and more, the 16-byte
+ * scan alone: the results stay the reference's ids and score bits.  Built only for dim a multiple of 128 up to 2 048 (up to 1 024 the scan keeps the queries resident in LDS, above it
+ * stages them beside the rows), 2^18 rows and more, the 16-byte
  * aligned layout, every element finite; where it cannot be built (memory included) the segment is created without it.  Honoured on f32 Euclid segments
  * only: on any other segment it does nothing, as QMX_SEG_I8_COPY and QMX_SEG_AUTO_COPY do nothing on a Euclid one.  Option "no_l2_prefilter" switches the
  * route off. */

@@ -321,7 +321,8 @@ static bool l2_copy_passes(qmx_segment *s) {
 }
 static int32_t segment_l2_copy(qmx_segment *s) {
     if (!(s->flags & QMX_SEG_L2_I8_COPY) || s->dtype != QMX_DTYPE_F32 || s->distance != QMX_DISTANCE_EUCLID || !l2i8_dim_ok(s->dim) || s->n < (1u << 18) ||
-        s->n >= 0xFFFFFFFFull || !s->fast_layout())
+        s->n >= 0xFFFFFFFFull || !s->fast_layout() ||
+        !l2i8_exact_pass_fits(((s->scan_dim * 4 + 127) & ~127u) + QUERY_AUX_BYTES))      // (a query entry, as query_alloc lays it out)
         return QMX_OK;
     const bool ok = l2_copy_passes(s);
     (void)hipGetLastError();

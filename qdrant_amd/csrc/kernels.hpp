@@ -405,7 +405,8 @@ int32_t launch_split_i8_sample_bound(hipStream_t st, const float *d_scores, cons
                                      float *d_band, const float *d_qscale, float *d_thr, float *d_t_exact, uint64_t *d_gthr);
 // the centred int8 copy of an f32 Euclid block (QMX_SEG_L2_I8_COPY), its pack, its 128-query pass and the conditional exact Euclid pass (scan_l2i8.hip; the
 // band: l2i8_band.hpp).  The copy's layout and size are the int8 copy's (split_i8_copy_bytes, split_i8_query_bytes); the scales come from split_i8_choose_scales
-bool l2i8_dim_ok(uint32_t dim);
+bool l2i8_dim_ok(uint32_t dim);              // a multiple of 128 up to 2 048 (up to 1 024: the resident scan, above: the staged one)
+bool l2i8_exact_pass_fits(uint32_t q_stride);      // 16 query entries of the conditional exact pass fit in LDS
 uint64_t l2i8_norm_entries(uint64_t n);      // entries of the row-norm column: n rounded up to whole 256-row tiles
 size_t l2i8_wlists_counts_bytes(int num_cus);
 size_t l2i8_wlists_bytes(int num_cus);       // d_wlists of launch_scan_l2i8: [counts][lists], 8 lists per block

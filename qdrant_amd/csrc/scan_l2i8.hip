@@ -18,7 +18,8 @@
 
 namespace qmx {
 
-constexpr uint32_t L2_MAX_NCH = 8;                           // rows of up to 1 024 coordinates: the queries' image stays resident in LDS (128 KiB at 1 024)
+constexpr uint32_t L2_RES_NCH = 8;                           // rows of up to 1 024 coordinates: the queries' image stays resident in LDS (128 KiB at 1 024) - scan_l2i8_kernel
+constexpr uint32_t L2_MAX_NCH = 16;                          // ... of up to 2 048: rows and queries staged through LDS rings - scan_l2i8_staged_kernel
 constexpr uint32_t L2_MAX_DIM = L2_MAX_NCH * 128;
 constexpr int L2_QT = SP_QT;                                 // queries per pass
 __host__ __device__ constexpr size_t l2_lds_bytes(uint32_t nch) { return (size_t)nch * SP_B_UNITS * 16 + 4 * L2_QT * 4; }
@@ -278,7 +279,7 @@ __global__ __launch_bounds__(SP3_THREADS, 1) void scan_l2i8_kernel(const ScanArg
     constexpr int SLOTS = AHEAD + 1, WAVES = SP3_THREADS / 64, THREADS = SP3_THREADS, MT = 2, NL = 2 * MT;
     static_assert(SP3_BM == WAVES * MT * 16, "a wave owns two row tiles of a 256-row tile");
     static_assert(NL * AHEAD <= 62, "vmcnt is six bits");
-    static_assert(L2_MAX_NCH * 128u * 127u * 127u < (1u << 24), "fl32(I) is exact");
+    static_assert(L2_RES_NCH * 128u * 127u * 127u < (1u << 24), "fl32(I) is exact");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint4 *lds = reinterpret_cast<uint4 *>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -424,6 +425,193 @@ __global__ __launch_bounds__(SP3_THREADS, 1) void scan_l2i8_kernel(const ScanArg
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- The scan of rows of 1 152 .. 2 048 coordinates: the queries' image (144 .. 256 KiB) no longer fits in LDS, so rows AND queries are staged, with the work
+// split and the rings of sp_staged_scan (split_common.hpp; this kernel is a text of its own: that one carries the dot route and the f16 copies).  block = 8
+// waves = 4 row quarters (wm) x 2 query halves (wn), acc[4][4] per wave; a stage = 256 rows x 128 coordinates = 32 KiB of rows (non-temporal LDS-DMA from the
+// copy) + 16 KiB of query images (LDS-DMA from L2), three stages of each in LDS; per stage and wave six 1 KiB requests spread between 32 matrix
+// instructions, ONE s_waitcnt vmcnt and the stage barrier.
+// The row term comes the way everything else does.  A wave needs the 64 N_r of its row quarter once per tile: at the top of the tile's FIRST stage - in front of
+// that stage's six requests - it requests them with one global_load_lds_dword (256 B; lane l <- N of row 256 tile + 64 wm + l) into a 256-byte slot of its own
+// behind the stage rings, and the tile's epilogue reads the lane's sixteen back with four ds_read_b128.  The wave reads only what it copied itself: no barrier.
+// The vector-memory count, stage by stage (it retires in order; g = the stage, requests of stage g: [N of the tile if kc == 0, queries of g + 2, rows of g + 2]):
+//   kc == 0: seven requests, s_waitcnt vmcnt(7);  kc > 0: six, vmcnt(6)
+// - either way exactly the stage's OWN requests stay out, so rows and queries of stage g + 1 have landed, and so have, after the tile's second stage, its N
+// (a tile has at least nine stages).  The epilogue of tile it runs at the top of tile it + 1, in FRONT of that stage's requests (its stores retire under the
+// same wait), or after the last stage.  The slot ring has TWO slots per wave, tile it -> slot it & 1: the request of tile it + 1, issued right after the
+// epilogue of tile it, lands in the OTHER slot; the one that lands on slot it & 1 again is tile it + 2's, a whole tile after those reads.
+// fl32(I) is no longer exact here (127^2 dim >= 2^24): l2i8_band.hpp term (6) pays for it in the band and in the compare. ----
+constexpr uint32_t L2S_RING_BYTES = (SP3_ARING * SP3_A_UNITS + 3 * SP_B_UNITS) * 16;      // 96 + 48 KiB
+constexpr uint32_t L2S_NSLOTS = 2;                                                        // N slots per wave
+constexpr uint32_t L2S_LDS = L2S_RING_BYTES + (SP3_THREADS / 64) * L2S_NSLOTS * 256;      // + 4 KiB = 148 KiB
+// 256 B of global memory (wave-uniform base, lane i fetches bytes 4 i .. 4 i + 3) into LDS at the wave-uniform byte address lds_dst
+__device__ __forceinline__ void l2_glds4(const unsigned char *src, uint32_t lane_off, uint32_t lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(lane_off), "s"(src), "s"(lds_dst) : "memory");
+}
+__global__ __launch_bounds__(SP3_THREADS, 1) void scan_l2i8_staged_kernel(const ScanArgs a, const L2I8Args s) {
+    constexpr int BRING = 3, WAVES = SP3_THREADS / 64;
+    static_assert(L2_MAX_NCH * 128u * 127u * 127u < (1u << 25), "fl32(I) is within 1 of I (l2i8_int_rounding)");
+    static_assert(L2S_LDS <= 160 * 1024, "one block per CU");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    uint4 *lds = reinterpret_cast<uint4 *>(smem_raw);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint64_t n_tiles = (a.n_cand + SP3_BM - 1) / SP3_BM;
+    const uint32_t nch = s.nch;
+    const uint64_t my_tiles = blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
+    if (my_tiles == 0) {
+        SpWaveList::none(s.wcnt, blockIdx.x * WAVES + (uint32_t)w, lane);
+        return;
+    }
+    auto my_tile = [&](uint64_t i) -> uint64_t { return blockIdx.x + i * gridDim.x; };
+    const uint32_t wm = (uint32_t)w & 3u, wn = (uint32_t)w >> 2;
+    const uint32_t kq_r = (uint32_t)lane >> 4, m_r = (uint32_t)lane & 15u;
+    const uint32_t a_rd = sp_unit(wm * 4, 0, kq_r, m_r), b_rd = sp_unit(wn * 4, 0, kq_r, m_r);
+    // the wave's 64 queries, 4 per lane (query 64 wn + 16 nt + m_r): the compare's a and -b, 2 t, Q; a slot past nq admits nothing
+    float ca[4], nb[4], t2[4], qn[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const uint32_t q = wn * 64 + (uint32_t)nt * 16 + m_r;
+        ca[nt] = q < s.nq ? s.ca[q] : __builtin_inff();
+        nb[nt] = -s.cb[q];
+        t2[nt] = s.q2t[q];
+        qn[nt] = s.qn[q];
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // from here on the kernel counts its vector-memory traffic itself
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(sp_lds_byte *)smem_raw;
+    const uint32_t lane_off = (uint32_t)lane * 16u;
+    uint4 *b_lds = lds + SP3_ARING * SP3_A_UNITS;
+    // the wave's N slots: bytes, and as the lane reads them (its rows 16 mt + 4 kq_r + j of the quarter: piece 4 mt + kq_r)
+    const uint32_t n_slot0 = L2S_RING_BYTES + (uint32_t)w * (L2S_NSLOTS * 256u);
+    const uint4 *n_rd = reinterpret_cast<const uint4 *>(smem_raw + n_slot0) + kq_r;
+    // the copy streams, as in sp_staged_scan: running (tile, stage) counters; past the block's last stage the requests repeat it into a slot nobody reads
+    uint64_t ra_it = 0;
+    uint32_t ra_kc = 0, ra_slot = 0, rb_kc = 0, rb_slot = 0;
+    const unsigned char *ra_src = nullptr, *rb_src = nullptr;
+    uint32_t ra_dst = 0, rb_dst = 0;
+    auto rows_begin = [&]() {
+        ra_src = sp_uniform_ptr((uint64_t)(uintptr_t)(s.rows_i8 + (my_tile(ra_it) * nch + ra_kc) * SP3_A_UNITS) + (uint32_t)w * 4096u);
+        ra_dst = lds0 + (ra_slot * SP3_A_UNITS) * 16u + (uint32_t)w * 4096u;
+        ra_slot = sp_ring_next<SP3_ARING>(ra_slot);
+        if (ra_kc + 1 < nch) ++ra_kc;
+        else if (ra_it + 1 < my_tiles) { ra_kc = 0; ++ra_it; }
+    };
+    auto rows_piece = [&](int i) { sp_glds16_nt(ra_src + i * 1024, lane_off, ra_dst + i * 1024); };
+    auto queries_begin = [&]() {
+        rb_src = sp_uniform_ptr((uint64_t)(uintptr_t)(s.bq + (uint64_t)rb_kc * SP_B_UNITS) + (uint32_t)w * 2048u);
+        rb_dst = lds0 + (SP3_ARING * SP3_A_UNITS + rb_slot * SP_B_UNITS) * 16u + (uint32_t)w * 2048u;
+        rb_slot = sp_ring_next<BRING>(rb_slot);
+        rb_kc = rb_kc + 1 == nch ? 0 : rb_kc + 1;
+    };
+    auto queries_piece = [&](int i) { sp_glds16(rb_src + i * 1024, lane_off, rb_dst + i * 1024); };
+    // N of the wave's row quarter of a tile -> slot it & 1 (inside the column also in the block's last tile: it is padded to whole tiles, l2i8_norm_entries)
+    auto request_norms = [&](uint64_t it) {
+        const unsigned char *src = sp_uniform_ptr((uint64_t)(uintptr_t)(s.norms + my_tile(it) * SP3_BM + wm * 64u));
+        l2_glds4(src, (uint32_t)lane * 4u, lds0 + n_slot0 + ((uint32_t)it & 1u) * 256u);
+    };
+    // the prologue: queries of stages 0 and 1, rows of stages 0 and 1, each stage's queries in front of its rows
+    for (int st = 0; st < 2; ++st) {
+        queries_begin();
+        queries_piece(0);
+        queries_piece(1);
+        rows_begin();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rows_piece(i);
+    }
+    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // all but the last six: queries and rows of stage 0 have landed
+    sp_stage_barrier();
+    uint32_t slot = 0, bslot = 0;
+    i32x4s acc[4][4];
+    SpWaveList list(s.wlist, s.wcap, blockIdx.x * WAVES + (uint32_t)w);
+    const uint32_t n_rows32 = (uint32_t)a.n_cand;
+    // the epilogue of tile it: accumulator register j of (mt, nt) = row 256 tile + 64 wm + 16 mt + 4 kq_r + j, query 64 wn + 16 nt + m_r.  The resident
+    // kernel's test and score, narrowing by wave-uniform steps as I8CopyOps::epilogue does: the query tile, the 16-row tile, the four rows of a lane.
+    auto epilogue = [&](uint64_t it) __attribute__((always_inline)) {
+        const uint32_t row0 = (uint32_t)(my_tile(it) * SP3_BM) + wm * 64 + 4 * kq_r;
+        const uint4 *np = n_rd + ((uint32_t)it & 1u) * 16u;
+        f32x4s nr[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) nr[mt] = *reinterpret_cast<const f32x4s *>(np + mt * 4);
+        bool hit[4];
+        bool maybe = false;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            float mx = -__builtin_inff();
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mx = __builtin_fmaxf(mx, __builtin_fmaf(nb[nt], nr[mt][j], (float)acc[mt][nt][j]));
+            hit[nt] = mx >= ca[nt];
+            maybe = maybe || hit[nt];
+        }
+        if (!__ballot(maybe)) return;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            if (!__ballot(hit[nt])) continue;
+            const uint32_t q = wn * 64 + (uint32_t)nt * 16 + m_r;
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                float m4 = -__builtin_inff();
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m4 = __builtin_fmaxf(m4, __builtin_fmaf(nb[nt], nr[mt][j], (float)acc[mt][nt][j]));
+                if (!__ballot(m4 >= ca[nt])) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float fi = (float)acc[mt][nt][j], n = nr[mt][j];
+                    const uint32_t row = row0 + (uint32_t)mt * 16 + (uint32_t)j;
+                    const float score = __builtin_fmaf(t2[nt], fi, -n) - qn[nt];
+                    list.append(__builtin_fmaf(nb[nt], n, fi) >= ca[nt] && row < n_rows32 && q < s.nq, score, row, q);
+                }
+            }
+        }
+    };
+    for (uint64_t it = 0; it < my_tiles; ++it) {
+        if (it) epilogue(it - 1);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = (i32x4s){0, 0, 0, 0};
+        for (uint32_t kc = 0; kc < nch; ++kc) {
+            if (kc == 0) request_norms(it);               // the stage's first request
+            queries_begin();                              // stage g + 2 -> the slot stage g - 1 was read from (everybody is past that barrier)
+            rows_begin();                                 // likewise
+            const uint4 *ab = lds + slot * SP3_A_UNITS + a_rd;
+            const uint4 *bb = b_lds + bslot * SP_B_UNITS + b_rd;
+            i32x4s b0[4], b1[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                b0[nt] = *reinterpret_cast<const i32x4s *>(bb + nt * 128);
+                b1[nt] = *reinterpret_cast<const i32x4s *>(bb + nt * 128 + 64);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const i32x4s a0 = *reinterpret_cast<const i32x4s *>(ab + mt * 128);
+                const i32x4s a1 = *reinterpret_cast<const i32x4s *>(ab + mt * 128 + 64);
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1[nt], acc[mt][nt], 0, 0, 0);
+                // the stage's six copy requests, in the order the wait below relies on (queries first), spread over the matrix work
+                if (mt == 0) queries_piece(0);
+                if (mt == 1) queries_piece(1);
+                if (mt == 2) { rows_piece(0); rows_piece(1); }
+                if (mt == 3) { rows_piece(2); rows_piece(3); }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0[nt], acc[mt][nt], 0, 0, 0);
+            }
+            slot = sp_ring_next<SP3_ARING>(slot);
+            bslot = sp_ring_next<BRING>(bslot);
+            // all but this stage's own requests have landed: rows and queries of stage g + 1 among them, and by the tile's second stage its N
+            if (kc == 0) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            sp_stage_barrier();
+        }
+    }
+    epilogue(my_tiles - 1);
+    list.finish(s.wcnt, blockIdx.x * WAVES + (uint32_t)w, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // nothing may land in LDS after the block is gone
+}
+
 // ---- The conditional exact pass: the queries whose lists overflowed (packed by launch_split_plan: a.queries, a.del.filter_of; *a.run_if = how many) take the
 // exact Euclid top-k scan, 16 per block row - grid.y = the 16-query groups of the batch, a block row whose group holds none returns at once, which on a
 // search without overflow is every block.  Per (row, query) the instructions of the 16-query tile of scan_kernel<RowF32<M_EUCLID>, 16, 2, 2> (scan_common.hpp:
@@ -523,6 +711,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_l2_exact_groups_kernel(const 
 
 // ---------------------------------------------------------------------------------------------------------------------------
 bool l2i8_dim_ok(uint32_t dim) { return dim % 128 == 0 && dim >= 128 && dim <= L2_MAX_DIM; }
+// the conditional exact pass keeps 16 query entries of q_stride bytes in LDS (launch_scan_l2_exact_groups): a segment whose entries would not fit gets no copy
+bool l2i8_exact_pass_fits(uint32_t q_stride) { return (size_t)16 * q_stride <= 160 * 1024; }
 uint64_t l2i8_norm_entries(uint64_t n) { return (n + SP3_BM - 1) / SP3_BM * SP3_BM; }
 size_t l2i8_wlists_counts_bytes(int num_cus) { return split_wlists_counts_bytes(num_cus); }
 size_t l2i8_wlists_bytes(int num_cus) { return split_wlists_counts_bytes(num_cus) + (size_t)num_cus * (SP3_THREADS / 64) * SP_WCAP * 16; }
@@ -599,15 +789,18 @@ int32_t launch_scan_l2i8(hipStream_t st, const ScanArgs &a, const void *d_rows_i
     s.wcap = SP_WCAP;
     const uint64_t n_tiles = (a.n_cand + SP3_BM - 1) / SP3_BM;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)num_cus, n_tiles);
-    auto kfn = scan_l2i8_kernel<1>;
+    // rows of up to 1 024 coordinates: the queries resident; longer ones: the staged rings
+    const bool resident = s.nch <= L2_RES_NCH;
+    void (*kfn)(const ScanArgs, const L2I8Args) = resident ? scan_l2i8_kernel<1> : scan_l2i8_staged_kernel;
     static thread_local DeviceOnce once;
     ::qmx::clear_stale_error();
     if (once.need()) {
-        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2_lds_bytes(L2_MAX_NCH)));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_l2i8_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2_lds_bytes(L2_RES_NCH)));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_l2i8_staged_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L2S_LDS));
         once.mark();
     }
     QMX_NOTE_KERNEL(kfn);
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(SP3_THREADS), l2_lds_bytes(s.nch), st, a, s);
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(SP3_THREADS), resident ? l2_lds_bytes(s.nch) : (size_t)L2S_LDS, st, a, s);
     QMX_HIP(hipGetLastError());
     if (grid_out) *grid_out = grid;
     return QMX_OK;
