@@ -159,6 +159,16 @@ typedef struct qmx_counters {
  * only: on any other segment it does nothing, as QMX_SEG_I8_COPY and QMX_SEG_AUTO_COPY do nothing on a Euclid one.  Option "no_l2_prefilter" switches the
  * route off. */
 #define QMX_SEG_L2_I8_COPY 0x200u
+/* Dense u8 blocks (QMX_DTYPE_U8; Dot, Euclid or Cosine): keep one int32 per row (Cosine: an int32 and an f32 streamed, a second int32 read per listed
+ * pair), made once on the device, and let top-k searches of the whole block (no id list, top <= 64) take 128 queries per pass of the u8 ROWS THEMSELVES
+ * on the int8 matrix cores (qdrant_amd/csrc/scan_u8w.hip): no copy of the block.  Both operands are biased by 128 (one xor per byte) and the exact integer
+ * of every pair follows from the biased product, the row's column and a per-query term; the pairs whose score reaches the k-th best of a sample - less a
+ * band that covers the f32 summation order of the reference's AVX2 leaf, zero for Dot / Euclid under QMX_SEG_U8_SCALAR_ORDER - are re-scored by the pair
+ * kernel, and a query whose candidate lists overflow (masses of ties) takes the exact u8 scan alone: ids and score bits stay the reference's.  Built only
+ * for dim a multiple of 64 in 64 .. 1 024, row stride a multiple of 16, 2^18 rows and more, row_stride * 255 + dim < 2^31; where it cannot be built
+ * (memory included) the segment is created without it, and on any other segment the flag does nothing.  Options "no_u8_wide" (the route off) and
+ * "u8_wide_min_queries" (batches below it keep the exact scans; 8, measured: profiles/u8_wide.md).  Longer rows need the staged form of the scan (scan_l2i8.hip has one): not built. */
+#define QMX_SEG_U8_WIDE 0x400u
 
 /* SQ-int8 parameters = `MetadataInt8` (lib/quantization/src/encoded_vectors_u8.rs:84-91).
  * Parity is defined on GIVEN (alpha, offset): the reference's quantile estimate samples
@@ -325,7 +335,7 @@ QMX_API uint32_t qmx_abi_version(void);
  * which wait for a CU without a scan block.  A batch with more than 16 overflowed queries then streams the block once per 16 of them instead of once
  * per 64: 10 M x 768 Student-t rows through a forced int8 copy, where all 128 queries of every batch overflow, take 39.9 ms per batch against 22.0
  * with the former passes - a block the library's own choice of copy keeps away from the int8 copy; the headline step, where nothing overflows, is
- * 1.4 - 1.5 % faster), "group_matrix_bytes", "no_l2_prefilter" (an f32 Euclid segment with QMX_SEG_L2_I8_COPY keeps the exact Euclid scans), "debug"
+ * 1.4 - 1.5 % faster), "group_matrix_bytes", "no_l2_prefilter" (an f32 Euclid segment with QMX_SEG_L2_I8_COPY keeps the exact Euclid scans), "no_u8_wide" (a u8 segment with QMX_SEG_U8_WIDE keeps the exact u8 scans), "u8_wide_min_queries" (8: that segment takes the 128-query pass from this many queries on), "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -
  * (qdrant_amd/csrc/common.hpp says what each selects; round 6 removed the experiments that had measured slower twice: their numbers stay under
  * profiles/).  Initial values come from the environment variables QMX_<NAME> read
@@ -430,7 +440,7 @@ QMX_API int32_t qmx_sparse_query_create_idf(const qmx_segment *seg, const uint64
  * trial at create measured.  (The reference's counterpart is the segment telemetry, `VectorIndexSearchesTelemetry` / `SegmentInfo`: which index and
  * quantization serve a segment is reported, not guessed.) */
 typedef struct qmx_segment_info {
-    uint32_t derived_copy;          /* 0 = none, else ONE of QMX_SEG_I8_COPY / QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY / QMX_SEG_L2_I8_COPY: the copy the prefilter streams */
+    uint32_t derived_copy;          /* 0 = none, else ONE of QMX_SEG_I8_COPY / QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY / QMX_SEG_L2_I8_COPY / QMX_SEG_U8_WIDE (no copy: the per-row columns): what the prefilter streams beside or instead of the rows */
     uint32_t chosen_by_trial;       /* 1 = QMX_SEG_AUTO_COPY decided it                                                                            */
     uint64_t derived_copy_bytes;    /* HBM the copy takes                                                                                          */
     float i8_scale_balance;         /* int8 copy: the range ratio G the column scales were balanced to (0 = every column at max |x| / 127)         */

@@ -29,6 +29,7 @@ SEG_I8_COPY = 0x40
 SEG_AUTO_COPY = 0x80
 SEG_PQ_PREFILTER_COPY = 0x100
 SEG_L2_I8_COPY = 0x200
+SEG_U8_WIDE = 0x400
 
 FILTER_NONE = 0xFFFFFFFF     # qmx_query_set_filters: a request without a filter
 

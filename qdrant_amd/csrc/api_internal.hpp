@@ -105,6 +105,11 @@ struct qmx_segment {
     float *d_l2_mu = nullptr, *d_l2_scale = nullptr;      // ... the column means and the columns' scales [dim]
     uint32_t *d_l2_stats = nullptr;   // ... {C1, C2^2, -, max_r N_r (f32 bits)}
     uint64_t l2_bytes = 0;            // bytes of the copy and the norm column
+    // dense u8 blocks, QMX_SEG_U8_WIDE (scan_u8w.hip): the per-row columns of the 128-query pass over the rows themselves
+    int32_t *d_u8w_col = nullptr;     // C[row], padded to whole 256-row tiles (u8w_col_entries); nullptr: no column, every search keeps the exact scans
+    float *d_u8w_colf = nullptr;      // ... Cosine: F[row], padded alike
+    int32_t *d_u8w_n2 = nullptr;      // ... Cosine: sum(x^2) per row [n], read by the finish of the listed pairs only
+    uint64_t u8w_bytes = 0;           // bytes of the columns
     SparseSeg *sparse = nullptr;      // QMX_DTYPE_SPARSE only
     bool f16_avx_order = false;       // the f16 block of a qmx_search_matrix call: rows in the layout of RowF16Avx, scanned by launch_scan_f16_avx alone
 
@@ -122,6 +127,7 @@ struct qmx_segment {
         dev_free(d_tq_tables); dev_free(d_tq_l1); dev_free(d_tq_norms);
         dev_free(d_rows_split); dev_free(d_i8_scale); dev_free(d_i8_stats);
         dev_free(d_l2_rows); dev_free(d_l2_norms); dev_free(d_l2_mu); dev_free(d_l2_scale); dev_free(d_l2_stats);
+        dev_free(d_u8w_col); dev_free(d_u8w_colf); dev_free(d_u8w_n2);
         sparse_delete(sparse);
     }
     bool fast_layout() const {

@@ -1,6 +1,6 @@
 // api_search.hip — the C-ABI of include/qdrant_amd.h, brute-force top-k: the exact scans, the prefilters, the merge, the oversampled quantized search.
 // (One of the api_*.hip translation units; what they share: api_internal.hpp.)
-// search_enqueue: search_plan decides the route once, then one function per route runs - tq_l1_search, pq_prefilter_search, wide_exact_search (SQ / TQ), l2_i8_search, and per
+// search_enqueue: search_plan decides the route once, then one function per route runs - tq_l1_search, pq_prefilter_search, wide_exact_search (SQ / TQ), l2_i8_search, u8_wide_search, and per
 // tile of the f32 / exact driver split_tile (f16_split_scan | i8_copy_scan) or exact_tile.  The prefilter routes share one skeleton, each step written once:
 // prefilter_begin (plan block, verification pool, sample), bound_enqueue, the route's approximate pass, verify_and_sort, overflow_passes, close_counters.
 #include "api_internal.hpp"
@@ -55,6 +55,7 @@ enum SearchRoute {
     ROUTE_SPLIT_F16,      // ... over an f16 copy (QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY)
     ROUTE_I8_COPY,        // ... over the int8 copy (QMX_SEG_I8_COPY)
     ROUTE_L2_I8,          // scan_l2i8.hip: f32 Euclid over the centred int8 copy (QMX_SEG_L2_I8_COPY)
+    ROUTE_U8_WIDE,        // scan_u8w.hip: dense u8 rows themselves, 128 queries per pass (QMX_SEG_U8_WIDE)
     ROUTE_EXACT,          // tiles of the exact scans
 };
 struct SearchPlan {
@@ -93,6 +94,10 @@ static SearchPlan search_plan(const qmx_query *q, uint32_t top, const uint32_t *
     if (s->dtype == QMX_DTYPE_F32 && s->distance == QMX_DISTANCE_EUCLID && s->d_l2_rows && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && n_cand <= s->n &&
         !option(OPT_NO_L2_PREFILTER))
         return whole(ROUTE_L2_I8, SPLIT_QT);
+    // dense u8 with the per-row columns (QMX_SEG_U8_WIDE), whole block: 128 queries per pass of the rows themselves from u8_wide_min_queries queries on
+    if (s->dtype == QMX_DTYPE_U8 && s->d_u8w_col && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && n_cand <= s->n && !option(OPT_NO_U8_WIDE) &&
+        q->nq >= (uint32_t)std::max<int64_t>(1, option(OPT_U8_WIDE_MIN_QUERIES)))
+        return whole(ROUTE_U8_WIDE, SPLIT_QT);
     // f32 dot / cosine rows of 256, 512 or 768 floats, whole block: 64 queries per pass (scan_mfma16.hip); everything else 32 / 16
     const bool q64 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && q->nq > MAX_QT_MFMA && mfma16_dim_ok(64, s->dim) && !option(OPT_NO_MFMA16);
     // ... and rows of 1024 .. 1536 floats 32 per pass: that kernel keeps the queries in registers, not in an LDS tile (tile_qt's limit)
@@ -500,7 +505,9 @@ constexpr uint32_t L2_FQT = 16;             // queries per block row of that lau
 static size_t l2_overflow_partial_bytes(const qmx_query *q, uint32_t top) {
     return (size_t)q->seg->num_cus * ((q->nq + L2_FQT - 1) / L2_FQT) * L2_FQT * top * sizeof(uint64_t);
 }
-static int32_t l2_overflow_pass(const SearchCall &c, const SplitPlanLayout &pl) {
+// (scan: the exact scan of 16-query block rows - launch_scan_l2_exact_groups, or the u8 route's)
+typedef int32_t (*GroupsScan)(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid);
+static int32_t l2_overflow_pass(const SearchCall &c, const SplitPlanLayout &pl, GroupsScan scan = launch_scan_l2_exact_groups) {
     qmx_query *q = c.q;
     unsigned char *plan = (unsigned char *)q->sp_plan.p;
     uint32_t *ovf_list = (uint32_t *)(plan + pl.list);
@@ -516,9 +523,9 @@ static int32_t l2_overflow_pass(const SearchCall &c, const SplitPlanLayout &pl) 
     a.run_if = (const int *)(plan + pl.count);
     uint32_t grid = (uint32_t)q->seg->num_cus;      // (the cap the reservation was made for)
     QMX_REQUIRE(l2_overflow_partial_bytes(q, c.top) <= q->partial.cap, QMX_ERR_OTHER, "Euclid fallback: partial lists");
-    QMX_TRY(launch_scan_l2_exact_groups(q->stream, a, q->seg->num_cus, &grid));
+    QMX_TRY(scan(q->stream, a, q->seg->num_cus, &grid));
     QMX_TRY(launch_merge_keys(q->stream, (const uint64_t *)q->partial.p, grid, L2_FQT, q->nq, c.top, c.d_out, c.d_counts, c.top, 0, nullptr, a.run_if, ovf_list, 0, true));
-    return split_stage(q, "Euclid fallback (conditional, one launch)");
+    return split_stage(q, "exact fallback of 16-query block rows (conditional, one launch)");
 }
 static int32_t l2_i8_search(SearchCall &c) {
     qmx_query *q = c.q;
@@ -575,6 +582,76 @@ static int32_t l2_i8_search(SearchCall &c) {
     // streamed: the copy and the norm column once per tile of queries + the sample's rows per group of the score kernel's queries
     close_counters(c, (uint64_t)q->nq * c.n_cand,
                    (uint64_t)n_tiles * l2i8_norm_entries(c.n_cand) * ((uint64_t)s->dim + 4) + (uint64_t)((q->nq + tile_qt(s, q) - 1) / tile_qt(s, q)) * S * s->row_bytes,
+                   c.launches, q->nq);
+    return QMX_OK;
+}
+
+// ---- dense u8 over the rows themselves (scan_u8w.hip, QMX_SEG_U8_WIDE): 128 queries per pass on the int8 matrix cores.  The steps of l2_i8_search: the
+// sample's exact k-th best score T_q, the pack (the biased bytes, the band of u8w_band.hpp, the compare's terms), the pass with the finish of its lists,
+// regroup (deleted rows, the batch filter and per-request filters dropped through DeletedView), the selection - A >= max(T_q - band, A_k - 2 band) -, the
+// pair kernel (the reference's bits in either order of QMX_SEG_U8_SCALAR_ORDER) and sort; the queries whose lists overflowed - masses of ties are normal
+// with integer scores - take the exact u8 scan in ONE conditional launch of 16-query block rows (launch_scan_u8_exact_groups) and one merge ----
+static int32_t u8_groups_dot(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid) { return launch_scan_u8_exact_groups(st, QMX_DISTANCE_DOT, a, num_cus, grid); }
+static int32_t u8_groups_euclid(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid) { return launch_scan_u8_exact_groups(st, QMX_DISTANCE_EUCLID, a, num_cus, grid); }
+static int32_t u8_groups_cosine(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid) { return launch_scan_u8_exact_groups(st, QMX_DISTANCE_COSINE, a, num_cus, grid); }
+static int32_t u8_wide_search(SearchCall &c) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    const SplitPlanLayout pl(q->nq, L2_FQT);
+    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT) * sizeof(uint64_t)));
+    QMX_TRY(q->sp_bq.reserve(u8w_query_bytes(s->dim)));
+    QMX_TRY(q->sp_f32.reserve(SplitF32::floats * sizeof(float)));
+    QMX_TRY(q->sp_cand.reserve((size_t)SPLIT_QT * SPLIT_CAND_CAP * sizeof(uint64_t)));
+    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
+    QMX_TRY(q->sp_wl.reserve(u8w_wlists_bytes(s->num_cus)));
+    QMX_TRY(q->sp_fq.reserve((size_t)pl.list_cap * q->q_stride));
+    QMX_TRY(q->partial.reserve(l2_overflow_partial_bytes(q, c.top)));
+    // the sample: every 256-th row (prescan_shift - 2; at least 8 192 rows), scored exactly
+    VerifyPool vp;
+    uint64_t S = 0;
+    QMX_TRY(prefilter_begin(q, pl, c.n_cand, -2, &vp, &S));
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    // the tile's per-query terms, SPLIT_QT entries each: T_q and the band where the int8 routes keep them, the compare's in thr / scales, the finish's in qmax
+    const SplitF32 f(q->sp_f32.p);
+    float *t_exact = f.i8_texact, *kq = f.thr, *aq = f.thr + SPLIT_QT, *cut = f.i8_qscale;
+    int32_t *thr_i = f.wide_thr, *qoff = f.wide_thr + SPLIT_QT, *n1 = (int32_t *)(f.i8_qscale + SPLIT_QT);
+    const bool cosine = s->distance == QMX_DISTANCE_COSINE;
+    uint32_t n_tiles = 0;
+    c.launches = 2;     // (the verification's two launches up front, as the wide routes count)
+    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += SPLIT_QT, ++n_tiles) {
+        const uint32_t nq_tile = std::min<uint32_t>(SPLIT_QT, q->nq - tile0);
+        QMX_CHECK_CANCELLED(c.is_stopped);
+        const ScanArgs a = tile_args(c, tile0, nq_tile);
+        // 1. exact scores of the sample -> the k-th best of each query = a lower bound of its final k-th best
+        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches, true));
+        // 2. the queries' biased bytes as operand images, the band, the compare's and the finish's terms
+        QMX_TRY(launch_u8w_pack(q->stream, a, s->distance, (const uint64_t *)q->gthr.p + tile0, q->sp_bq.p, t_exact, f.band, cut, thr_i, kq, aq, qoff, n1,
+                                (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+        QMX_TRY(split_stage(q, "u8 wide pack"));
+        // 3. the pass and the finish of its lists
+        uint32_t grid = 0;
+        QMX_TIMED_SCAN(c, launch_scan_u8w(q->stream, a, s->distance, q->sp_bq.p, thr_i, kq, aq, s->d_u8w_col, s->d_u8w_colf, s->d_u8w_n2, qoff, n1, cut, s->num_cus,
+                                          q->sp_wl.p, &grid));
+        QMX_TRY(split_stage(q, "u8 wide scan"));
+        // 4. per-wave lists -> per-query lists (deleted rows dropped), then the rows worth an exact score
+        int *tile_ovf = (int *)(plan + pl.tile_ovf) + n_tiles;
+        QMX_TRY(launch_regroup_lists(q->stream, a.del, (const unsigned char *)q->sp_wl.p + u8w_wlists_counts_bytes(s->num_cus), (const uint32_t *)q->sp_wl.p, u8w_wcap(),
+                                     grid * 8, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf));
+        QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, vp, tile0, tile_ovf,
+                                    (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan, t_exact, true));
+        QMX_TRY(split_stage(q, "select"));
+        c.launches += 5;
+    }
+    // 5. the selected rows through the pair kernel (the reference's bits), sorted; 6. the exact u8 scan of the queries whose lists overflowed
+    QMX_TRY(verify_and_sort(c, vp, q->nq));
+    QMX_TRY(l2_overflow_pass(c, pl, s->distance == QMX_DISTANCE_DOT ? u8_groups_dot : cosine ? u8_groups_cosine : u8_groups_euclid));
+    c.launches += 3;
+    q->last_split = true;
+    q->last_pq = false;
+    q->last_fqt = L2_FQT;
+    // streamed: the rows and the column(s) once per tile of queries + the sample's rows per group of the score kernel's queries
+    close_counters(c, (uint64_t)q->nq * c.n_cand,
+                   (uint64_t)n_tiles * c.n_cand * ((uint64_t)s->dim + (cosine ? 8 : 4)) + (uint64_t)((q->nq + tile_qt(s, q) - 1) / tile_qt(s, q)) * S * s->row_bytes,
                    c.launches, q->nq);
     return QMX_OK;
 }
@@ -825,6 +902,7 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
     if (plan.route == ROUTE_PQ_PREFILTER) return pq_prefilter_search(c);
     if (plan.route == ROUTE_TQ_WIDE || plan.route == ROUTE_SQ_WIDE) return wide_exact_search(c);
     if (plan.route == ROUTE_L2_I8) return l2_i8_search(c);
+    if (plan.route == ROUTE_U8_WIDE) return u8_wide_search(c);
     // tiles of plan.tile_q queries: the split tiles first, then - a remainder without a copy, or the whole batch - the exact ones
     const uint32_t TQ = plan.tile_q;
     QMX_TRY(q->partial.reserve((size_t)s->num_cus * 8 * std::min<uint32_t>(TQ, MAX_QT_TOPK) * std::min<uint32_t>(top, MAX_TOP_FAST) * sizeof(uint64_t)));

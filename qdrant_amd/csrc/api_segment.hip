@@ -336,6 +336,27 @@ static int32_t segment_l2_copy(qmx_segment *s) {
     return QMX_OK;
 }
 
+// ---- dense u8 blocks, QMX_SEG_U8_WIDE (scan_u8w.hip): the per-row columns of the 128-query pass, one pass over the block on the device.  Where they cannot be
+// built - the gate, memory - the segment is created without them and every search keeps today's route ----
+static int32_t segment_u8_wide(qmx_segment *s) {
+    if (!(s->flags & QMX_SEG_U8_WIDE) || s->dtype != QMX_DTYPE_U8 || !u8w_segment_ok(s->distance, s->dim, s->row_stride, s->n) || !s->fast_layout()) return QMX_OK;
+    const bool cosine = s->distance == QMX_DISTANCE_COSINE;
+    const size_t col_bytes = (size_t)u8w_col_entries(s->n) * 4;
+    bool ok = hipMalloc((void **)&s->d_u8w_col, col_bytes) == hipSuccess;
+    if (ok && cosine) ok = hipMalloc((void **)&s->d_u8w_colf, col_bytes) == hipSuccess && hipMalloc((void **)&s->d_u8w_n2, (size_t)s->n * 4) == hipSuccess;
+    if (ok) ok = launch_u8w_columns(nullptr, s->d_rows, s->row_stride, s->n, s->dim, s->distance, s->d_u8w_col, s->d_u8w_colf, s->d_u8w_n2) == QMX_OK &&
+                 hipDeviceSynchronize() == hipSuccess;
+    (void)hipGetLastError();
+    ::qmx::clear_stale_error();
+    if (!ok) {
+        dev_free(s->d_u8w_col); dev_free(s->d_u8w_colf); dev_free(s->d_u8w_n2);
+        (void)hipGetLastError();
+        return QMX_OK;
+    }
+    s->u8w_bytes = col_bytes * (cosine ? 2 : 1) + (cosine ? (uint64_t)s->n * 4 : 0);
+    return QMX_OK;
+}
+
 // SQ blocks large enough for the 128-query pass (scan_sqw.hip): the largest vector_offset, which its integer reject bound rests on
 static int32_t segment_sq_stats(qmx_segment *s) {
     if (s->dtype != QMX_DTYPE_SQ_U8 || s->n < (1u << 18) || !s->d_row_offsets || !sq_mfma_ok(s->distance, s->scan_dim) || !(s->sq.multiplier > 0.f) ||
@@ -666,6 +687,7 @@ int32_t qmx_segment_create(const qmx_segment_desc *desc, qmx_segment **out) {
     if (rc == QMX_OK) rc = segment_upload(s, desc);
     if (rc == QMX_OK) rc = segment_split_stats(s);
     if (rc == QMX_OK) rc = segment_l2_copy(s);
+    if (rc == QMX_OK) rc = segment_u8_wide(s);
     if (rc == QMX_OK) rc = segment_pq_rot(s);
     if (rc == QMX_OK) rc = segment_tq_stats(s);
     if (rc == QMX_OK) rc = segment_sq_stats(s);
@@ -878,9 +900,9 @@ int32_t qmx_segment_get_info(const qmx_segment *seg, qmx_segment_info *out) {
     QMX_REFUSE_SPARSE(seg);
     QMX_REQUIRE(seg && out, QMX_ERR_BAD_ARG, "NULL argument");
     memset(out, 0, sizeof(*out));
-    out->derived_copy = seg->d_l2_rows ? QMX_SEG_L2_I8_COPY : !seg->d_rows_split ? 0u : seg->split_i8 ? QMX_SEG_I8_COPY : seg->split_half ? QMX_SEG_HALF_COPY : QMX_SEG_SPLIT_COPY;
+    out->derived_copy = seg->d_u8w_col ? QMX_SEG_U8_WIDE : seg->d_l2_rows ? QMX_SEG_L2_I8_COPY : !seg->d_rows_split ? 0u : seg->split_i8 ? QMX_SEG_I8_COPY : seg->split_half ? QMX_SEG_HALF_COPY : QMX_SEG_SPLIT_COPY;
     out->chosen_by_trial = seg->auto_choice ? 1u : 0u;
-    out->derived_copy_bytes = seg->d_l2_rows ? seg->l2_bytes : seg->d_rows_split ? seg->copy_bytes : 0;
+    out->derived_copy_bytes = seg->d_u8w_col ? seg->u8w_bytes : seg->d_l2_rows ? seg->l2_bytes : seg->d_rows_split ? seg->copy_bytes : 0;
     out->i8_scale_balance = seg->split_i8 ? seg->i8_balance : 0.0f;
     out->trial_i8_ms = seg->auto_i8_ms;
     out->trial_half_ms = seg->auto_half_ms;

@@ -78,6 +78,8 @@ enum Option {
                               // overflowed.  The same lists; a batch with more than 16 overflowed queries streams the block once per 16 of them, not per 64
     OPT_GROUP_MATRIX_BYTES,   // qmx_group_search: byte budget of the fallback's score matrix, which tiles the unfinished queries (0 = 1 GiB)
     OPT_NO_L2_PREFILTER,      // f32 Euclid segments with the centred int8 copy (QMX_SEG_L2_I8_COPY) keep the exact Euclid scans (no scan_l2i8.hip prefilter + verification)
+    OPT_NO_U8_WIDE,           // dense u8 segments with QMX_SEG_U8_WIDE keep the exact u8 scans (no scan_u8w.hip pass + verification)
+    OPT_U8_WIDE_MIN_QUERIES,  // ... and take the 128-query pass from this many queries on (8: measured, profiles/u8_wide.md)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT
 };

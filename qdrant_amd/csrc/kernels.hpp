@@ -403,6 +403,21 @@ int32_t launch_split_i8_picks(hipStream_t st, const qmx_scored_point *d_lists, c
                               uint32_t *d_probe_ids, uint32_t *d_probe_cnt);
 int32_t launch_split_i8_sample_bound(hipStream_t st, const float *d_scores, const uint32_t *d_probe_ids, uint32_t *d_probe_cnt, uint32_t nq, uint32_t top,
                                      float *d_band, const float *d_qscale, float *d_thr, float *d_t_exact, uint64_t *d_gthr);
+// dense u8 blocks, QMX_SEG_U8_WIDE (scan_u8w.hip; the band and the compare: u8w_band.hpp): the per-row columns, the pack, the 128-query pass over the u8
+// rows themselves (with the finish of its lists) and the conditional exact u8 pass
+bool u8w_segment_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n);      // Dot / Euclid / Cosine, dim a multiple of 64 in 64 .. 1 024, 2^18 rows and more
+size_t u8w_query_bytes(uint32_t dim);
+size_t u8w_wlists_counts_bytes(int num_cus);
+size_t u8w_wlists_bytes(int num_cus);        // d_wlists of launch_scan_u8w: [counts][lists], 8 lists per block
+uint32_t u8w_wcap();
+uint64_t u8w_col_entries(uint64_t n);        // entries of a streamed column: n rounded up to whole 256-row tiles
+int32_t launch_u8w_columns(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, int distance, int32_t *d_col, float *d_colf, int32_t *d_n2);
+int32_t launch_u8w_pack(hipStream_t st, const ScanArgs &a, int distance, const uint64_t *d_gthr, void *d_bq, float *d_t_exact, float *d_band, float *d_cut,
+                        int32_t *d_thr_i, float *d_kq, float *d_aq, int32_t *d_qoff, int32_t *d_n1, uint32_t *d_cand_cnt, uint32_t n_cnt);
+int32_t launch_scan_u8w(hipStream_t st, const ScanArgs &a, int distance, const void *d_bq, const int32_t *d_thr_i, const float *d_kq, const float *d_aq,
+                        const int32_t *d_col, const float *d_colf, const int32_t *d_n2, const int32_t *d_qoff, const int32_t *d_n1, const float *d_cut, int num_cus,
+                        void *d_wlists, uint32_t *grid_out);
+int32_t launch_scan_u8_exact_groups(hipStream_t st, int distance, const ScanArgs &a, int num_cus, uint32_t *grid_out);
 // the centred int8 copy of an f32 Euclid block (QMX_SEG_L2_I8_COPY), its pack, its 128-query pass and the conditional exact Euclid pass (scan_l2i8.hip; the
 // band: l2i8_band.hpp).  The copy's layout and size are the int8 copy's (split_i8_copy_bytes, split_i8_query_bytes); the scales come from split_i8_choose_scales
 bool l2i8_dim_ok(uint32_t dim);              // a multiple of 128 up to 2 048 (up to 1 024: the resident scan, above: the staged one)
