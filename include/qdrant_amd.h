@@ -165,9 +165,10 @@ typedef struct qmx_counters {
  * of every pair follows from the biased product, the row's column and a per-query term; the pairs whose score reaches the k-th best of a sample - less a
  * band that covers the f32 summation order of the reference's AVX2 leaf, zero for Dot / Euclid under QMX_SEG_U8_SCALAR_ORDER - are re-scored by the pair
  * kernel, and a query whose candidate lists overflow (masses of ties) takes the exact u8 scan alone: ids and score bits stay the reference's.  Built only
- * for dim a multiple of 64 in 64 .. 1 024, row stride a multiple of 16, 2^18 rows and more, row_stride * 255 + dim < 2^31; where it cannot be built
+ * for dim a multiple of 64 in 64 .. 2 048 (up to 1 024 the scan keeps the queries resident in LDS, above it stages them beside the rows; 2 048 is where
+ * the band's derivation ends), row stride a multiple of 16, 2^18 rows and more, row_stride * 255 + dim < 2^31; where it cannot be built
  * (memory included) the segment is created without it, and on any other segment the flag does nothing.  Options "no_u8_wide" (the route off) and
- * "u8_wide_min_queries" (batches below it keep the exact scans; 8, measured: profiles/u8_wide.md).  Longer rows need the staged form of the scan (scan_l2i8.hip has one): not built. */
+ * "u8_wide_min_queries" (batches below it keep the exact scans; 8, measured: profiles/u8_wide.md, profiles/u8_wide_long_rows.md). */
 #define QMX_SEG_U8_WIDE 0x400u
 
 /* SQ-int8 parameters = `MetadataInt8` (lib/quantization/src/encoded_vectors_u8.rs:84-91).

@@ -405,7 +405,7 @@ int32_t launch_split_i8_sample_bound(hipStream_t st, const float *d_scores, cons
                                      float *d_band, const float *d_qscale, float *d_thr, float *d_t_exact, uint64_t *d_gthr);
 // dense u8 blocks, QMX_SEG_U8_WIDE (scan_u8w.hip; the band and the compare: u8w_band.hpp): the per-row columns, the pack, the 128-query pass over the u8
 // rows themselves (with the finish of its lists) and the conditional exact u8 pass
-bool u8w_segment_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n);      // Dot / Euclid / Cosine, dim a multiple of 64 in 64 .. 1 024, 2^18 rows and more
+bool u8w_segment_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n);      // Dot / Euclid / Cosine, dim a multiple of 64 in 64 .. 2 048 (up to 1 024: the resident scan, above: the staged one), 2^18 rows and more
 size_t u8w_query_bytes(uint32_t dim);
 size_t u8w_wlists_counts_bytes(int num_cus);
 size_t u8w_wlists_bytes(int num_cus);        // d_wlists of launch_scan_u8w: [counts][lists], 8 lists per block

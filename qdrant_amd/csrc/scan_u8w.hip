@@ -5,8 +5,10 @@
 // byte, in registers for the rows (after the wait for their loads), once per tile of queries for the queries (u8w_pack_kernel).  With x' = x - 128,
 // q' = q - 128 and I = sum q' x' the exact integers of a pair follow from I, a per-row column made once per segment and a per-query term (u8w_band.hpp: the
 // identities, the band |A - R| of the pass's score A against the reference's f32 score R, the integer / float compare and why it admits every pair the
-// selection's cut admits).  In the file's order: the per-row columns, u8w_pack_kernel, scan_u8w_kernel (the hot path: scan_sqw.hip's work split with the
-// bias, the columns and a per-metric epilogue), u8w_finish_kernel, and the conditional exact pass of the queries whose lists overflowed.
+// selection's cut admits).  In the file's order: the per-row columns, u8w_pack_kernel, scan_u8w_kernel (the hot path for rows of up to 1 024 bytes:
+// scan_sqw.hip's work split with the bias, the columns and a per-metric epilogue), scan_u8w_staged_kernel (rows of 1 088 .. 2 048 bytes: rows and queries
+// through LDS rings, the rows by LDS-DMA straight from the row-major block), u8w_finish_kernel, and the conditional exact pass of the queries whose lists
+// overflowed.
 //
 // The tail is the wide routes': a strided sample's exact k-th best score T_q admits the candidates (A >= T_q - band), per-wave lists are regrouped per
 // query, the selection keeps A >= max(T_q - band, A_k - 2 band), the pair kernel re-scores that (the reference's bits in either order of
@@ -23,9 +25,15 @@ constexpr int UW_THREADS = 512;
 constexpr int UW_BM = 256;                                   // rows per tile
 constexpr int UW_QT = 128;                                   // queries per pass
 constexpr int UW_B_UNITS = UW_QT * 4;                        // 16-byte units of a 64-byte stage of the queries' image: 8 KiB
-constexpr uint32_t UW_MAX_DIM = 1024;                        // the queries' whole image stays in LDS: 128 KiB
-constexpr int UW_LDS_TAIL = UW_QT * 12;                      // behind the image: the integer bounds, the cosine's k and a
-constexpr int UW_LDS_MAX = UW_MAX_DIM / 64 * UW_B_UNITS * 16 + UW_LDS_TAIL;
+constexpr uint32_t UW_RES_NCH = 16;                          // rows of up to 1 024 bytes: the queries' whole image stays in LDS (128 KiB at 1 024) - scan_u8w_kernel
+constexpr uint32_t UW_MAX_NCH = 32;                          // ... of up to 2 048: rows and queries staged through LDS rings - scan_u8w_staged_kernel
+constexpr uint32_t UW_MAX_DIM = UW_MAX_NCH * 64;
+constexpr int UW_LDS_TAIL = UW_QT * 12;                      // behind the resident image: the integer bounds, the cosine's k and a
+constexpr int UW_LDS_MAX = UW_RES_NCH * UW_B_UNITS * 16 + UW_LDS_TAIL;
+// what u8w_band.hpp's derivation asks of the longest row: the AVX2 leaf's eight lane totals convert exactly, a pair's integers stay below 2^27, I fits
+static_assert(65025ull * UW_MAX_DIM / 8 < (1ull << 24), "a lane total of the reference's AVX2 leaf converts to f32 exactly");
+static_assert(65025ull * UW_MAX_DIM < (1ull << 27), "|Z| < 2^27: one rounding of A, the compare's slack of 4 / 8 / 16");
+static_assert(128ull * 128ull * UW_MAX_DIM <= (1ull << 25), "I = sum q' x' fits the accumulator (and 2 I + C an int32)");
 constexpr uint32_t UW_WCAP = 8192;                           // candidates one wave may list per pass
 constexpr uint32_t UW_BIAS = 0x80808080u;
 
@@ -33,8 +41,8 @@ constexpr uint32_t UW_BIAS = 0x80808080u;
 __device__ __forceinline__ uint32_t uw_unit(uint32_t t, uint32_t kq, uint32_t m) { return (t * 4 + kq) * 16 + (m ^ (2 * kq)); }
 
 struct U8WideArgs {
-    const uint4 *bq;          // [nch][UW_B_UNITS] the queries' biased bytes as operand images (u8w_pack_kernel)
-    uint32_t nch;             // stages per tile: dim / 64
+    const uint4 *bq;          // the queries' biased bytes as operand images (u8w_pack_kernel): [nch][UW_B_UNITS], or - nch > UW_RES_NCH - [(nch + 1) / 2][SP_B_UNITS]
+    uint32_t nch;             // 64-byte chunks of a row: dim / 64 (the resident scan's stages per tile; the staged scan's are pairs of them)
     uint32_t nq;              // live queries (<= 128)
     const int32_t *thr_i;     // [128] Dot / Euclid: a pair with V below this cannot reach the query's cut
     const float *kq, *aq;     // [128] Cosine: a pair with fma(-k, F[row], fl32(V)) below a cannot
@@ -98,14 +106,21 @@ __global__ __launch_bounds__(64) void u8w_pack_kernel(const unsigned char *queri
         for (uint32_t i = lane; i < n_cnt; i += 64) cand_cnt[i] = 0;
     const unsigned char *entry = queries + (uint64_t)qi * q_stride;
     U8WQuery sums{0, 0, 0};
-    if (lane < dim / 16) {      // (dim <= 1024: one piece per lane)
+    // dim <= 1024: one piece per lane, the resident scan's image ([dim / 64][UW_B_UNITS]).  Longer rows: two pieces per lane, the staged scan's image -
+    // [stages of 128 bytes][SP_B_UNITS] in the unit order its LDS-DMA copies verbatim; a last stage of one 64-byte chunk (dim = 64 mod 128) gets its
+    // missing chunk as q' = 0, whose product is zero whatever the row bytes are
+    const uint32_t nch = dim / 64, n_pieces = nch > UW_RES_NCH ? (nch + 1) / 2 * 8 : nch * 4;
+    for (uint32_t p = lane; p < n_pieces; p += 64) {
+        const bool real = p < dim / 16;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (live) v = *reinterpret_cast<const uint4 *>(entry + (uint64_t)lane * 16);
+        if (live && real) v = *reinterpret_cast<const uint4 *>(entry + (uint64_t)p * 16);
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        if (live)
+        if (live && real)
 #pragma unroll
             for (int e = 0; e < 16; ++e) u8w_query_add(sums, (w[e / 4] >> (8 * (e % 4))) & 0xFFu);
-        bq[(uint64_t)(lane >> 2) * UW_B_UNITS + uw_unit(qi >> 4, lane & 3u, qi & 15u)] = make_uint4(v.x ^ UW_BIAS, v.y ^ UW_BIAS, v.z ^ UW_BIAS, v.w ^ UW_BIAS);
+        const uint4 image = real ? make_uint4(v.x ^ UW_BIAS, v.y ^ UW_BIAS, v.z ^ UW_BIAS, v.w ^ UW_BIAS) : make_uint4(0u, 0u, 0u, 0u);
+        if (nch > UW_RES_NCH) bq[(uint64_t)(p >> 3) * SP_B_UNITS + sp_unit(qi >> 4, (p >> 2) & 1u, p & 3u, qi & 15u)] = image;
+        else bq[(uint64_t)(p >> 2) * UW_B_UNITS + uw_unit(qi >> 4, p & 3u, qi & 15u)] = image;
     }
     for (int o = 32; o >= 1; o >>= 1) {
         sums.sum_q += __shfl_xor(sums.sum_q, o, 64);
@@ -370,6 +385,238 @@ __global__ __launch_bounds__(UW_THREADS, 1) void scan_u8w_kernel(const ScanArgs 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- The scan of rows of 1 088 .. 2 048 bytes: the queries' image (136 .. 256 KiB) no longer fits in LDS, so rows AND queries are staged, with the work split
+// and the rings of sp_staged_scan / scan_l2i8_staged_kernel (this kernel is a text of its own: its rows are no LDS image but the row-major u8 block itself).
+// block = 8 waves = 4 row quarters (wm) x 2 query halves (wn), acc[4][4] per wave; a stage = 256 rows x 128 bytes of K = 32 KiB of rows + 16 KiB of query
+// images (u8w_pack_kernel wrote them in LDS order: a verbatim LDS-DMA copy from L2), three stages of each in LDS; per stage and wave six 1 KiB requests spread
+// between 32 matrix instructions, ONE s_waitcnt vmcnt and the stage barrier.
+// The rows.  LDS-DMA puts lane i's 16 bytes at dst + 16 i, but the GLOBAL address is the lane's own: the lane that owns unit p of a request fetches the
+// (row, piece) the operand layout sp_unit wants at p.  Request i (0 .. 3) of wave w fills units 256 w + 64 i + lane = sp_unit(2 w + (i >> 1), i & 1, kq, m)
+// with kq = lane >> 4, m = (lane & 15) ^ (2 kq): bytes [64 (i & 1) + 16 kq, + 16) of the stage's 128 of row 16 (2 w + (i >> 1)) + m of the tile.  An
+// instruction touches sixteen 64-byte half-lines (the resident kernel's pattern); requests 2 j and 2 j + 1 ask for the two halves of the same sixteen lines
+// back to back.  Lane offsets are 32-bit inside a tile (u8w_segment_ok).  Rows past the block (the last tile) clamp to its last row and are dropped by number.
+// A row of 64 (mod 128) bytes ends in a stage of ONE chunk: the requests of the missing chunk repeat the real one - no byte past dim of any row is read - and
+// the pack made the queries' missing chunk q' = 0.  The bias is applied to the A operand in registers, between its ds_read and the matrix instruction.
+// The columns come the way N_r does in scan_l2i8_staged_kernel: at the top of a tile's FIRST stage - in front of that stage's requests - a wave requests the
+// 64 C[row] of its row quarter with one global_load_lds_dword (Cosine: the 64 F[row] with a second) into a slot of its own behind the rings, tile it -> slot
+// it & 1, and the tile's epilogue reads the lane's sixteen back with four ds_read_b128 (eight).  The wave reads only what it copied itself: no barrier.
+// The vector-memory count, stage by stage (it retires in order; requests of stage g: [C (, F) of the tile if kc == 0, queries of g + 2, rows of g + 2]):
+//   kc == 0: seven requests (Cosine: eight), s_waitcnt vmcnt(7) (vmcnt(8));  kc > 0: six, vmcnt(6)
+// - either way exactly the stage's OWN requests stay out, so rows and queries of stage g + 1 have landed, and so have, after the tile's second stage, its
+// columns (a tile has at least nine stages).  The epilogue of tile it runs at the top of tile it + 1, in FRONT of that stage's requests (its stores retire
+// under the same wait), or after the last stage.  The request of tile it + 1, issued right after the epilogue of tile it, lands in the OTHER slot; the one
+// that lands on slot it & 1 again is tile it + 2's, a whole tile after those reads.
+// The epilogue is the resident kernel's per metric, from registers: the lane's four queries' bound (Dot, Euclid) or k and a (Cosine), narrowing by
+// wave-uniform steps - the query tile, the 16-row tile, the lane's four rows. ----
+constexpr uint32_t UWS_RING_BYTES = (SP3_ARING * SP3_A_UNITS + 3 * SP_B_UNITS) * 16;      // 96 + 48 KiB
+constexpr uint32_t UWS_NSLOTS = 2;                                                        // column slots per wave
+constexpr uint32_t uws_lds_bytes(bool cosine) { return UWS_RING_BYTES + (UW_THREADS / 64) * UWS_NSLOTS * (cosine ? 512u : 256u); }      // + 4 KiB (Cosine: 8)
+// 256 B of global memory (wave-uniform base, lane i fetches bytes 4 i .. 4 i + 3) into LDS at the wave-uniform byte address lds_dst
+__device__ __forceinline__ void uw_glds4(const unsigned char *src, uint32_t lane_off, uint32_t lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(lane_off), "s"(src), "s"(lds_dst) : "memory");
+}
+template <int METRIC>
+__global__ __launch_bounds__(UW_THREADS, 1) void scan_u8w_staged_kernel(const ScanArgs a, const U8WideArgs s) {
+    constexpr int BRING = 3, WAVES = UW_THREADS / 64, BM = UW_BM;
+    constexpr bool COS = METRIC == M_COSINE;
+    constexpr uint32_t CB = COS ? 512u : 256u;                    // bytes of a column slot: C, then F
+    static_assert(UW_THREADS == SP3_THREADS && UW_BM == SP3_BM && UW_QT == SP_QT, "the staged scans' work split");
+    static_assert(uws_lds_bytes(true) <= 160 * 1024, "one block per CU");
+    static_assert((UW_RES_NCH + 2) / 2 >= 3, "the shortest staged tile ((UW_RES_NCH + 2) / 2 stages): its columns land at least two stages before its epilogue");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    uint4 *lds = reinterpret_cast<uint4 *>(smem_raw);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint64_t n_tiles = (a.n_cand + BM - 1) / BM;
+    const uint32_t nch = s.nch, nst = (nch + 1) / 2;              // 64-byte chunks, 128-byte stages per tile
+    const uint64_t my_tiles = blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
+    if (my_tiles == 0) {
+        SpWaveList::none(s.wcnt, blockIdx.x * WAVES + (uint32_t)w, lane);
+        return;
+    }
+    auto my_tile = [&](uint64_t i) -> uint64_t { return blockIdx.x + i * gridDim.x; };
+    const uint32_t wm = (uint32_t)w & 3u, wn = (uint32_t)w >> 2;
+    const uint32_t kq_r = (uint32_t)lane >> 4, m_r = (uint32_t)lane & 15u;
+    const uint32_t a_rd = sp_unit(wm * 4, 0, kq_r, m_r), b_rd = sp_unit(wn * 4, 0, kq_r, m_r);
+    // the wave's 64 queries, 4 per lane (query 64 wn + 16 nt + m_r): the compare's terms; a dead slot or a query without a bound admits nothing (u8w_pack_kernel)
+    typedef std::conditional_t<COS, float, int32_t> val_t;       // what a pair is compared in: Dot V = I + C, Euclid V = 2 I + C, Cosine fma(-k, F, fl32(I + C))
+    val_t lim[4];                                                 // ... against the integer bound, or the cosine's a
+    float nk[4];                                                  // the cosine's -k
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const uint32_t q = wn * 64 + (uint32_t)nt * 16 + m_r;
+        if constexpr (COS) {
+            lim[nt] = s.aq[q];
+            nk[nt] = -s.kq[q];
+        } else {
+            lim[nt] = s.thr_i[q];
+            nk[nt] = 0.0f;
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // from here on the kernel counts its vector-memory traffic itself
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(sp_lds_byte *)smem_raw;
+    const uint32_t lane_off = (uint32_t)lane * 16u;
+    uint4 *b_lds = lds + SP3_ARING * SP3_A_UNITS;
+    // the wave's column slots: bytes, and as the lane reads them (its rows 16 mt + 4 kq_r + j of the quarter: piece 4 mt + kq_r)
+    const uint32_t c_slot0 = UWS_RING_BYTES + (uint32_t)w * (UWS_NSLOTS * CB);
+    const uint4 *c_rd = reinterpret_cast<const uint4 *>(smem_raw + c_slot0) + kq_r;
+    const unsigned char *rows = reinterpret_cast<const unsigned char *>(a.rows);
+    const uint64_t last_row = a.n_cand - 1;
+    const uint32_t row_stride32 = (uint32_t)a.row_stride;
+    // the rows the lane fetches for requests 0, 1 and 2, 3 of a stage, and its piece of their 64-byte chunk
+    const uint32_t rl0 = (uint32_t)w * 32u + (m_r ^ (2u * kq_r)), rl1 = rl0 + 16u;
+    // the copy streams, as in sp_staged_scan: running (tile, stage) counters; past the block's last stage the requests repeat it into a slot nobody reads
+    uint64_t ra_it = 0;
+    uint32_t ra_kc = 0, ra_slot = 0, rb_kc = 0, rb_slot = 0;
+    const unsigned char *ra_src = nullptr, *rb_src = nullptr;
+    uint32_t ra_dst = 0, rb_dst = 0, ra_hi = 0, ra_off0 = 0, ra_off1 = 0;
+    auto rows_begin = [&]() {
+        const uint64_t row0 = my_tile(ra_it) * BM;
+        ra_src = sp_uniform_ptr((uint64_t)(uintptr_t)(rows + row0 * a.row_stride + ra_kc * 128u));
+        ra_hi = ra_kc * 2u + 1u < nch ? 64u : 0u;                // the stage's second chunk, or - past the row's end - the first again
+        uint32_t r0 = rl0, r1 = rl1;
+        const uint64_t room = last_row - row0;                   // (row0 <= last_row: the tile exists)
+        if (room < BM - 1) {                                     // the block's last, partial tile (wave-uniform)
+            r0 = (uint64_t)rl0 < room ? rl0 : (uint32_t)room;
+            r1 = (uint64_t)rl1 < room ? rl1 : (uint32_t)room;
+        }
+        ra_off0 = r0 * row_stride32 + kq_r * 16u;
+        ra_off1 = r1 * row_stride32 + kq_r * 16u;
+        ra_dst = lds0 + (ra_slot * SP3_A_UNITS) * 16u + (uint32_t)w * 4096u;
+        ra_slot = sp_ring_next<SP3_ARING>(ra_slot);
+        if (ra_kc + 1 < nst) ++ra_kc;
+        else if (ra_it + 1 < my_tiles) { ra_kc = 0; ++ra_it; }
+    };
+    // (non-temporal: both halves of a line are asked for back to back and never again)
+    auto rows_piece = [&](int i) { sp_glds16_nt(ra_src + (i & 1 ? ra_hi : 0u), i & 2 ? ra_off1 : ra_off0, ra_dst + i * 1024); };
+    auto queries_begin = [&]() {
+        rb_src = sp_uniform_ptr((uint64_t)(uintptr_t)(s.bq + (uint64_t)rb_kc * SP_B_UNITS) + (uint32_t)w * 2048u);
+        rb_dst = lds0 + (SP3_ARING * SP3_A_UNITS + rb_slot * SP_B_UNITS) * 16u + (uint32_t)w * 2048u;
+        rb_slot = sp_ring_next<BRING>(rb_slot);
+        rb_kc = rb_kc + 1 == nst ? 0 : rb_kc + 1;
+    };
+    auto queries_piece = [&](int i) { sp_glds16(rb_src + i * 1024, lane_off, rb_dst + i * 1024); };
+    // C (and F) of the wave's row quarter of a tile -> slot it & 1 (inside the columns also in the block's last tile: they are padded to whole tiles, u8w_col_entries)
+    auto request_cols = [&](uint64_t it) {
+        const uint64_t row0 = my_tile(it) * BM + wm * 64u;
+        const uint32_t dst = lds0 + c_slot0 + ((uint32_t)it & 1u) * CB;
+        uw_glds4(sp_uniform_ptr((uint64_t)(uintptr_t)(s.col + row0)), (uint32_t)lane * 4u, dst);
+        if constexpr (COS) uw_glds4(sp_uniform_ptr((uint64_t)(uintptr_t)(s.colf + row0)), (uint32_t)lane * 4u, dst + 256u);
+    };
+    // the prologue: queries of stages 0 and 1, rows of stages 0 and 1, each stage's queries in front of its rows
+    for (int st = 0; st < 2; ++st) {
+        queries_begin();
+        queries_piece(0);
+        queries_piece(1);
+        rows_begin();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rows_piece(i);
+    }
+    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // all but the last six: queries and rows of stage 0 have landed
+    sp_stage_barrier();
+    uint32_t slot = 0, bslot = 0;
+    i32x4s acc[4][4];
+    SpWaveList list(s.wlist, s.wcap, blockIdx.x * WAVES + (uint32_t)w);
+    const uint32_t n_rows32 = (uint32_t)a.n_cand;
+    // the epilogue of tile it: accumulator register j of (mt, nt) = row 256 tile + 64 wm + 16 mt + 4 kq_r + j, query 64 wn + 16 nt + m_r
+    auto epilogue = [&](uint64_t it) __attribute__((always_inline)) {
+        const uint32_t row0 = (uint32_t)(my_tile(it) * BM) + wm * 64 + 4 * kq_r;
+        const uint4 *cp = c_rd + ((uint32_t)it & 1u) * (CB / 16u);
+        i32x4s cr[4];
+        f32x4s fr[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            cr[mt] = *reinterpret_cast<const i32x4s *>(cp + mt * 4);
+            if constexpr (COS) fr[mt] = *reinterpret_cast<const f32x4s *>(cp + 16 + mt * 4);
+        }
+        auto val = [&](int mt, int nt, int j) __attribute__((always_inline)) -> val_t {
+            const int v = (METRIC == M_EUCLID ? 2 * acc[mt][nt][j] : acc[mt][nt][j]) + cr[mt][j];
+            if constexpr (COS) return __builtin_fmaf(nk[nt], fr[mt][j], (float)v);
+            else return v;
+        };
+        auto max4 = [&](int mt, int nt) __attribute__((always_inline)) -> val_t {
+            val_t mx = val(mt, nt, 0);
+#pragma unroll
+            for (int j = 1; j < 4; ++j) mx = val(mt, nt, j) > mx ? val(mt, nt, j) : mx;
+            return mx;
+        };
+        bool hit[4];
+        bool maybe = false;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            val_t mx = max4(0, nt);
+#pragma unroll
+            for (int mt = 1; mt < 4; ++mt) mx = max4(mt, nt) > mx ? max4(mt, nt) : mx;
+            hit[nt] = mx >= lim[nt];
+            maybe = maybe || hit[nt];
+        }
+        if (!__ballot(maybe)) return;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            if (!__ballot(hit[nt])) continue;
+            const uint32_t q = wn * 64 + (uint32_t)nt * 16 + m_r;
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                if (!__ballot(max4(mt, nt) >= lim[nt])) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t row = row0 + (uint32_t)mt * 16 + (uint32_t)j;
+                    list.append_raw(val(mt, nt, j) >= lim[nt] && row < n_rows32 && q < s.nq, (uint32_t)acc[mt][nt][j], row, q);
+                }
+            }
+        }
+    };
+    const i32x4s bias = {(int)UW_BIAS, (int)UW_BIAS, (int)UW_BIAS, (int)UW_BIAS};
+    for (uint64_t it = 0; it < my_tiles; ++it) {
+        if (it) epilogue(it - 1);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = (i32x4s){0, 0, 0, 0};
+        for (uint32_t kc = 0; kc < nst; ++kc) {
+            if (kc == 0) request_cols(it);                // the stage's first request(s)
+            queries_begin();                              // stage g + 2 -> the slot stage g - 1 was read from (everybody is past that barrier)
+            rows_begin();                                 // likewise
+            const uint4 *ab = lds + slot * SP3_A_UNITS + a_rd;
+            const uint4 *bb = b_lds + bslot * SP_B_UNITS + b_rd;
+            i32x4s b0[4], b1[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                b0[nt] = *reinterpret_cast<const i32x4s *>(bb + nt * 128);
+                b1[nt] = *reinterpret_cast<const i32x4s *>(bb + nt * 128 + 64);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                // the bias: unsigned bytes -> int8 (x - 128), in the operand registers
+                const i32x4s a0 = *reinterpret_cast<const i32x4s *>(ab + mt * 128) ^ bias;
+                const i32x4s a1 = *reinterpret_cast<const i32x4s *>(ab + mt * 128 + 64) ^ bias;
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1[nt], acc[mt][nt], 0, 0, 0);
+                // the stage's six copy requests, in the order the wait below relies on (queries first), spread over the matrix work; the two halves of the
+                // rows' 128-byte lines back to back
+                if (mt == 0) queries_piece(0);
+                if (mt == 1) queries_piece(1);
+                if (mt == 2) { rows_piece(0); rows_piece(1); }
+                if (mt == 3) { rows_piece(2); rows_piece(3); }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0[nt], acc[mt][nt], 0, 0, 0);
+            }
+            slot = sp_ring_next<SP3_ARING>(slot);
+            bslot = sp_ring_next<BRING>(bslot);
+            // all but this stage's own requests have landed: rows and queries of stage g + 1 among them, and by the tile's second stage its columns
+            if (kc == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(COS ? 8 : 7) : "memory");
+            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            sp_stage_barrier();
+        }
+    }
+    epilogue(my_tiles - 1);
+    list.finish(s.wcnt, blockIdx.x * WAVES + (uint32_t)w, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // nothing may land in LDS after the block is gone
+}
+
 // ---- after the scan: an entry (I, row, query) becomes (key lo, key hi, query) with the pass's score A (u8w_score of the pair's exact integers) when A is
 // not below the query's cut T - band, else an entry the regroup skips.  One wave per list. ----
 __global__ __launch_bounds__(256) void u8w_finish_kernel(uint4 *wlist, const uint32_t *wcnt, uint32_t wcap, uint32_t n_lists, int metric, const int32_t *col,
@@ -504,7 +751,11 @@ bool u8w_segment_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n)
     return u8w_metric(distance) >= 0 && dim % 64 == 0 && dim >= 64 && dim <= UW_MAX_DIM && row_stride % 16 == 0 && n >= (1u << 18) && n < 0xFFFFFFFFull &&
            row_stride * (UW_BM - 1) + dim < (1ull << 31);
 }
-size_t u8w_query_bytes(uint32_t dim) { return (size_t)(dim / 64) * UW_B_UNITS * 16; }
+// the queries' image: [dim / 64] stages of 8 KiB for the resident scan, [stages of 128 bytes] of 16 KiB for the staged one (u8w_pack_kernel)
+size_t u8w_query_bytes(uint32_t dim) {
+    const uint32_t nch = dim / 64;
+    return nch <= UW_RES_NCH ? (size_t)nch * UW_B_UNITS * 16 : (size_t)((nch + 1) / 2) * SP_B_UNITS * 16;
+}
 size_t u8w_wlists_counts_bytes(int num_cus) { return ((size_t)num_cus * (UW_THREADS / 64) * 4 + 255) / 256 * 256; }
 size_t u8w_wlists_bytes(int num_cus) { return u8w_wlists_counts_bytes(num_cus) + (size_t)num_cus * (UW_THREADS / 64) * UW_WCAP * 16; }
 uint32_t u8w_wcap() { return UW_WCAP; }
@@ -557,12 +808,18 @@ int32_t launch_scan_u8w(hipStream_t st, const ScanArgs &a, int distance, const v
     s.wcap = UW_WCAP;
     const uint64_t n_tiles = (a.n_cand + UW_BM - 1) / UW_BM;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)num_cus, n_tiles);
-    const size_t lds_bytes = (size_t)s.nch * UW_B_UNITS * 16 + UW_LDS_TAIL;
+    // rows of up to 1 024 bytes: the queries resident; longer ones: the staged rings
+    const bool resident = s.nch <= UW_RES_NCH;
+    const size_t lds_bytes = resident ? (size_t)s.nch * UW_B_UNITS * 16 + UW_LDS_TAIL : (size_t)uws_lds_bytes(metric == U8W_COSINE);
     void (*kfn)(const ScanArgs, const U8WideArgs) =
-        metric == U8W_DOT ? scan_u8w_kernel<M_DOT, 2, 2> : metric == U8W_EUCLID ? scan_u8w_kernel<M_EUCLID, 2, 2> : scan_u8w_kernel<M_COSINE, 2, 2>;
+        resident ? (metric == U8W_DOT ? scan_u8w_kernel<M_DOT, 2, 2> : metric == U8W_EUCLID ? scan_u8w_kernel<M_EUCLID, 2, 2> : scan_u8w_kernel<M_COSINE, 2, 2>)
+                 : (metric == U8W_DOT ? scan_u8w_staged_kernel<M_DOT> : metric == U8W_EUCLID ? scan_u8w_staged_kernel<M_EUCLID> : scan_u8w_staged_kernel<M_COSINE>);
     static thread_local DeviceOnce once;
     ::qmx::clear_stale_error();
     if (once.need()) {
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_u8w_staged_kernel<M_DOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)uws_lds_bytes(false)));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_u8w_staged_kernel<M_EUCLID>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)uws_lds_bytes(false)));
+        QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_u8w_staged_kernel<M_COSINE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)uws_lds_bytes(true)));
         QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_u8w_kernel<M_DOT, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, UW_LDS_MAX));
         QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_u8w_kernel<M_EUCLID, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, UW_LDS_MAX));
         QMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(scan_u8w_kernel<M_COSINE, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, UW_LDS_MAX));

@@ -95,6 +95,11 @@ int main() {
     for (int m = 0; m < 3; ++m) {
         bad += check_block(metrics[m], 200, 64, 6, 0, 1 + m);
         bad += check_block(metrics[m], 60, 1024, 4, 200, 4 + m);      // totals past 2^24
+        // the staged scan's rows: its shortest (a last stage of one 64-byte chunk) and the derivation's limit (lane totals just under 2^24, totals under 2^27)
+        for (uint32_t dim : {1088u, 2048u}) {
+            bad += check_block(metrics[m], 60, dim, 4, 0, 7 + m + dim);
+            bad += check_block(metrics[m], 60, dim, 4, 200, 10 + m + dim);
+        }
     }
     if (bad) {
         printf("u8w_band_check: %d pairs outside the band or the compare\n", bad);
