@@ -170,6 +170,15 @@ typedef struct qmx_counters {
  * (memory included) the segment is created without it, and on any other segment the flag does nothing.  Options "no_u8_wide" (the route off) and
  * "u8_wide_min_queries" (batches below it keep the exact scans; 8, measured: profiles/u8_wide.md, profiles/u8_wide_long_rows.md). */
 #define QMX_SEG_U8_WIDE 0x400u
+/* Dense f16 blocks (QMX_DTYPE_F16; Dot, Cosine or Euclid): let top-k searches of the whole block (no id list, top <= 64) take 128 queries per pass of the
+ * f16 ROWS THEMSELVES on the f16 matrix cores (qdrant_amd/csrc/scan_f16w.hip): no copy of the block - Euclid keeps one f32 per row (|x|^2), Dot / Cosine
+ * nothing.  The pairs whose score reaches the k-th best of a sample, less a band that covers the matrix cores' summation order, the reference's own
+ * rounding and subnormal operands (qdrant_amd/csrc/f16w_band.hpp), are re-scored by a pair kernel that sums in the order of the reference's AVX leaf, and a
+ * query whose candidate lists overflow takes an exact pass in that order alone: on this route the ids and the score BITS are the reference's, which the
+ * exact f16 scans (device order, within 1e-5) do not promise.  Takes effect only for dim a multiple of 32 in 64 .. 1 024, row stride a multiple of 16, 2^18 rows and
+ * more, every element finite; otherwise (memory included) the segment is created without it, and on any other segment the flag does nothing.  Options
+ * "no_f16_wide" (the route off) and "f16_wide_min_queries" (batches below it keep the exact scans; 33, measured: profiles/f16_wide.md).  Rows above dim 1 024: not built. */
+#define QMX_SEG_F16_WIDE 0x800u
 
 /* SQ-int8 parameters = `MetadataInt8` (lib/quantization/src/encoded_vectors_u8.rs:84-91).
  * Parity is defined on GIVEN (alpha, offset): the reference's quantile estimate samples
@@ -336,7 +345,7 @@ QMX_API uint32_t qmx_abi_version(void);
  * which wait for a CU without a scan block.  A batch with more than 16 overflowed queries then streams the block once per 16 of them instead of once
  * per 64: 10 M x 768 Student-t rows through a forced int8 copy, where all 128 queries of every batch overflow, take 39.9 ms per batch against 22.0
  * with the former passes - a block the library's own choice of copy keeps away from the int8 copy; the headline step, where nothing overflows, is
- * 1.4 - 1.5 % faster), "group_matrix_bytes", "no_l2_prefilter" (an f32 Euclid segment with QMX_SEG_L2_I8_COPY keeps the exact Euclid scans), "no_u8_wide" (a u8 segment with QMX_SEG_U8_WIDE keeps the exact u8 scans), "u8_wide_min_queries" (8: that segment takes the 128-query pass from this many queries on), "debug"
+ * 1.4 - 1.5 % faster), "group_matrix_bytes", "no_l2_prefilter" (an f32 Euclid segment with QMX_SEG_L2_I8_COPY keeps the exact Euclid scans), "no_u8_wide" (a u8 segment with QMX_SEG_U8_WIDE keeps the exact u8 scans), "u8_wide_min_queries" (8: that segment takes the 128-query pass from this many queries on), "no_f16_wide" (an f16 segment with QMX_SEG_F16_WIDE keeps the exact f16 scans), "f16_wide_min_queries" (33: that segment takes the 128-query pass from this many queries on), "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -
  * (qdrant_amd/csrc/common.hpp says what each selects; round 6 removed the experiments that had measured slower twice: their numbers stay under
  * profiles/).  Initial values come from the environment variables QMX_<NAME> read
@@ -441,7 +450,7 @@ QMX_API int32_t qmx_sparse_query_create_idf(const qmx_segment *seg, const uint64
  * trial at create measured.  (The reference's counterpart is the segment telemetry, `VectorIndexSearchesTelemetry` / `SegmentInfo`: which index and
  * quantization serve a segment is reported, not guessed.) */
 typedef struct qmx_segment_info {
-    uint32_t derived_copy;          /* 0 = none, else ONE of QMX_SEG_I8_COPY / QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY / QMX_SEG_L2_I8_COPY / QMX_SEG_U8_WIDE (no copy: the per-row columns): what the prefilter streams beside or instead of the rows */
+    uint32_t derived_copy;          /* 0 = none, else ONE of QMX_SEG_I8_COPY / QMX_SEG_HALF_COPY / QMX_SEG_SPLIT_COPY / QMX_SEG_L2_I8_COPY / QMX_SEG_U8_WIDE / QMX_SEG_F16_WIDE (no copy: the per-row columns, if any): what the prefilter streams beside or instead of the rows */
     uint32_t chosen_by_trial;       /* 1 = QMX_SEG_AUTO_COPY decided it                                                                            */
     uint64_t derived_copy_bytes;    /* HBM the copy takes                                                                                          */
     float i8_scale_balance;         /* int8 copy: the range ratio G the column scales were balanced to (0 = every column at max |x| / 127)         */

@@ -30,6 +30,7 @@ SEG_AUTO_COPY = 0x80
 SEG_PQ_PREFILTER_COPY = 0x100
 SEG_L2_I8_COPY = 0x200
 SEG_U8_WIDE = 0x400
+SEG_F16_WIDE = 0x800
 
 FILTER_NONE = 0xFFFFFFFF     # qmx_query_set_filters: a request without a filter
 

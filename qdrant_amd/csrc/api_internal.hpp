@@ -110,6 +110,12 @@ struct qmx_segment {
     float *d_u8w_colf = nullptr;      // ... Cosine: F[row], padded alike
     int32_t *d_u8w_n2 = nullptr;      // ... Cosine: sum(x^2) per row [n], read by the finish of the listed pairs only
     uint64_t u8w_bytes = 0;           // bytes of the columns
+    // dense f16 blocks, QMX_SEG_F16_WIDE (scan_f16w.hip): what the 128-query pass over the rows themselves needs of the block
+    bool f16_wide = false;            // the flag took effect (the gate, every element finite): searches inside search_plan's gate take the pass
+    float *d_f16w_col = nullptr;      // Euclid: |x|^2 per row as f32, padded to whole 256-row tiles (f16w_col_entries); Dot / Cosine keep no column
+    float f16w_rowmax = 0.0f;         // not below the largest row norm
+    bool f16w_subnormal = false;      // some element of the block is an f16 subnormal (f16w_band.hpp (5))
+    uint64_t f16w_bytes = 0;          // bytes of the column
     SparseSeg *sparse = nullptr;      // QMX_DTYPE_SPARSE only
     bool f16_avx_order = false;       // the f16 block of a qmx_search_matrix call: rows in the layout of RowF16Avx, scanned by launch_scan_f16_avx alone
 
@@ -128,6 +134,7 @@ struct qmx_segment {
         dev_free(d_rows_split); dev_free(d_i8_scale); dev_free(d_i8_stats);
         dev_free(d_l2_rows); dev_free(d_l2_norms); dev_free(d_l2_mu); dev_free(d_l2_scale); dev_free(d_l2_stats);
         dev_free(d_u8w_col); dev_free(d_u8w_colf); dev_free(d_u8w_n2);
+        dev_free(d_f16w_col);
         sparse_delete(sparse);
     }
     bool fast_layout() const {

@@ -1,6 +1,6 @@
 // api_search.hip — the C-ABI of include/qdrant_amd.h, brute-force top-k: the exact scans, the prefilters, the merge, the oversampled quantized search.
 // (One of the api_*.hip translation units; what they share: api_internal.hpp.)
-// search_enqueue: search_plan decides the route once, then one function per route runs - tq_l1_search, pq_prefilter_search, wide_exact_search (SQ / TQ), l2_i8_search, u8_wide_search, and per
+// search_enqueue: search_plan decides the route once, then one function per route runs - tq_l1_search, pq_prefilter_search, wide_exact_search (SQ / TQ), l2_i8_search, u8_wide_search, f16_wide_search, and per
 // tile of the f32 / exact driver split_tile (f16_split_scan | i8_copy_scan) or exact_tile.  The prefilter routes share one skeleton, each step written once:
 // prefilter_begin (plan block, verification pool, sample), bound_enqueue, the route's approximate pass, verify_and_sort, overflow_passes, close_counters.
 #include "api_internal.hpp"
@@ -56,6 +56,7 @@ enum SearchRoute {
     ROUTE_I8_COPY,        // ... over the int8 copy (QMX_SEG_I8_COPY)
     ROUTE_L2_I8,          // scan_l2i8.hip: f32 Euclid over the centred int8 copy (QMX_SEG_L2_I8_COPY)
     ROUTE_U8_WIDE,        // scan_u8w.hip: dense u8 rows themselves, 128 queries per pass (QMX_SEG_U8_WIDE)
+    ROUTE_F16_WIDE,       // scan_f16w.hip: dense f16 rows themselves, 128 queries per pass (QMX_SEG_F16_WIDE)
     ROUTE_EXACT,          // tiles of the exact scans
 };
 struct SearchPlan {
@@ -98,6 +99,10 @@ static SearchPlan search_plan(const qmx_query *q, uint32_t top, const uint32_t *
     if (s->dtype == QMX_DTYPE_U8 && s->d_u8w_col && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && n_cand <= s->n && !option(OPT_NO_U8_WIDE) &&
         q->nq >= (uint32_t)std::max<int64_t>(1, option(OPT_U8_WIDE_MIN_QUERIES)))
         return whole(ROUTE_U8_WIDE, SPLIT_QT);
+    // dense f16 where QMX_SEG_F16_WIDE took effect, whole block: 128 queries per pass of the rows themselves from f16_wide_min_queries queries on
+    if (s->dtype == QMX_DTYPE_F16 && s->f16_wide && !d_ids && top <= MAX_TOP_FAST && n_cand >= (1u << 18) && n_cand <= s->n && !option(OPT_NO_F16_WIDE) &&
+        q->nq >= (uint32_t)std::max<int64_t>(1, option(OPT_F16_WIDE_MIN_QUERIES)))
+        return whole(ROUTE_F16_WIDE, SPLIT_QT);
     // f32 dot / cosine rows of 256, 512 or 768 floats, whole block: 64 queries per pass (scan_mfma16.hip); everything else 32 / 16
     const bool q64 = s->dtype == QMX_DTYPE_F32 && mfma_scan_ok(s) && q->nq > MAX_QT_MFMA && mfma16_dim_ok(64, s->dim) && !option(OPT_NO_MFMA16);
     // ... and rows of 1024 .. 1536 floats 32 per pass: that kernel keeps the queries in registers, not in an LDS tile (tile_qt's limit)
@@ -209,7 +214,15 @@ static int32_t verify_and_sort(const SearchCall &c, const VerifyPool &vp, uint32
     qmx_query *q = c.q;
     const void *scan_kernel = q->last_kernel;      // (the pair kernel is not what the search reports)
     PairSel sel{vp.qsel, 0, nullptr, vp.used};
-    QMX_TRY(score_pairs_device(q, sel, vp.ids, vp.cap, (float *)q->sp_vscores.p, false));
+    if (q->seg->dtype == QMX_DTYPE_F16 && q->seg->f16_wide) {      // the f16 route's lists carry the reference's AVX-order bits (scan_f16w.hip); every other f16 caller keeps launch_pairs_dense
+        ScanArgs a;
+        fill_args(q, 0, q->nq, a);
+        a.ids = vp.ids;
+        a.n_cand = vp.cap;
+        a.scores = (float *)q->sp_vscores.p;
+        QMX_TRY(launch_pairs_f16_avx(q->stream, (int)q->seg->distance, a, sel, vp.cap, q->seg->num_cus));
+    } else
+        QMX_TRY(score_pairs_device(q, sel, vp.ids, vp.cap, (float *)q->sp_vscores.p, false));
     q->last_kernel = scan_kernel;
     QMX_TRY(split_stage(q, "verify gather"));
     QMX_TRY(launch_sort_scored(q->stream, (const float *)q->sp_vscores.p, vp.ids, vp.cnt, 0, nq, c.top, c.d_out, c.d_counts, vp.off));
@@ -656,6 +669,73 @@ static int32_t u8_wide_search(SearchCall &c) {
     return QMX_OK;
 }
 
+// ---- dense f16 over the rows themselves (scan_f16w.hip, QMX_SEG_F16_WIDE): 128 queries per pass on the f16 matrix cores.  The steps of u8_wide_search: the
+// sample's k-th best score T_q from the exact f16 scans, the pack (the operand images, Q, the band of f16w_band.hpp, the cut), the pass, regroup (deleted
+// rows, the batch filter and per-request filters dropped through DeletedView), the selection - A >= max(T_q - band, A_k - 2 band) -, the AVX-order pair
+// kernel (the reference's bits) and sort; the queries whose lists overflowed take the AVX-order exact scan in ONE conditional launch of 16-query block
+// rows (launch_scan_f16_avx_groups) and one merge ----
+static int32_t f16_groups_dot(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid) { return launch_scan_f16_avx_groups(st, QMX_DISTANCE_DOT, a, num_cus, grid); }
+static int32_t f16_groups_euclid(hipStream_t st, const ScanArgs &a, int num_cus, uint32_t *grid) { return launch_scan_f16_avx_groups(st, QMX_DISTANCE_EUCLID, a, num_cus, grid); }
+static int32_t f16_wide_search(SearchCall &c) {
+    qmx_query *q = c.q;
+    const qmx_segment *s = q->seg;
+    const SplitPlanLayout pl(q->nq, L2_FQT);
+    QMX_TRY(q->gthr.reserve((size_t)std::max<uint32_t>(q->nq_padded, SPLIT_QT) * sizeof(uint64_t)));
+    QMX_TRY(q->sp_bq.reserve(f16w_query_bytes(s->dim)));
+    QMX_TRY(q->sp_f32.reserve(SplitF32::floats * sizeof(float)));
+    QMX_TRY(q->sp_cand.reserve((size_t)SPLIT_QT * SPLIT_CAND_CAP * sizeof(uint64_t)));
+    QMX_TRY(q->sp_cnt.reserve((size_t)SPLIT_QT_MAX * 4));
+    QMX_TRY(q->sp_wl.reserve(f16w_wlists_bytes(s->num_cus)));
+    QMX_TRY(q->sp_fq.reserve((size_t)pl.list_cap * q->q_stride));
+    QMX_TRY(q->partial.reserve(l2_overflow_partial_bytes(q, c.top)));
+    // the sample: every 256-th row (prescan_shift - 2; at least 8 192 rows), scored by the exact f16 scans
+    VerifyPool vp;
+    uint64_t S = 0;
+    QMX_TRY(prefilter_begin(q, pl, c.n_cand, -2, &vp, &S));
+    unsigned char *plan = (unsigned char *)q->sp_plan.p;
+    // the tile's per-query terms, SPLIT_QT entries each: T_q and the band where the int8 routes keep them, the cut in thr, Q in i8_qscale
+    const SplitF32 f(q->sp_f32.p);
+    float *t_exact = f.i8_texact, *cut = f.thr, *qq = f.i8_qscale;
+    const bool euclid = s->distance == QMX_DISTANCE_EUCLID;
+    uint32_t n_tiles = 0;
+    c.launches = 2;     // (the verification's two launches up front, as the wide routes count)
+    for (uint32_t tile0 = 0; tile0 < q->nq; tile0 += SPLIT_QT, ++n_tiles) {
+        const uint32_t nq_tile = std::min<uint32_t>(SPLIT_QT, q->nq - tile0);
+        QMX_CHECK_CANCELLED(c.is_stopped);
+        const ScanArgs a = tile_args(c, tile0, nq_tile);
+        // 1. device-order scores of the sample -> the k-th best of each query: within the band's term (4) of a lower bound of its final k-th best
+        QMX_TRY(bound_enqueue(c, tile0, nq_tile, (const uint32_t *)q->sp_sample.p, S, c.top, a.del, &c.launches, true));
+        // 2. the queries' f16 bytes as operand images, Q, the band and the cut
+        QMX_TRY(launch_f16w_pack(q->stream, a, s->distance, s->f16w_rowmax, s->f16w_subnormal, (const uint64_t *)q->gthr.p + tile0, q->sp_bq.p, t_exact, f.band, cut, qq,
+                                 (uint32_t *)q->sp_cnt.p, SPLIT_QT_MAX));
+        QMX_TRY(split_stage(q, "f16 wide pack"));
+        // 3. the pass
+        uint32_t grid = 0;
+        QMX_TIMED_SCAN(c, launch_scan_f16w(q->stream, a, s->distance, q->sp_bq.p, cut, qq, s->d_f16w_col, s->num_cus, q->sp_wl.p, &grid));
+        QMX_TRY(split_stage(q, "f16 wide scan"));
+        // 4. per-wave lists -> per-query lists (deleted rows dropped), then the rows worth the reference's score
+        int *tile_ovf = (int *)(plan + pl.tile_ovf) + n_tiles;
+        QMX_TRY(launch_regroup_lists(q->stream, a.del, (const unsigned char *)q->sp_wl.p + f16w_wlists_counts_bytes(s->num_cus), (const uint32_t *)q->sp_wl.p, f16w_wcap(),
+                                     grid * 8, (uint64_t *)q->sp_cand.p, (uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, tile_ovf));
+        QMX_TRY(launch_split_select(q->stream, (const uint64_t *)q->sp_cand.p, (const uint32_t *)q->sp_cnt.p, SPLIT_CAND_CAP, f.band, nq_tile, c.top, vp, tile0, tile_ovf,
+                                    (uint32_t *)(plan + pl.ovf_q) + tile0, (SplitStats *)plan, t_exact, true));
+        QMX_TRY(split_stage(q, "select"));
+        c.launches += 4;
+    }
+    // 5. the selected rows through the AVX-order pair kernel, sorted; 6. the AVX-order exact scan of the queries whose lists overflowed
+    QMX_TRY(verify_and_sort(c, vp, q->nq));
+    QMX_TRY(l2_overflow_pass(c, pl, euclid ? f16_groups_euclid : f16_groups_dot));
+    c.launches += 3;
+    q->last_split = true;
+    q->last_pq = false;
+    q->last_fqt = L2_FQT;
+    // streamed: the rows and the column once per tile of queries + the sample's rows per group of the score kernel's queries
+    close_counters(c, (uint64_t)q->nq * c.n_cand,
+                   (uint64_t)n_tiles * c.n_cand * ((uint64_t)s->dim * 2 + (euclid ? 4 : 0)) + (uint64_t)((q->nq + tile_qt(s, q) - 1) / tile_qt(s, q)) * S * s->row_bytes,
+                   c.launches, q->nq);
+    return QMX_OK;
+}
+
 // ---- the f32 prefilters (scan_split.hip, scan_i8copy.hip, split_select.hip): tiles of 128 / 256 queries; their verification and, if ever needed, the exact passes run once for all of them
 // after the tile loop ----
 struct SplitTiles {
@@ -903,6 +983,7 @@ int32_t search_enqueue(qmx_query *q, uint32_t top, const uint32_t *d_ids, uint64
     if (plan.route == ROUTE_TQ_WIDE || plan.route == ROUTE_SQ_WIDE) return wide_exact_search(c);
     if (plan.route == ROUTE_L2_I8) return l2_i8_search(c);
     if (plan.route == ROUTE_U8_WIDE) return u8_wide_search(c);
+    if (plan.route == ROUTE_F16_WIDE) return f16_wide_search(c);
     // tiles of plan.tile_q queries: the split tiles first, then - a remainder without a copy, or the whole batch - the exact ones
     const uint32_t TQ = plan.tile_q;
     QMX_TRY(q->partial.reserve((size_t)s->num_cus * 8 * std::min<uint32_t>(TQ, MAX_QT_TOPK) * std::min<uint32_t>(top, MAX_TOP_FAST) * sizeof(uint64_t)));

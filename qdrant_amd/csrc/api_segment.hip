@@ -1,6 +1,7 @@
 // api_segment.hip — the C-ABI of include/qdrant_amd.h, segments (upload, derived copies, files), preprocess / casts, quantizer encoders and fits.
 // (One of the api_*.hip translation units; what they share: api_internal.hpp.)
 #include "api_internal.hpp"
+#include "f16w_band.hpp"
 
 extern "C" {
 
@@ -357,6 +358,35 @@ static int32_t segment_u8_wide(qmx_segment *s) {
     return QMX_OK;
 }
 
+// ---- dense f16 blocks, QMX_SEG_F16_WIDE (scan_f16w.hip): one pass over the block on the device - the largest row norm, whether any element is subnormal,
+// whether all are finite, Euclid: the column |x|^2.  Where the flag cannot take effect - the gate, an Inf / NaN, memory - the segment is created without it
+// and every search keeps today's route ----
+static int32_t segment_f16_wide(qmx_segment *s) {
+    if (!(s->flags & QMX_SEG_F16_WIDE) || s->dtype != QMX_DTYPE_F16 || !f16w_segment_ok(s->distance, s->dim, s->row_stride, s->n) || !s->fast_layout()) return QMX_OK;
+    const bool euclid = s->distance == QMX_DISTANCE_EUCLID;
+    const size_t col_bytes = euclid ? (size_t)f16w_col_entries(s->n) * 4 : 0;
+    uint32_t *d_stats = nullptr, stats[3] = {0, 1, 0};
+    bool ok = hipMalloc((void **)&d_stats, sizeof(stats)) == hipSuccess && hipMemset(d_stats, 0, sizeof(stats)) == hipSuccess;
+    if (ok && euclid) ok = hipMalloc((void **)&s->d_f16w_col, col_bytes) == hipSuccess;
+    if (ok) ok = launch_f16w_stats(nullptr, s->d_rows, s->row_stride, s->n, s->dim, s->distance, s->d_f16w_col, d_stats) == QMX_OK &&
+                 hipMemcpy(stats, d_stats, sizeof(stats), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipGetLastError();
+    ::qmx::clear_stale_error();
+    dev_free(d_stats);
+    float max_sq;
+    memcpy(&max_sq, &stats[0], 4);
+    if (!ok || stats[1] != 0 || !(max_sq < 3.0e38f)) {      // (an Inf / NaN element: the band's arithmetic is over finite numbers)
+        dev_free(s->d_f16w_col);
+        (void)hipGetLastError();
+        return QMX_OK;
+    }
+    s->f16_wide = true;
+    s->f16w_rowmax = f16w_up(sqrt((double)max_sq));
+    s->f16w_subnormal = stats[2] != 0;
+    s->f16w_bytes = col_bytes;
+    return QMX_OK;
+}
+
 // SQ blocks large enough for the 128-query pass (scan_sqw.hip): the largest vector_offset, which its integer reject bound rests on
 static int32_t segment_sq_stats(qmx_segment *s) {
     if (s->dtype != QMX_DTYPE_SQ_U8 || s->n < (1u << 18) || !s->d_row_offsets || !sq_mfma_ok(s->distance, s->scan_dim) || !(s->sq.multiplier > 0.f) ||
@@ -688,6 +718,7 @@ int32_t qmx_segment_create(const qmx_segment_desc *desc, qmx_segment **out) {
     if (rc == QMX_OK) rc = segment_split_stats(s);
     if (rc == QMX_OK) rc = segment_l2_copy(s);
     if (rc == QMX_OK) rc = segment_u8_wide(s);
+    if (rc == QMX_OK) rc = segment_f16_wide(s);
     if (rc == QMX_OK) rc = segment_pq_rot(s);
     if (rc == QMX_OK) rc = segment_tq_stats(s);
     if (rc == QMX_OK) rc = segment_sq_stats(s);
@@ -900,9 +931,9 @@ int32_t qmx_segment_get_info(const qmx_segment *seg, qmx_segment_info *out) {
     QMX_REFUSE_SPARSE(seg);
     QMX_REQUIRE(seg && out, QMX_ERR_BAD_ARG, "NULL argument");
     memset(out, 0, sizeof(*out));
-    out->derived_copy = seg->d_u8w_col ? QMX_SEG_U8_WIDE : seg->d_l2_rows ? QMX_SEG_L2_I8_COPY : !seg->d_rows_split ? 0u : seg->split_i8 ? QMX_SEG_I8_COPY : seg->split_half ? QMX_SEG_HALF_COPY : QMX_SEG_SPLIT_COPY;
+    out->derived_copy = seg->f16_wide ? QMX_SEG_F16_WIDE : seg->d_u8w_col ? QMX_SEG_U8_WIDE : seg->d_l2_rows ? QMX_SEG_L2_I8_COPY : !seg->d_rows_split ? 0u : seg->split_i8 ? QMX_SEG_I8_COPY : seg->split_half ? QMX_SEG_HALF_COPY : QMX_SEG_SPLIT_COPY;
     out->chosen_by_trial = seg->auto_choice ? 1u : 0u;
-    out->derived_copy_bytes = seg->d_u8w_col ? seg->u8w_bytes : seg->d_l2_rows ? seg->l2_bytes : seg->d_rows_split ? seg->copy_bytes : 0;
+    out->derived_copy_bytes = seg->f16_wide ? seg->f16w_bytes : seg->d_u8w_col ? seg->u8w_bytes : seg->d_l2_rows ? seg->l2_bytes : seg->d_rows_split ? seg->copy_bytes : 0;
     out->i8_scale_balance = seg->split_i8 ? seg->i8_balance : 0.0f;
     out->trial_i8_ms = seg->auto_i8_ms;
     out->trial_half_ms = seg->auto_half_ms;

@@ -80,6 +80,8 @@ enum Option {
     OPT_NO_L2_PREFILTER,      // f32 Euclid segments with the centred int8 copy (QMX_SEG_L2_I8_COPY) keep the exact Euclid scans (no scan_l2i8.hip prefilter + verification)
     OPT_NO_U8_WIDE,           // dense u8 segments with QMX_SEG_U8_WIDE keep the exact u8 scans (no scan_u8w.hip pass + verification)
     OPT_U8_WIDE_MIN_QUERIES,  // ... and take the 128-query pass from this many queries on (8: measured, profiles/u8_wide.md)
+    OPT_NO_F16_WIDE,          // dense f16 segments with QMX_SEG_F16_WIDE keep the exact f16 scans (no scan_f16w.hip pass + verification)
+    OPT_F16_WIDE_MIN_QUERIES, // ... and take the 128-query pass from this many queries on (33: measured - where the exact Dot / Cosine scans need a second pass; Euclid alone would pay from 8 on; profiles/f16_wide.md)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT
 };

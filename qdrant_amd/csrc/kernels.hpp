@@ -418,6 +418,21 @@ int32_t launch_scan_u8w(hipStream_t st, const ScanArgs &a, int distance, const v
                         const int32_t *d_col, const float *d_colf, const int32_t *d_n2, const int32_t *d_qoff, const int32_t *d_n1, const float *d_cut, int num_cus,
                         void *d_wlists, uint32_t *grid_out);
 int32_t launch_scan_u8_exact_groups(hipStream_t st, int distance, const ScanArgs &a, int num_cus, uint32_t *grid_out);
+// dense f16 blocks, QMX_SEG_F16_WIDE (scan_f16w.hip; the band: f16w_band.hpp): the per-segment statistics (Euclid: with the column |x|^2), the pack, the
+// 128-query pass over the f16 rows themselves, and - the reference's AVX-order bits over the stored layout - the pair kernel and the conditional exact pass
+bool f16w_segment_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n);     // Dot / Cosine / Euclid, dim a multiple of 32 in 64 .. 1 024, 2^18 rows and more
+size_t f16w_query_bytes(uint32_t dim);
+size_t f16w_wlists_counts_bytes(int num_cus);
+size_t f16w_wlists_bytes(int num_cus);       // d_wlists of launch_scan_f16w: [counts][lists], 8 lists per block
+uint32_t f16w_wcap();
+uint64_t f16w_col_entries(uint64_t n);       // entries of the streamed column: n rounded up to whole 256-row tiles
+int32_t launch_f16w_stats(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, int distance, float *d_col, uint32_t *d_stats);
+int32_t launch_f16w_pack(hipStream_t st, const ScanArgs &a, int distance, float rowmax, bool seg_subnormal, const uint64_t *d_gthr, void *d_bq, float *d_t_exact,
+                         float *d_band, float *d_cut, float *d_qq, uint32_t *d_cand_cnt, uint32_t n_cnt);
+int32_t launch_scan_f16w(hipStream_t st, const ScanArgs &a, int distance, const void *d_bq, const float *d_cut, const float *d_qq, const float *d_col, int num_cus,
+                         void *d_wlists, uint32_t *grid_out);
+int32_t launch_pairs_f16_avx(hipStream_t st, int distance, const ScanArgs &a, const PairSel &sel, uint64_t n_items, int num_cus);
+int32_t launch_scan_f16_avx_groups(hipStream_t st, int distance, const ScanArgs &a, int num_cus, uint32_t *grid_out);
 // the centred int8 copy of an f32 Euclid block (QMX_SEG_L2_I8_COPY), its pack, its 128-query pass and the conditional exact Euclid pass (scan_l2i8.hip; the
 // band: l2i8_band.hpp).  The copy's layout and size are the int8 copy's (split_i8_copy_bytes, split_i8_query_bytes); the scales come from split_i8_choose_scales
 bool l2i8_dim_ok(uint32_t dim);              // a multiple of 128 up to 2 048 (up to 1 024: the resident scan, above: the staged one)
