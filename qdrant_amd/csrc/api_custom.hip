@@ -134,16 +134,47 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
         QMX_REQUIRE(point_offsets[p] <= point_offsets[p + 1], QMX_ERR_BAD_ARG, "point_offsets is not ascending at %u", p);
     QMX_REQUIRE(point_offsets[n_points] <= n_rows, QMX_ERR_OUT_OF_BOUNDS, "point_offsets reach past the %llu inner rows of the segment",
                 (unsigned long long)n_rows);
-    QMX_REQUIRE((uint64_t)inner->nq * n_rows * 4 <= (48ull << 30), QMX_ERR_NOT_SUPPORTED, "similarity matrix of %llu x %u floats is too large",
-                (unsigned long long)n_rows, inner->nq);
+    // dense f32 Dot / Cosine rows of 32, 64, .. 256 coordinates: maxsim_fused.hip streams the candidates' rows once and keeps no similarity
+    const bool fused = s->dtype == QMX_DTYPE_F32 && !s->f16_avx_order && (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) &&
+                       maxsim_fused_dim_ok(s->dim) && s->scan_dim == s->dim && s->row_stride % 16 == 0 && ((uintptr_t)s->d_rows % 16) == 0 &&
+                       n < 0xFFFFFFFFull && !option(OPT_NO_MAXSIM_FUSED);
+    if (fused)
+        QMX_REQUIRE((uint64_t)inner->nq * n * 4 <= (48ull << 30), QMX_ERR_NOT_SUPPORTED, "per-token maxima of %llu candidates x %u floats are too large",
+                    (unsigned long long)n, inner->nq);
+    else
+        QMX_REQUIRE((uint64_t)inner->nq * n_rows * 4 <= (48ull << 30), QMX_ERR_NOT_SUPPORTED, "similarity matrix of %llu x %u floats is too large",
+                    (unsigned long long)n_rows, inner->nq);
     QMX_TRY(inner->mv_qfirst.reserve((size_t)(n_queries + 1) * 4));
     QMX_TRY(inner->mv_offsets.reserve((size_t)(n_points + 1) * 8));
     QMX_HIP(hipMemcpyAsync(inner->mv_qfirst.p, query_first, (size_t)(n_queries + 1) * 4, hipMemcpyHostToDevice, inner->stream));
     QMX_HIP(hipMemcpyAsync(inner->mv_offsets.p, point_offsets, (size_t)(n_points + 1) * 8, hipMemcpyHostToDevice, inner->stream));
-    QMX_TRY(inner->cq_sims.reserve((size_t)inner->nq * n_rows * 4));
     QMX_TRY(inner->cq_scores.reserve((size_t)n_queries * n * 4));
+    if (fused) {
+        const uint64_t *d_S = (const uint64_t *)inner->mv_offsets.p, *d_delta = nullptr;
+        uint64_t s0 = point_offsets[0], total = point_offsets[n_points] - point_offsets[0];
+        if (d_ids) {      // the candidates' rows as one stream: its prefix sums come from the device (the list may live there), its length comes back
+            QMX_TRY(inner->mv_stream.reserve((size_t)(n + 1) * 8));
+            QMX_TRY(inner->mv_delta.reserve((size_t)n * 8));
+            QMX_TRY(launch_maxsim_prefix(inner->stream, d_ids, n, d_S, n_points, (uint64_t *)inner->mv_stream.p, (uint64_t *)inner->mv_delta.p, inner->d_err));
+            d_S = (const uint64_t *)inner->mv_stream.p;
+            d_delta = (const uint64_t *)inner->mv_delta.p;
+            s0 = 0;
+            QMX_HIP(hipMemcpyAsync(&total, d_S + n, 8, hipMemcpyDeviceToHost, inner->stream));
+            QMX_HIP(hipStreamSynchronize(inner->stream));
+        }
+        QMX_TRY(inner->mv_cmap.reserve((size_t)total * 4));
+        QMX_TRY(inner->mv_pack.reserve((size_t)maxsim_fused_pack_floats(s->dim, inner->nq) * 4));
+        QMX_TRY(inner->mv_tokmax.reserve((size_t)inner->nq * n * 4));
+        QMX_TRY(launch_maxsim_fused(inner->stream, s->d_rows, s->row_stride, s->dim, inner->d_queries, inner->q_stride, inner->nq, d_S, d_delta, n, s0, total,
+                                    (uint32_t *)inner->mv_cmap.p, (float *)inner->mv_pack.p, (float *)inner->mv_tokmax.p, (const uint32_t *)inner->mv_qfirst.p,
+                                    n_queries, (float *)inner->cq_scores.p, s->num_cus));
+        inner->last_kernel = last_noted_kernel();
+        return QMX_OK;
+    }
+    QMX_TRY(inner->cq_sims.reserve((size_t)inner->nq * n_rows * 4));
     // similarity(inner query, inner row) for every pair, with the dense scan's lane policies (score mode: deleted flags are not consulted)
     QMX_TRY(score_ids_device(inner, nullptr, n_rows, (float *)inner->cq_sims.p, nullptr));
+    inner->last_kernel = last_noted_kernel();      // (the scan behind the matrix: a batch that took the fused route before no longer reports it)
     return launch_maxsim(inner->stream, (const float *)inner->cq_sims.p, n_rows, (const uint32_t *)inner->mv_qfirst.p, n_queries,
                          (const uint64_t *)inner->mv_offsets.p, n_points, d_ids, n, (float *)inner->cq_scores.p, inner->d_err);
 }
@@ -195,7 +226,9 @@ int32_t qmx_multi_search_topk(qmx_query *inner, const uint32_t *query_first, uin
             del.point_deleted = (const uint64_t *)d_bits;
             del.n_point_bits = n_deleted_bits;
         }
+        const void *maxsim_kernel_used = inner->last_kernel;      // (the selection kernel is not what the search reports)
         QMX_TRY(launch_custom_topk(inner->stream, (const float *)inner->cq_scores.p, n, (const uint32_t *)d_ids, del, n_queries, top, d_out, d_oc));
+        inner->last_kernel = maxsim_kernel_used;
     }
     if (!out_dev) QMX_TRY(copy_out(inner->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
     if (!cnt_dev) QMX_TRY(copy_out(inner->stream, out_counts, d_oc, (size_t)n_queries * 4));
@@ -262,7 +295,9 @@ int32_t qmx_multi_custom_search_topk(qmx_query *inner, const uint32_t *example_f
             del.point_deleted = (const uint64_t *)d_bits;
             del.n_point_bits = n_deleted_bits;
         }
+        const void *maxsim_kernel_used = inner->last_kernel;
         QMX_TRY(launch_custom_topk(inner->stream, (const float *)inner->cq_multi.p, n, (const uint32_t *)d_ids, del, n_queries, top, d_out, d_oc));
+        inner->last_kernel = maxsim_kernel_used;
     }
     if (!out_dev) QMX_TRY(copy_out(inner->stream, out, d_out, (size_t)n_queries * top * sizeof(qmx_scored_point)));
     if (!cnt_dev) QMX_TRY(copy_out(inner->stream, out_counts, d_oc, (size_t)n_queries * 4));

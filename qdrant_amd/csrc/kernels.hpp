@@ -528,6 +528,16 @@ int32_t launch_custom_combine(hipStream_t st, const qmx_custom_query *d_queries,
                               const float *d_coefs, float *d_out);
 int32_t launch_maxsim(hipStream_t st, const float *d_sims, uint64_t n_rows, const uint32_t *d_qfirst, uint32_t n_queries, const uint64_t *d_offsets,
                       uint32_t n_points, const uint32_t *d_ids, uint64_t n, float *d_out, int *err_flag);
+// MaxSim without the similarity matrix (maxsim_fused.hip): dense f32 rows, Dot / Cosine, dim a multiple of 32 in 32 .. 256.  With a candidate list
+// launch_maxsim_prefix writes d_S [n + 1] (the prefix sums of the candidates' lengths, S[0] = 0) and d_delta [n]; without one d_S is the point offsets and
+// d_delta is null.  s0 = S[0], total = S[n] - S[0] (the host's copy).  Scratch: d_cmap [total] u32, d_pack [maxsim_fused_pack_floats] f32, d_tokmax [n_tokens][n] f32.
+bool maxsim_fused_dim_ok(uint32_t dim);
+uint64_t maxsim_fused_pack_floats(uint32_t dim, uint32_t n_tokens);
+int32_t launch_maxsim_prefix(hipStream_t st, const uint32_t *d_ids, uint64_t n, const uint64_t *d_offsets, uint32_t n_points, uint64_t *d_S, uint64_t *d_delta,
+                             int *err_flag);
+int32_t launch_maxsim_fused(hipStream_t st, const void *d_rows, uint64_t row_stride, uint32_t dim, const void *d_tokens, uint32_t q_stride, uint32_t n_tokens,
+                            const uint64_t *d_S, const uint64_t *d_delta, uint64_t n, uint64_t s0, uint64_t total, uint32_t *d_cmap, float *d_pack,
+                            float *d_tokmax, const uint32_t *d_qfirst, uint32_t n_queries, float *d_out, int num_cus);
 int32_t launch_custom_topk(hipStream_t st, const float *d_scores, uint64_t n, const uint32_t *d_ids, const DeletedView &del, uint32_t n_queries,
                            uint32_t top, qmx_scored_point *d_out, uint32_t *d_counts, uint64_t *d_bound = nullptr,    // d_bound[q] = the k-th best key of a full list, else 0
                            bool beside_scan = false);   // a prefilter's sample bound: the 256-thread kernel where it applies (option prescan_beside_scan)

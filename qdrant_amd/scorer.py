@@ -551,7 +551,8 @@ class MultiDenseVectorStorage:
         qs = [np.atleast_2d(np.asarray(q, dtype=np.float32)) for q in multi_queries]
         first = np.zeros(len(qs) + 1, dtype=np.uint32)
         first[1:] = np.cumsum([len(q) for q in qs])
-        return new_raw_scorer(np.concatenate(qs, axis=0), self.inner), first
+        self.last_scorer = new_raw_scorer(np.concatenate(qs, axis=0), self.inner)      # (`_ffi.last_kernel(st.last_scorer._h)`: the kernel the call ran)
+        return self.last_scorer, first
 
     def score_points(self, multi_queries, ids) -> np.ndarray:
         """`MultiMetricQueryScorer::score_stored_batch` for every multi-query: [n_queries, len(ids)] f32."""
