@@ -138,7 +138,13 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
     const bool fused = s->dtype == QMX_DTYPE_F32 && !s->f16_avx_order && (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) &&
                        maxsim_fused_dim_ok(s->dim) && s->scan_dim == s->dim && s->row_stride % 16 == 0 && ((uintptr_t)s->d_rows % 16) == 0 &&
                        n < 0xFFFFFFFFull && !option(OPT_NO_MAXSIM_FUSED);
-    if (fused)
+    // dense f16 Dot / Cosine rows of the same lengths in a segment created with QMX_SEG_F16_WIDE (every element finite: f16_maxsim_ok): maxsim_f16.hip,
+    // the same stream on the f16 matrix cores + an exact re-score - the reference's bits, which the two-step f16 route does not give
+    const bool fused16 = s->dtype == QMX_DTYPE_F16 && s->f16_maxsim_ok && !s->f16_avx_order &&
+                         (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) && maxsim_f16_dim_ok(s->dim) && s->row_stride % 16 == 0 &&
+                         ((uintptr_t)s->d_rows % 16) == 0 && inner->q_stride % 16 == 0 && n < 0xFFFFFFFFull && n_rows < 0xFFFFFFFFull &&
+                         !option(OPT_NO_MAXSIM_FUSED);
+    if (fused || fused16)      // (f16: two such arrays, the maxima and the rows that gave them)
         QMX_REQUIRE((uint64_t)inner->nq * n * 4 <= (48ull << 30), QMX_ERR_NOT_SUPPORTED, "per-token maxima of %llu candidates x %u floats are too large",
                     (unsigned long long)n, inner->nq);
     else
@@ -149,7 +155,7 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
     QMX_HIP(hipMemcpyAsync(inner->mv_qfirst.p, query_first, (size_t)(n_queries + 1) * 4, hipMemcpyHostToDevice, inner->stream));
     QMX_HIP(hipMemcpyAsync(inner->mv_offsets.p, point_offsets, (size_t)(n_points + 1) * 8, hipMemcpyHostToDevice, inner->stream));
     QMX_TRY(inner->cq_scores.reserve((size_t)n_queries * n * 4));
-    if (fused) {
+    if (fused || fused16) {
         const uint64_t *d_S = (const uint64_t *)inner->mv_offsets.p, *d_delta = nullptr;
         uint64_t s0 = point_offsets[0], total = point_offsets[n_points] - point_offsets[0];
         if (d_ids) {      // the candidates' rows as one stream: its prefix sums come from the device (the list may live there), its length comes back
@@ -163,8 +169,19 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
             QMX_HIP(hipStreamSynchronize(inner->stream));
         }
         QMX_TRY(inner->mv_cmap.reserve((size_t)total * 4));
-        QMX_TRY(inner->mv_pack.reserve((size_t)maxsim_fused_pack_floats(s->dim, inner->nq) * 4));
         QMX_TRY(inner->mv_tokmax.reserve((size_t)inner->nq * n * 4));
+        if (fused16) {
+            QMX_REQUIRE(total < 0xFFFFFFFFull, QMX_ERR_NOT_SUPPORTED, "the candidates' %llu rows are more than the fused f16 MaxSim names (2^32 - 2)",
+                        (unsigned long long)total);
+            QMX_TRY(inner->mv_pack16.reserve((size_t)maxsim_f16_pack_bytes(s->dim, inner->nq)));
+            QMX_TRY(inner->mv_ridx.reserve((size_t)inner->nq * n * 4));
+            QMX_TRY(launch_maxsim_f16(inner->stream, s->d_rows, s->row_stride, s->dim, s->f16w_rowmax, s->f16w_subnormal, inner->d_queries, inner->q_stride,
+                                      inner->nq, d_S, d_delta, n, s0, total, (uint32_t *)inner->mv_cmap.p, inner->mv_pack16.p, (float *)inner->mv_tokmax.p,
+                                      (uint32_t *)inner->mv_ridx.p, (const uint32_t *)inner->mv_qfirst.p, n_queries, (float *)inner->cq_scores.p, s->num_cus));
+            inner->last_kernel = last_noted_kernel();
+            return QMX_OK;
+        }
+        QMX_TRY(inner->mv_pack.reserve((size_t)maxsim_fused_pack_floats(s->dim, inner->nq) * 4));
         QMX_TRY(launch_maxsim_fused(inner->stream, s->d_rows, s->row_stride, s->dim, inner->d_queries, inner->q_stride, inner->nq, d_S, d_delta, n, s0, total,
                                     (uint32_t *)inner->mv_cmap.p, (float *)inner->mv_pack.p, (float *)inner->mv_tokmax.p, (const uint32_t *)inner->mv_qfirst.p,
                                     n_queries, (float *)inner->cq_scores.p, s->num_cus));

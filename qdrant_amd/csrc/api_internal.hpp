@@ -116,6 +116,7 @@ struct qmx_segment {
     float f16w_rowmax = 0.0f;         // not below the largest row norm
     bool f16w_subnormal = false;      // some element of the block is an f16 subnormal (f16w_band.hpp (5))
     uint64_t f16w_bytes = 0;          // bytes of the column
+    bool f16_maxsim_ok = false;       // the flag on Dot / Cosine rows of 32 .. 256 halves, a block of any size, every element finite: rowmax and subnormal above are set, the fused MaxSim (maxsim_f16.hip) may take the block
     SparseSeg *sparse = nullptr;      // QMX_DTYPE_SPARSE only
     bool f16_avx_order = false;       // the f16 block of a qmx_search_matrix call: rows in the layout of RowF16Avx, scanned by launch_scan_f16_avx alone
 
@@ -185,6 +186,7 @@ struct qmx_query {
     DevBuf partial, out, counts, ids, scores, misc, enc, bounds, gthr;
     DevBuf mv_qfirst, mv_offsets, mv_deleted;        // multi-vector MaxSim: query ranges, point offsets, point-level deleted bits
     DevBuf mv_stream, mv_delta, mv_cmap, mv_pack, mv_tokmax;   // ... the fused route (maxsim_fused.hip): prefix sums and row deltas of a candidate list, candidate of every stream row, packed tokens, per-(token, candidate) maxima
+    DevBuf mv_pack16, mv_ridx;         // ... its f16 sibling (maxsim_f16.hip): the tokens as f16 operands with their bands, per (token, candidate) the best row or the flag
     DevBuf cq_multi;          // custom queries over multi-vector points: the combined scores (cq_scores holds the per-example MaxSim rows)
     DevBuf cq_sims, cq_scores, cq_desc, cq_coefs;   // custom queries: example similarities, combined scores, descriptors, feedback coefficients
     uint32_t n_cq_coefs = 0;

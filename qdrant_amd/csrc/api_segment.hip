@@ -360,9 +360,14 @@ static int32_t segment_u8_wide(qmx_segment *s) {
 
 // ---- dense f16 blocks, QMX_SEG_F16_WIDE (scan_f16w.hip): one pass over the block on the device - the largest row norm, whether any element is subnormal,
 // whether all are finite, Euclid: the column |x|^2.  Where the flag cannot take effect - the gate, an Inf / NaN, memory - the segment is created without it
-// and every search keeps today's route ----
+// and every search keeps today's route.  The same statistics admit the fused f16 MaxSim (maxsim_f16.hip: Dot / Cosine rows of 32 .. 256 halves, a block of
+// any size) when the block is a multi-vector storage's inner rows: f16_maxsim_ok, which changes nothing the searches or qmx_segment_get_info see ----
 static int32_t segment_f16_wide(qmx_segment *s) {
-    if (!(s->flags & QMX_SEG_F16_WIDE) || s->dtype != QMX_DTYPE_F16 || !f16w_segment_ok(s->distance, s->dim, s->row_stride, s->n) || !s->fast_layout()) return QMX_OK;
+    if (!(s->flags & QMX_SEG_F16_WIDE) || s->dtype != QMX_DTYPE_F16 || !s->fast_layout()) return QMX_OK;
+    const bool wide = f16w_segment_ok(s->distance, s->dim, s->row_stride, s->n);
+    const bool maxsim = (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) && maxsim_f16_dim_ok(s->dim) && s->scan_dim == s->dim &&
+                        f16w_stats_ok(s->distance, s->dim, s->row_stride, s->n);
+    if (!wide && !maxsim) return QMX_OK;
     const bool euclid = s->distance == QMX_DISTANCE_EUCLID;
     const size_t col_bytes = euclid ? (size_t)f16w_col_entries(s->n) * 4 : 0;
     uint32_t *d_stats = nullptr, stats[3] = {0, 1, 0};
@@ -380,7 +385,8 @@ static int32_t segment_f16_wide(qmx_segment *s) {
         (void)hipGetLastError();
         return QMX_OK;
     }
-    s->f16_wide = true;
+    s->f16_wide = wide;
+    s->f16_maxsim_ok = maxsim;
     s->f16w_rowmax = f16w_up(sqrt((double)max_sq));
     s->f16w_subnormal = stats[2] != 0;
     s->f16w_bytes = col_bytes;

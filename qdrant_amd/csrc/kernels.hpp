@@ -421,6 +421,7 @@ int32_t launch_scan_u8_exact_groups(hipStream_t st, int distance, const ScanArgs
 // dense f16 blocks, QMX_SEG_F16_WIDE (scan_f16w.hip; the band: f16w_band.hpp): the per-segment statistics (Euclid: with the column |x|^2), the pack, the
 // 128-query pass over the f16 rows themselves, and - the reference's AVX-order bits over the stored layout - the pair kernel and the conditional exact pass
 bool f16w_segment_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n);     // Dot / Cosine / Euclid, dim a multiple of 32 in 64 .. 1 024, 2^18 rows and more
+bool f16w_stats_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n);       // what launch_f16w_stats itself takes: the same without the row count's floor, dim from 32
 size_t f16w_query_bytes(uint32_t dim);
 size_t f16w_wlists_counts_bytes(int num_cus);
 size_t f16w_wlists_bytes(int num_cus);       // d_wlists of launch_scan_f16w: [counts][lists], 8 lists per block
@@ -538,6 +539,18 @@ int32_t launch_maxsim_prefix(hipStream_t st, const uint32_t *d_ids, uint64_t n, 
 int32_t launch_maxsim_fused(hipStream_t st, const void *d_rows, uint64_t row_stride, uint32_t dim, const void *d_tokens, uint32_t q_stride, uint32_t n_tokens,
                             const uint64_t *d_S, const uint64_t *d_delta, uint64_t n, uint64_t s0, uint64_t total, uint32_t *d_cmap, float *d_pack,
                             float *d_tokmax, const uint32_t *d_qfirst, uint32_t n_queries, float *d_out, int num_cus);
+int32_t launch_maxsim_map(hipStream_t st, const uint64_t *d_S, uint64_t n, uint64_t s0, uint32_t *d_cmap);      // cmap[stream row - s0] = its candidate
+int32_t launch_maxsim_sum(hipStream_t st, const float *d_tokmax, const uint64_t *d_S, uint64_t n, const uint32_t *d_qfirst, uint32_t n_queries, float *d_out);
+// The same over dense f16 rows with the reference's bits (maxsim_f16.hip): an approximate pass on the f16 matrix cores that keeps the best row, the best and
+// the second best similarity per (token, candidate), then an exact re-score of that row - or, where the two are within the band of f16w_band.hpp, of the
+// whole point.  rowmax / seg_subnormal: the segment's statistics (launch_f16w_stats), every element finite; total < 2^32 - 1.  Scratch as above, d_pack
+// maxsim_f16_pack_bytes, and d_ridx [n_tokens][n] u32 beside d_tokmax.
+bool maxsim_f16_dim_ok(uint32_t dim);
+uint64_t maxsim_f16_pack_bytes(uint32_t dim, uint32_t n_tokens);
+int32_t launch_maxsim_f16(hipStream_t st, const void *d_rows, uint64_t row_stride, uint32_t dim, float rowmax, bool seg_subnormal, const void *d_tokens,
+                          uint32_t q_stride, uint32_t n_tokens, const uint64_t *d_S, const uint64_t *d_delta, uint64_t n, uint64_t s0, uint64_t total,
+                          uint32_t *d_cmap, void *d_pack, float *d_tokmax, uint32_t *d_ridx, const uint32_t *d_qfirst, uint32_t n_queries, float *d_out,
+                          int num_cus);
 int32_t launch_custom_topk(hipStream_t st, const float *d_scores, uint64_t n, const uint32_t *d_ids, const DeletedView &del, uint32_t n_queries,
                            uint32_t top, qmx_scored_point *d_out, uint32_t *d_counts, uint64_t *d_bound = nullptr,    // d_bound[q] = the k-th best key of a full list, else 0
                            bool beside_scan = false);   // a prefilter's sample bound: the 256-thread kernel where it applies (option prescan_beside_scan)

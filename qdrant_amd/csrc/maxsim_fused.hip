@@ -29,30 +29,11 @@
 // quarter into running maxima that restart at every point start; then per (point end in the tile, token) the maxima of the quarters the
 // point spans and the carry of a point that began in an earlier tile are merged, and written to tokmax[token][candidate] - or carried on
 // when the point continues.  maxsim_sum_kernel does the serial sums (a point without rows: -inf per token).
-#include "kernels.hpp"
+#include "maxsim_common.hpp"      // (the LDS-DMA copy, the LDS-only barrier, MSF_NONE, MSF_SIM_P: shared with maxsim_f16.hip)
 
 namespace qmx {
 
 typedef float msf_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) unsigned char msf_lds_byte;
-
-// 64 16-byte pieces (per-lane source) -> LDS at the wave-uniform byte address lds_dst + 16 lane.  Invisible to the compiler's s_waitcnt
-// bookkeeping on purpose: the tile loop counts these loads itself (the compiler's own loads only make its counts stricter).
-__device__ __forceinline__ void msf_glds16(const unsigned char *src, uint32_t lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-}
-
-// the block's barrier for LDS traffic alone: no vmcnt(0), which would drain the row stream
-__device__ __forceinline__ void msf_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-constexpr uint32_t MSF_NONE = 0xFFFFFFFFu;      // cmap / tile meta: no candidate (rows past the block's stream)
-constexpr int MSF_SIM_P = 68;                   // pitch of the scratch tile in floats: rows 4 k + j of a D register land 16 banks apart
 
 template <int D32>
 struct MsfShape {
@@ -343,6 +324,18 @@ int32_t launch_maxsim_prefix(hipStream_t st, const uint32_t *d_ids, uint64_t n, 
     return QMX_OK;
 }
 
+int32_t launch_maxsim_map(hipStream_t st, const uint64_t *d_S, uint64_t n, uint64_t s0, uint32_t *d_cmap) {
+    hipLaunchKernelGGL(maxsim_map_kernel, dim3((uint32_t)std::min<uint64_t>((n + 3) / 4, 8192)), dim3(256), 0, st, d_S, n, s0, d_cmap);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+
+int32_t launch_maxsim_sum(hipStream_t st, const float *d_tokmax, const uint64_t *d_S, uint64_t n, const uint32_t *d_qfirst, uint32_t n_queries, float *d_out) {
+    hipLaunchKernelGGL(maxsim_sum_kernel, dim3((uint32_t)((n + 255) / 256), n_queries), dim3(256), 0, st, d_tokmax, d_S, n, d_qfirst, n_queries, d_out);
+    QMX_HIP(hipGetLastError());
+    return QMX_OK;
+}
+
 template <int D32>
 static int32_t launch_msf(hipStream_t st, const MsfArgs &a, int num_cus) {
     typedef MsfShape<D32> S;
@@ -375,8 +368,7 @@ int32_t launch_maxsim_fused(hipStream_t st, const void *d_rows, uint64_t row_str
         hipLaunchKernelGGL(maxsim_pack_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, st, (const unsigned char *)d_tokens, q_stride, n_tokens, d32,
                            ks, count, d_pack);
         QMX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(maxsim_map_kernel, dim3((uint32_t)std::min<uint64_t>((n + 3) / 4, 8192)), dim3(256), 0, st, d_S, n, s0, d_cmap);
-        QMX_HIP(hipGetLastError());
+        QMX_TRY(launch_maxsim_map(st, d_S, n, s0, d_cmap));
         MsfArgs a;
         a.rows = (const unsigned char *)d_rows; a.row_stride = row_stride; a.S = d_S; a.cmap = d_cmap; a.delta = d_delta; a.bpack = d_pack;
         a.tokmax = d_tokmax; a.n = n; a.s0 = s0; a.total = total; a.n_tokens = n_tokens;
@@ -394,9 +386,7 @@ int32_t launch_maxsim_fused(hipStream_t st, const void *d_rows, uint64_t row_str
     } else {
         QMX_NOTE_KERNEL(maxsim_fused_kernel<4>);      // (no rows or no tokens: the sums alone)
     }
-    hipLaunchKernelGGL(maxsim_sum_kernel, dim3((uint32_t)((n + 255) / 256), n_queries), dim3(256), 0, st, d_tokmax, d_S, n, d_qfirst, n_queries, d_out);
-    QMX_HIP(hipGetLastError());
-    return QMX_OK;
+    return launch_maxsim_sum(st, d_tokmax, d_S, n, d_qfirst, n_queries, d_out);
 }
 
 }  // namespace qmx

@@ -13,6 +13,7 @@
 // The tail is the wide routes': a strided sample's k-th best score T_q admits the candidates (A >= T_q - band), per-wave lists are regrouped per query,
 // the selection keeps A >= max(T_q - band, A_k - 2 band), the pair kernel re-scores that and a query whose lists overflowed takes the exact pass.
 #include "dense_policies.hpp"
+#include "f16_avx_leaf.hpp"
 #include "f16w_band.hpp"
 #include "split_common.hpp"
 
@@ -47,8 +48,6 @@ struct F16WideArgs {
     uint32_t *wcnt;           // [waves] entries each wave wanted to append (may run past wcap: overflow)
     uint32_t wcap;
 };
-
-__device__ __forceinline__ float fw_h2f(uint32_t bits16) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16); }
 
 // ---- once per segment, one pass over the block: stats[0] = the largest |x|^2 as f32 bits, moved up (non-negative floats order as their bits),
 // stats[1] != 0: an Inf / NaN element, stats[2] != 0: a subnormal element; Euclid: col[row] = fl32(|x|^2 summed in f64), padded with zeros to whole
@@ -571,16 +570,7 @@ __global__ __launch_bounds__(FW_THREADS, 1) void scan_f16w_staged_kernel(const S
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // nothing may land in LDS after the block is gone
 }
 
-// ---- the reference's bits.  half_avx (metric_f16/avx/{dot,euclid}.rs) keeps 32 running f32 sums: element i feeds sum i % 32 - register (i % 32) / 8,
-// SIMD lane i % 8 - by one fma per 32-element iteration (Euclid: d = a - b rounded, then fma(d, d, s)); hsum256_ps_avx of each register is
-// ((s[0] + s[4]) + (s[1] + s[5])) + ((s[2] + s[6]) + (s[3] + s[7])), the four results are added left to right.  dim is a multiple of 32 here: no tail. ----
-template <int METRIC>
-__device__ __forceinline__ float fw_term(float acc, float qv, float xv) {
-    if constexpr (METRIC == M_EUCLID) {
-        const float d = qv - xv;
-        return __builtin_fmaf(d, d, acc);
-    } else return __builtin_fmaf(qv, xv, acc);
-}
+// ---- the reference's bits: half_avx's 32 running f32 sums and their fold (f16_avx_leaf.hpp: fw_term, f16_avx_pair).  dim is a multiple of 32 here: no tail. ----
 __device__ __forceinline__ float fw_hsum8(const float (&s)[8]) { return ((s[4] + s[0]) + (s[5] + s[1])) + ((s[6] + s[2]) + (s[7] + s[3])); }
 
 // the pair kernel over the stored row-major layout: 32 lanes per pair, lane l owns sum l and takes elements l, l + 32, ... in order
@@ -603,15 +593,7 @@ __global__ __launch_bounds__(256) void f16w_pairs_kernel(const ScanArgs a, const
         }
         const unsigned short *x = reinterpret_cast<const unsigned short *>(rows + (uint64_t)id * a.row_stride) + l;
         const unsigned short *y = reinterpret_cast<const unsigned short *>(queries + (uint64_t)qi * a.q_stride) + l;
-        float sum = 0.0f;
-#pragma unroll 8
-        for (uint32_t i = 0; i < a.dim; i += 32) sum = fw_term<METRIC>(sum, fw_h2f(y[i]), fw_h2f(x[i]));
-        // hsum256_ps_avx inside each group of eight lanes (lane j < 4: s[j + 4] + s[j]; lane 0: (lr0 + lr1) + (lr2 + lr3)), then the four registers
-        sum = __shfl_xor(sum, 4, 64) + sum;
-        sum = sum + __shfl_xor(sum, 1, 64);
-        sum = sum + __shfl_xor(sum, 2, 64);
-        const uint32_t g0 = lane & 32u;
-        const float result = ((__shfl(sum, g0, 64) + __shfl(sum, g0 + 8, 64)) + __shfl(sum, g0 + 16, 64)) + __shfl(sum, g0 + 24, 64);
+        const float result = f16_avx_pair<METRIC>(x, y, a.dim, lane);
         if (valid && l == 0) a.scores[item] = METRIC == M_EUCLID ? -result : result;
     }
 }
@@ -719,6 +701,11 @@ bool f16w_segment_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n
     return f16w_metric(distance) >= 0 && dim % 32 == 0 && dim >= 64 && dim <= F16W_MAX_DIM && row_stride % 16 == 0 && row_stride >= (uint64_t)dim * 2 && n >= (1u << 18) &&
            n < 0xFFFFFFFFull && row_stride * (FW_BM - 1) + (uint64_t)dim * 2 < (1ull << 31);
 }
+// the statistics pass alone (the fused f16 MaxSim wants them of small blocks and of rows of 32 halves too: maxsim_f16.hip)
+bool f16w_stats_ok(int distance, uint32_t dim, uint64_t row_stride, uint64_t n) {
+    return f16w_metric(distance) >= 0 && dim % 32 == 0 && dim >= 32 && dim <= F16W_MAX_DIM && row_stride % 16 == 0 && row_stride >= (uint64_t)dim * 2 && n >= 1 &&
+           n < 0xFFFFFFFFull;
+}
 // the queries' image: [dim / 32] chunks of 8 KiB for the resident scan, [stages of 128 bytes] of 16 KiB for the staged one (f16w_pack_kernel)
 size_t f16w_query_bytes(uint32_t dim) {
     const uint32_t nch = dim / 32;
@@ -731,7 +718,7 @@ uint64_t f16w_col_entries(uint64_t n) { return (n + FW_BM - 1) / FW_BM * FW_BM; 
 
 // d_col: f16w_col_entries(n) floats (Euclid) or nullptr; d_stats: three zeroed dwords
 int32_t launch_f16w_stats(hipStream_t st, const void *rows, uint64_t row_stride, uint64_t n, uint32_t dim, int distance, float *d_col, uint32_t *d_stats) {
-    QMX_REQUIRE(f16w_segment_ok(distance, dim, row_stride, n) && d_stats && (f16w_metric(distance) != F16W_EUCLID || d_col), QMX_ERR_BAD_ARG, "f16 wide statistics of dim %u", dim);
+    QMX_REQUIRE(f16w_stats_ok(distance, dim, row_stride, n) && d_stats && (f16w_metric(distance) != F16W_EUCLID || d_col), QMX_ERR_BAD_ARG, "f16 wide statistics of dim %u", dim);
     ::qmx::clear_stale_error();
     const uint64_t n_pad = f16w_col_entries(n);
     hipLaunchKernelGGL(f16w_stats_kernel, dim3((uint32_t)std::min<uint64_t>(8192, n_pad / 16)), dim3(256), 0, st, (const unsigned char *)rows, row_stride, n, n_pad, dim,

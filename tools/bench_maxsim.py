@@ -6,7 +6,13 @@ Data: `--rows` x `--dim` standard normal f32 rows (seeded), cut into points of 5
 `--queries`.  Two shapes per batch: "rerank" - qmx_multi_search_topk over `--candidates` random points - and "block" - the same call without a
 candidate list.  The call is synchronous (it ends with a stream synchronise), so the wall time of a call is device-synchronised; per leg the median,
 min and max over `--steps` timed calls after `--warmup` of both legs.  "lists_equal": ids and score bits of the two legs' lists.  One JSON line on
-stdout; `--out` also writes it to a file."""
+stdout; `--out` also writes it to a file.
+
+`--dtype f16`: the same rows as f16 in a segment created with SEG_F16_WIDE, three legs alternating call by call: "fused" = maxsim_f16.hip, "two_step" =
+the f16 scans + maxsim_kernel (no_maxsim_fused = 1), "f32_fused" = maxsim_fused.hip over the f32 rows.  Per cell also "oracle_equal" - the f16 fused
+leg's scores against the CPU oracle's MaxSim of the listed points, bit for bit, and that no unlisted candidate scores higher (rerank cells; block cells
+at one query) - and "flagged_share": the share of (token, candidate) pairs whose best and second best similarity lie inside the token's band, counted on
+the host from f32 similarities (numpy) with f16w_band's formula - an estimate of what the kernel flags, not a counter read from it."""
 import argparse
 import json
 import os
@@ -23,8 +29,40 @@ from qdrant_amd import _ffi as F  # noqa: E402
 from qdrant_amd.scorer import ScoredPointOffset  # noqa: E402
 
 
+def flagged_share(rows, lens, tokens, seg_subnormal, rowmax):
+    """share of (token, point) pairs with second best >= best - band(token); rows / tokens: the f16 values as f32, every point non-empty"""
+    dim, u = rows.shape[1], 2.0 ** -24
+    starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    sims = rows @ tokens.T
+    m1 = np.maximum.reduceat(sims, starts, axis=0)
+    at_max = sims == np.repeat(m1, lens, axis=0)
+    ties = np.add.reduceat(at_max, starts, axis=0, dtype=np.int64)
+    sims[at_max] = -np.inf
+    m2 = np.where(ties > 1, m1, np.maximum.reduceat(sims, starts, axis=0))
+    t64 = tokens.astype(np.float64)
+    b = np.sqrt((t64 * t64).sum(axis=1)) * rowmax
+    e_ar = (1.001 * dim / 4194304.0 + 1.0 / 262144.0 + 38.0 * 1.001 * u) * b
+    e_sub = ((np.abs(t64).sum(axis=1) if seg_subnormal else 0.0) + np.sqrt(((t64 != 0) & (np.abs(t64) < 2.0 ** -14)).sum(axis=1)) * rowmax) / 16384.0
+    band = (2.0 * (e_ar + e_sub) + 4.0 * u * b).astype(np.float32)
+    return float((~(m2 < m1 - band[None, :])).mean())
+
+
+def oracle_equal(O, rows16, offsets, points, queries, lists):
+    """the lists of one leg against the oracle's MaxSim over `points` (all of them scored): score bits in order, and each listed id has its score"""
+    lens = (offsets[points.astype(np.int64) + 1] - offsets[points]).astype(np.int64)
+    take = np.concatenate([np.arange(int(offsets[p]), int(offsets[p + 1])) for p in points])
+    sub = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    first = np.concatenate([[0], np.cumsum([len(q) for q in queries])]).astype(np.uint32)
+    full = O.multi_scores(O.DenseStorage(O.F16, O.DOT, rows16[take]), np.concatenate(queries), first, sub, np.arange(len(points)))
+    where = {int(p): i for i, p in enumerate(points)}
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)       # noqa: E731
+    return all(np.array_equal(bits(res["score"]), bits(np.sort(sc)[::-1][:len(res)])) and
+               np.array_equal(bits(sc[[where[int(i)] for i in res["idx"]]]), bits(res["score"])) for res, sc in zip(lists, full))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", choices=("f32", "f16"), default="f32")
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--tokens", type=int, default=32)
@@ -41,20 +79,34 @@ def main():
     offsets = offsets[offsets <= args.rows].astype(np.uint64)
     n_points = len(offsets) - 1
     rows = rng.standard_normal((args.rows, args.dim), dtype=np.float32)
-    st = qa.MultiDenseVectorStorage(rows, offsets, qa.Distance.Dot)
+    st32 = qa.MultiDenseVectorStorage(rows, offsets, qa.Distance.Dot)
     ids = np.ascontiguousarray(rng.permutation(n_points)[:args.candidates], dtype=np.uint32)
     lib = F.lib()
-    result = {"tool": "bench_maxsim", "rows": args.rows, "dim": args.dim, "points": n_points, "tokens": args.tokens, "candidates": len(ids),
+    result = {"tool": "bench_maxsim", "dtype": args.dtype, "rows": args.rows, "dim": args.dim, "points": n_points, "tokens": args.tokens, "candidates": len(ids),
               "candidate_rows": int((offsets[ids.astype(np.int64) + 1] - offsets[ids]).sum()), "top": args.top, "cells": {}}
+    legs = [("fused", st32, 0), ("two_step", st32, 1)]
+    if args.dtype == "f16":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import oracle_ffi as O      # (the checker: not timed)
+        rows16 = O.to_f16(rows)
+        vals16 = O.f16_to_f32(rows16)
+        seg_subnormal = bool(((vals16 != 0) & (np.abs(vals16) < 2.0 ** -14)).any())
+        rowmax = float(np.sqrt((vals16.astype(np.float64) ** 2).sum(axis=1).max()))
+        inner = qa.VectorStorage(rows16.view(np.float16), qa.Distance.Dot, qa.VectorStorageDatatype.Float16, flags=F.SEG_F16_WIDE)
+        st16 = qa.MultiDenseVectorStorage(None, offsets, qa.Distance.Dot, inner_storage=inner)
+        legs = [("fused", st16, 0), ("two_step", st16, 1), ("f32_fused", st32, 0)]
+    all_points = np.arange(n_points, dtype=np.uint32)
     for nq in [int(x) for x in args.queries.split(",") if x]:
-        scorer, first = st._queries([rng.standard_normal((args.tokens, args.dim), dtype=np.float32) for _ in range(nq)])
+        queries = [rng.standard_normal((args.tokens, args.dim), dtype=np.float32) for _ in range(nq)]
+        scorers = {id(s): s._queries(queries) for s in {id(leg[1]): leg[1] for leg in legs}.values()}
         for shape, cand in (("rerank", ids), ("block", None)):
-            out = {k: np.zeros((nq, args.top), dtype=ScoredPointOffset) for k in ("fused", "two_step")}
+            out = {leg[0]: np.zeros((nq, args.top), dtype=ScoredPointOffset) for leg in legs}
             counts = np.zeros(nq, dtype=np.uint32)
             times = {k: [] for k in out}
             kernels = {}
             for step in range(args.warmup + args.steps):
-                for name, off in (("fused", 0), ("two_step", 1)):
+                for name, st, off in legs:
+                    scorer, first = scorers[id(st)]
                     qa.set_option("no_maxsim_fused", off)
                     t0 = time.perf_counter()
                     F.check(lib.qmx_multi_search_topk(scorer._h, F.ptr(first), nq, F.ptr(offsets), n_points, None, 0, args.top, F.ptr(cand),
@@ -68,6 +120,16 @@ def main():
             cell["lists_equal"] = bool(np.array_equal(out["fused"]["idx"], out["two_step"]["idx"]) and
                                        np.array_equal(out["fused"]["score"].copy().view(np.uint32), out["two_step"]["score"].copy().view(np.uint32)))
             cell["two_step_over_fused"] = round(cell["two_step"]["median_ms"] / cell["fused"]["median_ms"], 3)
+            if args.dtype == "f16":
+                points = all_points if cand is None else cand
+                lens = (offsets[points.astype(np.int64) + 1] - offsets[points]).astype(np.int64)
+                row_bytes = int(lens.sum()) * args.dim * 2 * ((nq * args.tokens + 63) // 64)      # one pass of the candidates' rows per 64-token group
+                cell["fused_row_gbytes_per_s"] = round(row_bytes / cell["fused"]["median_ms"] / 1e6, 1)
+                cell["f32_fused_over_fused"] = round(cell["f32_fused"]["median_ms"] / cell["fused"]["median_ms"], 3)
+                if cand is not None or nq == 1:
+                    cell["oracle_equal"] = bool(oracle_equal(O, rows16, offsets, points, queries, [out["fused"][j, :counts[j]] for j in range(nq)]))
+                take = np.concatenate([np.arange(int(offsets[p]), int(offsets[p + 1])) for p in points])
+                cell["flagged_share"] = round(flagged_share(vals16[take], lens, O.f16_to_f32(O.to_f16(queries[0])), seg_subnormal, rowmax), 5)
             result["cells"]["%s_q%d" % (shape, nq)] = cell
     line = json.dumps(result)
     print(line)
