@@ -345,7 +345,7 @@ QMX_API uint32_t qmx_abi_version(void);
  * which wait for a CU without a scan block.  A batch with more than 16 overflowed queries then streams the block once per 16 of them instead of once
  * per 64: 10 M x 768 Student-t rows through a forced int8 copy, where all 128 queries of every batch overflow, take 39.9 ms per batch against 22.0
  * with the former passes - a block the library's own choice of copy keeps away from the int8 copy; the headline step, where nothing overflows, is
- * 1.4 - 1.5 % faster), "group_matrix_bytes", "no_l2_prefilter" (an f32 Euclid segment with QMX_SEG_L2_I8_COPY keeps the exact Euclid scans), "no_u8_wide" (a u8 segment with QMX_SEG_U8_WIDE keeps the exact u8 scans), "u8_wide_min_queries" (8: that segment takes the 128-query pass from this many queries on), "no_f16_wide" (an f16 segment with QMX_SEG_F16_WIDE keeps the exact f16 scans), "f16_wide_min_queries" (33: that segment takes the 128-query pass from this many queries on), "no_maxsim_fused" (the brute-force qmx_multi_* calls over dense f32 Dot / Cosine rows of 32, 64, .. 256 coordinates keep the [tokens][rows] similarity matrix and maxsim_kernel instead of maxsim_fused_kernel: the same score bits), "debug"
+ * 1.4 - 1.5 % faster), "group_matrix_bytes", "no_l2_prefilter" (an f32 Euclid segment with QMX_SEG_L2_I8_COPY keeps the exact Euclid scans), "no_u8_wide" (a u8 segment with QMX_SEG_U8_WIDE keeps the exact u8 scans), "u8_wide_min_queries" (8: that segment takes the 128-query pass from this many queries on), "no_f16_wide" (an f16 segment with QMX_SEG_F16_WIDE keeps the exact f16 scans), "f16_wide_min_queries" (33: that segment takes the 128-query pass from this many queries on), "no_maxsim_fused" (the brute-force qmx_multi_* calls over dense f32 Dot / Cosine rows of 32, 64, .. 256 coordinates keep the [tokens][rows] similarity matrix and maxsim_kernel instead of maxsim_fused_kernel: the same score bits; likewise dense f16 rows of a QMX_SEG_F16_WIDE segment instead of maxsim_f16_kernel, and dense u8 Dot / Cosine / Euclid rows of those lengths instead of maxsim_u8_kernel: the same score bits), "debug"
  * - and one that selects the ORDER AMONG EQUAL SCORES of the plain HNSW walk: "hnsw_reference_heap_order" (see qmx_hnsw_search_traced) -
  * (qdrant_amd/csrc/common.hpp says what each selects; round 6 removed the experiments that had measured slower twice: their numbers stay under
  * profiles/).  Initial values come from the environment variables QMX_<NAME> read

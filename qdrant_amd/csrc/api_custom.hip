@@ -144,7 +144,13 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
                          (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE) && maxsim_f16_dim_ok(s->dim) && s->row_stride % 16 == 0 &&
                          ((uintptr_t)s->d_rows % 16) == 0 && inner->q_stride % 16 == 0 && n < 0xFFFFFFFFull && n_rows < 0xFFFFFFFFull &&
                          !option(OPT_NO_MAXSIM_FUSED);
-    if (fused || fused16)      // (f16: two such arrays, the maxima and the rows that gave them)
+    // dense u8 Dot / Cosine / Euclid rows of the same lengths, any segment: maxsim_u8.hip, the same stream on the int8 matrix cores.  A pair's integers
+    // are below 2^24 there, so the reference's bits come out of the one kernel, in either order of QMX_SEG_U8_SCALAR_ORDER
+    const bool fused8 = s->dtype == QMX_DTYPE_U8 && s->fast_layout() &&
+                        (s->distance == QMX_DISTANCE_DOT || s->distance == QMX_DISTANCE_COSINE || s->distance == QMX_DISTANCE_EUCLID) &&
+                        maxsim_u8_dim_ok(s->dim) && s->scan_dim == s->dim && s->row_stride % 16 == 0 && ((uintptr_t)s->d_rows % 16) == 0 &&
+                        inner->q_stride % 16 == 0 && n < 0xFFFFFFFFull && !option(OPT_NO_MAXSIM_FUSED);
+    if (fused || fused16 || fused8)      // (f16: two such arrays, the maxima and the rows that gave them)
         QMX_REQUIRE((uint64_t)inner->nq * n * 4 <= (48ull << 30), QMX_ERR_NOT_SUPPORTED, "per-token maxima of %llu candidates x %u floats are too large",
                     (unsigned long long)n, inner->nq);
     else
@@ -155,7 +161,7 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
     QMX_HIP(hipMemcpyAsync(inner->mv_qfirst.p, query_first, (size_t)(n_queries + 1) * 4, hipMemcpyHostToDevice, inner->stream));
     QMX_HIP(hipMemcpyAsync(inner->mv_offsets.p, point_offsets, (size_t)(n_points + 1) * 8, hipMemcpyHostToDevice, inner->stream));
     QMX_TRY(inner->cq_scores.reserve((size_t)n_queries * n * 4));
-    if (fused || fused16) {
+    if (fused || fused16 || fused8) {
         const uint64_t *d_S = (const uint64_t *)inner->mv_offsets.p, *d_delta = nullptr;
         uint64_t s0 = point_offsets[0], total = point_offsets[n_points] - point_offsets[0];
         if (d_ids) {      // the candidates' rows as one stream: its prefix sums come from the device (the list may live there), its length comes back
@@ -178,6 +184,14 @@ static int32_t multi_prepare(qmx_query *inner, const uint32_t *query_first, uint
             QMX_TRY(launch_maxsim_f16(inner->stream, s->d_rows, s->row_stride, s->dim, s->f16w_rowmax, s->f16w_subnormal, inner->d_queries, inner->q_stride,
                                       inner->nq, d_S, d_delta, n, s0, total, (uint32_t *)inner->mv_cmap.p, inner->mv_pack16.p, (float *)inner->mv_tokmax.p,
                                       (uint32_t *)inner->mv_ridx.p, (const uint32_t *)inner->mv_qfirst.p, n_queries, (float *)inner->cq_scores.p, s->num_cus));
+            inner->last_kernel = last_noted_kernel();
+            return QMX_OK;
+        }
+        if (fused8) {
+            QMX_TRY(inner->mv_pack16.reserve((size_t)maxsim_u8_pack_bytes(s->dim, inner->nq)));
+            QMX_TRY(launch_maxsim_u8(inner->stream, (int)s->distance, s->d_rows, s->row_stride, s->dim, inner->d_queries, inner->q_stride, inner->nq, d_S, d_delta,
+                                     n, s0, total, (uint32_t *)inner->mv_cmap.p, inner->mv_pack16.p, (float *)inner->mv_tokmax.p,
+                                     (const uint32_t *)inner->mv_qfirst.p, n_queries, (float *)inner->cq_scores.p, s->num_cus));
             inner->last_kernel = last_noted_kernel();
             return QMX_OK;
         }

@@ -186,7 +186,7 @@ struct qmx_query {
     DevBuf partial, out, counts, ids, scores, misc, enc, bounds, gthr;
     DevBuf mv_qfirst, mv_offsets, mv_deleted;        // multi-vector MaxSim: query ranges, point offsets, point-level deleted bits
     DevBuf mv_stream, mv_delta, mv_cmap, mv_pack, mv_tokmax;   // ... the fused route (maxsim_fused.hip): prefix sums and row deltas of a candidate list, candidate of every stream row, packed tokens, per-(token, candidate) maxima
-    DevBuf mv_pack16, mv_ridx;         // ... its f16 sibling (maxsim_f16.hip): the tokens as f16 operands with their bands, per (token, candidate) the best row or the flag
+    DevBuf mv_pack16, mv_ridx;         // ... its f16 sibling (maxsim_f16.hip): the tokens as f16 operands with their bands, per (token, candidate) the best row or the flag; the u8 sibling (maxsim_u8.hip) keeps its biased token operands and their constants in mv_pack16
     DevBuf cq_multi;          // custom queries over multi-vector points: the combined scores (cq_scores holds the per-example MaxSim rows)
     DevBuf cq_sims, cq_scores, cq_desc, cq_coefs;   // custom queries: example similarities, combined scores, descriptors, feedback coefficients
     uint32_t n_cq_coefs = 0;

@@ -82,7 +82,7 @@ enum Option {
     OPT_U8_WIDE_MIN_QUERIES,  // ... and take the 128-query pass from this many queries on (8: measured, profiles/u8_wide.md)
     OPT_NO_F16_WIDE,          // dense f16 segments with QMX_SEG_F16_WIDE keep the exact f16 scans (no scan_f16w.hip pass + verification)
     OPT_F16_WIDE_MIN_QUERIES, // ... and take the 128-query pass from this many queries on (33: measured - where the exact Dot / Cosine scans need a second pass; Euclid alone would pay from 8 on; profiles/f16_wide.md)
-    OPT_NO_MAXSIM_FUSED,      // brute-force MaxSim over dense f32 Dot / Cosine rows of 32 .. 256 coordinates keeps the similarity matrix + maxsim_kernel (no maxsim_fused.hip); the same for dense f16 rows of a QMX_SEG_F16_WIDE segment (no maxsim_f16.hip)
+    OPT_NO_MAXSIM_FUSED,      // brute-force MaxSim over dense f32 Dot / Cosine rows of 32 .. 256 coordinates keeps the similarity matrix + maxsim_kernel (no maxsim_fused.hip); the same for dense f16 rows of a QMX_SEG_F16_WIDE segment (no maxsim_f16.hip) and for dense u8 Dot / Cosine / Euclid rows (no maxsim_u8.hip)
     OPT_DEBUG,                // log dropped stale HIP errors
     OPT_COUNT
 };

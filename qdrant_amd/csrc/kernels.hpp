@@ -551,6 +551,13 @@ int32_t launch_maxsim_f16(hipStream_t st, const void *d_rows, uint64_t row_strid
                           uint32_t q_stride, uint32_t n_tokens, const uint64_t *d_S, const uint64_t *d_delta, uint64_t n, uint64_t s0, uint64_t total,
                           uint32_t *d_cmap, void *d_pack, float *d_tokmax, uint32_t *d_ridx, const uint32_t *d_qfirst, uint32_t n_queries, float *d_out,
                           int num_cus);
+// The same over dense u8 rows on the int8 matrix cores (maxsim_u8.hip): Dot / Cosine / Euclid, one kernel, the reference's bits in either order of
+// QMX_SEG_U8_SCALAR_ORDER (every integer of a pair is below 2^24 at dim <= 256).  Scratch as above, d_pack maxsim_u8_pack_bytes.
+bool maxsim_u8_dim_ok(uint32_t dim);
+uint64_t maxsim_u8_pack_bytes(uint32_t dim, uint32_t n_tokens);
+int32_t launch_maxsim_u8(hipStream_t st, int distance, const void *d_rows, uint64_t row_stride, uint32_t dim, const void *d_tokens, uint32_t q_stride,
+                         uint32_t n_tokens, const uint64_t *d_S, const uint64_t *d_delta, uint64_t n, uint64_t s0, uint64_t total, uint32_t *d_cmap,
+                         void *d_pack, float *d_tokmax, const uint32_t *d_qfirst, uint32_t n_queries, float *d_out, int num_cus);
 int32_t launch_custom_topk(hipStream_t st, const float *d_scores, uint64_t n, const uint32_t *d_ids, const DeletedView &del, uint32_t n_queries,
                            uint32_t top, qmx_scored_point *d_out, uint32_t *d_counts, uint64_t *d_bound = nullptr,    // d_bound[q] = the k-th best key of a full list, else 0
                            bool beside_scan = false);   // a prefilter's sample bound: the 256-thread kernel where it applies (option prescan_beside_scan)

@@ -72,12 +72,10 @@ struct MshShape {
     static constexpr int OFF_META = OFF_PLANES + 3 * PLANE_B;
     static constexpr int OFF_CARRY = OFF_META + META_B;
     static constexpr int LDS = OFF_CARRY + CARRY_B;
-    static constexpr uint32_t SWZ_MASK = D32 % 2 ? 3u : D32 % 4 ? 7u : 15u;
+    static constexpr uint32_t SWZ_MASK = msf_swz16_mask(PPR);
     static_assert(NBUF >= 2 && LDS <= 160 * 1024 && (NBUF - 1) * IPW < 64, "a ring of two tiles at least; the CU's LDS; the vmcnt field");
     static_assert(PPR % (SWZ_MASK + 1) == 0, "the swizzle stays inside the row");
 };
-
-__device__ __forceinline__ uint32_t msh_swz(uint32_t m) { return ((0x78u >> (2u * ((m >> 2) & 3u))) & 3u) | ((m & 2u) << 1) | ((m & 1u) << 3); }
 
 struct MshTriple {
     float m1;          // the best similarity
@@ -123,15 +121,8 @@ __global__ __launch_bounds__(256) void maxsim_f16_kernel(const MshArgs a) {
     const uint32_t ring0 = (uint32_t)(uintptr_t)(msf_lds_byte *)msh_smem + S::OFF_RING;
 
     // ---- the block's run of the stream: the candidates whose start falls in [lo, hi)
-    const uint64_t end = a.s0 + a.total;
-    const uint64_t share = (a.total + gridDim.x - 1) / gridDim.x;
-    auto first_start_from = [&](uint64_t x) -> uint64_t {       // the smallest candidate start >= x that has rows behind it (or the stream's end)
-        if (x >= end) return end;
-        const uint32_t c = a.cmap[x - a.s0];
-        return a.S[c] == x ? x : a.S[(uint64_t)c + 1];
-    };
-    const uint64_t lo = a.s0 + (uint64_t)blockIdx.x * share;
-    const uint64_t b0 = first_start_from(lo), b1 = first_start_from(lo + share);
+    const MsfRun run = msf_block_run(a.S, a.cmap, a.s0, a.total);
+    const uint64_t b0 = run.b0, b1 = run.b1;
     if (b0 >= b1) return;
     const uint64_t n_tiles = (b1 - b0 + TR - 1) / TR;
 
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(256) void maxsim_f16_kernel(const MshArgs a) {
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
             const uint32_t g = (uint32_t)(w * IPW + i) * 64u + (uint32_t)lane;
-            const uint32_t m = g / PPR, e = (g % PPR) ^ (msh_swz(m & 15u) & S::SWZ_MASK);
+            const uint32_t m = g / PPR, e = (g % PPR) ^ (msf_swz16(m & 15u) & S::SWZ_MASK);
             const uint32_t slo = (uint32_t)__shfl((int)blo, (int)m), shi = (uint32_t)__shfl((int)bhi, (int)m);
             const unsigned char *src = reinterpret_cast<const unsigned char *>(((uint64_t)shi << 32) | slo) + e * 16u;
             msf_glds16(src, ring0 + slot * (uint32_t)S::TILE_B + (uint32_t)(w * IPW + i) * 1024u);
@@ -178,7 +169,7 @@ __global__ __launch_bounds__(256) void maxsim_f16_kernel(const MshArgs a) {
     uint32_t c_cur = load_cand(NBUF);       // cmap of the tile staged during iteration 0
 
     const uint32_t mrow = (uint32_t)(w * 16 + (lane & 15)), kq = (uint32_t)lane >> 4;
-    const uint32_t a_row = mrow * (uint32_t)(PPR * 16), sw = msh_swz(mrow & 15u) & S::SWZ_MASK;
+    const uint32_t a_row = mrow * (uint32_t)(PPR * 16), sw = msf_swz16(mrow & 15u) & S::SWZ_MASK;
     const uint4 *lds_b = reinterpret_cast<const uint4 *>(msh_smem) + lane;
     uint32_t slot = 0;
     uint32_t prev_last = MSF_NONE;          // candidate of the previous tile's last row

@@ -82,15 +82,8 @@ __global__ __launch_bounds__(256) void maxsim_fused_kernel(const MsfArgs a) {
     const uint32_t ring0 = (uint32_t)(uintptr_t)(msf_lds_byte *)msf_smem + S::OFF_RING;
 
     // ---- the block's run of the stream: the candidates whose start falls in [lo, hi)
-    const uint64_t end = a.s0 + a.total;
-    const uint64_t share = (a.total + gridDim.x - 1) / gridDim.x;
-    auto first_start_from = [&](uint64_t x) -> uint64_t {       // the smallest candidate start >= x that has rows behind it (or the stream's end)
-        if (x >= end) return end;
-        const uint32_t c = a.cmap[x - a.s0];
-        return a.S[c] == x ? x : a.S[(uint64_t)c + 1];
-    };
-    const uint64_t lo = a.s0 + (uint64_t)blockIdx.x * share;
-    const uint64_t b0 = first_start_from(lo), b1 = first_start_from(lo + share);
+    const MsfRun run = msf_block_run(a.S, a.cmap, a.s0, a.total);
+    const uint64_t b0 = run.b0, b1 = run.b1;
     if (b0 >= b1) return;
     const uint64_t n_tiles = (b1 - b0 + TR - 1) / TR;
 

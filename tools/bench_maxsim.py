@@ -12,7 +12,12 @@ stdout; `--out` also writes it to a file.
 the f16 scans + maxsim_kernel (no_maxsim_fused = 1), "f32_fused" = maxsim_fused.hip over the f32 rows.  Per cell also "oracle_equal" - the f16 fused
 leg's scores against the CPU oracle's MaxSim of the listed points, bit for bit, and that no unlisted candidate scores higher (rerank cells; block cells
 at one query) - and "flagged_share": the share of (token, candidate) pairs whose best and second best similarity lie inside the token's band, counted on
-the host from f32 similarities (numpy) with f16w_band's formula - an estimate of what the kernel flags, not a counter read from it."""
+the host from f32 similarities (numpy) with f16w_band's formula - an estimate of what the kernel flags, not a counter read from it.
+
+`--dtype u8`: uniform random u8 rows and integer-valued tokens, one storage per distance (Dot, Cosine, Euclid) over the same rows; per cell and distance
+the legs "fused" = maxsim_u8.hip and "two_step" = the exact u8 scans + maxsim_kernel (no_maxsim_fused = 1), alternating call by call, with "lists_equal"
+and "fused_row_gbytes_per_s" (the candidates' row bytes, once per 64-token group, over the fused leg's median).  Beside the Dot legs, for scale:
+"f32_fused" and "f16_fused", the sibling kernels over normal rows of the same shape."""
 import argparse
 import json
 import os
@@ -62,7 +67,7 @@ def oracle_equal(O, rows16, offsets, points, queries, lists):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dtype", choices=("f32", "f16"), default="f32")
+    ap.add_argument("--dtype", choices=("f32", "f16", "u8"), default="f32")
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--tokens", type=int, default=32)
@@ -81,7 +86,6 @@ def main():
     rows = rng.standard_normal((args.rows, args.dim), dtype=np.float32)
     st32 = qa.MultiDenseVectorStorage(rows, offsets, qa.Distance.Dot)
     ids = np.ascontiguousarray(rng.permutation(n_points)[:args.candidates], dtype=np.uint32)
-    lib = F.lib()
     result = {"tool": "bench_maxsim", "dtype": args.dtype, "rows": args.rows, "dim": args.dim, "points": n_points, "tokens": args.tokens, "candidates": len(ids),
               "candidate_rows": int((offsets[ids.astype(np.int64) + 1] - offsets[ids]).sum()), "top": args.top, "cells": {}}
     legs = [("fused", st32, 0), ("two_step", st32, 1)]
@@ -95,28 +99,14 @@ def main():
         inner = qa.VectorStorage(rows16.view(np.float16), qa.Distance.Dot, qa.VectorStorageDatatype.Float16, flags=F.SEG_F16_WIDE)
         st16 = qa.MultiDenseVectorStorage(None, offsets, qa.Distance.Dot, inner_storage=inner)
         legs = [("fused", st16, 0), ("two_step", st16, 1), ("f32_fused", st32, 0)]
+    if args.dtype == "u8":
+        return main_u8(args, rng, rows, offsets, n_points, ids, st32, result)
     all_points = np.arange(n_points, dtype=np.uint32)
     for nq in [int(x) for x in args.queries.split(",") if x]:
         queries = [rng.standard_normal((args.tokens, args.dim), dtype=np.float32) for _ in range(nq)]
         scorers = {id(s): s._queries(queries) for s in {id(leg[1]): leg[1] for leg in legs}.values()}
         for shape, cand in (("rerank", ids), ("block", None)):
-            out = {leg[0]: np.zeros((nq, args.top), dtype=ScoredPointOffset) for leg in legs}
-            counts = np.zeros(nq, dtype=np.uint32)
-            times = {k: [] for k in out}
-            kernels = {}
-            for step in range(args.warmup + args.steps):
-                for name, st, off in legs:
-                    scorer, first = scorers[id(st)]
-                    qa.set_option("no_maxsim_fused", off)
-                    t0 = time.perf_counter()
-                    F.check(lib.qmx_multi_search_topk(scorer._h, F.ptr(first), nq, F.ptr(offsets), n_points, None, 0, args.top, F.ptr(cand),
-                                                      0 if cand is None else len(cand), F.ptr(out[name]), F.ptr(counts)))
-                    if step >= args.warmup:
-                        times[name].append(1e3 * (time.perf_counter() - t0))
-                    kernels[name] = F.last_kernel(scorer._h).split("(")[0]
-            qa.set_option("no_maxsim_fused", -1)
-            cell = {k: {"median_ms": round(float(np.median(t)), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "kernel": kernels[k]}
-                    for k, t in times.items()}
+            cell, out, counts = timed_cell(args, legs, scorers, nq, offsets, n_points, cand)
             cell["lists_equal"] = bool(np.array_equal(out["fused"]["idx"], out["two_step"]["idx"]) and
                                        np.array_equal(out["fused"]["score"].copy().view(np.uint32), out["two_step"]["score"].copy().view(np.uint32)))
             cell["two_step_over_fused"] = round(cell["two_step"]["median_ms"] / cell["fused"]["median_ms"], 3)
@@ -131,11 +121,68 @@ def main():
                 take = np.concatenate([np.arange(int(offsets[p]), int(offsets[p + 1])) for p in points])
                 cell["flagged_share"] = round(flagged_share(vals16[take], lens, O.f16_to_f32(O.to_f16(queries[0])), seg_subnormal, rowmax), 5)
             result["cells"]["%s_q%d" % (shape, nq)] = cell
+    emit(args, result)
+
+
+def emit(args, result):
     line = json.dumps(result)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def timed_cell(args, legs, scorers, nq, offsets, n_points, cand):
+    """the legs (name, storage, no_maxsim_fused) alternating call by call: per leg median / min / max of the timed calls and the kernel; the lists"""
+    lib = F.lib()
+    out = {leg[0]: np.zeros((nq, args.top), dtype=ScoredPointOffset) for leg in legs}
+    counts = np.zeros(nq, dtype=np.uint32)
+    times = {k: [] for k in out}
+    kernels = {}
+    for step in range(args.warmup + args.steps):
+        for name, st, off in legs:
+            scorer, first = scorers[id(st)]
+            qa.set_option("no_maxsim_fused", off)
+            t0 = time.perf_counter()
+            F.check(lib.qmx_multi_search_topk(scorer._h, F.ptr(first), nq, F.ptr(offsets), n_points, None, 0, args.top, F.ptr(cand),
+                                              0 if cand is None else len(cand), F.ptr(out[name]), F.ptr(counts)))
+            if step >= args.warmup:
+                times[name].append(1e3 * (time.perf_counter() - t0))
+            kernels[name] = F.last_kernel(scorer._h).split("(")[0]
+    qa.set_option("no_maxsim_fused", -1)
+    cell = {k: {"median_ms": round(float(np.median(t)), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "kernel": kernels[k]}
+            for k, t in times.items()}
+    return cell, out, counts
+
+
+def main_u8(args, rng, rows32, offsets, n_points, ids, st32, result):
+    rows8 = rng.integers(0, 256, (args.rows, args.dim), dtype=np.uint8)
+    dists = (("dot", qa.Distance.Dot), ("cosine", qa.Distance.Cosine), ("euclid", qa.Distance.Euclid))
+    st8 = {name: qa.MultiDenseVectorStorage(None, offsets, d, inner_storage=qa.VectorStorage(rows8, d, qa.VectorStorageDatatype.Uint8)) for name, d in dists}
+    inner16 = qa.VectorStorage(rows32.astype(np.float16), qa.Distance.Dot, qa.VectorStorageDatatype.Float16, flags=F.SEG_F16_WIDE)
+    st16 = qa.MultiDenseVectorStorage(None, offsets, qa.Distance.Dot, inner_storage=inner16)
+    for nq in [int(x) for x in args.queries.split(",") if x]:
+        queries8 = [rng.integers(0, 256, (args.tokens, args.dim)).astype(np.float32) for _ in range(nq)]
+        queries32 = [rng.standard_normal((args.tokens, args.dim), dtype=np.float32) for _ in range(nq)]
+        scorers = {id(s): s._queries(queries8) for s in st8.values()}
+        scorers[id(st32)], scorers[id(st16)] = st32._queries(queries32), st16._queries(queries32)
+        for shape, cand in (("rerank", ids), ("block", None)):
+            points = np.arange(n_points, dtype=np.uint32) if cand is None else cand
+            n_rows = int((offsets[points.astype(np.int64) + 1] - offsets[points]).sum())
+            row_bytes = n_rows * args.dim * ((nq * args.tokens + 63) // 64)      # one pass of the candidates' rows per 64-token group
+            cells = {}
+            for name, _ in dists:
+                legs = [("fused", st8[name], 0), ("two_step", st8[name], 1)]
+                if name == "dot":
+                    legs += [("f32_fused", st32, 0), ("f16_fused", st16, 0)]
+                cell, out, _ = timed_cell(args, legs, scorers, nq, offsets, n_points, cand)
+                cell["lists_equal"] = bool(np.array_equal(out["fused"]["idx"], out["two_step"]["idx"]) and
+                                           np.array_equal(out["fused"]["score"].copy().view(np.uint32), out["two_step"]["score"].copy().view(np.uint32)))
+                cell["two_step_over_fused"] = round(cell["two_step"]["median_ms"] / cell["fused"]["median_ms"], 3)
+                cell["fused_row_gbytes_per_s"] = round(row_bytes / cell["fused"]["median_ms"] / 1e6, 1)
+                cells[name] = cell
+            result["cells"]["%s_q%d" % (shape, nq)] = cells
+    emit(args, result)
 
 
 if __name__ == "__main__":
